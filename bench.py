@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the VTC retrieval forward/eval hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one forward pass of BASELINE.json configs[2] -- the largest single-GPU configuration -- over one batch
@@ -9,7 +9,13 @@ resident in HBM: PretrainedCLIP_TimeSformer_finaltf (8-frame 224x224 TimeSformer
 operands / fp32 accumulate, synthetic random pixels and tokens, random-init weights of the real architecture.
 `value` = pairs encoded per second over the whole job (all ranks; weak scaling: pairs per GPU fixed).
 
-Top-level objects beside the contract's fields:
+A plain run sets up, runs W warm-up and K timed steps and prints the contract's fields (+ `config`); `ms_per_step` is the
+wall time of one timed step.  `--dump-outputs DIR` (rank 0) writes what the last timed step returned -- feats_vis [B, 512],
+feats_text [B, 512], sim [B, B] -- as DIR/<name>.npy in float32 (a fixed, seeded sample of rows when they would exceed
+64 MB); the inputs and weights are seeded, so two builds can be compared output for output.
+
+With `--full` (off by default) the run goes on to measure and check everything below; --no-extra / --no-cpu / --no-sweep /
+--no-independence trim that part.  Top-level objects beside the contract's fields:
   roofline      the dominant kernel class of the step (16-bit-operand MFMA GEMMs): achieved = sum(2MNK) / sum(kernel
                 time), measured live with HIP events on the launch stream (vtc_prof_*), peak 2.5 PFLOP/s dense bf16;
                 traffic = HBM bytes per launch from this round's PMC passes of the same command (profiles/), with their
@@ -600,6 +606,24 @@ def headline_independence(m3, vid, title, comments, B):
     return res
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # all arrays together, under 64 MB with the .npy headers
+
+
+def dump_outputs(outdir, out):
+    """The arrays the timed step returned, as DIR/<name>.npy (float32).  Above DUMP_LIMIT_BYTES in all, the same seeded sample
+    of rows of every array (sorted row ids; identical from run to run for a given --batch)."""
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in zip(("feats_vis", "feats_text", "sim"), out)}
+    rows = arrays["feats_vis"].shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    if row_bytes * rows > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, max(1, DUMP_LIMIT_BYTES // row_bytes), replace=False))
+        arrays = {n: a[keep] for n, a in arrays.items()}
+    os.makedirs(outdir, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(outdir, n + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step written to {outdir}: " + ", ".join(f"{n} {list(a.shape)}" for n, a in arrays.items()))
+
+
 def spawn_ranks(n):
     """One process per GPU through torch.distributed.run, as the driver itself launches an N > 1 run."""
     import socket
@@ -635,13 +659,16 @@ def main():
     ap.add_argument("--batch", type=int, default=1024, help="pairs per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"],
                     help="operand arithmetic: bf16 (BASELINE's; text blocks on IEEE half), f16 (IEEE half in both towers), f32 (the reference's)")
-    ap.add_argument("--no-extra", action="store_true", help="skip config 2, the stress encoder and the extra sweep precisions")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the N x N sweeps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: batch-independence check, instrumented roofline steps, extras, sweeps, CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip config 2, the stress encoder and the extra sweep precisions")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the N x N sweeps")
     ap.add_argument("--no-independence", action="store_true",
-                    help="skip the headline batch-independence check (profiling passes only: its B = 16 forwards would mix into the per-kernel averages)")
-    ap.add_argument("--sweep-n", type=int, default=10000)
-    ap.add_argument("--stress-n", type=int, default=50000, help="second sweep size (0 = skip)")
+                    help="--full: skip the headline batch-independence check (profiling passes only: its B = 16 forwards would mix into the per-kernel averages)")
+    ap.add_argument("--sweep-n", type=int, default=10000, help="--full: first sweep size")
+    ap.add_argument("--stress-n", type=int, default=50000, help="--full: second sweep size (0 = skip)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -729,6 +756,38 @@ def main():
     log(f"timed region: {dt:.2f} s for {args.steps} steps")
     assert torch.isfinite(out[2]).all()
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    n_tok = int((torch.cat([title, comments.reshape(-1, 77)]).argmax(-1) + 1).sum().item())
+    result = {
+        "metric": "video-text pairs encoded/sec (config 3: 8-frame TimeSformer video + title + 5 comments, CAM) + 10k x 10k sim+R@K ms",
+        "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("bf16 (video tower) + f16 (text tower blocks), fp32 accumulate" if args.dtype == "bf16" and TW.TEXT_HALF_LAYERS > 0 else
+                  "f16 (IEEE-half operands in both towers), fp32 accumulate" if args.dtype == "f16" else args.dtype),
+        "data": "synthetic",
+        "config": {"workload": "configs/pretrained_clip_timesformer_comments_attention.jsonc PretrainedCLIP_TimeSformer_finaltf forward: "
+                               f"{B} pairs/GPU/step = {B} videos (8 x 3 x 224 x 224) + {B} titles + {5 * B} comments (77 tokens) + CAM + sim",
+                   "pairs_per_gpu": B, "frames": 8,
+                   "text_tower": ("ragged: tokens after EOT are not computed, identical outputs" if TW.TEXT_RAGGED else "dense: all 77 positions"),
+                   "text_tokens_computed_frac": round(n_tok / (6 * B * 77), 4) if TW.TEXT_RAGGED else 1.0,
+                   "last_block": ("queries, out_proj + MLP of each tower's LAST block on the rows that reach the output only (x[:, 0] / the EOT row; keys and values for every row; the other rows "
+                                  "of that block are read by nothing) -- identical embeddings; extra.config3_B*_full_last_block_pairs_per_s computes them anyway"
+                                  if not (TW.DEFAULT_FLAGS & L.TOWER_FULL_LAST_LAYER) else "every row"),
+                   "parallelism": f"dp{world} (one process per GPU, no collective in the encode path)"},
+    }
+    if not args.full:
+        # a plain run: the headline figure and nothing else
+        if rccl:
+            result["rccl"] = rccl
+        log("done")
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+
     if args.no_independence:
         indep = {"max_err": None, "ok": True, "skipped": "--no-independence"}
     else:
@@ -765,7 +824,6 @@ def main():
     attn_flop = TSF_ATTN_GFLOP_PER_LAYER_VIDEO * 1e9 * 12 * B
     attn_frac = attn_flop / (attn_ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12) if attn_ms > 0 else 0.0
     traffic, traffic_src = pmc_traffic({"bf16": "config3", "f16": "config3_f16", "f32": "config3_f32"}[args.dtype])
-    n_tok = int((torch.cat([title, comments.reshape(-1, 77)]).argmax(-1) + 1).sum().item())
     roofline = dict(bound="mfma", achieved=round(achieved, 1), peak=peak, unit="TFLOP/s", frac=round(achieved / peak, 4),
                     traffic=traffic, traffic_source=traffic_src,
                     kernel=("16-bit-operand MFMA GEMMs of the step (gemm_phased_kernel / gemm_kernel), all epilogues" if args.dtype != "f32"
@@ -773,22 +831,7 @@ def main():
                     launches_per_step=g["launches"] // n_prof, avg_launch_us=round(1e3 * g["ms"] / max(1, g["launches"]), 2),
                     flop_per_launch=round(g["work"] / max(1, g["launches"]) / 1e9, 3),
                     dominant_instantiation=dominant_gemm(recs, gk, n_prof, peak))
-    result = {
-        "metric": "video-text pairs encoded/sec (config 3: 8-frame TimeSformer video + title + 5 comments, CAM) + 10k x 10k sim+R@K ms",
-        "value": round(value, 1), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": ("bf16 (video tower) + f16 (text tower blocks), fp32 accumulate" if args.dtype == "bf16" and TW.TEXT_HALF_LAYERS > 0 else
-                  "f16 (IEEE-half operands in both towers), fp32 accumulate" if args.dtype == "f16" else args.dtype),
-        "data": "synthetic",
-        "config": {"workload": "configs/pretrained_clip_timesformer_comments_attention.jsonc PretrainedCLIP_TimeSformer_finaltf forward: "
-                               f"{B} pairs/GPU/step = {B} videos (8 x 3 x 224 x 224) + {B} titles + {5 * B} comments (77 tokens) + CAM + sim",
-                   "pairs_per_gpu": B, "frames": 8,
-                   "text_tower": ("ragged: tokens after EOT are not computed, identical outputs" if TW.TEXT_RAGGED else "dense: all 77 positions"),
-                   "text_tokens_computed_frac": round(n_tok / (6 * B * 77), 4) if TW.TEXT_RAGGED else 1.0,
-                   "last_block": ("queries, out_proj + MLP of each tower's LAST block on the rows that reach the output only (x[:, 0] / the EOT row; keys and values for every row; the other rows "
-                                  "of that block are read by nothing) -- identical embeddings; extra.config3_B*_full_last_block_pairs_per_s computes them anyway"
-                                  if not (TW.DEFAULT_FLAGS & L.TOWER_FULL_LAST_LAYER) else "every row"),
-                   "parallelism": f"dp{world} (one process per GPU, no collective in the encode path)"},
+    result.update({
         "roofline": roofline,
         "timesformer_attention_mfma_frac": round(attn_frac, 4),
         "timesformer_attention": {"ms_per_step": round(attn_ms, 3), "launches": attn_launches,
@@ -800,7 +843,7 @@ def main():
         "ms_per_step_with_events": round(1e3 * dt_instr / n_prof, 3),
         "headline_batch_independence_max_err": indep["max_err"],
         "headline_batch_independence": indep,
-    }
+    })
     if rccl:
         result["rccl"] = rccl
     extra = {}

@@ -14,6 +14,11 @@ import torch.multiprocessing as mp
 from oracle import eval_ref as E
 
 
+# CPU ranks over gloo.  Where a GPU is present, init_from_env puts each rank on card LOCAL_RANK, which a one-GPU machine lacks
+# for rank >= 1: every rank takes card 0 instead, as in the one-card rehearsals (no effect without a GPU).
+ONE_CARD = {"VTC_LOCAL_DEVICE": "0"}
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -28,7 +33,7 @@ def _cpu_topk(g, q, depth):
 
 
 def _worker(rank, world, port, n, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), **ONE_CARD)
     from vtc_amd import dist as vdist
     r, _, w = vdist.init_from_env(backend="gloo")
     assert (r, w) == (rank, world)
@@ -64,7 +69,7 @@ def _shard_ops():
 
 
 def _worker_one_matrix(rank, world, port, n, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), **ONE_CARD)
     from vtc_amd import dist as vdist
     vdist.init_from_env(backend="gloo")
     rng = np.random.default_rng(0)
@@ -137,7 +142,7 @@ def _rank_ops():
 
 
 def _worker_rank_sharded(rank, world, port, n, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), **ONE_CARD)
     from vtc_amd import dist as vdist
     vdist.init_from_env(backend="gloo")
     rng = np.random.default_rng(1)
@@ -209,7 +214,7 @@ def test_bench_gpus_n_launches_its_own_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(VTC_DIST_BACKEND="gloo", VTC_BENCH_RENDEZVOUS_ONLY="1")
+    env.update(VTC_DIST_BACKEND="gloo", VTC_BENCH_RENDEZVOUS_ONLY="1", **ONE_CARD)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -249,7 +254,7 @@ def test_ranks_sharing_a_card_select_the_multi_launch_cam(monkeypatch):
 
 
 def _shared_card_worker(rank, world, port, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), **ONE_CARD)
     from vtc_amd import dist as vdist
     from vtc_amd import towers
     # ranks 0 and 2 claim the same card, rank 1 another
@@ -293,7 +298,7 @@ def test_single_rank_path_of_sharded_recall_is_the_plain_recall():
 
 
 def _worker_nonfinite(rank, world, port, n, out):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), **ONE_CARD)
     from vtc_amd import dist as vdist
     vdist.init_from_env(backend="gloo")
     rng = np.random.default_rng(1)

@@ -19,7 +19,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp
 export VTC_OVERLAP=0
-B="--no-extra --no-cpu --no-sweep --no-independence"
+B="--full --no-extra --no-cpu --no-sweep --no-independence"
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has stats; then
   rm -rf $O/${TAG}_stats

@@ -86,7 +86,7 @@ def main():
         json.dump({"kernel": k, "launches": c, "read_bytes_per_launch": rd / c, "write_bytes_per_launch": wt / c,
                    "traffic_bytes_per_launch": (rd + wt) / c, "workload": workload, "commit": commit,
                    "date": __import__("datetime").datetime.utcnow().strftime("%Y-%m-%d"), "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes",
-                   "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --no-extra --no-cpu --no-sweep`; "
+                   "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --no-extra --no-cpu --no-sweep`; "
                              "reads = 2 x FETCH_SIZE KiB (gfx950 correction), writes = WRITE_SIZE KiB"},
                   open(out + "_traffic.json", "w"), indent=1)
     open(out + ".md", "w").write("\n".join(lines) + "\n")
