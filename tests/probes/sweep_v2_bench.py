@@ -1,5 +1,5 @@
-"""EXACT sweep: block-minima path (v2) vs split-bf16 materialising path (v1), per tile variant; ids vs fp64 oracle sample.
-usage: python tests/probes/sweep_v2_bench.py N    (env VTC_SWEEP_EXACT_V1=1 / VTC_SWEEP_MIN_TILE=0|1 / VTC_SWEEP_DEBUG=1)"""
+"""EXACT sweep, block-minima path: bidirectional vs one direction; ids vs fp64 oracle sample.
+usage: python tests/probes/sweep_v2_bench.py N"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -21,4 +21,4 @@ rows = np.arange(3, N, max(1, N // 500))[:500]
 r1 = E.l2_topk(va.numpy(), tb.numpy()[rows], 11, np.float64)[0]
 r2 = E.l2_topk(tb.numpy(), va.numpy()[rows], 11, np.float64)[0]
 ok = bool(np.array_equal(i1.cpu().numpy()[rows], r1) and np.array_equal(i2.cpu().numpy()[rows], r2) and np.array_equal(j1.cpu().numpy()[rows], r1))
-print(f"N={N} EXACT: bidir {t2:.3f} ms | one direction {t1:.3f} ms | sample == fp64 oracle: {ok} | v1={os.environ.get('VTC_SWEEP_EXACT_V1','0')} tile={os.environ.get('VTC_SWEEP_MIN_TILE','0')}", flush=True)
+print(f"N={N} EXACT: bidir {t2:.3f} ms | one direction {t1:.3f} ms | sample == fp64 oracle: {ok}", flush=True)

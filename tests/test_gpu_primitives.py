@@ -276,8 +276,8 @@ def test_gemm_phased_epilogues():
 
 
 def test_gemm_random_shapes_all_kernels():
-    """Randomised shapes over every kernel configuration (64x64, 128x128, 256x256 phased; forced through
-    VTC_GEMM_TILE-independent heuristics by size), ragged edges in M and N, K from one K-tile up, every epilogue --
+    """Randomised shapes over every kernel configuration (64x64, 128x128, 256x256 phased; each reached through the
+    shape heuristic by size), ragged edges in M and N, K from one K-tile up, every epilogue --
     integer-valued operands make the fp32 result exact, so any indexing mistake shows as a mismatch."""
     L, ops = _ops()
     rng = np.random.default_rng(2024)

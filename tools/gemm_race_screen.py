@@ -1,7 +1,7 @@
-"""Race screen for the 256 x 256 GEMM's K-loop schedules (guide 5: "a sync-structure edit makes a NEW template: screen it for races over
+"""Race screen for the GEMM kernels the product runs (guide 5: "a sync-structure edit makes a NEW template: screen it for races over
 many runs at several sizes").  Integer-valued operands make every output exact in fp32, so ANY stale LDS read / early re-fill shows as
 a mismatch; a side stream streams large copies meanwhile so that LDS-DMA return times vary.
-usage: python tools/gemm_race_screen.py [reps]        (VTC_GEMM_DEEP=0|1 selects the loop; default = the product's)"""
+usage: python tools/gemm_race_screen.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -41,5 +41,5 @@ for (M, N, K) in SHAPES:
     bad_total += n
     print(f"M={M:6d} N={N:5d} K={K:5d}: {reps} launches (+{(reps + 7) // 8} residual), mismatching launches: {n}", flush=True)
     del a, w, ref, out, x0
-print("VTC_GEMM_DEEP =", os.environ.get("VTC_GEMM_DEEP", "default"), "-> total mismatching launches:", bad_total)
+print("total mismatching launches:", bad_total)
 sys.exit(1 if bad_total else 0)

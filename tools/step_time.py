@@ -31,5 +31,5 @@ for B in [int(x) for x in sys.argv[1:]] or [1, 50, 1024]:
             m(vid, title, comments)
         torch.cuda.synchronize()
         best = min(best, (time.perf_counter() - t0) / reps)
-    print(f"B={B:5d}: {1e3 * best:8.3f} ms per forward, {B / best:8.1f} pairs/s  (compute dtype {str(PIX).split('.')[-1]}, VTC_GEMM_DEEP={os.environ.get('VTC_GEMM_DEEP', 'default')})", flush=True)
+    print(f"B={B:5d}: {1e3 * best:8.3f} ms per forward, {B / best:8.1f} pairs/s  (compute dtype {str(PIX).split('.')[-1]})", flush=True)
     del vid

@@ -29,4 +29,4 @@ for noise in noises:
         e0.record(); ops.recall_bidir(ta, tb, [1, 5, 10], hits=hits); e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
-    print(f"N={n} noise={noise}: {np.median(ts):.3f} ms per sweep (planes: {os.environ.get('VTC_SWEEP_PLANES', 'default')}); R@1/5/10 = {(hits[0].cpu().numpy() / n).round(4).tolist()}", flush=True)
+    print(f"N={n} noise={noise}: {np.median(ts):.3f} ms per sweep; R@1/5/10 = {(hits[0].cpu().numpy() / n).round(4).tolist()}", flush=True)

@@ -1,5 +1,5 @@
 """Per-(epilogue, N, K) GEMM time of one video-tower forward (HIP events around every launch): which instantiation costs what.
-usage: python tools/tower_modes.py [B]    (env knobs of gemm.hip apply, e.g. VTC_GEMM_RESID_SMALL_K=768)"""
+usage: python tools/tower_modes.py [B]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

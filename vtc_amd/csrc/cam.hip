@@ -47,7 +47,6 @@ struct CamFusedParams {
   float *x, *big, *att;       // residual stream [rows, D]; qkv [rows, 3 D] / MLP hidden [rows, 4 D] (never live together); attention output
   int *bar;                   // grid-barrier words (grid_barrier; CAM_BAR_BYTES, zeroed before the launch); bar[1]: error word
   int *err_host;              // device-visible pinned host word (never reset): a barrier that gave up sets it, the next launch reports it
-  unsigned long long *stamps; // diagnostics (VTC_CAM_STAMPS=1): s_memrealtime of workgroup 0 at the start and after every barrier; else NULL
   int act;
   float scale;
   const float *bn_mean, *bn_var;
@@ -274,18 +273,10 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
   const int TW = gridDim.x * 4, gw = blockIdx.x * 4 + wave;
   const int g = lane >> 4, n = lane & 15;
   const Sc1Buf bx(p.x, (size_t)p.rows * D * 4), bbig(p.big, (size_t)p.rows * 4 * D * 4), batt(p.att, (size_t)p.rows * D * 4);
-  if (p.stamps && threadIdx.x == 0 && blockIdx.x == 0) p.stamps[0] = __builtin_amdgcn_s_memrealtime();
   int phase = 0;
-  // diagnostics (VTC_CAM_STAMPS): workgroup 0's clock after each phase's compute (slot 3 i + 1), after the prestage of the next
-  // weights (3 i + 2) and after the barrier (3 i + 3)
-  auto stamp = [&](int slot) {
-    if (p.stamps && threadIdx.x == 0 && blockIdx.x == 0) p.stamps[slot] = __builtin_amdgcn_s_memrealtime();
-  };
   auto sync_grid = [&]() {
-    stamp(3 * phase + 2);
     ++phase;
     grid_barrier(p.bar, phase);
-    stamp(3 * phase);
   };
   // P5's first unit of this workgroup: slice (-1: none), staged ahead like the projection phases'
   const int p5_slices = D / 16, p5_wgps = max(1, min(p.ntiles, (int)gridDim.x / p5_slices));
@@ -298,7 +289,6 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
     // ---- P1: ln_1 (folded) + in_proj -> qkv (layer 0: from the tokens) -----------------------------------------------------
     if (l == 0) proj_phase<D, 0, true, true>(wlds, p, nullptr, p.qkv_wf[l], p.qkv_c[l], p.qkv_s[l], p.big, 3 * D, true);
     else proj_phase<D, 0, true, false>(wlds, p, p.x, p.qkv_wf[l], p.qkv_c[l], p.qkv_s[l], p.big, 3 * D, true);
-    stamp(3 * phase + 1);
     sync_grid();
     // ---- P2: attention core, one wave per (item, head) ---------------------------------------------------------------------
     // lane = head dimension d for the loads and the output; the Lc x Lc scores are taken by one lane each from q / k rows staged in
@@ -364,16 +354,13 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
       }
       if (has_unit) prestage_proj<D>(wlds, p, p.out_w[l], D);
     }
-    stamp(3 * phase + 1);
     sync_grid();
     // ---- P3: out_proj + residual ---------------------------------------------------------------------------------------------
     proj_phase<D, 2, false, false>(wlds, p, p.att, p.out_w[l], p.out_b[l], nullptr, p.x, D, true);
-    stamp(3 * phase + 1);
     prestage_proj<D>(wlds, p, p.fc_wf[l], 4 * D);
     sync_grid();
     // ---- P4: ln_2 (folded) + c_fc + QuickGELU -> hidden ------------------------------------------------------------------------
     proj_phase<D, 1, true, false>(wlds, p, p.x, p.fc_wf[l], p.fc_c[l], p.fc_s[l], p.big, 4 * D, true);
-    stamp(3 * phase + 1);
     prestage_p5(l);
     sync_grid();
     // ---- P5: c_proj (K = 4 D, a quarter per wave of the workgroup) + residual ---------------------------------------------------
@@ -415,7 +402,6 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
         }
       }
     }
-    stamp(3 * phase + 1);
     if (l + 1 < p.layers) prestage_proj<D>(wlds, p, p.qkv_wf[l + 1], 3 * D);
     sync_grid();
   }
@@ -491,22 +477,19 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
 
 namespace vtcgemm { int num_cus(); }
 
-// Largest token count B (1 + nc) the one-launch CAM takes (env VTC_CAM_FUSED_MAX_ROWS; 0 disables it): above it the GEMM launches
-// of towers.hip fill the chip and win (measured crossover).
-int cam_fused_max_rows() {
-  static const int v = [] { const char *e = getenv("VTC_CAM_FUSED_MAX_ROWS"); return e ? atoi(e) : 512; }();
-  return v;
-}
+// Largest token count B (1 + nc) the one-launch CAM takes: above it the GEMM launches of towers.hip fill the chip and win
+// (measured crossover).  A model opts out with VTC_CAM_NO_FUSED.
+constexpr int CAM_FUSED_MAX_ROWS = 512;
 
 bool cam_fused_supported(const vtc_cam_w *w, int B, int nc, int dtype) {
   const int Lc = 1 + nc;
   for (int l = 0; l < w->layers && l < CAM_MAX_LAYERS; ++l)      // the folded-LayerNorm weights (fp32) must have been packed
     if (!w->blocks[l].qkv_wf || !w->blocks[l].qkv_s || !w->blocks[l].qkv_c || !w->blocks[l].fc_wf || !w->blocks[l].fc_s || !w->blocks[l].fc_c) return false;
   return dtype == VTC_F32 && w->init_from_avg && !(w->flags & VTC_CAM_NO_FUSED) && (w->width == 512 || w->width == 128) &&
-         w->width == w->heads * 64 && w->layers >= 1 && w->layers <= CAM_MAX_LAYERS && Lc <= 15 && B * Lc <= cam_fused_max_rows();
+         w->width == w->heads * 64 && w->layers >= 1 && w->layers <= CAM_MAX_LAYERS && Lc <= 15 && B * Lc <= CAM_FUSED_MAX_ROWS;
 }
 
-// Two cooperative launches on ONE device at the same time (two streams, two host threads) would split the CUs between them and
+// Two one-launch CAMs on ONE device at the same time (two streams, two host threads) would split the CUs between them and
 // each would wait at its first barrier for workgroups that cannot become resident (a width-512 workgroup takes a whole CU's
 // LDS): the bounded spin would end it after seconds, with garbage.  So the launcher remembers, per device, the stream and a
 // completion event of the last one-launch CAM: same stream -> ordered behind it; another stream and the event not yet complete
@@ -541,7 +524,7 @@ int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *c
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
   std::lock_guard<std::mutex> lk(g_cam_mu);
   // the error word of this device: pinned, device-visible, allocated once.  A grid barrier that gave up (the launch lost its
-  // residency guarantee: it cannot under a cooperative launch) wrote NaN embeddings AND set this word.
+  // residency guarantee) wrote NaN embeddings AND set this word.
   if (!g_cam_err_words[dev]) {
     int *h = nullptr;
     if (hipHostMalloc((void **)&h, 64, hipHostMallocMapped) != hipSuccess || !h) return -1;     // no error word: take the multi-launch path
@@ -585,30 +568,20 @@ int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *c
     p.proj_w[l] = (const float *)b.proj_w; p.proj_b[l] = b.proj_b;
   }
   p.x = x; p.big = big; p.att = att; p.bar = bar;
-  static const bool want_stamps = [] { const char *e = getenv("VTC_CAM_STAMPS"); return e && e[0] == '1'; }();
-  static unsigned long long *stamps = nullptr;       // diagnostics only: a buffer of its own that no kernel reads
-  if (want_stamps && !stamps) (void)hipMalloc(&stamps, 64 * sizeof(unsigned long long));
-  if (want_stamps && stamps) (void)hipMemsetAsync(stamps, 0, 64 * sizeof(unsigned long long), stream);
-  p.stamps = want_stamps ? stamps : nullptr;
   p.act = w->residual_activation; p.scale = w->squash_scale; p.bn_mean = w->bn_mean; p.bn_var = w->bn_var;
   p.out = adapted;
   VTC_CHECK(hipMemsetAsync(bar, 0, CAM_BAR_BYTES, stream) == hipSuccess, "cam_fused: barrier reset failed");
   // Every workgroup must be resident for the grid barrier: one per CU (width 512: 136 KiB of LDS each, so exactly one fits).
-  // nothing guaranteed that.  Two launch forms, measured in round 4 (profiles/r04_experiments.txt):
-  //   * default -- an ordinary launch behind an occupancy check of THIS kernel on THIS device (grid <= CUs x resident workgroups per
-  //     CU, else -1: the caller takes the multi-launch path).  What the check cannot see (a foreign kernel holding a CU: another
-  //     process, RCCL, a CU mask) ends in the bounded spin of grid_barrier: NaN embeddings AND the device-visible error word
-  //     below, which fails every later call on the device with a message -- loud, never a silent wrong answer;
-  //   * VTC_CAM_COOP=1 (read once) -- hipLaunchCooperativeKernel: the runtime validates residency and serialises cooperative
-  //     grids.  Not the default because it costs +0.11 ms per forward at B = 1 (+6 %; the cooperative queue hand-over) and because
-  //     rocprofv3 of ROCm 7.2 segfaults in its teardown in any process that made one (tools/exit_probe.py).
+  // nothing guaranteed that.  An ordinary launch behind an occupancy check of THIS kernel on THIS device (grid <=
+  // CUs x resident workgroups per CU, else -1: the caller takes the multi-launch path).  What the check cannot see (a foreign kernel
+  // holding a CU: another process, RCCL, a CU mask) ends in the bounded spin of grid_barrier: NaN embeddings AND the device-visible
+  // error word below, which fails every later call on the device with a message -- loud, never a silent wrong answer.
+  // (hipLaunchCooperativeKernel, round 4: +0.11 ms per forward at B = 1 and a rocprofv3 teardown crash -- profiles/r04_experiments.txt 3)
   const int grid = vtcgemm::num_cus();
   ProfScope prof(VTC_PROF_GEMM_F32, 2.0 * p.rows * 12.0 * w->width * w->width * w->layers, stream);
   void *kargs[] = {&p};
   hipError_t le;
-  static const bool coop = [] { const char *e = getenv("VTC_CAM_COOP"); return e && e[0] == '1'; }();
   auto launch = [&](const void *fn, int shmem) -> hipError_t {
-    if (coop) return hipLaunchCooperativeKernel(fn, dim3(grid), dim3(256), kargs, shmem, stream);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, shmem) != hipSuccess || per_cu < 1) return hipErrorCooperativeLaunchTooLarge;
     return hipLaunchKernel(fn, dim3(grid), dim3(256), kargs, shmem, stream);
@@ -628,16 +601,6 @@ int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *c
     return -1;
   }
   cam_fused_mark_locked(dev, stream);
-  if (want_stamps && stamps) {     // diagnostics: synchronises
-    unsigned long long h[64];
-    (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(h, stamps, sizeof(h), hipMemcpyDeviceToHost);
-    const int nph = 5 * w->layers;
-    fprintf(stderr, "[cam stamps] B=%d rows=%d: total %.1f us; per phase compute/prestage/barrier (us):", B, p.rows, (h[3 * nph] - h[0]) * 0.01);
-    for (int i = 0; i < nph; ++i)
-      fprintf(stderr, " %.1f/%.1f/%.1f", (h[3 * i + 1] - h[3 * i]) * 0.01, (h[3 * i + 2] - h[3 * i + 1]) * 0.01, (h[3 * i + 3] - h[3 * i + 2]) * 0.01);
-    fprintf(stderr, "\n");
-  }
   return 0;
 }
 

@@ -202,10 +202,10 @@ struct GemmEpi {
   int ldo = 0;                // output leading dimension (0 => N)
   // internal: block-minima epilogue of the sweep (mode 6): no matrix is written.  Per (row, block of 64 columns): the three
   // smallest distance keys + the fourth smallest as a bound -> rowk[4][nblk_c][M]; with colk != nullptr also per (column,
-  // block of RB rows, RB = the kernel's wave tile height) -> colk[4][nblk_r][N].
+  // block of 128 rows, the phased kernel's wave tile height) -> colk[4][nblk_r][N].
   // key = (bits(max(d, 0)) & ~127) | index in block: a non-negative float, compared as an unsigned integer.
   unsigned *rowk = nullptr, *colk = nullptr;
-  int nblk_c = 0, nblk_r = 0, rb = 0;
+  int nblk_c = 0, nblk_r = 0;
   // internal: residual epilogue + the FOLLOWING LayerNorm (mode 7; 16-bit operands, N a multiple of 256, N <= 1024): the column
   // tile that finishes a 256-row block last normalises the block's rows (LN(out) * ln_g + ln_b -> ln_out, operand format).
   // ln_cnt: one arrival counter per row block, zeroed by the launcher.

@@ -6,11 +6,11 @@
 // model/timesformer_clip_alt.py:50,65,148,174 and upstream nn.MultiheadAttention / nn.Linear.
 //
 // gfx950 design
-//   * two tile configurations of one kernel template:
-//       "big"   256x256 output tile, 512 threads (8 waves as 2x4, 128x64 per wave), one workgroup
+//   * two tile configurations:
+//       "big"   256x256 output tile (gemm_phased_kernel), 512 threads (8 waves as 2x4, 128x64 per wave), one workgroup
 //               per CU, 128 KiB LDS -- 131 FLOP per byte staged from L2, used when the problem
 //               has enough tiles to fill the chip;
-//       "small" 128x128 tile, 256 threads (4 waves as 2x2, 64x64 per wave), two workgroups per CU
+//       "small" 128x128 tile (gemm_kernel; 64x64 for the fewest tiles), 256 threads (4 waves as 2x2, 64x64 per wave), two workgroups per CU
 //               -- for the skinny problems (CAM, output projections, edge cases) and for fp32;
 //   * K is consumed in 128-byte rows (64 bf16 / 32 fp32 per step); both operands go L2 -> LDS with
 //     global_load_lds_dwordx4 (LDS-DMA, no VGPR round trip), double buffered, issued from inline
@@ -42,7 +42,9 @@
 // the code in the history (commit 3ac3430).  What remains are the cycle-stamp diagnostics (correct results, slower), kept out of
 // line in gemm_stamps.h and compiled only with -DVTC_GEMM_STAMPS / -DVTC_GEMM_PHASE_STAMPS.  The three alternative K-loop schedules
 // of round 4 (DEEP 2 / 3 / 4: bit-identical results, measured level or slower -- profiles/r04_experiments.txt 1, 14, 16) left the
-// product source in round 5 (commit 7fd3e13 has them); __graft_entry__.build() refuses every -DVTC_* flag.
+// product source in round 5 (commit 7fd3e13 has them); __graft_entry__.build() refuses every -DVTC_* flag.  The run-time environment
+// knobs (forced tile incl. the free-running 256 x 256 kernel, DEEP = 0 override, column groups / super-rows of the tile walk, start
+// stagger, CU budget, residual K threshold, im2row patch embedding) left after round 6 (commit dda8438 has them).
 #if defined(VTC_ABLATE_STORES) || defined(VTC_ABLATE_DMA) || defined(VTC_ABLATE_HALF_DMA) || defined(VTC_ABLATE_DMA_EXEC1) || \
     defined(VTC_ABLATE_VMWAIT) || defined(VTC_ABLATE_LDSREAD) || defined(VTC_PROBE_MFMA32) || defined(VTC_PHASED_WAIT_FIRST) || \
     defined(VTC_PHASED_ONE_BARRIER) || defined(VTC_NO_RELAXED_FIRST) || defined(VTC_ROW_PANEL_PROBE)
@@ -53,9 +55,6 @@
 #ifndef VTC_MFMA_PRIO
 #define VTC_MFMA_PRIO 3      // s_setprio of a wave inside its MFMA cluster.  Round 5 A/B (tools/gemm_ab.py, 6 rounds x 30 reps, bit-identical): 3 against
                              // round 4's 1: c_proj +1.2 %, QKV +1.0 %, c_fc / out-proj / text shapes +0.2 ... +0.8 % (profiles/r05_experiments.txt 5)
-#endif
-#ifndef VTC_GEMM_DEEP_DEFAULT
-#define VTC_GEMM_DEEP_DEFAULT 1     // the 256 x 256 kernel's LDS-DMA pipeline: 1 = deep (round 4), 0 = one quarter in flight (rounds 1-3)
 #endif
 
 using namespace vtcgemm;
@@ -173,25 +172,6 @@ struct MinK {
 // mantissa bits, one v_bfi per key, where the four-plane form spends fma + add + max per value first.  |.| instead of the clamp at zero: a distance
 // that rounding made negative by x <= eps reads x instead of 0, still within eps of the exact one.  The keys are HALF distances (recall_rank_kernel<2>
 // halves its thresholds).  The next tile's norms are requested before a tile's epilogue and land under it.
-template <int WM, int WN, int TM, int TN>
-__device__ __forceinline__ void l2min2_half_norms(const GemmParams &p, int m0, int n0, float (&hr)[TM], float (&hc)[TN][4]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wr = wave / WN, wc = wave % WN, g = lane >> 4, l15 = lane & 15;
-  const int mbase = m0 + wr * TM * 16, nbase = n0 + wc * TN * 16;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = mbase + 16 * i + l15;
-    hr[i] = m < p.M ? -0.5f * p.epi.rown[m] : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < TN; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = nbase + 16 * j + 4 * g + e;
-      hc[j][e] = n < p.N ? -0.5f * p.epi.coln[n] : 0.f;
-    }
-}
-
 template <int WM, int WN, int TM, int TN, int NPLR, int NPL>      // NPLR / NPL: planes of the row / column direction
 __device__ __forceinline__ void l2min_epilogue(f32x4 (&acc)[TM][TN], const GemmParams &p, int m0, int n0) {
   static_assert(TN == 4, "a wave's columns are one 64-column block");
@@ -844,6 +824,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
 template <typename T, int MODE, typename OutT, int WM, int WN, int TM, int TN, int NSTAGE>
 __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
   constexpr int NW = WM * WN, BM = WM * TM * 16, BN = WN * TN * 16;
+  static_assert(!l2min_half_keys(MODE), "EPI_L2MIN2 / 3 start from pre-loaded accumulators: the phased kernel only");
   if (p.epi.m_dev) {        // the row count lives in device memory (GemmEpi::m_dev): the grid was sized for the host's upper bound
     p.M = *p.epi.m_dev;
     p.MT = (p.M + BM - 1) / BM;
@@ -955,18 +936,13 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
   wait_all_but(ahead);                       // slab 0 has landed
   __syncthreads();
 
-  [[maybe_unused]] float hr[TM], hc[TN][4];       // EPI_L2MIN2: -(norms) / 2 of the tile about to start (l2min2_half_norms)
-  if constexpr (l2min_half_keys(MODE) && TN == 4) l2min2_half_norms<WM, WN, TM, TN>(p, m0, n0, hr, hc);
   while (true) {
 
     f32x4 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (l2min_half_keys(MODE) && TN == 4) acc[i][j] = (f32x4){hr[i] + hc[j][0], hr[i] + hc[j][1], hr[i] + hc[j][2], hr[i] + hc[j][3]};
-        else acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
+      for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     for (int t = 0; t < ksteps; ++t) {
       // Stagger (MI355X_MICROARCH "two waves per SIMD", item 9): the two waves that share a SIMD run the
@@ -1016,9 +992,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
       cur = cur + 1 == NSTAGE ? 0 : cur + 1;
     }
 
-    if constexpr (l2min_half_keys(MODE) && TN == 4) {
-      if (has_next) l2min2_half_norms<WM, WN, TM, TN>(p, m0n, n0n, hr, hc);
-    }
     tile_epilogue<T, MODE, OutT, WM, WN, TM, TN, STAGE / NW>(acc, p, m0, n0, ((cur + NSTAGE - 1) % NSTAGE) * STAGE);
     if (has_next) __syncthreads();         // the transposition area becomes the next K-step's staging buffer
 
@@ -1120,7 +1093,7 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
     p.MT = (p.M + BM - 1) / BM;
   }
   constexpr int A_BYTES = BM * ROWB, STAGE = (BM + BN) * ROWB;
-  const int SUPER = p.super_tiles > 0 ? p.super_tiles : SUPER_ROWS / BM;
+  constexpr int SUPER = SUPER_ROWS / BM;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
@@ -1132,28 +1105,17 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
   const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
   const int nt_x = (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
   const int start_x = xcd * (ntiles >> 3) + min(xcd, ntiles & 7);
-  // Logical order: column groups of `cg` column tiles (all of them when col_group == 0); inside a group super-rows of SUPER
-  // row blocks, inside a super-row column by column.  A group's weight panels are what an XCD keeps in its L2 while it walks
-  // down the rows.
-  const int cg = p.col_group > 0 ? min(p.col_group, p.NT) : p.NT;
+  // Logical order: super-rows of SUPER row blocks, inside a super-row column by column (as gemm_kernel).
   auto decode = [&](int logical, int &m0, int &n0) {
-    const int full = p.MT * cg;
-    const int gi = logical / full;
-    const int c0 = gi * cg, cgi = min(cg, p.NT - c0);
-    const int in_g = logical - gi * full;
-    const int per_super = SUPER * cgi;
-    const int sr = in_g / per_super, rem = in_g - sr * per_super;
+    const int per_super = SUPER * p.NT;
+    const int sr = logical / per_super, rem = logical - sr * per_super;
     const int gsz = min(SUPER, p.MT - sr * SUPER);
     const int nt = rem / gsz;
     m0 = (sr * SUPER + (rem - nt * gsz)) * BM;
-    n0 = (c0 + nt) * BN;
+    n0 = nt * BN;
   };
   int li = slot;
   if (li >= nt_x) return;                      // uniform for the whole workgroup
-  if (p.stagger_groups > 1) {
-    const long long t_end = (long long)__builtin_amdgcn_s_memrealtime() + (long long)(slot % p.stagger_groups) * p.stagger_ticks;
-    while ((long long)__builtin_amdgcn_s_memrealtime() < t_end) __builtin_amdgcn_s_sleep(8);
-  }
   int m0, n0;
   decode(start_x + li, m0, n0);
   int m0n = 0, n0n = 0;
@@ -1314,7 +1276,7 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        if constexpr (l2min_half_keys(MODE)) {     // (l2min2_half_norms' layout: row 16 i + (lane & 15) of the wave's 128, columns 16 j + 4 g .. + 3 of its 64)
+        if constexpr (l2min_half_keys(MODE)) {     // (the MFMA layout: row 16 i + (lane & 15) of the wave's 128, columns 16 j + 4 g .. + 3 of its 64)
           const float hr = nrm[wr * 128 + 16 * i + (lane & 15)];
           const float4 hc = *reinterpret_cast<const float4 *>(nrm + 256 + wc * 64 + 16 * j + 4 * g);
           acc[i][j] = (f32x4){hr + hc.x, hr + hc.y, hr + hc.z, hr + hc.w};
@@ -1555,15 +1517,12 @@ int run(GemmParams p, hipStream_t stream) {
   return 0;
 }
 
-int g_cu_budget = 0;                  // > 0: the persistent 256 x 256 grid takes at most this many workgroups (= CUs) -- two streams' GEMMs side by side (diagnostics: VTC_GEMM_CU_BUDGET)
-int g_deep = VTC_GEMM_DEEP_DEFAULT;   // pipeline depth of the 256 x 256 kernel: 0 = one quarter in flight (rounds 1-3), 1 = deep (VTC_GEMM_DEEP)
-
 template <int MODE, typename OutT, typename T, int DEEP>
 int run_phased_d(GemmParams p, hipStream_t stream) {
   p.MT = cdiv(p.M, 256); p.NT = cdiv(p.N, 256);
   const int ntiles = p.MT * p.NT;
   const size_t shmem = (size_t)2 * 512 * ROWB + (MODE == EPI_RESID_LN ? 16 : 0) + (l2min_half_keys(MODE) ? 2048 : 0);   // 128 KiB: one workgroup per CU (+ the ticket word / the tile's half norms)
-  const int grid = min(ntiles, g_cu_budget > 0 ? min(g_cu_budget, num_cus()) : num_cus());
+  const int grid = min(ntiles, num_cus());
   static PerDeviceOnce attr;
   if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&gemm_phased_kernel<MODE, OutT, T, DEEP>), (int)shmem, "gemm_phased")) return 1;
   VTC_STAMP_HOST_BEFORE(p, stream);
@@ -1578,33 +1537,20 @@ int run_phased(const GemmParams &p, hipStream_t stream) {
   // round-3 loop (register budgets: EPI_L2MIN with the deep loop spills 18 registers and measures the same, r04_experiments.txt 7)
   // (round 5: with the epilogue's thread index opaque the two-plane form fits the deep loop without spills -- 2.94 - 2.96 against 2.89 - 2.93 ms at 50k: no gain)
   if constexpr (MODE != EPI_RESID_LN && MODE != EPI_L2MIN && !l2min_half_keys(MODE)) {
-    if (p.K >= 128) {
-      if (g_deep >= 1) return run_phased_d<MODE, OutT, T, 1>(p, stream);
-    }
+    if (p.K >= 128) return run_phased_d<MODE, OutT, T, 1>(p, stream);
   }
   return run_phased_d<MODE, OutT, T, 0>(p, stream);
 }
-
-int g_resid_small_k = 0; // residual epilogues with K <= this take the 128 x 128 kernel (two workgroups per CU: one's epilogue under the other's K loop); 0 = heuristic only (VTC_GEMM_RESID_SMALL_K)
-int g_force_tile = 0;   // 0 = heuristic, 1 = 128x128, 2 = 256x256 free-running, 4 = 256x256 phased, 5 = 64x64 (diagnostics: VTC_GEMM_TILE)
 
 template <typename T, int MODE, typename OutT>
 int run_cfg(const GemmParams &p, hipStream_t stream) {
   if constexpr (sizeof(T) == 2) {
     // Tile choice by estimated rounds: a round of 256x256 tiles (one per CU) costs ~1.0, a round of 128x128 tiles
-    // (two per CU) ~0.65 of that (calibrated on the vision-tower shapes, tools/gemm_tile_choice.py: 150 big tiles
+    // (two per CU) ~0.65 of that (calibrated on the vision-tower shapes, tools/gemm_tile_choice.py of commit dda8438: 150 big tiles
     // -> big, 297 -> small, 75 -> small, 256 -> big, 450 and more -> big).
     const long tb = (long)cdiv(p.M, 256) * cdiv(p.N, 256), ts = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
     const long rb = (tb + num_cus() - 1) / num_cus(), rs = (ts + 2 * num_cus() - 1) / (2 * num_cus());
-    bool big = rb * 100 <= rs * 65;
-    if constexpr (MODE == VTC_EPI_RESID || MODE == EPI_RESID_FOLD || MODE == EPI_RESID_FOLD_C) {
-      if (g_resid_small_k > 0 && p.K <= g_resid_small_k) big = false;
-    }
-    if (g_force_tile == 1) big = false;
-    if (g_force_tile == 2) big = true;
-    if (g_force_tile == 4) big = true;
-    if (big && g_force_tile != 2) return run_phased<MODE, OutT, T>(p, stream);
-    if (big) return run<T, MODE, OutT, 2, 4, 8, 4, 2>(p, stream);
+    if (rb * 100 <= rs * 65) return run_phased<MODE, OutT, T>(p, stream);
   }
   // few 128x128 tiles (CAM: 1536 x 512, the output projections): 64x64 tiles, two waves, put 4x the workgroups
   // on the chip -- these launches are bounded by one tile's serial K loop, not by throughput
@@ -1612,7 +1558,7 @@ int run_cfg(const GemmParams &p, hipStream_t stream) {
 #ifndef VTC_SMALL_NSTAGE
 #define VTC_SMALL_NSTAGE 3      // LDS stages of the 64 x 64 configuration: two K-steps of LDS-DMA in flight (these launches are one tile's serial K loop: B = 1 forward 2.36 -> 1.98 ms from 2 to 3 stages in round 2; 5 stages, round 5: no further gain -- 1.83 against 1.78 - 1.80 ms, profiles/r05_experiments.txt 8)
 #endif
-  if ((ts128 * 2 <= num_cus() && g_force_tile == 0) || g_force_tile == 5) {
+  if (ts128 * 2 <= num_cus()) {
     // the slabs staged ahead may reach into the NEXT tile but not beyond it: a K loop of ksteps slabs carries at most ksteps + 1 stages
     const int ksteps = p.K / Mma<T>::KPR;
     if (ksteps >= VTC_SMALL_NSTAGE - 1) return run<T, MODE, OutT, 2, 1, 2, 4, VTC_SMALL_NSTAGE>(p, stream);
@@ -1622,22 +1568,14 @@ int run_cfg(const GemmParams &p, hipStream_t stream) {
   return run<T, MODE, OutT, 2, 2, 4, 4, 2>(p, stream);
 }
 
-// sweep epilogue: 0 = phased 256 x 256 tiles (row blocks of 128), 1 = 128 x 128 tiles, two workgroups per CU (row blocks of 64)
-int l2min_row_block(int variant) { return variant == 0 ? 128 : 64; }
+// sweep epilogue: phased 256 x 256 tiles, row blocks of 128 (the 128 x 128 form with row blocks of 64 is in commit dda8438)
 int run_l2min(const GemmParams &p, hipStream_t stream) {
   // (round 5: a third form -- two 4-wave workgroups per CU on 128 x 256 tiles, K = 32 slabs, so that one's epilogue runs under the
   //  other's K loop -- was built, passes the sweep tests and measures 5.2 ms against 4.6 at 50k: tools/probes/gemm_l2min2.hip,
   //  profiles/r05_experiments.txt 3)
-  if (p.epi.mode == EPI_L2MIN2) {
-    if (p.epi.rb == 128) return run_phased<EPI_L2MIN2, float, bf16_t>(p, stream);
-    return run<bf16_t, EPI_L2MIN2, float, 2, 2, 4, 4, 2>(p, stream);
-  }
-  if (p.epi.mode == EPI_L2MIN3) {
-    if (p.epi.rb == 128) return run_phased<EPI_L2MIN3, float, bf16_t>(p, stream);
-    return run<bf16_t, EPI_L2MIN3, float, 2, 2, 4, 4, 2>(p, stream);
-  }
-  if (p.epi.rb == 128) return run_phased<EPI_L2MIN, float, bf16_t>(p, stream);
-  return run<bf16_t, EPI_L2MIN, float, 2, 2, 4, 4, 2>(p, stream);
+  if (p.epi.mode == EPI_L2MIN2) return run_phased<EPI_L2MIN2, float, bf16_t>(p, stream);
+  if (p.epi.mode == EPI_L2MIN3) return run_phased<EPI_L2MIN3, float, bf16_t>(p, stream);
+  return run_phased<EPI_L2MIN, float, bf16_t>(p, stream);
 }
 
 template <typename T>
@@ -1698,8 +1636,7 @@ int dispatch(GemmParams p, hipStream_t stream) {
 // Patch embedding without the im2row matrix: 16-bit pixels in the operand format, conv1's kernel = stride = 16 or 32 (a
 // K-tile of 64 is then whole pixel rows of one channel), 16-byte aligned pixel rows, 32-bit byte offsets.
 bool gemm_patch_gather_supported(int n_frames, int grid, int patch, int res, int pixel_dtype, int dtype) {
-  static const bool off = [] { const char *e = getenv("VTC_PATCH_IM2ROW"); return e && e[0] == '1'; }();
-  return !off && pixel_dtype == dtype && (dtype == VTC_BF16 || dtype == VTC_F16) && (patch == 16 || patch == 32) && res == grid * patch &&
+  return pixel_dtype == dtype && (dtype == VTC_BF16 || dtype == VTC_F16) && (patch == 16 || patch == 32) && res == grid * patch &&
          (size_t)n_frames * 3 * res * res * 2 < (1ull << 32);
 }
 
@@ -1744,32 +1681,12 @@ int launch_gemm(const void *A, const void *W, const float *bias, void *out, int 
                       : ((epi.mode == VTC_EPI_STORE || epi.mode == VTC_EPI_GELU) && epi.out_dtype != VTC_F32 && epi.fold_s != nullptr),
               "gemm: folded LayerNorm arguments do not go with epilogue %d", epi.mode);
   }
-  // diagnostics knobs, read once (C++11 static initialisation is thread-safe; never written afterwards)
-  struct Env { int tile = 0, sg = 0, st = 0, cg = -1, rsk = 0, deep = VTC_GEMM_DEEP_DEFAULT, super = 0, cus = 0; };
-  static const Env env = [] {
-    Env v;
-    if (const char *e = getenv("VTC_GEMM_TILE")) v.tile = atoi(e);
-    if (const char *e = getenv("VTC_GEMM_CG")) v.cg = atoi(e);
-    if (const char *e = getenv("VTC_GEMM_DEEP")) v.deep = atoi(e);
-    if (const char *e = getenv("VTC_GEMM_SUPER")) v.super = atoi(e);
-    if (const char *e = getenv("VTC_GEMM_RESID_SMALL_K")) v.rsk = atoi(e);
-    if (const char *e = getenv("VTC_GEMM_STAGGER")) sscanf(e, "%d,%d", &v.sg, &v.st);
-    if (const char *e = getenv("VTC_GEMM_CU_BUDGET")) v.cus = atoi(e);
-    return v;
-  }();
-  g_force_tile = env.tile;
-  g_resid_small_k = env.rsk;
-  g_deep = env.deep;
-  g_cu_budget = env.cus;
   GemmParams p;
   p.A = (const char *)A; p.W = (const char *)W; p.bias = bias; p.out = out;
   p.M = M; p.N = N; p.K = K;
   p.lda_bytes = K * esz; p.ldw_bytes = K * esz;
   p.ldo = epi.ldo > 0 ? epi.ldo : N;
   p.MT = 0; p.NT = 0;
-  p.col_group = env.cg >= 0 ? env.cg : 0;
-  p.super_tiles = env.super;
-  p.stagger_groups = env.sg; p.stagger_ticks = env.st;
   p.epi = epi;
   ProfScope prof(dtype != VTC_F32 ? VTC_PROF_GEMM_BF16 : VTC_PROF_GEMM_F32, epi.m_dev ? 2.0 * N * K : 2.0 * M * N * K, stream,
                  epi.m_dev);   // 16-bit operand class; device row count: work per row

@@ -1218,14 +1218,8 @@ static int exact_finish(const float *gallery, const float *queries, int ng, int 
 // that provably (given the per-entry error bound exact2_kappa, derived there) contains the query's true top-k (or says that it cannot), exact_rerank_kernel orders it by fp64 distances,
 // the uncertified queries are recomputed by fp64 brute force.
 namespace {
-int exact2_variant() {        // 0: 256 x 256 phased tiles (row blocks of 128); 1: 128 x 128 tiles, two workgroups per CU (row blocks of 64)
-  static const int v = [] { const char *e = getenv("VTC_SWEEP_MIN_TILE"); return e ? atoi(e) : 0; }();
-  return v;
-}
-bool exact2_enabled(int ng, int nq, int depth) {
-  static const bool off = [] { const char *e = getenv("VTC_SWEEP_EXACT_V1"); return e && e[0] == '1'; }();
-  return !off && depth <= 32 && ng >= 1024 && nq >= 1;
-}
+constexpr int RB2 = 128;      // queries per column block: the row block of the phased 256 x 256 tiles' waves
+bool exact2_enabled(int ng, int nq, int depth) { return depth <= 32 && ng >= 1024 && nq >= 1; }
 constexpr int CD2 = 64;       // capacity of a candidate list of the block-minima path
 // worst-case |approx - exact| of a key's distance, relative to |q|^2 + max|g|^2.  bf16 keeps 8 significant bits, so its unit
 // roundoff under round-to-nearest-even is u = 2^-8 (NOT 2^-9: rounds 1-2 had half this constant -- random embeddings sit far
@@ -1243,7 +1237,7 @@ struct Sweep2Ws {
   float *pmax;                       // sweep_prep_kernel's per-block maxima
   bf16_t *qb, *gb;
   unsigned *rowk, *colk;
-  int nblk_c, nblk_r, rb;
+  int nblk_c, nblk_r;
   int64_t *cand, *cand2;
   int *cand_n, *cand2_n;
   float *theta, *theta2;
@@ -1255,9 +1249,8 @@ Sweep2Ws plan2(char *ws, int ng, int nq, int d, bool bidir) {
   Sweep2Ws s;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
-  s.rb = exact2_variant() == 0 ? 128 : 64;
   s.nblk_c = cdiv(ng, 64);
-  s.nblk_r = cdiv(nq, s.rb);
+  s.nblk_r = cdiv(nq, RB2);
   s.qn = (float *)take((size_t)nq * 4);
   s.gn = (float *)take((size_t)ng * 4);
   s.gmax = (float *)take(256);
@@ -1303,12 +1296,8 @@ Sweep2Ws plan2(char *ws, int ng, int nq, int d, bool bidir) {
 // with two entries in reach of a target goes to fp64 whole, which for a target with r closer entries happens about r^2 / (2 x blocks) of the time:
 // rare at 50k (782 / 391 blocks).  At 10k (157 / 79 blocks) it is not, and the COLUMN direction -- blocks of 128 rows: twice as likely and twice
 // as dear as the rows' blocks of 64 -- made the finish kernel 93 us of a 0.3 ms sweep on low-recall data: there the columns keep two keys + bound
-// (EPI_L2MIN3: rows two planes, columns three; 7 per value).  max(k) > 16: three keys + bound in both.  VTC_SWEEP_PLANES=2|3|4 forces a form.
+// (EPI_L2MIN3: rows two planes, columns three; 7 per value).  max(k) > 16: three keys + bound in both.
 static int recall_mode(int kmax, int n_total) {
-  static const int force = [] { const char *e = getenv("VTC_SWEEP_PLANES"); return e ? atoi(e) : 0; }();
-  if (force == 2) return EPI_L2MIN2;
-  if (force == 3) return EPI_L2MIN3;
-  if (force == 4) return EPI_L2MIN;
   if (kmax > 16) return EPI_L2MIN;
   return n_total < 16384 ? EPI_L2MIN3 : EPI_L2MIN2;
 }
@@ -1690,7 +1679,7 @@ int exact2_impl(const float *a, const float *b, int na, int nb, int d, int depth
   VTC_LAUNCH_CHECK("l2_topk prologue");
   GemmEpi e;
   e.mode = EPI_L2MIN; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
-  e.rowk = s.rowk; e.colk = ids_a2b ? s.colk : nullptr; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r; e.rb = s.rb;
+  e.rowk = s.rowk; e.colk = ids_a2b ? s.colk : nullptr; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r;
   if (colk_out) {
     e.colk = colk_out; e.nblk_r = nblk_r_pad;
     // blocks this rank has no rows for (shards differ by a row): +inf keys
@@ -1712,7 +1701,7 @@ int exact2_impl(const float *a, const float *b, int na, int nb, int d, int depth
   }
   // both directions: ONE launch per stage (rounds 2-3: two) -- the stages of the two directions are independent, and at 10k x 10k
   // a direction alone leaves CUs idle (313 minsel workgroups, a re-rank wave per row)
-  const MinselArgs m2 = minsel_args(s.colk, na, s.nblk_r, s.rb, s.nblk_r, nullptr, depth, s.gn, s.gst, s.qmax, kappa, s.cand2, s.cand2_n, s.theta2);
+  const MinselArgs m2 = minsel_args(s.colk, na, s.nblk_r, RB2, s.nblk_r, nullptr, depth, s.gn, s.gst, s.qmax, kappa, s.cand2, s.cand2_n, s.theta2);
   {
     ProfScope prof(VTC_PROF_TOPK, (double)(L2MIN_PLANES + 1) * ((double)s.nblk_c * nb + (double)s.nblk_r * na) * 4, stream);
     launch_minsel(m1, &m2, stream);
@@ -1728,7 +1717,7 @@ int exact2_impl(const float *a, const float *b, int na, int nb, int d, int depth
   {
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     const RescanArgs q1{b, a, na, d, depth, s.flags, s.rowk, nb, s.nblk_c, 64, s.nblk_c, 1, nullptr, s.theta, ids_b2a, dists_b2a};
-    const RescanArgs q2{a, b, nb, d, depth, s.flags2, s.colk, na, s.nblk_r, s.rb, s.nblk_r, 1, nullptr, s.theta2, ids_a2b, dists_a2b};
+    const RescanArgs q2{a, b, nb, d, depth, s.flags2, s.colk, na, s.nblk_r, RB2, s.nblk_r, 1, nullptr, s.theta2, ids_a2b, dists_a2b};
     const int g1 = std::min(nb, 1024), g2 = std::min(na, 1024);
     hipLaunchKernelGGL(block_rescan_kernel, dim3(g1 + g2), dim3(256), 0, stream, q1, q2, g1);
   }
@@ -1752,14 +1741,14 @@ int recall_bidir_impl(const float *a, const float *b, int n, int d, const int *k
   const int mode = recall_mode(kmax, n);
   GemmEpi e;
   e.mode = mode; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
-  e.rowk = s.rowk; e.colk = s.colk; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r; e.rb = s.rb;
+  e.rowk = s.rowk; e.colk = s.colk; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r;
   if (int rc = launch_gemm(s.qb, s.gb, nullptr, nullptr, n, n, d, VTC_BF16, e, stream)) return rc;
   const float kappa = exact2_kappa(d);
   kmax = 0;
   static_assert(RK_WORK * sizeof(int) <= CD2 * sizeof(int64_t) && 3 + 2 * RK_UB + RK_AMB <= RK_WORK, "a deferred row's lists fit its candidate-list slot");
   const int nwg = cdiv(n, RK_OW);            // (4 ints per workgroup in the cand_n arrays: n / 8 <= n)
   RankArgs r1{s.rowk, n, s.nblk_c, 64, 1, nullptr, 0, b, a, n, d, s.qn, s.qst, s.gmax, kappa, 0, nk, {0, 0, 0, 0}, hits_b_from_a, s.flags, (int *)s.cand, s.cand_n, nwg};
-  RankArgs r2{s.colk, n, s.nblk_r, s.rb, 1, nullptr, 0, a, b, n, d, s.gn, s.gst, s.qmax, kappa, 0, nk, {0, 0, 0, 0}, hits_a_from_b, s.flags2, (int *)s.cand2, s.cand2_n, nwg};
+  RankArgs r2{s.colk, n, s.nblk_r, RB2, 1, nullptr, 0, a, b, n, d, s.gn, s.gst, s.qmax, kappa, 0, nk, {0, 0, 0, 0}, hits_a_from_b, s.flags2, (int *)s.cand2, s.cand2_n, nwg};
   for (int i = 0; i < nk; ++i) { r1.k[i] = r2.k[i] = k_vals[i]; kmax = std::max(kmax, k_vals[i]); }
   r1.kmax = r2.kmax = kmax;
   {
@@ -1780,7 +1769,7 @@ int recall_bidir_impl(const float *a, const float *b, int n, int d, const int *k
 }  // namespace
 
 // ---- sharded sweep: ONE [N/G, N] distance GEMM per rank for both directions (include/vtc_hip.h) ---------------------------
-extern "C" int vtc_l2_sweep_row_block(void) { return exact2_variant() == 0 ? 128 : 64; }
+extern "C" int vtc_l2_sweep_row_block(void) { return RB2; }
 
 extern "C" int vtc_l2_sweep_shard_supported(int n_total, int n_local, int depth) {
   return exact2_enabled(n_total, n_local, depth) && n_local >= 1 && depth <= n_total;
@@ -1817,7 +1806,6 @@ extern "C" int vtc_l2_sweep_shard_cols(const float *b_all, const float *a_local,
   VTC_CHECK(ws_bytes >= vtc_l2_sweep_shard_workspace_bytes(n_total, n_local, d), "l2_sweep_shard_cols: workspace too small");
   // gallery = b_all (n_total), queries = a_local (n_local): the plan's qn/gn/cand/flags/fallback areas fit as they are
   Sweep2Ws s = plan2((char *)ws, n_total, n_local, d, false);
-  const int rb = vtc_l2_sweep_row_block();
   {   // statistics only (the operands were rounded by the ranks that ran the GEMMs -- with this same rounding)
     ProfScope prof(VTC_PROF_TOPK, (double)(n_total + n_local) * d * 4, stream);
     const PrepSide A{a_local, nullptr, s.qn, s.qst, s.qmax, n_local}, B{b_all, nullptr, s.gn, s.gst, s.gmax, n_total};
@@ -1826,11 +1814,11 @@ extern "C" int vtc_l2_sweep_shard_cols(const float *b_all, const float *a_local,
   const float kappa = exact2_kappa(d);
   {
     ProfScope prof(VTC_PROF_TOPK, (double)(L2MIN_PLANES + 1) * n_src * nblk_pad * n_local * 4, stream);
-    const MinselArgs m = minsel_args(planes, n_local, n_src * nblk_pad, rb, nblk_pad, src_base, depth, s.qn, s.qst, s.gmax, kappa, s.cand, s.cand_n, s.theta);
+    const MinselArgs m = minsel_args(planes, n_local, n_src * nblk_pad, RB2, nblk_pad, src_base, depth, s.qn, s.qst, s.gmax, kappa, s.cand, s.cand_n, s.theta);
     launch_minsel(m, nullptr, stream);
   }
   VTC_LAUNCH_CHECK("minsel shard cols");
-  const Rescan rs{planes, n_local, n_src * nblk_pad, rb, nblk_pad, n_src, src_base, s.theta};
+  const Rescan rs{planes, n_local, n_src * nblk_pad, RB2, nblk_pad, n_src, src_base, s.theta};
   return exact_finish(b_all, a_local, n_total, n_local, d, depth, CD2, s.cand, nullptr, s.qn, s.gn, s.gmax, s.flags, ids, dists, stream,
                       s.cand_n, &s.fb, &rs);
 }
@@ -1892,7 +1880,7 @@ extern "C" int vtc_l2_recall_shard_rows(const float *a_all, const float *b_local
   const int mode = recall_mode(kmax, n_total), npl = l2min_col_planes(mode);
   GemmEpi e;
   e.mode = mode; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
-  e.rowk = s.rowk; e.colk = col_planes; e.nblk_c = s.nblk_c; e.nblk_r = nblk_pad; e.rb = s.rb;
+  e.rowk = s.rowk; e.colk = col_planes; e.nblk_c = s.nblk_c; e.nblk_r = nblk_pad;
   for (int pl = 0; pl < npl && nblk_pad > s.nblk_r; ++pl)     // blocks this rank has no rows for (shards differ by a row): +inf keys
     (void)hipMemsetD32Async((hipDeviceptr_t)(col_planes + ((size_t)pl * nblk_pad + s.nblk_r) * n_total), 0x7F800000,
                             (size_t)(nblk_pad - s.nblk_r) * n_total, stream);
@@ -1926,22 +1914,12 @@ extern "C" int vtc_l2_recall_shard_cols(const float *b_all, const float *a_local
   int kmax_ = 0;
   for (int i = 0; i < nk; ++i) kmax_ = std::max(kmax_, k_vals[i]);
   const int npl = l2min_col_planes(recall_mode(kmax_, n_total));
-  RankArgs r{planes, n_local, nblk_pad, vtc_l2_sweep_row_block(), n_src, src_bounds, row_base, a_local, b_all, n_total, d, s.qn, s.qst, s.gmax,
+  RankArgs r{planes, n_local, nblk_pad, RB2, n_src, src_bounds, row_base, a_local, b_all, n_total, d, s.qn, s.qst, s.gmax,
              exact2_kappa(d), 0, nk, {0, 0, 0, 0}, (unsigned long long *)hits_a_from_b, s.flags, (int *)s.cand, s.cand_n, cdiv(n_local, RK_OW)};
   fill_k(r, k_vals, nk);
   launch_rank_one(r, npl, stream);
   VTC_LAUNCH_CHECK("l2_recall_shard_cols");
   return 0;
-}
-
-// diagnostics (tests/probes/sweep_v2_debug.py; not part of the public header): the raw block-minima planes of one distance GEMM.
-// qb [nb, d], gb [na, d] bf16; qn, gn fp32 squared norms; rowk [4, ceil(na / 64), nb], colk [4, ceil(nb / rb), na] (or NULL)
-extern "C" int vtc_debug_l2min(const void *qb, const void *gb, const float *qn, const float *gn, int nb, int na, int d, int rb,
-                               unsigned *rowk, unsigned *colk, void *stream) {
-  GemmEpi e;
-  e.mode = EPI_L2MIN; e.out_dtype = VTC_F32; e.rown = qn; e.coln = gn;
-  e.rowk = rowk; e.colk = colk; e.nblk_c = cdiv(na, 64); e.nblk_r = cdiv(nb, rb); e.rb = rb;
-  return launch_gemm(qb, gb, nullptr, nullptr, nb, na, d, VTC_BF16, e, (hipStream_t)stream);
 }
 
 extern "C" size_t vtc_l2_topk_workspace_bytes(int n_gallery, int n_queries, int d, int precision, int rows_per_block) {
@@ -2040,14 +2018,6 @@ static int exact_finish(const float *gallery, const float *queries, int ng, int 
   hipLaunchKernelGGL(exact_fallback_kernel, dim3(std::min(nq, 2048)), dim3(256), 0, stream, queries, gallery, ng, d, depth, flags, ids,
                      dists, f_first);
   VTC_LAUNCH_CHECK("l2_topk exact");
-  static const bool dbg = [] { const char *e = getenv("VTC_SWEEP_DEBUG"); return e && e[0] == '1'; }();
-  if (dbg) {   // diagnostics only: synchronises
-    int n_flagged = -1;
-    (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(&n_flagged, flags, sizeof(int), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[sweep] exact_finish nq=%d ng=%d cdepth=%d %s: %d rows not certified -> fp64 brute force\n", nq, ng, cdepth,
-            cand_n ? "block-minima" : "split-bf16", n_flagged);
-  }
   return 0;
 }
 
