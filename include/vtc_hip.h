@@ -188,6 +188,23 @@ int vtc_cam_forward(const vtc_cam_w *w, const float *main_feats, const float *co
  * it speaks for a given forward once the forward's stream has been synchronised). */
 int vtc_cam_fused_gave_up(int device);
 
+/* The CAM with na extra tokens per item after the comments (the audio branch, model/model.py:220-230): item b's sequence is
+ * [main[b], comment tokens as in vtc_cam_forward, aux[b*na + 0 .. b*na + na - 1]]; aux rows are normalised like the others and never
+ * replaced by mask_embedding.  aux: [B*na, D] fp32 (NULL when na = 0).  1 + nc + na <= 80; the one-launch path takes
+ * 1 + nc + na <= 15.  With na = 0 the result is bit-identical to vtc_cam_forward.  Workspace: vtc_cam_aux_workspace_bytes. */
+size_t vtc_cam_aux_workspace_bytes(const vtc_cam_w *w, int B, int nc, int na, int dtype);
+int vtc_cam_forward_aux(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments,
+                        const float *aux, int ctx, int B, int nc, int na, float *adapted, void *ws, size_t ws_bytes, int dtype,
+                        void *stream);
+
+/* The audio branch's feature MLP (model/model.py:80-94, eval mode), fp32, one launch (audio.hip):
+ *   y = w2 relu(w1 x + b1) + b2,  x, y: [n, d] fp32, d = 512; w1, w2: [d, d] row-major ([out, in], as nn.Linear.weight), b1, b2: [d].
+ * w1 / b1 carry the BatchNorm1d running statistics folded in by the caller.  ws: vtc_feature_mlp_workspace_bytes(n, d) bytes
+ * (may be 0, then ws may be NULL). */
+size_t vtc_feature_mlp_workspace_bytes(int n, int d);
+int vtc_feature_mlp(const float *x, int n, int d, const float *w1, const float *b1, const float *w2, const float *b2, float *y,
+                    void *ws, size_t ws_bytes, void *stream);
+
 /* ---- small fp32 ops of the wrappers (model/model.py:26-27, 338, 357-362, 369) -------- */
 int vtc_normalize_rows(const float *x, float *out, int n, int d, void *stream);
 /* Both embedding sets of a forward in one launch: outx = rows of x [nx, d] / their norms, outy likewise for y [ny, d] (the two

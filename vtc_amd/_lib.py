@@ -73,6 +73,11 @@ SIGNATURES = {
     "vtc_cam_workspace_bytes": (C.c_size_t, [C.POINTER(CamW), C.c_int, C.c_int, C.c_int]),
     "vtc_cam_forward": (C.c_int, [C.POINTER(CamW), fp, fp, ip, C.c_int, C.c_int, C.c_int, fp, vp, C.c_size_t, C.c_int, vp]),
     "vtc_cam_fused_gave_up": (C.c_int, [C.c_int]),
+    "vtc_cam_aux_workspace_bytes": (C.c_size_t, [C.POINTER(CamW), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtc_cam_forward_aux": (C.c_int, [C.POINTER(CamW), fp, fp, ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, vp, C.c_size_t, C.c_int,
+                                      vp]),
+    "vtc_feature_mlp_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "vtc_feature_mlp": (C.c_int, [fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]),
     "vtc_normalize_rows": (C.c_int, [fp, fp, C.c_int, C.c_int, vp]),
     "vtc_normalize_rows2": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, vp, vp]),
     "vtc_mean_groups": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, vp]),

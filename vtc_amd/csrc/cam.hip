@@ -16,7 +16,7 @@
 // tile (v_mfma_f32_16x16x4_f32: exact fp32; the k order inside a 16-float chunk is permuted identically for both operands), so
 // a layer's weights are read ONCE, 49 KB per CU.  Phases of a layer, each closed by a grid barrier:
 //     P1  ln_1 (fp32 LayerNorm of the streamed row tile) + in_proj + bias                        -> qkv   [rows, 3 D]
-//         (layer 0 builds the normalised tokens from main / comments / mask_embedding on the way and stores x)
+//         (layer 0 builds the normalised tokens from main / comments / mask_embedding / aux on the way and stores x)
 //     P2  softmax(q k^T / 8) v per (item, head): one wave each, lane = head dimension              -> att   [rows, D]
 //     P3  out_proj + bias + residual                                                               -> x
 //     P4  ln_2 + c_fc + bias + QuickGELU                                                           -> hid   [rows, 4 D]
@@ -39,8 +39,9 @@ constexpr size_t CAM_BAR_BYTES = 32 * 17 * 4;       // grid_barrier: top + error
 
 struct CamFusedParams {
   const float *main_f, *comm, *mask_emb;
+  const float *aux;           // [B * na, D] extra tokens after the comments (audio clips), never masked; NULL when na = 0
   const int64_t *comments;
-  int B, nc, ctx, Lc, rows, ntiles, layers, heads;
+  int B, nc, na, ctx, Lc, rows, ntiles, layers, heads;
   // folded LayerNorms (vtc_block_w qkv_wf / qkv_s / qkv_c, fc_wf / fc_s / fc_c, fp32) + the two plain projections
   const float *qkv_wf[CAM_MAX_LAYERS], *qkv_s[CAM_MAX_LAYERS], *qkv_c[CAM_MAX_LAYERS], *out_w[CAM_MAX_LAYERS], *out_b[CAM_MAX_LAYERS];
   const float *fc_wf[CAM_MAX_LAYERS], *fc_s[CAM_MAX_LAYERS], *fc_c[CAM_MAX_LAYERS], *proj_w[CAM_MAX_LAYERS], *proj_b[CAM_MAX_LAYERS];
@@ -184,13 +185,14 @@ __device__ __forceinline__ void proj_phase(float *wlds, const CamFusedParams &p,
       const float *src = nullptr;
       [[maybe_unused]] const int soff = (r * D + 4 * g) * 4;      // byte offset of the lane's first chunk in a [rows, D] buffer
       if constexpr (TOK) {
-        // X[b Lc + 0] = normalize(main[b]);  X[b Lc + 1 + c] = normalize(empty(b, c) ? mask_embedding : comm[b nc + c])
+        // X[b Lc + 0] = normalize(main[b]);  X[b Lc + 1 + c] = normalize(empty(b, c) ? mask_embedding : comm[b nc + c]);
+        // X[b Lc + 1 + nc + a] = normalize(aux[b na + a])
         const int b = r / p.Lc, tk = r - b * p.Lc;
         if (tk == 0) src = p.main_f + (size_t)b * D;
-        else {
+        else if (tk <= p.nc) {
           const int ci = b * p.nc + (tk - 1);
           src = p.comments[(size_t)ci * p.ctx + 1] == 49407 ? p.mask_emb : p.comm + (size_t)ci * D;      // model/model.py:208
-        }
+        } else src = p.aux + ((size_t)b * p.na + (tk - 1 - p.nc)) * D;
         src += 4 * g;
       }
       auto piece = [&](int pc, int c) -> float4 {
@@ -481,8 +483,8 @@ namespace vtcgemm { int num_cus(); }
 // (measured crossover).  A model opts out with VTC_CAM_NO_FUSED.
 constexpr int CAM_FUSED_MAX_ROWS = 512;
 
-bool cam_fused_supported(const vtc_cam_w *w, int B, int nc, int dtype) {
-  const int Lc = 1 + nc;
+bool cam_fused_supported(const vtc_cam_w *w, int B, int nc, int na, int dtype) {
+  const int Lc = 1 + nc + na;
   for (int l = 0; l < w->layers && l < CAM_MAX_LAYERS; ++l)      // the folded-LayerNorm weights (fp32) must have been packed
     if (!w->blocks[l].qkv_wf || !w->blocks[l].qkv_s || !w->blocks[l].qkv_c || !w->blocks[l].fc_wf || !w->blocks[l].fc_s || !w->blocks[l].fc_c) return false;
   return dtype == VTC_F32 && w->init_from_avg && !(w->flags & VTC_CAM_NO_FUSED) && (w->width == 512 || w->width == 128) &&
@@ -518,8 +520,8 @@ static void cam_fused_mark_locked(int dev, hipStream_t stream) {
 // Returns 0 on success, 1 on error, -1 when another stream's one-launch CAM may still be running on this device (nothing was
 // enqueued: the caller takes the multi-launch path).
 size_t cam_fused_bar_bytes() { return CAM_BAR_BYTES; }
-int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments, int ctx, int B, int nc,
-                     float *adapted, float *x, float *big, float *att, int *bar, hipStream_t stream) {
+int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments, const float *aux, int ctx,
+                     int B, int nc, int na, float *adapted, float *x, float *big, float *att, int *bar, hipStream_t stream) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
   std::lock_guard<std::mutex> lk(g_cam_mu);
@@ -559,7 +561,8 @@ int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *c
     p.err_host = (int *)dptr;
   }
   p.main_f = main_feats; p.comm = comm_feats; p.mask_emb = w->mask_embedding; p.comments = comments;
-  p.B = B; p.nc = nc; p.ctx = ctx; p.Lc = 1 + nc; p.rows = B * (1 + nc); p.ntiles = cdiv(p.rows, 16); p.layers = w->layers; p.heads = w->heads;
+  p.aux = aux; p.na = na;
+  p.B = B; p.nc = nc; p.ctx = ctx; p.Lc = 1 + nc + na; p.rows = B * p.Lc; p.ntiles = cdiv(p.rows, 16); p.layers = w->layers; p.heads = w->heads;
   for (int l = 0; l < w->layers; ++l) {
     const vtc_block_w &b = w->blocks[l];
     p.qkv_wf[l] = (const float *)b.qkv_wf; p.qkv_s[l] = b.qkv_s; p.qkv_c[l] = b.qkv_c;

@@ -238,22 +238,24 @@ __global__ __launch_bounds__(1024) void scan_offsets_kernel(const int *__restric
   }
 }
 
-// X[b*Lc + 0] = normalize(main[b]);  X[b*Lc + 1 + c] = normalize(empty(b,c) ? mask : comm[b*nc + c])
+// X[b*Lc + 0] = normalize(main[b]);  X[b*Lc + 1 + c] = normalize(empty(b,c) ? mask : comm[b*nc + c]);
+// X[b*Lc + 1 + nc + a] = normalize(aux[b*na + a])  (audio clips after the comments: never masked, model/model.py:220-230)
 __global__ __launch_bounds__(256) void cam_tokens_kernel(const float *__restrict__ main_f, const float *__restrict__ comm,
                                                          const int64_t *__restrict__ comments, const float *__restrict__ mask_emb,
-                                                         float *__restrict__ X, int B, int nc, int ctx, int D) {
+                                                         const float *__restrict__ aux, float *__restrict__ X, int B, int nc, int na,
+                                                         int ctx, int D) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int Lc = 1 + nc;
+  const int Lc = 1 + nc + na;
   if (r >= B * Lc) return;
   const int b = r / Lc, t = r - b * Lc;
   const float *src;
   if (t == 0) src = main_f + (size_t)b * D;
-  else {
+  else if (t <= nc) {
     const int ci = b * nc + (t - 1);
     const bool empty = comments[(size_t)ci * ctx + 1] == 49407;   // model/model.py:208
     src = empty ? mask_emb : comm + (size_t)ci * D;
-  }
+  } else src = aux + ((size_t)b * na + (t - 1 - nc)) * D;
   float s = 0.f;
   for (int c = lane; c < D; c += 64) s += src[c] * src[c];
   const float nrm = sqrtf(wave_sum(s));
@@ -513,10 +515,10 @@ int launch_text_embed_ragged(const TextIds &ids, const float *tok, const float *
   return 0;
 }
 
-int launch_cam_tokens(const float *main_f, const float *comm, const int64_t *comments, const float *mask_emb, float *X, int B,
-                      int nc, int ctx, int D, hipStream_t stream) {
-  hipLaunchKernelGGL(cam_tokens_kernel, dim3(cdiv(B * (1 + nc), 4)), dim3(256), 0, stream, main_f, comm, comments, mask_emb, X, B,
-                     nc, ctx, D);
+int launch_cam_tokens(const float *main_f, const float *comm, const int64_t *comments, const float *mask_emb, const float *aux,
+                      float *X, int B, int nc, int na, int ctx, int D, hipStream_t stream) {
+  hipLaunchKernelGGL(cam_tokens_kernel, dim3(cdiv(B * (1 + nc + na), 4)), dim3(256), 0, stream, main_f, comm, comments, mask_emb, aux,
+                     X, B, nc, na, ctx, D);
   VTC_LAUNCH_CHECK("cam_tokens");
   return 0;
 }

@@ -43,14 +43,14 @@ int launch_text_embed(const TextIds &ids, const float *tok, const float *pos, fl
 int launch_text_embed_ragged(const TextIds &ids, const float *tok, const float *pos, const int *seq_offsets, float *x, int *eot_row, int n_seq, int ctx, int W, int vocab, hipStream_t stream);
 int launch_attention_ragged(const void *qkv, void *out, int n_seq, int max_L, int heads, int causal, const int *seq_offsets, double flops, const int *rows_dev, int dtype, hipStream_t stream);
 int launch_attention_generic_small(const void *qkv, void *out, int n_seq, int L, int heads, int hd, int dtype, hipStream_t stream);
-int launch_cam_tokens(const float *main_f, const float *comm, const int64_t *comments, const float *mask_emb, float *X, int B, int nc, int ctx, int D, hipStream_t stream);
+int launch_cam_tokens(const float *main_f, const float *comm, const int64_t *comments, const float *mask_emb, const float *aux, float *X, int B, int nc, int na, int ctx, int D, hipStream_t stream);
 int launch_cls_global_attention(const void *qkv, void *out, int n_items, int Ttok, int heads, int dtype, hipStream_t stream);
 int launch_cam_finalize(const float *Y, const float *lin, const float *main_f, float *out, int B, int Lc, int D, int init_from_avg, int act, float scale, const float *bn_mean, const float *bn_var, hipStream_t stream);
 
-bool cam_fused_supported(const vtc_cam_w *w, int B, int nc, int dtype);
+bool cam_fused_supported(const vtc_cam_w *w, int B, int nc, int na, int dtype);
 size_t cam_fused_bar_bytes();
-int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments, int ctx, int B, int nc,
-                     float *adapted, float *x, float *big, float *att, int *bar, hipStream_t stream);
+int launch_cam_fused(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments, const float *aux, int ctx,
+                     int B, int nc, int na, float *adapted, float *x, float *big, float *att, int *bar, hipStream_t stream);
 namespace {
 
 // (Rounds 1-4 carried a fused QKV projection + attention-core kernel behind per-model flags; it measured slower than GEMM + core in
@@ -598,31 +598,37 @@ extern "C" int vtc_text_forward_ragged(const vtc_text_w *w, const int64_t *ids, 
 }
 
 // ------------------------------------------------------------------------------------------
-extern "C" size_t vtc_cam_workspace_bytes(const vtc_cam_w *w, int B, int nc, int dtype) {
-  TextWs t = plan_text(B * (1 + nc), B, w->width, dtype, nullptr);
+// The module over B items of Lc = 1 + nc + na tokens: [main, nc comments (empty -> mask_embedding), na aux rows (never masked)].
+static size_t cam_ws_bytes(const vtc_cam_w *w, int B, int Lc, int dtype) {
+  TextWs t = plan_text(B * Lc, B, w->width, dtype, nullptr);
   return t.total + align_up((size_t)B * w->width * 4, 256) + align_up(cam_fused_bar_bytes(), 256);
 }
 
-extern "C" int vtc_cam_forward(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments,
-                               int ctx, int B, int nc, float *adapted, void *ws, size_t ws_bytes, int dtype, void *stream_) {
-  hipStream_t s = (hipStream_t)stream_;
-  VTC_CHECK(w && main_feats && comm_feats && comments && adapted && ws, "cam_forward: null argument");
+extern "C" size_t vtc_cam_workspace_bytes(const vtc_cam_w *w, int B, int nc, int dtype) { return cam_ws_bytes(w, B, 1 + nc, dtype); }
+
+extern "C" size_t vtc_cam_aux_workspace_bytes(const vtc_cam_w *w, int B, int nc, int na, int dtype) {
+  return cam_ws_bytes(w, B, 1 + nc + na, dtype);
+}
+
+static int cam_forward_impl(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments, const float *aux,
+                            int ctx, int B, int nc, int na, float *adapted, void *ws, size_t ws_bytes, int dtype, hipStream_t s) {
+  VTC_CHECK(w && main_feats && comm_feats && comments && adapted && ws && (aux || na == 0), "cam_forward: null argument");
   VTC_CHECK(dtype == VTC_F32 || dtype == VTC_BF16, "cam_forward: bad dtype %d", dtype);
-  VTC_CHECK(B > 0 && nc >= 0 && 1 + nc <= 80, "cam_forward: B=%d nc=%d", B, nc);
-  VTC_CHECK(w->heads >= 1 && w->width % w->heads == 0 && (w->width == w->heads * 64 || (w->width / w->heads <= 128 && 1 + nc <= 16)),
+  VTC_CHECK(B > 0 && nc >= 0 && na >= 0 && 1 + nc + na <= 80, "cam_forward: B=%d nc=%d na=%d", B, nc, na);
+  const int D = w->width, Lc = 1 + nc + na, rows = B * Lc;
+  VTC_CHECK(w->heads >= 1 && w->width % w->heads == 0 && (w->width == w->heads * 64 || (w->width / w->heads <= 128 && Lc <= 16)),
             "cam_forward: head_dim %d / %d: 64, or <= 128 with at most 16 tokens per item", w->width, w->heads);
-  const int D = w->width, Lc = 1 + nc, rows = B * Lc;
   TextWs t = plan_text(rows, B, D, dtype, ws);
   float *lin = (float *)((char *)ws + t.total);
-  VTC_CHECK(ws_bytes >= vtc_cam_workspace_bytes(w, B, nc, dtype), "cam_forward: workspace too small");
+  VTC_CHECK(ws_bytes >= cam_ws_bytes(w, B, Lc, dtype), "cam_forward: workspace too small");
   // small batches: the whole module as one cooperative launch (cam.hip)
-  if (cam_fused_supported(w, B, nc, dtype)) {
-    const int rc = launch_cam_fused(w, main_feats, comm_feats, comments, ctx, B, nc, adapted, t.x, (float *)t.big, (float *)t.h,
+  if (cam_fused_supported(w, B, nc, na, dtype)) {
+    const int rc = launch_cam_fused(w, main_feats, comm_feats, comments, aux, ctx, B, nc, na, adapted, t.x, (float *)t.big, (float *)t.h,
                                     (int *)((char *)ws + t.total + align_up((size_t)B * w->width * 4, 256)), s);
     if (rc >= 0) return rc;      // -1: another stream's cooperative launch may still be running: the multi-launch path below
   }
-  RUN(launch_cam_tokens(main_feats, comm_feats, comments, w->mask_embedding, t.x, B, nc, ctx, D, s));
-  Fold nofold;      // B (1 + nc) tokens: the LayerNorm kernels
+  RUN(launch_cam_tokens(main_feats, comm_feats, comments, w->mask_embedding, aux, t.x, B, nc, na, ctx, D, s));
+  Fold nofold;      // B (1 + nc + na) tokens: the LayerNorm kernels
   for (int l = 0; l < w->layers; ++l) {
     const vtc_block_w &b = w->blocks[l];
     RUN(attn_part_contig(nofold, b, t.x, t.h, t.big, B, Lc, D, w->heads, 0, dtype, 0, s));
@@ -634,4 +640,15 @@ extern "C" int vtc_cam_forward(const vtc_cam_w *w, const float *main_feats, cons
   }
   RUN(launch_cam_finalize(t.x, lin, main_feats, adapted, B, Lc, D, w->init_from_avg, w->residual_activation, w->squash_scale, w->bn_mean, w->bn_var, s));
   return 0;
+}
+
+extern "C" int vtc_cam_forward(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments,
+                               int ctx, int B, int nc, float *adapted, void *ws, size_t ws_bytes, int dtype, void *stream_) {
+  return cam_forward_impl(w, main_feats, comm_feats, comments, nullptr, ctx, B, nc, 0, adapted, ws, ws_bytes, dtype, (hipStream_t)stream_);
+}
+
+extern "C" int vtc_cam_forward_aux(const vtc_cam_w *w, const float *main_feats, const float *comm_feats, const int64_t *comments,
+                                   const float *aux, int ctx, int B, int nc, int na, float *adapted, void *ws, size_t ws_bytes, int dtype,
+                                   void *stream_) {
+  return cam_forward_impl(w, main_feats, comm_feats, comments, aux, ctx, B, nc, na, adapted, ws, ws_bytes, dtype, (hipStream_t)stream_);
 }

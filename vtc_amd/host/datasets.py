@@ -133,13 +133,47 @@ class ImTextDataset(_ReferenceNamedDataset):
     def __init__(self, csv_file, root="", train=True, test=False, add_comments="train_only", num_comms=0,
                  comment_sampling="random", cached_vision_features=None, test_on_over_k_comms=None, test_set_limit=None,
                  use_augmentation=False, cached_audio_features=None, audio_with_comms=None, audio_instead_of_title=False,
-                 n_pairs=None, seed=123, resolution=224, context=77):
-        if cached_audio_features is not None or audio_with_comms or audio_instead_of_title:
-            raise NotImplementedError("ImTextDataset: the audio branch (needs the external GDT repository) is out of scope")
+                 n_pairs=None, seed=123, resolution=224, context=77, n_audio_clips=5):
+        if audio_instead_of_title:
+            raise NotImplementedError("ImTextDataset: audio_instead_of_title yields (im, audio_clips) items (dataset_loaders.py:1036-1037), "
+                                      "which no model of the reference takes: forward(vis, title, comments) has no audio-only input")
+        if cached_audio_features and not audio_with_comms:
+            raise NotImplementedError("ImTextDataset: cached_audio_features without audio_with_comms yields (im, title, audio_clips) items "
+                                      "(dataset_loaders.py:1040-1041), which the model would read as comment token ids: only "
+                                      "audio_with_comms=True reaches the audio branch (model/model.py:220-230)")
         if cached_vision_features is not None:
             raise NotImplementedError("ImTextDataset: cached features are produced/consumed by vtc_amd.host.cache_features")
         self.root, self.comment_sampling = root, (comment_sampling if train else None)
         self._setup(csv_file, train, test, add_comments, num_comms, n_pairs, seed, resolution, context)
+        self.audio_with_comms = bool(audio_with_comms)
+        self.audio_feats = None
+        if self.audio_with_comms:
+            if cached_audio_features:
+                self.audio_feats = load_audio_features(cached_audio_features, range(self.n))
+            else:
+                # DEVIATION: the reference yields no audio for an empty path (`if self.cached_audio_features:`, dataset_loaders.py:1033);
+                # with synthetic pairs the clips are synthetic too -- seeded, n_audio_clips per item (the shipped config's 5)
+                g = torch.Generator().manual_seed(self.seed + 7919)
+                self.audio_feats = torch.randn(self.n, int(n_audio_clips), 512, generator=g)
+
+    def __getitem__(self, i):
+        vis, title, comments, meta = super().__getitem__(i)
+        if self.audio_feats is None:
+            return vis, title, comments, meta
+        return vis, title, (comments, self.audio_feats[i]), meta            # dataset_loaders.py:1038-1039
+
+
+def load_audio_features(path, ids):
+    """dataset_loaders.py:162-184 (``load_features``, the array form): ``{"reddit_ids": int64 [N], "embeddings": fp32 [N, n_clips, 512]}``
+    -> the rows of ``ids`` (the items' ids), in that order."""
+    stored = torch.load(path, map_location="cpu")
+    assert stored["reddit_ids"].dtype is torch.int64
+    assert stored["embeddings"].dtype is torch.float32
+    lookup = {int(el): i for i, el in enumerate(stored["reddit_ids"])}
+    missing = [int(i) for i in ids if int(i) not in lookup]
+    if missing:
+        raise KeyError(f"{path}: no audio features for ids {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+    return stored["embeddings"][[lookup[int(i)] for i in ids]]
 
 
 class VideoDatasetSegments(_ReferenceNamedDataset):

@@ -113,8 +113,12 @@ def main(config: ConfigParser, args, checkpoint_path=None, device="cuda"):
             if num_irrelevant_comments:
                 assert num_irrelevant_comments <= config["batch_size"], \
                     "Number of irrelevant comments needs to be smaller than batch size."        # eval.py:105-107
-                comments = add_irrelevant_comms(comments, num_irrelevant_comments)
-            out = model.forward(vis.to(device), title.to(device), comments.to(device))
+                comments = (add_irrelevant_comms(comments, num_irrelevant_comments) if torch.is_tensor(comments) else
+                            [add_irrelevant_comms(comments[0], num_irrelevant_comments), *comments[1:]])
+            # an audio-branch item collates to [comments, audio_clips] (default_collate turns the item's tuple into a list): moved
+            # element by element (the reference's comments.to(device), evaluation/eval.py:112, fails on it)
+            comments = comments.to(device) if torch.is_tensor(comments) else [c.to(device) for c in comments]
+            out = model.forward(vis.to(device), title.to(device), comments)
             res_vis.append(out[0])
             res_text.append(out[1])
     res_vis, res_text = torch.cat(res_vis), torch.cat(res_text)

@@ -14,7 +14,8 @@ The forward pass is forward/eval only and runs entirely in libvtc_hip.so: inputs
 a ROCm GPU and the module in ``eval()`` mode, anything else raises (there is deliberately no
 CPU or PyTorch fallback -- the CPU restatement lives in ``oracle/`` and is test-only).
 Out of scope (raise): training-mode branches (random comment masking / skip adapter),
-the audio branch, feature-MLP baselines.
+feature-MLP baselines.  The audio branch (``PretrainedCLIP_finaltf(init_audio_model=True)``) runs on pre-extracted clip
+features: its ``audio_model.mlp`` is a HIP kernel, GDT's raw-audio network (``audio_model.base``) is a state-dict sink only.
 """
 from __future__ import annotations
 
@@ -153,6 +154,8 @@ class PretrainedCLIPBase(nn.Module):
                 # the CAM sees B*(1+nc) tokens of width 512 -- negligible work -- so it always runs in fp32
                 p["cam"] = towers.PackedCam(sd, torch.float32, self.final_transformer.heads, self.init_from_avg,
                                             self.residual_activation)
+            if getattr(self, "init_audio_model", False):
+                p["audio"] = towers.PackedAudioMlp(sd, "audio_model.mlp.layers.")      # fp32 too: it feeds the CAM
             self._packed = p
         return self._packed
 
@@ -276,12 +279,14 @@ class PretrainedCLIPBase(nn.Module):
             return ops.mean_groups(f, shp[1])
         raise ValueError(f"unsupported visual input shape {tuple(shp)}")
 
-    def _forward_with_cam(self, vis, title, comments):
+    def _forward_with_cam(self, vis, title, comments, audio=None):
         """forward() of the two *_finaltf wrappers up to the normalised pair: model/model.py:458-478 / :596-621 = towers (:464-472) +
         _encode_with_comments (:216-266, eval path).  Same arithmetic as _encode_all + _encode_with_comments below; what differs is the
         ORDER OF ENQUEUEING: with the text branch adapted, the CAM needs the title and comment features only, so it is enqueued behind
         the text tower on the caller's stream while the visual tower still runs on the side stream (multi-launch form: see
-        PackedCam.forward) -- at small batch the CAM's ~0.2 ms left the critical path."""
+        PackedCam.forward) -- at small batch the CAM's ~0.2 ms left the critical path.
+        audio [B, na, 512] fp32 (audio branch, model/model.py:220-230): the clips go through the audio MLP and join the CAM as na
+        never-masked tokens after the comments; the MLP is enqueued right before the CAM, on the CAM's stream."""
         branch = self.branch_to_adapt_val
         if branch not in ("text", "image", "skip"):
             raise Exception("Unknown branch_to_adapt")
@@ -290,13 +295,14 @@ class PretrainedCLIPBase(nn.Module):
         else:
             b, ncomms, ntoks = comments.shape
             ids_c = comments.reshape(b * ncomms, ntoks)
+            aux = (lambda: None) if audio is None else (lambda: self._packed["audio"].forward(audio.reshape(-1, audio.shape[-1])))
             if branch == "text":
                 def tail(ft_all, overlapped):
-                    return self._packed["cam"].forward(ft_all[:b], ft_all[b:], comments, fused=False if overlapped else None)
+                    return self._packed["cam"].forward(ft_all[:b], ft_all[b:], comments, fused=False if overlapped else None, aux=aux())
                 fv, ft = self._encode_both(vis, title, ids_c, text_tail=tail)
             else:
                 fv, ft_all = self._encode_both(vis, title, ids_c)
-                fv, ft = self._packed["cam"].forward(fv, ft_all[b:], comments), ft_all[:b]
+                fv, ft = self._packed["cam"].forward(fv, ft_all[b:], comments, aux=aux()), ft_all[:b]
         return self._finish(fv, ft)
 
     def _encode_all(self, vis, title, comments):
@@ -404,27 +410,96 @@ class PretrainedCLIP(PretrainedCLIPBase):
         return feats_vis, feats_text, self._sim(feats_vis, feats_text)
 
 
+class _StateSink(nn.Module):
+    """`audio_model.base` of the audio branch: GDT's resnet9 (model/model.py:419), which the eval forward never calls (clip features
+    arrive pre-extracted).  Accepts ANY tensors under its prefix in load_state_dict (strict included), keeps them as buffers -- they
+    follow .to() -- and returns them under the same keys from state_dict(), so checkpoints round-trip."""
+    _SEP = ":"            # buffer names cannot hold ".": "layer1.0.conv.weight" is kept as "layer1:0:conv:weight"
+
+    def load_tensors(self, tensors):
+        for k, v in tensors.items():
+            name = k.replace(".", self._SEP)
+            if name in self._buffers and self._buffers[name] is not None and self._buffers[name].shape == v.shape:
+                with torch.no_grad():
+                    self._buffers[name].copy_(v)
+            else:
+                self._buffers.pop(name, None)
+                self.register_buffer(name, v.detach().clone())
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        self.load_tensors({k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)})
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        for name, v in self._buffers.items():
+            if v is not None:
+                destination[prefix + name.replace(self._SEP, ".")] = v if keep_vars else v.detach()
+
+
+class AudioMLP(nn.Module):
+    """model/model.py:80-94, the reference's parameter names (``layers.{1,2,4}``)."""
+
+    def __init__(self, num_classes=512, num_features=512, p=0.2):
+        super().__init__()
+        self.layers = nn.Sequential(nn.Dropout(p), nn.Linear(num_features, num_features), nn.BatchNorm1d(num_features), nn.ReLU(),
+                                    nn.Linear(num_features, num_classes))
+
+
+class AudioModel(nn.Module):
+    """``audio_model`` of model/model.py:419-438 without GDT: ``base`` (state-dict sink), ``fc`` (Identity), ``mlp``."""
+
+    def __init__(self):
+        super().__init__()
+        self.base = _StateSink()
+        self.fc = nn.Identity()
+        self.mlp = AudioMLP()
+
+
 class PretrainedCLIP_finaltf(PretrainedCLIPBase):
     def __init__(self, model_type="ViT-B/32", freeze=False, branch_to_adapt="text", branch_to_adapt_val="text",
                  residual_activation=None, n_layers=2, n_heads=8, init_from_avg=True, random_comment_masking=False,
                  random_skip_adapter=True, init_audio_model=False, audio_model_ckpt=None, clip_audio_ckpt=None):
         super().__init__()
-        if init_audio_model:
-            raise NotImplementedError("the audio branch (model/model.py:409-438) needs the external GDT repository: out of scope")
         self.model = clip_arch.load(model_type, device="cpu")
         self.feature_dim = self.model.ln_final.normalized_shape[0]
         self.branch_to_adapt, self.branch_to_adapt_val = branch_to_adapt, branch_to_adapt_val
         self.residual_activation = residual_activation
         self.init_from_avg = init_from_avg
         self.random_comment_masking, self.random_skip_adapter = random_comment_masking, random_skip_adapter
-        self.init_audio_model = False
+        self.init_audio_model = bool(init_audio_model)
         self._init_cam(n_layers, n_heads, init_from_avg)
+        if self.init_audio_model:
+            self._init_audio(audio_model_ckpt, clip_audio_ckpt)
         self._common_init()
         self._freeze(freeze)
 
+    def _init_audio(self, audio_model_ckpt, clip_audio_ckpt):
+        """model/model.py:409-438 without GDT.  An empty path counts as "not given" (the shipped config carries "")."""
+        if self.feature_dim != AudioMLP().layers[4].out_features:
+            # the reference concatenates the MLP's 512-d outputs after the comment features (model/model.py:226) and fails in torch.cat
+            raise ValueError(f"init_audio_model=True: the audio MLP produces 512-d clip features, but this CLIP's embedding width is "
+                             f"{self.feature_dim}; the audio branch needs a 512-wide model (e.g. ViT-B/32 or ViT-B/16)")
+        self.audio_model = AudioModel()
+        if audio_model_ckpt:
+            # model/model.py:420-428: the GDT checkpoint's audio tensors belong to audio_model.base (the resnet9), never read here
+            ckpt = torch.load(audio_model_ckpt, map_location="cpu")
+            ckpt = {k.split("audio_network.")[1]: v for k, v in ckpt["model"].items() if "audio" in k}
+            stray = sorted(k for k in ckpt if not k.startswith("base."))
+            if stray:
+                raise KeyError(f"audio_model_ckpt {audio_model_ckpt!r}: keys outside the audio base network: {stray[:5]}")
+            self.audio_model.base.load_tensors({k[len("base."):]: v for k, v in ckpt.items()})
+        if clip_audio_ckpt:
+            pretrained_clip = torch.load(clip_audio_ckpt, map_location="cpu")          # model/model.py:428-435
+            clip_ckpt = {k[len("model."):]: v for k, v in pretrained_clip["state_dict"].items() if "model" in k}
+            self.model.load_state_dict(clip_ckpt)
+
     def forward(self, vis, title, comments):
-        self._check_mode(vis, title, comments)
-        feats_vis, feats_text = self._forward_with_cam(vis, title, comments)
+        audio = None
+        if self.init_audio_model and isinstance(comments, list):         # model/model.py:220-224 (default_collate: tuple -> list)
+            comments, audio = comments
+        self._check_mode(vis, title, comments, audio)
+        if audio is not None and (audio.dim() != 3 or audio.shape[0] != comments.shape[0] or audio.shape[2] != self.feature_dim):
+            raise ValueError(f"audio clips: expected [B, n_clips, {self.feature_dim}] with B = {comments.shape[0]}, got {tuple(audio.shape)}")
+        feats_vis, feats_text = self._forward_with_cam(vis, title, comments, audio)
         return feats_vis, feats_text, self._sim(feats_vis, feats_text)
 
 

@@ -31,6 +31,10 @@ EOT = 49407
 def main(config: ConfigParser, args=None, device="cuda"):
     arch = config["arch"]
     a = dict(arch.get("args", {}))
+    if a.get("init_audio_model"):
+        raise NotImplementedError("train: the audio branch is eval-only on the HIP path -- training it needs the audio MLP's backward "
+                                  "(audio_model.mlp, model/model.py:80-94) and its train-mode Dropout and BatchNorm (batch statistics, "
+                                  "running-statistic updates), none of which is implemented; eval.py runs the audio configs")
     if not arch["type"].endswith("_finaltf") or "all" not in str(a.get("freeze", "")):
         raise NotImplementedError("train: only adapter-only fine-tuning is implemented (a *_finaltf wrapper with freeze='all'); "
                                   "tower backward is outside the hot path (DESIGN.md 7)")

@@ -449,18 +449,20 @@ class PackedCam:
         self.w = w
 
     @ops.on_device
-    def forward(self, main: torch.Tensor, comm_feats: torch.Tensor, comments: torch.Tensor, fused: Optional[bool] = None) -> torch.Tensor:
+    def forward(self, main: torch.Tensor, comm_feats: torch.Tensor, comments: torch.Tensor, fused: Optional[bool] = None,
+                aux: Optional[torch.Tensor] = None) -> torch.Tensor:
         """main [B,D], comm_feats [B*nc,D] fp32, comments [B,nc,ctx] int64 -> adapted [B,D].
         fused=False: the multi-launch path for THIS call (the caller has another tower's kernels in flight on a second stream: the
         one-launch form's grid barrier needs every CU to itself and would serialise with them -- or give up; the small launches of the
-        multi-launch form interleave)."""
+        multi-launch form interleave).
+        aux [B*na,D] fp32: na more tokens per item after the comments, never masked (the audio clips, model/model.py:220-230)."""
         w = self.w
         if _CAM_SHARED_CARD:
             w.flags |= L.CAM_NO_FUSED
         if fused is False and not (w.flags & L.CAM_NO_FUSED):
             w.flags |= L.CAM_NO_FUSED
             try:
-                return self.forward(main, comm_feats, comments)
+                return self.forward(main, comm_feats, comments, aux=aux)
             finally:
                 w.flags &= ~L.CAM_NO_FUSED
         main, comm_feats = ops._gpu(main, torch.float32, "main"), ops._gpu(comm_feats, torch.float32, "comm_feats")
@@ -469,7 +471,54 @@ class PackedCam:
         assert main.shape == (B, w.width) and comm_feats.shape == (B * nc, w.width)
         out = torch.empty(B, w.width, dtype=torch.float32, device=main.device)
         lib = L.lib()
-        ws = _ws(lib.vtc_cam_workspace_bytes(C.byref(w), B, nc, self.code), main.device)
-        L.check(lib.vtc_cam_forward(C.byref(w), main.data_ptr(), comm_feats.data_ptr(), comments.data_ptr(), ctx, B, nc,
-                                    out.data_ptr(), ws.data_ptr(), ws.numel(), self.code, ops._stream()), "vtc_cam_forward")
+        if aux is None:
+            ws = _ws(lib.vtc_cam_workspace_bytes(C.byref(w), B, nc, self.code), main.device)
+            L.check(lib.vtc_cam_forward(C.byref(w), main.data_ptr(), comm_feats.data_ptr(), comments.data_ptr(), ctx, B, nc,
+                                        out.data_ptr(), ws.data_ptr(), ws.numel(), self.code, ops._stream()), "vtc_cam_forward")
+            return out
+        aux = ops._gpu(aux, torch.float32, "aux")
+        if aux.dim() != 2 or aux.shape[1] != w.width or aux.shape[0] % B:
+            raise ValueError(f"aux tokens: expected [B*na, {w.width}] with B = {B}, got {tuple(aux.shape)}")
+        na = aux.shape[0] // B
+        ws = _ws(lib.vtc_cam_aux_workspace_bytes(C.byref(w), B, nc, na, self.code), main.device)
+        L.check(lib.vtc_cam_forward_aux(C.byref(w), main.data_ptr(), comm_feats.data_ptr(), comments.data_ptr(), aux.data_ptr(), ctx, B,
+                                        nc, na, out.data_ptr(), ws.data_ptr(), ws.numel(), self.code, ops._stream()), "vtc_cam_forward_aux")
+        return out
+
+
+class PackedAudioMlp:
+    """The audio branch's feature MLP (model/model.py:80-94: Dropout, Linear, BatchNorm1d, ReLU, Linear), eval mode, packed for
+    vtc_feature_mlp: BatchNorm's running statistics are folded into the first Linear on the host in fp64 --
+    W1' = (gamma / sqrt(var + eps)) W1,  b1' = (b1 - mean) gamma / sqrt(var + eps) + beta -- and the four fp32 arrays share one
+    arena.  fp32 in every compute_dtype mode (as the CAM it feeds)."""
+    WIDTH = 512
+
+    def __init__(self, sd: SD, prefix: str = "audio_model.mlp.layers."):
+        sd, dev = _host_sd(sd, prefix)
+        w1, b1 = sd["1.weight"].double(), sd["1.bias"].double()
+        w2, b2 = sd["4.weight"], sd["4.bias"]
+        if tuple(w1.shape) != (self.WIDTH, self.WIDTH) or tuple(w2.shape) != (self.WIDTH, self.WIDTH):
+            raise NotImplementedError(f"audio MLP: the kernel takes 512 x 512 layers, got {tuple(w1.shape)} and {tuple(w2.shape)}")
+        eps = 1e-5                                         # nn.BatchNorm1d default (model/model.py:87)
+        scale = sd["2.weight"].double() / torch.sqrt(sd["2.running_var"].double() + eps)
+        w1f = (w1 * scale[:, None]).float()
+        b1f = ((b1 - sd["2.running_mean"].double()) * scale + sd["2.bias"].double()).float()
+        self.keep = k = _Keep(dev, arena_bytes=2 * (self.WIDTH * self.WIDTH + self.WIDTH) * 4 + 4 * 256)
+        self.w1, self.b1, self.w2, self.b2 = k.f32(w1f), k.f32(b1f), k.f32(w2), k.f32(b2)
+
+    @ops.on_device
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x [n, 512] fp32 -> y [n, 512] fp32, row i from row i (rows = the clips of a batch, b * na + a)."""
+        x = ops._gpu(x, torch.float32, "audio features")
+        if x.dim() != 2 or x.shape[1] != self.WIDTH:
+            raise ValueError(f"audio features: expected [n, {self.WIDTH}], got {tuple(x.shape)}")
+        n = x.shape[0]
+        out = torch.empty(n, self.WIDTH, dtype=torch.float32, device=x.device)
+        if n == 0:
+            return out
+        lib = L.lib()
+        nb = lib.vtc_feature_mlp_workspace_bytes(n, self.WIDTH)
+        ws = _ws(nb, x.device) if nb else None
+        L.check(lib.vtc_feature_mlp(x.data_ptr(), n, self.WIDTH, self.w1, self.b1, self.w2, self.b2, out.data_ptr(),
+                                    ws.data_ptr() if ws is not None else None, nb, ops._stream()), "vtc_feature_mlp")
         return out
