@@ -209,7 +209,9 @@ int vtc_feature_mlp(const float *x, int n, int d, const float *w1, const float *
 int vtc_normalize_rows(const float *x, float *out, int n, int d, void *stream);
 /* Both embedding sets of a forward in one launch: outx = rows of x [nx, d] / their norms, outy likewise for y [ny, d] (the two
  * `normalize` calls that end every PretrainedCLIP*.forward, model/model.py:263-264, 366-367), and the non-finite watchdog with it:
- * flag[0] (int32, device; NULL: none) |= 1 when a row of x holds a NaN / inf, |= 2 for y (ABI 7; see vtc_nonfinite_flag2). */
+ * flag[0] (int32, device; NULL: none) |= 1 when a row of x holds a NaN / inf OR has a squared norm of zero -- an all-zero row, or
+ * one whose squares all underflow: its output row is 0/0 = NaN (x/0 = inf), as in the reference -- |= 2 for y: the word is raised
+ * whenever vtc_nonfinite_flag2 would raise it on the two OUTPUTS (ABI 7). */
 int vtc_normalize_rows2(const float *x, float *outx, int nx, const float *y, float *outy, int ny, int d, int *flag, void *stream);
 /* out[g] = mean over `group` consecutive rows (frames -> video, title+comments -> text) */
 int vtc_mean_groups(const float *x, float *out, int n_groups, int group, int d, void *stream);
@@ -386,7 +388,8 @@ int vtc_quickgelu(const float *x, const float *dy, float *out, size_t n, void *s
 int vtc_normalize_rows_bwd(const float *x, const float *dy, float *dx, int n, int d, void *stream);
 /* dsim = d clip_loss / d sim; ws >= 4 n floats */
 int vtc_clip_loss_bwd(const float *sim, int n, float *dsim, void *ws, size_t ws_bytes, void *stream);
-/* torch.optim.Adam single-tensor step (weight_decay 0); step counts from 1; vmax only when amsgrad */
+/* torch.optim.Adam single-tensor step (weight_decay 0); step counts from 1; vmax only when amsgrad (NULL otherwise).  The bias
+ * corrections 1 - beta^step are formed in double from the float betas, as torch.optim forms them from its Python floats */
 int vtc_adam_step(float *p, const float *g, float *m, float *v, float *vmax, size_t n, float lr, float beta1, float beta2,
                   float eps, int step, int amsgrad, void *stream);
 int vtc_axpby(float *out, const float *x, const float *y, float a, float b, size_t n, void *stream);   /* out = a x + b y  */

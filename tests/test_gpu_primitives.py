@@ -307,6 +307,68 @@ def test_gemm_random_shapes_all_kernels():
         assert (out - quick_gelu(ref)).abs().max() < 2e-2 * max(1.0, float(ref.abs().max())), (M, N, K, "gelu")
 
 
+def test_gemm_f32_operands_random_shapes():
+    """The integer-exact scheme of test_gemm_random_shapes_all_kernels for fp32 operands (the reference's own arithmetic mode and the
+    training path's dgrad / wgrad): K = 32 * odd and the one-K-step K = 32 (the two-stage instantiation of the 64 x 64
+    configuration), ragged M / N on the 64 x 64 configuration ((M, N) in [1, 700]) and on the 128 x 128 one ((M, N) in [1500, 2600]:
+    more than 128 tiles of 128 x 128, i.e. more than two per CU), with and without bias, every epilogue."""
+    L, ops = _ops()
+    rng = np.random.default_rng(32)
+    Ks = [32, 64, 96, 160, 224, 1056]
+    shapes = [(int(rng.integers(1, 701)), int(rng.integers(1, 701))) for _ in range(8)]
+    shapes += [(int(rng.integers(1500, 2601)), int(rng.integers(1500, 2601))) for _ in range(4)]
+    cases = [(M, N, Ks[(i + j) % 6]) for i, (M, N) in enumerate(shapes) for j in (0, 3)]     # every K on both configurations
+    assert {K for _, _, K in cases[:16]} == set(Ks) and {K for _, _, K in cases[16:]} == set(Ks)
+    for n_case, (M, N, K) in enumerate(cases):
+        g = torch.Generator().manual_seed(M * 31 + N + K)
+        a = torch.randint(-2, 3, (M, K), generator=g).float().cuda()
+        w = (torch.randint(-2, 3, (N, K), generator=g).float() + torch.arange(N).float()[:, None] % 3).cuda()    # W rows distinct
+        bias = torch.randint(-4, 5, (N,), generator=g).float().cuda() if n_case % 2 == 0 else None
+        ref = a @ w.t() + (bias if bias is not None else 0)      # exact in fp32: integers below 2^24
+        out = ops.gemm(a, w, bias, out_dtype=torch.float32)
+        assert torch.equal(out, ref), (M, N, K, "store f32", float((out - ref).abs().max()))
+        out = ops.gemm(a, w, bias, out_dtype=torch.bfloat16)
+        assert torch.equal(out.float(), ref.bfloat16().float()), (M, N, K, "store bf16")
+        x0 = torch.randint(-8, 9, (M, N), generator=g).float().cuda()
+        x = x0.clone()
+        ops.gemm(a, w, bias, epilogue=L.EPI_RESID, out=x, skip_mod=7)
+        want = x0 + ref
+        want[0::7] = x0[0::7]
+        assert torch.equal(x, want), (M, N, K, "resid")
+        out = ops.gemm(a, w, bias, epilogue=L.EPI_GELU, out_dtype=torch.float32)
+        assert (out - quick_gelu(ref)).abs().max() < 1e-5 * max(1.0, float(ref.abs().max())), (M, N, K, "gelu")
+
+
+def test_gemm_f32_operands_refuse_k_off_the_32_grid():
+    L, ops = _ops()
+    out = torch.full((4, 8), 5.0, device="cuda")
+    with pytest.raises(RuntimeError, match="K=48"):
+        ops.gemm(torch.zeros(4, 48, device="cuda"), torch.zeros(8, 48, device="cuda"), None, out=out)
+    assert float(out.min()) == 5.0
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-5), (torch.bfloat16, 2e-2), (torch.float16, 3e-3)])
+def test_attention_short_and_off_grid_lengths(dtype, tol, causal):
+    """vtc_attention at the lengths nobody runs (the smallest tested L was 6; the adapter's train step at nc = 3 needs L = 4):
+    contiguous sequences, n_seq * heads = 15 (not a multiple of the waves per workgroup), against softmax(q k^T / 8 [+ causal]) v
+    in fp32 on the rounded operands, at the tolerances of test_attention_contiguous / test_layernorm_and_attention_f16."""
+    L, ops = _ops()
+    heads, n_seq = 3, 5
+    W = heads * 64
+    worst = {}
+    for L_ in (1, 2, 3, 4, 5, 7, 9, 17, 33, 49, 64, 65, 80):
+        g = torch.Generator().manual_seed(1000 + L_)
+        qd = torch.randn(n_seq * L_, 3 * W, generator=g).cuda().to(dtype)
+        q, k, v = qd.float().cpu().reshape(n_seq, L_, 3, heads, 64).permute(2, 0, 3, 1, 4)
+        ref = ref_attention(q, k, v, causal).permute(0, 2, 1, 3).reshape(n_seq * L_, W)
+        out = ops.attention(qd, n_seq, L_, heads, causal=causal)
+        assert out.dtype == dtype
+        worst[L_] = float((out.float().cpu() - ref).abs().max())
+    print(f"[e] attention {dtype} causal={causal}: " + "  ".join(f"L={k} {v:.2e}" for k, v in worst.items()))
+    assert all(v < tol for v in worst.values()), worst
+
+
 # ---- IEEE-half operands (VTC_F16): the text tower's blocks in bf16 mode --------------------------------------------
 @pytest.mark.parametrize("M,N,K", [(300, 384, 192), (77, 512, 3072), (8200, 3000, 768)])
 def test_gemm_f16_operands(M, N, K):

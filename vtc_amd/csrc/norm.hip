@@ -293,8 +293,9 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float *__restrict_
 }
 
 // The last launch of a wrapper's forward: both embedding sets normalised in ONE launch (rows 0 .. nx - 1 from x, the rest from y), and the
-// non-finite watchdog with it -- a NaN / inf anywhere in a row makes its squared norm non-finite: flag |= 1 (x) / 2 (y).  Per row the
-// arithmetic of normalize_kernel.
+// non-finite watchdog with it -- a NaN / inf anywhere in a row makes its squared norm non-finite, and a squared norm of zero (an all-zero
+// row, or one whose squares all underflow) makes the OUTPUT row 0/0 = NaN or x/0 = inf: flag |= 1 (x) / 2 (y) in both cases, which is what
+// vtc_nonfinite_flag2 says of the normalised rows.  Per row the arithmetic of normalize_kernel.
 __global__ __launch_bounds__(256) void normalize2_kernel(const float *__restrict__ x, float *__restrict__ outx, int nx, const float *__restrict__ y,
                                                          float *__restrict__ outy, int ny, int d, int *flag) {
   const int lane = threadIdx.x & 63;
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(256) void normalize2_kernel(const float *__restrict
   s = wave_sum(s);
   const float nrm = sqrtf(s);
   for (int c = lane; c < d; c += 64) o[c] = xr[c] / nrm;   // x / x.norm(): division, as the reference
-  if (flag && lane == 0 && (__float_as_uint(s) & 0x7F800000u) == 0x7F800000u) atomicOr(flag, second ? 2 : 1);
+  if (flag && lane == 0 && (s == 0.f || (__float_as_uint(s) & 0x7F800000u) == 0x7F800000u)) atomicOr(flag, second ? 2 : 1);
 }
 
 __global__ __launch_bounds__(256) void mean_groups_kernel(const float *__restrict__ x, float *__restrict__ out, int n_groups,

@@ -451,3 +451,120 @@ def recall_hits(ids: torch.Tensor, k_vals: Sequence[int], target_offset: int = 0
     L.check(L.lib().vtc_recall_hits(ids.data_ptr(), nq, depth, int(target_offset), ks, len(k_vals), hits.data_ptr(), _stream()),
             "vtc_recall_hits")
     return hits
+
+
+@on_device
+def nonfinite_flag(x: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
+    """flag[0] |= 1 when ``x`` holds a NaN / inf (vtc_nonfinite_flag).  flag: int32 in device memory."""
+    x = _gpu(x, torch.float32, "x")
+    L.check(L.lib().vtc_nonfinite_flag(x.data_ptr(), x.numel(), flag.data_ptr(), _stream()), "vtc_nonfinite_flag")
+    return flag
+
+
+# ---- adapter-only training step: backward + optimizer primitives (train.hip) --------------------
+# Thin forms of the C ABI for callers that bring their own output buffers (vtc_amd/host/adapter_train.py keeps its private
+# helpers); `out` buffers, where given, are written as they are -- the entry points own their zeroing.
+def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    return _gpu(t, torch.float32, name)
+
+
+@on_device
+def transpose(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[c][r] = x[r][c]."""
+    x = _f32(x, "x")
+    r, c = x.shape
+    out = torch.empty(c, r, dtype=torch.float32, device=x.device) if out is None else out
+    L.check(L.lib().vtc_transpose_f32(x.data_ptr(), out.data_ptr(), r, c, _stream()), "vtc_transpose_f32")
+    return out
+
+
+@on_device
+def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[c] = sum_r x[r][c] (the entry point zeroes ``out`` itself)."""
+    x = _f32(x, "x")
+    out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device) if out is None else out
+    L.check(L.lib().vtc_colsum_f32(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], _stream()), "vtc_colsum_f32")
+    return out
+
+
+@on_device
+def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dx: Optional[torch.Tensor] = None, accumulate_dx: bool = False,
+                  dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None):
+    """(dx, dgamma, dbeta) of LayerNorm (eps 1e-5, biased variance); with ``accumulate_dx`` the row gradients are ADDED to ``dx``.
+    dgamma / dbeta are zeroed by the entry point."""
+    x, gamma, dy = _f32(x, "x"), _f32(gamma, "gamma"), _f32(dy, "dy")
+    if dx is None:
+        assert not accumulate_dx
+        dx = torch.empty_like(x)
+    dgamma = torch.empty_like(gamma) if dgamma is None else dgamma
+    dbeta = torch.empty_like(gamma) if dbeta is None else dbeta
+    L.check(L.lib().vtc_layernorm_bwd(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                      x.shape[0], x.shape[1], int(accumulate_dx), _stream()), "vtc_layernorm_bwd")
+    return dx, dgamma, dbeta
+
+
+@on_device
+def attention_small_bwd(qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, L_: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dqkv of the unmasked attention on contiguous sequences, L <= 16, head_dim 64: qkv [n_seq * L, 3 W], dout [n_seq * L, W]."""
+    qkv, dout = _f32(qkv, "qkv"), _f32(dout, "dout")
+    out = torch.empty_like(qkv) if out is None else out
+    L.check(L.lib().vtc_attention_small_bwd(qkv.data_ptr(), dout.data_ptr(), out.data_ptr(), n_seq, L_, heads, _stream()), "vtc_attention_small_bwd")
+    return out
+
+
+@on_device
+def quickgelu(x: torch.Tensor, dy: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x sigmoid(1.702 x), or with ``dy`` its backward dy * d/dx."""
+    x = _f32(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.lib().vtc_quickgelu(x.data_ptr(), _f32(dy, "dy").data_ptr() if dy is not None else None, out.data_ptr(), x.numel(), _stream()),
+            "vtc_quickgelu")
+    return out
+
+
+@on_device
+def normalize_rows_bwd(x: torch.Tensor, dy: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx of y = x / |x| per row."""
+    x, dy = _f32(x, "x"), _f32(dy, "dy")
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.lib().vtc_normalize_rows_bwd(x.data_ptr(), dy.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], _stream()), "vtc_normalize_rows_bwd")
+    return out
+
+
+@on_device
+def clip_loss_bwd(sim: torch.Tensor, out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dsim = d clip_loss / d sim.  ws: at least 4 n floats (allocated when not given)."""
+    sim = _f32(sim, "sim")
+    n = sim.shape[0]
+    assert sim.shape == (n, n)
+    out = torch.empty_like(sim) if out is None else out
+    ws = torch.empty(4 * n, dtype=torch.float32, device=sim.device) if ws is None else ws
+    L.check(L.lib().vtc_clip_loss_bwd(sim.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "vtc_clip_loss_bwd")
+    return out
+
+
+@on_device
+def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, vmax: Optional[torch.Tensor], lr: float, beta1: float,
+              beta2: float, eps: float, step: int, amsgrad: bool) -> torch.Tensor:
+    """torch.optim.Adam single-tensor step in place on p, m, v (and vmax with amsgrad); ``step`` counts from 1."""
+    p, g, m, v = _f32(p, "p"), _f32(g, "g"), _f32(m, "m"), _f32(v, "v")
+    L.check(L.lib().vtc_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _f32(vmax, "vmax").data_ptr() if vmax is not None else None,
+                                  p.numel(), lr, beta1, beta2, eps, int(step), int(amsgrad), _stream()), "vtc_adam_step")
+    return p
+
+
+@on_device
+def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = a x + b y (y None: a x); ``out`` may be ``x``."""
+    x = _f32(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.lib().vtc_axpby(out.data_ptr(), x.data_ptr(), _f32(y, "y").data_ptr() if y is not None else None, a, b, x.numel(), _stream()), "vtc_axpby")
+    return out
+
+
+@on_device
+def scale_rows(x: torch.Tensor, s: torch.Tensor, group: int = 1) -> torch.Tensor:
+    """x[r] *= s[r // group], in place."""
+    x, s = _f32(x, "x"), _f32(s, "s")
+    L.check(L.lib().vtc_scale_rows(x.data_ptr(), s.data_ptr(), x.shape[0], x.shape[1], group, _stream()), "vtc_scale_rows")
+    return x
