@@ -280,7 +280,7 @@ int vtc_l2_topk_bidir(const float *a, const float *b, int n_a, int n_b, int d, i
  *   vtc_l2_sweep_shard_cols   planes [n_src, 4, nblk_pad, n_local] = what the n_src ranks sent for this rank's columns, in
  *                             rank order; src_base[n_src] (device int32) = lo_r of each source.  ids [n_local, depth] =
  *                             vtc_l2_topk(gallery = b_all, queries = a_local), bit-identical to the single-GPU search
- *                             (certified candidates re-ranked in fp64, uncertified columns by fp64 brute force).
+ *                             (certified candidates re-ranked in fp64, uncertified columns settled in fp64 from their own planes).
  * VTC_SWEEP_EXACT only; d % 64 == 0; vtc_l2_sweep_shard_supported tells whether the shape is covered (else: two vtc_l2_topk). */
 int vtc_l2_sweep_row_block(void);
 int vtc_l2_sweep_shard_supported(int n_total, int n_local, int depth);

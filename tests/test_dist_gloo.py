@@ -294,7 +294,7 @@ def test_single_rank_path_of_sharded_recall_is_the_plain_recall():
     r_ab, r_ba = vdist.sharded_recall(torch.from_numpy(a), torch.from_numpy(b), n, [1, 5, 10], 0, 1, topk=_cpu_topk, phases=ph)
     assert r_ab == dict(E.recall_at_k(a, b, [1, 5, 10])) and r_ba == dict(E.recall_at_k(b, a, [1, 5, 10]))
     assert vdist.sweep_path(n, 3, 1).startswith("two searches") and vdist.sweep_path(10000, 3, 1).startswith("one distance matrix")
-    assert not vdist.one_matrix_sharded(10000, 3, 1, 11)
+    assert vdist.choose_sweep_path(10000, 512, 3, 1) not in (vdist.SweepPath.ONE_MATRIX_SHARDED, vdist.SweepPath.RANK_SHARDED)
 
 
 def _worker_nonfinite(rank, world, port, n, out):

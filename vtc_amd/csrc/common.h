@@ -238,6 +238,7 @@ enum { EPI_PATCH = 3, EPI_L2DIST = 4, EPI_SCALE = 5, EPI_L2MIN = 6, EPI_RESID_LN
        EPI_RESID_FOLD_C = 11 /* ... that also re-centres the stream (fold_stat given) */,
        EPI_L2MIN2 = 12 /* EPI_L2MIN with TWO planes per block (the smallest key + the second as a bound): the recall-only sweep at small k */,
        EPI_L2MIN3 = 13 /* ... rows two planes, columns THREE (two keys + bound): small galleries, whose few, long column blocks make two planes' fp64 fallback frequent */ };
+#define VTC_L2MIN_INF 0x7F800000u // an empty key slot: +inf
 #define L2MIN_PLANES 4            // planes of EPI_L2MIN (three keys + bound); EPI_L2MIN2 / 3 write the first two / three plane slots of the same layout
 constexpr int l2min_row_planes(int mode) { return (mode == EPI_L2MIN2 || mode == EPI_L2MIN3) ? 2 : L2MIN_PLANES; }     // per (row, block of 64 columns)
 constexpr int l2min_col_planes(int mode) { return mode == EPI_L2MIN2 ? 2 : (mode == EPI_L2MIN3 ? 3 : L2MIN_PLANES); }  // per (column, block of RB rows)

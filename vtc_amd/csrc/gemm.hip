@@ -103,7 +103,6 @@ constexpr int fast_epilogue_trailing_stores() { return TM * (sizeof(OutT) == 2 ?
 // by an index inside the block: unsigned-integer order = distance order, ties by index, and min / max / med3 on the keys
 // are single VALU instructions.  An empty slot is +inf (0x7F800000).
 // (Integer min / max / med3 on the bit patterns: the float forms would each drag a canonicalising v_max_f32 x, x, x along.)
-#define VTC_L2MIN_INF 0x7F800000u
 __device__ __forceinline__ unsigned umed3(unsigned x, unsigned y, unsigned z) {
   unsigned r;
   asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));

@@ -771,12 +771,12 @@ __global__ __launch_bounds__(256) void exact_rerank_kernel(const RerankArgs PA, 
 // workgroup per row, a sorted (distance, index) list per wave (one entry per lane), merged by wave 0.
 __global__ __launch_bounds__(256) void exact_fallback_kernel(const float *__restrict__ queries, const float *__restrict__ gallery, int ng,
                                                              int d, int depth, const int *__restrict__ flags, int64_t *__restrict__ ids,
-                                                             float *__restrict__ dists, int f_first) {
+                                                             float *__restrict__ dists) {
   __shared__ double sd[4][64];
   __shared__ int si[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_flagged = flags[0];
-  for (int f = f_first + blockIdx.x; f < n_flagged; f += gridDim.x) {   // uniform for the workgroup; normally zero trips
+  for (int f = blockIdx.x; f < n_flagged; f += gridDim.x) {   // uniform for the workgroup; normally zero trips
   const int r = flags[1 + f];
   const float *q = queries + (size_t)r * d;
   double bd = INFINITY;
@@ -806,124 +806,6 @@ __global__ __launch_bounds__(256) void exact_fallback_kernel(const float *__rest
     }
   }
   __syncthreads();                                         // sd / si are reused by the next flagged row
-  }
-}
-
-// The same brute force spread over FB_CHUNKS workgroups per flagged row (the first FB_ROWS flagged rows; a row is a chain of
-// dependent gather latencies, so one workgroup per row takes ~10 ms at 50k): workgroup (x, y) scans gallery slice y for the
-// flagged rows x, x + gridDim.x, ... and leaves its slice's best `depth` in part_*; fallback_merge_kernel merges the slices.
-constexpr int FB_CHUNKS = 512, FB_ROWS = 256, FB_SLOT = 32;   // FB_SLOT >= the largest depth of the block-minima path
-__global__ __launch_bounds__(256) void exact_fallback_chunk_kernel(const float *__restrict__ queries, const float *__restrict__ gallery, int ng,
-                                                                   int d, int depth, const int *__restrict__ flags, double *__restrict__ part_d,
-                                                                   int *__restrict__ part_i) {
-  __shared__ double sd[4][64];
-  __shared__ int si[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_flagged = min(flags[0], FB_ROWS);
-  const int chunk = blockIdx.y;
-  const int per = (ng + FB_CHUNKS - 1) / FB_CHUNKS;
-  const int j_lo = chunk * per, j_hi = min(ng, j_lo + per);
-  for (int f = blockIdx.x; f < n_flagged; f += gridDim.x) {   // uniform for the workgroup; normally zero trips
-    const int r = flags[1 + f];
-    const float *q = queries + (size_t)r * d;
-    double bd = INFINITY;
-    int bi = 0x7fffffff;
-    auto offer = [&](double cv, int ci) {                   // wave-uniform candidate
-      const double tau = __shfl(bd, depth - 1, 64);
-      const int tau_i = __shfl(bi, depth - 1, 64);
-      if (!(cv < tau || (cv == tau && ci < tau_i))) return;
-      const bool less = bd < cv || (bd == cv && bi < ci);
-      const int pos = __popcll(__ballot(less));
-      const double ud = __shfl_up(bd, 1, 64);
-      const int ui = __shfl_up(bi, 1, 64);
-      if (lane > pos) { bd = ud; bi = ui; }
-      if (lane == pos) { bd = cv; bi = ci; }
-    };
-    // four gallery rows per step: their loads are all in flight before the first butterfly (same arithmetic and order as
-    // wave_dist64 per row, so a distance has the same bits whichever kernel forms it)
-    for (int j0 = j_lo + 4 * wave; j0 < j_hi; j0 += 16) {
-      double sacc[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int c = lane * 4; c < d; c += 256) {
-        const float4 a = *reinterpret_cast<const float4 *>(q + c);
-        float4 b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) b[u] = *reinterpret_cast<const float4 *>(gallery + (size_t)min(j0 + u, j_hi - 1) * d + c);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const double e0 = (double)a.x - (double)b[u].x, e1 = (double)a.y - (double)b[u].y, e2 = (double)a.z - (double)b[u].z,
-                       e3 = (double)a.w - (double)b[u].w;
-          sacc[u] += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sacc[u] += __shfl_xor(sacc[u], o, 64);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (j0 + u < j_hi) offer(sacc[u], j0 + u);
-    }
-    sd[wave][lane] = bd;
-    si[wave][lane] = bi;
-    __syncthreads();
-    if (wave == 0) {
-      for (int w = 1; w < 4; ++w)
-        for (int e = 0; e < depth; ++e)
-          if (si[w][e] != 0x7fffffff) offer(sd[w][e], si[w][e]);
-      if (lane < depth) {
-        part_d[((size_t)f * FB_CHUNKS + chunk) * FB_SLOT + lane] = bd;
-        part_i[((size_t)f * FB_CHUNKS + chunk) * FB_SLOT + lane] = bi;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// one wave per flagged row (the first FB_ROWS): merge the FB_CHUNKS slice lists -- 64 candidates per step, screened against the
-// running depth-th best, the few survivors inserted one by one
-__global__ __launch_bounds__(256) void exact_fallback_merge_kernel(int depth, const int *__restrict__ flags, const double *__restrict__ part_d,
-                                                                   const int *__restrict__ part_i, int64_t *__restrict__ ids,
-                                                                   float *__restrict__ dists) {
-  const int lane = threadIdx.x & 63;
-  const int n_flagged = min(flags[0], FB_ROWS);
-  const int total = FB_CHUNKS * depth;
-  for (int f = blockIdx.x * 4 + (threadIdx.x >> 6); f < n_flagged; f += gridDim.x * 4) {
-    const int r = flags[1 + f];
-    double bd = INFINITY;
-    int bi = 0x7fffffff;
-    for (int base = 0; base < total; base += 64) {
-      const int k = base + lane;
-      const int c = k / depth, e = k - c * depth;
-      double cv = INFINITY;
-      int ci = 0x7fffffff;
-      if (k < total) {
-        cv = part_d[((size_t)f * FB_CHUNKS + c) * FB_SLOT + e];
-        ci = part_i[((size_t)f * FB_CHUNKS + c) * FB_SLOT + e];
-      }
-      const double tau0 = __shfl(bd, depth - 1, 64);
-      const int tau0_i = __shfl(bi, depth - 1, 64);
-      unsigned long long mask = __ballot(ci != 0x7fffffff && (cv < tau0 || (cv == tau0 && ci < tau0_i)));
-      while (mask) {
-        const int l = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const double xv = __shfl(cv, l, 64);
-        const int xi = __shfl(ci, l, 64);
-        const double tau = __shfl(bd, depth - 1, 64);
-        const int tau_i = __shfl(bi, depth - 1, 64);
-        if (!(xv < tau || (xv == tau && xi < tau_i))) continue;
-        const bool less = bd < xv || (bd == xv && bi < xi);
-        const int pos = __popcll(__ballot(less));
-        const double ud = __shfl_up(bd, 1, 64);
-        const int ui = __shfl_up(bi, 1, 64);
-        if (lane > pos) { bd = ud; bi = ui; }
-        if (lane == pos) { bd = xv; bi = xi; }
-      }
-    }
-    if (lane < depth) {
-      ids[(size_t)r * depth + lane] = bi == 0x7fffffff ? -1 : (int64_t)bi;
-      if (dists) dists[(size_t)r * depth + lane] = (float)bd;
-    }
   }
 }
 
@@ -1195,29 +1077,90 @@ SweepWs plan(char *ws, int ng, int nq, int d, int precision, int rows_per_block,
   return s;
 }
 
-}  // namespace
+// col_ids != nullptr: also the transposed direction (for every gallery row its nearest query rows), read off the same
+// distance blocks by col_topk_kernel.
+static int l2_topk_impl(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int precision,
+                        int64_t *ids, float *dists, const SweepWs &s, hipStream_t stream, int64_t *col_ids = nullptr,
+                        float *col_dists = nullptr) {
+  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, stream, queries, s.qn, nq, d);
+  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(ng, 4)), dim3(256), 0, stream, gallery, s.gn, ng, d);
+  const int parts = precision == VTC_SWEEP_BF16X3 ? 3 : 1;
+  if (precision != VTC_SWEEP_F32) {
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)nq * d + 255) / 256)), dim3(256), 0, stream, queries, s.qb, nq, d, parts, 0);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)ng * d + 255) / 256)), dim3(256), 0, stream, gallery, s.gb, ng, d, parts, 1);
+  }
+  VTC_LAUNCH_CHECK("l2_topk prologue");
+  for (int r0 = 0; r0 < nq; r0 += s.rows_per_block) {
+    const int rows = min(s.rows_per_block, nq - r0);
+    GemmEpi e;
+    e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
+    int rc;
+    if (precision == VTC_SWEEP_F32)
+      rc = launch_gemm(queries + (size_t)r0 * d, gallery, nullptr, s.dist, rows, ng, d, VTC_F32, e, stream);
+    else
+      rc = launch_gemm(s.qb + (size_t)r0 * d * parts, s.gb, nullptr, s.dist, rows, ng, d * parts, VTC_BF16, e, stream);
+    if (rc) return rc;
+    {
+      // enough (row, segment) waves to fill the chip (32 waves per CU)
+      // (every segment pays its own warm-up insertions, so segments are used only when rows alone cannot fill the chip)
+      int S = cdiv(8192, rows);
+      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
+      int seg_cols = cdiv(cdiv(ng, S), 1024) * 1024;
+      S = cdiv(ng, seg_cols);
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * ng * 4, stream);
+      hipLaunchKernelGGL(row_topk_kernel, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, ng, rows, ng, depth, S, seg_cols, ids,
+                         dists, (size_t)r0, s.part_d, s.part_i);
+      if (S > 1)
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, s.part_d, s.part_i, rows, S, depth, ids, dists,
+                           (size_t)r0);
+    }
+    VTC_LAUNCH_CHECK("row_topk");
+    if (col_ids) {
+      const int seg_rows = cdiv(cdiv(rows, s.c_seg), 64) * 64;
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * ng * 4, stream);
+      hipLaunchKernelGGL(col_topk_kernel, dim3(cdiv(ng, 64) * s.c_seg), dim3(256), 0, stream, s.dist, ng, rows, ng, depth, r0, s.c_seg,
+                         seg_rows, s.c_total, 0, r0 > 0 ? 1 : 0, s.cpart_d, s.cpart_i);
+      VTC_LAUNCH_CHECK("col_topk");
+    }
+  }
+  if (col_ids) {
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(cdiv(ng, 4)), dim3(256), 0, stream, s.cpart_d, s.cpart_i, ng, s.c_total, depth, col_ids,
+                       col_dists, (size_t)0);
+    VTC_LAUNCH_CHECK("col_topk merge");
+  }
+  return 0;
+}
 
-struct FallbackWs {       // scratch of the chunked fp64 brute force (exact_fallback_chunk_kernel)
-  double *part_d;
-  int *part_i;
-};
-struct Rescan {           // the block-minima planes an uncertified owner is re-read from (block_rescan_kernel)
-  const unsigned *keys;
-  int R, nblk, bw, nbs, n_src;
-  const int *src_base;
-  const float *theta;
-};
-static int exact_finish(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int cdepth, const int64_t *cand,
-                        const float *cand_d, const float *qn, const float *gn, float *gmax, int *flags, int64_t *ids, float *dists,
-                        hipStream_t stream, const int *cand_n, const FallbackWs *fb, const Rescan *rs = nullptr);
+// EXACT tail of the split-bf16 candidate lists (galleries under 1 024 rows, depth over 32): re-rank the lists with fp64 distances,
+// accept the rows whose list provably holds the true top-k, recompute the others by fp64 brute force.  qn / gn: fp32 squared norms
+// of the queries / gallery rows.
+static int exact_finish_lists(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int cdepth, const int64_t *cand,
+                              const float *cand_d, const float *qn, const float *gn, float *gmax, int *flags, int64_t *ids, float *dists,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, stream, gn, ng, gmax);
+  // worst-case error of a split-bf16 distance, relative to |q|^2 + max|g|^2.
+  // With u = 2^-8 (bf16's unit roundoff): x = hi + lo + r, |lo| <= u |x|, |r| <= u^2 |x|; the GEMM forms hi.hi + hi.lo + lo.hi,
+  // so the product misses lo.lo (u^2 |q||g|) and the two residual terms (2 u^2 |q||g|): 3 u^2 |q||g| <= 3 u^2 (|q|^2 + |g|^2) / 2,
+  // twice that on the distance = 3 * 2^-16 (rounds 1-2 had 3 * 2^-18); fp32 accumulation of 3 d products (3 d * 2^-24), fp32 row
+  // norms (d * 2^-24), the epilogue's three roundings.
+  const float kappa = 3.0f / 65536.0f + 4.0f * d / 16777216.0f + 1e-6f;
+  (void)hipMemsetAsync(flags, 0, sizeof(int), stream);
+  const RerankArgs ra{queries, gallery, nq, ng, d, cand, cand_d, cdepth, depth, qn, gmax, kappa, ids, dists, flags, nullptr};
+  {   // (work = bytes gathered at ~2 x depth candidates per row: the lists' lengths live on the device)
+    ProfScope prof(VTC_PROF_TOPK, (double)nq * (2.0 * depth + 1.0) * d * 4, stream);
+    hipLaunchKernelGGL(exact_rerank_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, stream, ra, ra, cdiv(nq, 4));
+  }
+  hipLaunchKernelGGL(exact_fallback_kernel, dim3(std::min(nq, 2048)), dim3(256), 0, stream, queries, gallery, ng, d, depth, flags, ids, dists);
+  VTC_LAUNCH_CHECK("l2_topk exact");
+  return 0;
+}
 
 // ---- VTC_SWEEP_EXACT, block-minima path ("v2") -----------------------------------------------------------------------
 // ONE plain-bf16 distance GEMM whose epilogue keeps, per (query, block of 64 gallery rows), the three smallest distances and
 // the fourth as a bound (gemm.hip, EPI_L2MIN) -- and, for vtc_l2_topk_bidir, the same per (gallery row, block of RB queries)
 // from the same accumulators; no N x N matrix is written or read.  minsel_kernel turns the block minima into a candidate set
 // that provably (given the per-entry error bound exact2_kappa, derived there) contains the query's true top-k (or says that it cannot), exact_rerank_kernel orders it by fp64 distances,
-// the uncertified queries are recomputed by fp64 brute force.
-namespace {
+// the uncertified queries are settled from their own planes (block_rescan_kernel).
 constexpr int RB2 = 128;      // queries per column block: the row block of the phased 256 x 256 tiles' waves
 bool exact2_enabled(int ng, int nq, int depth) { return depth <= 32 && ng >= 1024 && nq >= 1; }
 constexpr int CD2 = 64;       // capacity of a candidate list of the block-minima path
@@ -1242,7 +1185,6 @@ struct Sweep2Ws {
   int *cand_n, *cand2_n;
   float *theta, *theta2;
   int *flags, *flags2;               // uncertified rows of the row / column direction (count + list)
-  FallbackWs fb;
   size_t total;
 };
 Sweep2Ws plan2(char *ws, int ng, int nq, int d, bool bidir) {
@@ -1273,8 +1215,6 @@ Sweep2Ws plan2(char *ws, int ng, int nq, int d, bool bidir) {
   }
   s.flags = (int *)take((size_t)(std::max(nq, bidir ? ng : 0) + 1) * 4);
   s.flags2 = bidir ? (int *)take((size_t)(ng + 1) * 4) : nullptr;
-  s.fb.part_d = (double *)take((size_t)FB_ROWS * FB_CHUNKS * FB_SLOT * 8);
-  s.fb.part_i = (int *)take((size_t)FB_ROWS * FB_CHUNKS * FB_SLOT * 4);
   s.total = off;
   return s;
 }
@@ -1666,103 +1606,165 @@ __global__ __launch_bounds__(64 * RK_FW) void recall_rank_finish_kernel(const Ra
   }
 }
 
+// ---- host side of the block-minima paths: the launches every entry point below is made of ------------------------------------------
+// Prologue of every block-minima entry point: norms, rounding-error statistics and their maxima of both sets in ONE launch (rounds 1-3:
+// six), which also zeroes up to two fallback counters.  round_operands: the bf16 operand rows too (false: statistics only -- the
+// operands were rounded by the ranks that ran the GEMMs, with this same rounding).
+void sweep_prologue(const Sweep2Ws &s, const float *queries, int nq, const float *gallery, int ng, int d, bool round_operands,
+                    hipStream_t stream, int *zero_a = nullptr, int *zero_b = nullptr) {
+  ProfScope prof(VTC_PROF_TOPK, (double)(nq + ng) * d * (round_operands ? 6 : 4), stream);
+  const PrepSide A{queries, round_operands ? s.qb : nullptr, s.qn, s.qst, s.qmax, nq}, B{gallery, round_operands ? s.gb : nullptr, s.gn, s.gst, s.gmax, ng};
+  launch_sweep_prep(A, B, d, s.pmax, stream, zero_a, zero_b);
+}
+
+// Finish of the CERTIFIED candidate lists (minsel_kernel): fp64 re-rank, then the uncertified owners are settled from their own planes
+// (block_rescan_kernel: no pass over the gallery).  One problem (B == nullptr) or both directions in one launch per stage (rounds 2-3:
+// two) -- the stages of the two directions are independent, and at 10k x 10k a direction alone leaves CUs idle (a re-rank wave per row).
+struct Certified {
+  RescanArgs rs;           // the direction's problem, key planes and outputs
+  const int64_t *cand;     // [R][CD2] candidate lists
+  const int *cand_n;       // their lengths (< 0: not certified)
+  int *flags;              // = rs.flags, writable: the re-rank lists the uncertified owners there
+};
+int certified_finish(const Certified &A, const Certified *B, hipStream_t stream) {
+  auto rerank_args = [](const Certified &c) {     // (certified lists carry no error bound: cand_d, qn, gmax and kappa are not read)
+    return RerankArgs{c.rs.queries, c.rs.gallery, c.rs.R, c.rs.ng, c.rs.d, c.cand, nullptr, CD2, c.rs.depth, nullptr, nullptr, 0.f,
+                      c.rs.ids, c.rs.dists, c.flags, c.cand_n};
+  };
+  const Certified &Bv = B ? *B : A;
+  // both counters: one fill (B's flags lie behind A's in the plan; the lists between them are rewritten anyway)
+  (void)hipMemsetAsync(A.flags, 0, (size_t)((char *)Bv.flags - (char *)A.flags) + sizeof(int), stream);
+  {   // (work = bytes gathered at ~2 x depth candidates per row: the lists' lengths live on the device)
+    ProfScope prof(VTC_PROF_TOPK, (double)(A.rs.R + (B ? B->rs.R : 0)) * (2.0 * A.rs.depth + 1.0) * A.rs.d * 4, stream);
+    const int na = cdiv(A.rs.R, 4), nb = B ? cdiv(B->rs.R, 4) : 0;
+    hipLaunchKernelGGL(exact_rerank_kernel, dim3(na + nb), dim3(256), 0, stream, rerank_args(A), rerank_args(Bv), na);
+  }
+  {
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    const int cap = B ? 1024 : 2048;
+    const int ga = std::min(A.rs.R, cap), gb = B ? std::min(B->rs.R, cap) : 0;
+    hipLaunchKernelGGL(block_rescan_kernel, dim3(ga + gb), dim3(256), 0, stream, A.rs, Bv.rs, ga);
+  }
+  VTC_LAUNCH_CHECK("l2_topk exact (certified lists)");
+  return 0;
+}
+
+// Sharded sweep: the column planes go to a [npl, nblk_pad, n_cols] buffer sized for the LARGEST shard; the row blocks this rank has no
+// rows for (shards differ by a row) hold +inf keys.
+void fill_absent_row_blocks(unsigned *colk, int npl, int nblk_pad, int nblk, int n_cols, hipStream_t stream) {
+  for (int pl = 0; pl < npl && nblk_pad > nblk; ++pl)
+    (void)hipMemsetD32Async((hipDeviceptr_t)(colk + ((size_t)pl * nblk_pad + nblk) * n_cols), VTC_L2MIN_INF, (size_t)(nblk_pad - nblk) * n_cols, stream);
+}
+
+// The C ABI's (k_vals, nk): one to four values, each in [1, k_limit]; unused slots are 0.  Returns 0, or 1 with the error set (as VTC_CHECK).
+struct KList {
+  int k[4], nk, kmax;
+};
+int read_k(KList &kl, const char *fn, const int *k_vals, int nk, int k_limit) {
+  VTC_CHECK(k_vals && nk >= 1 && nk <= 4, "%s: nk=%d must be in [1, 4]", fn, nk);
+  kl = KList{{0, 0, 0, 0}, nk, 0};
+  for (int i = 0; i < nk; ++i) {
+    VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= k_limit, "%s: k=%d outside [1, %d]", fn, k_vals[i], k_limit);
+    kl.k[i] = k_vals[i];
+    kl.kmax = std::max(kl.kmax, k_vals[i]);
+  }
+  return 0;
+}
+
+// The ROW direction of a plan2 workspace: the owners are the GEMM's rows (its queries), their keys s.rowk in blocks of 64 rows of the
+// other side.  The column direction and the sharded column finish start from this and re-assign, by name, what differs.
+RankArgs rank_args(const Sweep2Ws &s, const float *own, const float *other, int R, int ng, int d, int tgt_off, const KList &kl,
+                   unsigned long long *hits) {
+  static_assert(RK_WORK * sizeof(int) <= CD2 * sizeof(int64_t) && 3 + 2 * RK_UB + RK_AMB <= RK_WORK, "a deferred row's lists fit its candidate-list slot");
+  RankArgs r;
+  r.keys = s.rowk; r.R = R; r.nblk = s.nblk_c; r.bw = 64;
+  r.nsrc = 1; r.bounds = nullptr; r.tgt_off = tgt_off;
+  r.own = own; r.other = other; r.ng = ng; r.d = d;
+  r.own_norm = s.qn; r.own_st = s.qst; r.other_max = s.gmax; r.kappa = exact2_kappa(d);
+  r.kmax = kl.kmax; r.nk = kl.nk;
+  for (int i = 0; i < 4; ++i) r.k[i] = kl.k[i];
+  r.hits = hits; r.flags = s.flags;
+  r.work = (int *)s.cand;
+  r.part = s.cand_n; r.nparts = cdiv(R, RK_OW);            // (4 ints per workgroup in the cand_n array: R / 8 <= R)
+  return r;
+}
+
+// recall_rank_kernel + recall_rank_finish_kernel (the fallback launch, normally empty) for one direction (B == nullptr: the second
+// argument block is not used, every workgroup is "first") or both in one launch per stage.  npl_*: key planes per block of the direction;
+// both directions run as <2, 2>, <2, 3> or <4, 4> (EPI_L2MIN2 / L2MIN3 / L2MIN), a single one as <npl, npl>.
+void launch_rank(const RankArgs &A, int npl_a, const RankArgs *B, int npl_b, hipStream_t stream) {
+  const RankArgs &Bv = B ? *B : A;
+  if (!B) npl_b = npl_a;
+  {
+    double work = (double)npl_a * A.nsrc * A.nblk * A.R * 4 + 2.0 * A.R * A.d * 4;
+    if (B) work += (double)npl_b * B->nsrc * B->nblk * B->R * 4 + 2.0 * B->R * B->d * 4;
+    ProfScope prof(VTC_PROF_TOPK, work, stream);
+    const int na = cdiv(A.R, RK_OW), nb = B ? cdiv(B->R, RK_OW) : 0;
+    auto kernel = npl_a == 4 ? recall_rank_kernel<4, 4> : npl_a == 3 ? recall_rank_kernel<3, 3> : npl_b == 3 ? recall_rank_kernel<2, 3> : recall_rank_kernel<2, 2>;
+    hipLaunchKernelGGL(kernel, dim3(na + nb), dim3(256), 0, stream, A, Bv, na);
+  }
+  {
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    const int ga = std::min(A.R, 1024), gb = B ? std::min(B->R, 1024) : 0;
+    hipLaunchKernelGGL(recall_rank_finish_kernel, dim3(ga + gb), dim3(64 * RK_FW), 0, stream, A, Bv, ga);
+  }
+}
+
 // gallery a [na], queries b [nb]; ids_a2b != nullptr: also the transposed direction
 // colk_out != NULL (sharded sweep, rank-local rows): the column planes go to the caller's [4, nblk_r_pad, na] buffer and the
 // column direction is NOT finished here (vtc_l2_sweep_shard_cols does, after the exchange)
 int exact2_impl(const float *a, const float *b, int na, int nb, int d, int depth, int64_t *ids_b2a, float *dists_b2a, int64_t *ids_a2b,
                 float *dists_a2b, const Sweep2Ws &s, hipStream_t stream, unsigned *colk_out = nullptr, int nblk_r_pad = 0) {
-  {   // norms, bf16 operands, rounding-error statistics and their maxima of both sets: one launch (rounds 1-3: six)
-    ProfScope prof(VTC_PROF_TOPK, (double)(na + nb) * d * 6, stream);
-    const PrepSide A{b, s.qb, s.qn, s.qst, s.qmax, nb}, B{a, s.gb, s.gn, s.gst, s.gmax, na};
-    launch_sweep_prep(A, B, d, s.pmax, stream);
-  }
+  sweep_prologue(s, b, nb, a, na, d, true, stream);
   VTC_LAUNCH_CHECK("l2_topk prologue");
   GemmEpi e;
   e.mode = EPI_L2MIN; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
   e.rowk = s.rowk; e.colk = ids_a2b ? s.colk : nullptr; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r;
   if (colk_out) {
     e.colk = colk_out; e.nblk_r = nblk_r_pad;
-    // blocks this rank has no rows for (shards differ by a row): +inf keys
-    for (int pl = 0; pl < L2MIN_PLANES && nblk_r_pad > s.nblk_r; ++pl)
-      (void)hipMemsetD32Async((hipDeviceptr_t)(colk_out + ((size_t)pl * nblk_r_pad + s.nblk_r) * na), 0x7F800000,
-                              (size_t)(nblk_r_pad - s.nblk_r) * na, stream);
+    fill_absent_row_blocks(colk_out, L2MIN_PLANES, nblk_r_pad, s.nblk_r, na, stream);
   }
   if (int rc = launch_gemm(s.qb, s.gb, nullptr, nullptr, nb, na, d, VTC_BF16, e, stream)) return rc;
   const float kappa = exact2_kappa(d);
   const MinselArgs m1 = minsel_args(s.rowk, nb, s.nblk_c, 64, s.nblk_c, nullptr, depth, s.qn, s.qst, s.gmax, kappa, s.cand, s.cand_n, s.theta);
-  const Rescan rs1{s.rowk, nb, s.nblk_c, 64, s.nblk_c, 1, nullptr, s.theta};
+  const Certified c1{{b, a, na, d, depth, s.flags, s.rowk, nb, s.nblk_c, 64, s.nblk_c, 1, nullptr, s.theta, ids_b2a, dists_b2a}, s.cand, s.cand_n, s.flags};
   if (!ids_a2b) {
     {
       ProfScope prof(VTC_PROF_TOPK, (double)(L2MIN_PLANES + 1) * s.nblk_c * nb * 4, stream);
       launch_minsel(m1, nullptr, stream);
     }
     VTC_LAUNCH_CHECK("minsel");
-    return exact_finish(a, b, na, nb, d, depth, CD2, s.cand, nullptr, s.qn, s.gn, s.gmax, s.flags, ids_b2a, dists_b2a, stream, s.cand_n, &s.fb, &rs1);
+    return certified_finish(c1, nullptr, stream);
   }
-  // both directions: ONE launch per stage (rounds 2-3: two) -- the stages of the two directions are independent, and at 10k x 10k
-  // a direction alone leaves CUs idle (313 minsel workgroups, a re-rank wave per row)
+  // both directions: ONE launch per stage (at 10k x 10k a direction alone is 313 minsel workgroups)
   const MinselArgs m2 = minsel_args(s.colk, na, s.nblk_r, RB2, s.nblk_r, nullptr, depth, s.gn, s.gst, s.qmax, kappa, s.cand2, s.cand2_n, s.theta2);
+  const Certified c2{{a, b, nb, d, depth, s.flags2, s.colk, na, s.nblk_r, RB2, s.nblk_r, 1, nullptr, s.theta2, ids_a2b, dists_a2b}, s.cand2, s.cand2_n, s.flags2};
   {
     ProfScope prof(VTC_PROF_TOPK, (double)(L2MIN_PLANES + 1) * ((double)s.nblk_c * nb + (double)s.nblk_r * na) * 4, stream);
     launch_minsel(m1, &m2, stream);
   }
   VTC_LAUNCH_CHECK("minsel");
-  (void)hipMemsetAsync(s.flags, 0, (size_t)((char *)s.flags2 - (char *)s.flags) + sizeof(int), stream);     // both counters: one fill (the lists between them are rewritten anyway)
-  const RerankArgs r1{b, a, nb, na, d, s.cand, nullptr, CD2, depth, s.qn, s.gmax, 0.f, ids_b2a, dists_b2a, s.flags, s.cand_n};
-  const RerankArgs r2{a, b, na, nb, d, s.cand2, nullptr, CD2, depth, s.gn, s.qmax, 0.f, ids_a2b, dists_a2b, s.flags2, s.cand2_n};
-  {
-    ProfScope prof(VTC_PROF_TOPK, (double)(na + nb) * (2.0 * depth + 1.0) * d * 4, stream);
-    hipLaunchKernelGGL(exact_rerank_kernel, dim3(cdiv(nb, 4) + cdiv(na, 4)), dim3(256), 0, stream, r1, r2, cdiv(nb, 4));
-  }
-  {
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    const RescanArgs q1{b, a, na, d, depth, s.flags, s.rowk, nb, s.nblk_c, 64, s.nblk_c, 1, nullptr, s.theta, ids_b2a, dists_b2a};
-    const RescanArgs q2{a, b, nb, d, depth, s.flags2, s.colk, na, s.nblk_r, RB2, s.nblk_r, 1, nullptr, s.theta2, ids_a2b, dists_a2b};
-    const int g1 = std::min(nb, 1024), g2 = std::min(na, 1024);
-    hipLaunchKernelGGL(block_rescan_kernel, dim3(g1 + g2), dim3(256), 0, stream, q1, q2, g1);
-  }
-  VTC_LAUNCH_CHECK("l2_topk exact (both directions)");
-  return 0;
+  return certified_finish(c1, &c2, stream);
 }
 
 // R@K hit counters of BOTH directions of n paired rows (a_i <-> b_i) without the sorted lists: prologue, ONE distance GEMM, ONE
 // rank launch (+ the fallback launch, normally empty).  hits_b_from_a[j] += #{ i : rank of a_i among the a's for query b_i < k_j }
 // (= RecallAtK.compute(a, b)), hits_a_from_b the transposed direction (= compute(b, a)).
-int recall_bidir_impl(const float *a, const float *b, int n, int d, const int *k_vals, int nk, unsigned long long *hits_b_from_a,
+int recall_bidir_impl(const float *a, const float *b, int n, int d, const KList &kl, unsigned long long *hits_b_from_a,
                       unsigned long long *hits_a_from_b, const Sweep2Ws &s, hipStream_t stream) {
-  {
-    ProfScope prof(VTC_PROF_TOPK, (double)2 * n * d * 6, stream);
-    const PrepSide A{b, s.qb, s.qn, s.qst, s.qmax, n}, B{a, s.gb, s.gn, s.gst, s.gmax, n};
-    launch_sweep_prep(A, B, d, s.pmax, stream, s.flags, s.flags2);       // ... and the two fallback counters zeroed
-  }
+  sweep_prologue(s, b, n, a, n, d, true, stream, s.flags, s.flags2);
   VTC_LAUNCH_CHECK("l2_recall prologue");
-  int kmax = 0;
-  for (int i = 0; i < nk; ++i) kmax = std::max(kmax, k_vals[i]);
-  const int mode = recall_mode(kmax, n);
+  const int mode = recall_mode(kl.kmax, n);
   GemmEpi e;
   e.mode = mode; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
   e.rowk = s.rowk; e.colk = s.colk; e.nblk_c = s.nblk_c; e.nblk_r = s.nblk_r;
   if (int rc = launch_gemm(s.qb, s.gb, nullptr, nullptr, n, n, d, VTC_BF16, e, stream)) return rc;
-  const float kappa = exact2_kappa(d);
-  kmax = 0;
-  static_assert(RK_WORK * sizeof(int) <= CD2 * sizeof(int64_t) && 3 + 2 * RK_UB + RK_AMB <= RK_WORK, "a deferred row's lists fit its candidate-list slot");
-  const int nwg = cdiv(n, RK_OW);            // (4 ints per workgroup in the cand_n arrays: n / 8 <= n)
-  RankArgs r1{s.rowk, n, s.nblk_c, 64, 1, nullptr, 0, b, a, n, d, s.qn, s.qst, s.gmax, kappa, 0, nk, {0, 0, 0, 0}, hits_b_from_a, s.flags, (int *)s.cand, s.cand_n, nwg};
-  RankArgs r2{s.colk, n, s.nblk_r, RB2, 1, nullptr, 0, a, b, n, d, s.gn, s.gst, s.qmax, kappa, 0, nk, {0, 0, 0, 0}, hits_a_from_b, s.flags2, (int *)s.cand2, s.cand2_n, nwg};
-  for (int i = 0; i < nk; ++i) { r1.k[i] = r2.k[i] = k_vals[i]; kmax = std::max(kmax, k_vals[i]); }
-  r1.kmax = r2.kmax = kmax;
-  {
-    ProfScope prof(VTC_PROF_TOPK, ((double)l2min_row_planes(mode) * s.nblk_c + (double)l2min_col_planes(mode) * s.nblk_r) * n * 4 + 4.0 * n * d * 4, stream);
-    const int nb = cdiv(n, RK_OW);
-    if (mode == EPI_L2MIN2) hipLaunchKernelGGL((recall_rank_kernel<2, 2>), dim3(2 * nb), dim3(256), 0, stream, r1, r2, nb);
-    else if (mode == EPI_L2MIN3) hipLaunchKernelGGL((recall_rank_kernel<2, 3>), dim3(2 * nb), dim3(256), 0, stream, r1, r2, nb);
-    else hipLaunchKernelGGL((recall_rank_kernel<4, 4>), dim3(2 * nb), dim3(256), 0, stream, r1, r2, nb);
-  }
-  {
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    const int g = std::min(n, 1024);
-    hipLaunchKernelGGL(recall_rank_finish_kernel, dim3(2 * g), dim3(64 * RK_FW), 0, stream, r1, r2, g);
-  }
+  const RankArgs r1 = rank_args(s, b, a, n, n, d, 0, kl, hits_b_from_a);
+  RankArgs r2 = rank_args(s, a, b, n, n, d, 0, kl, hits_a_from_b);      // the column direction: the other side's planes, statistics and scratch
+  r2.keys = s.colk; r2.nblk = s.nblk_r; r2.bw = RB2;
+  r2.own_norm = s.gn; r2.own_st = s.gst; r2.other_max = s.qmax;
+  r2.flags = s.flags2; r2.work = (int *)s.cand2; r2.part = s.cand2_n;
+  launch_rank(r1, l2min_row_planes(mode), &r2, l2min_col_planes(mode), stream);
   VTC_LAUNCH_CHECK("l2_recall_bidir");
   return 0;
 }
@@ -1804,51 +1806,22 @@ extern "C" int vtc_l2_sweep_shard_cols(const float *b_all, const float *a_local,
   VTC_CHECK(vtc_l2_sweep_shard_supported(n_total, n_local, depth) && n_src >= 1 && nblk_pad >= 1,
             "l2_sweep_shard_cols: unsupported shape (n_total=%d n_local=%d depth=%d n_src=%d)", n_total, n_local, depth, n_src);
   VTC_CHECK(ws_bytes >= vtc_l2_sweep_shard_workspace_bytes(n_total, n_local, d), "l2_sweep_shard_cols: workspace too small");
-  // gallery = b_all (n_total), queries = a_local (n_local): the plan's qn/gn/cand/flags/fallback areas fit as they are
+  // gallery = b_all (n_total), queries = a_local (n_local): the plan's qn/gn/cand/flags areas fit as they are
   Sweep2Ws s = plan2((char *)ws, n_total, n_local, d, false);
-  {   // statistics only (the operands were rounded by the ranks that ran the GEMMs -- with this same rounding)
-    ProfScope prof(VTC_PROF_TOPK, (double)(n_total + n_local) * d * 4, stream);
-    const PrepSide A{a_local, nullptr, s.qn, s.qst, s.qmax, n_local}, B{b_all, nullptr, s.gn, s.gst, s.gmax, n_total};
-    launch_sweep_prep(A, B, d, s.pmax, stream);
-  }
-  const float kappa = exact2_kappa(d);
+  sweep_prologue(s, a_local, n_local, b_all, n_total, d, false, stream);
   {
     ProfScope prof(VTC_PROF_TOPK, (double)(L2MIN_PLANES + 1) * n_src * nblk_pad * n_local * 4, stream);
-    const MinselArgs m = minsel_args(planes, n_local, n_src * nblk_pad, RB2, nblk_pad, src_base, depth, s.qn, s.qst, s.gmax, kappa, s.cand, s.cand_n, s.theta);
+    const MinselArgs m = minsel_args(planes, n_local, n_src * nblk_pad, RB2, nblk_pad, src_base, depth, s.qn, s.qst, s.gmax, exact2_kappa(d), s.cand, s.cand_n, s.theta);
     launch_minsel(m, nullptr, stream);
   }
   VTC_LAUNCH_CHECK("minsel shard cols");
-  const Rescan rs{planes, n_local, n_src * nblk_pad, RB2, nblk_pad, n_src, src_base, s.theta};
-  return exact_finish(b_all, a_local, n_total, n_local, d, depth, CD2, s.cand, nullptr, s.qn, s.gn, s.gmax, s.flags, ids, dists, stream,
-                      s.cand_n, &s.fb, &rs);
+  const Certified c{{a_local, b_all, n_total, d, depth, s.flags, planes, n_local, n_src * nblk_pad, RB2, nblk_pad, n_src, src_base, s.theta, ids, dists}, s.cand, s.cand_n, s.flags};
+  return certified_finish(c, nullptr, stream);
 }
 
 // ---- the same exchange with the recall-only finish (round 5): hit counters instead of sorted lists ---------------------------
-// One direction of recall_rank_kernel + recall_rank_finish_kernel (the second argument block is not used: every workgroup is "first").
-static void launch_rank_one(const RankArgs &r, int npl, hipStream_t stream) {
-  {
-    ProfScope prof(VTC_PROF_TOPK, (double)npl * r.nsrc * r.nblk * r.R * 4 + 2.0 * r.R * r.d * 4, stream);
-    const int nb = cdiv(r.R, RK_OW);
-    if (npl == 2) hipLaunchKernelGGL((recall_rank_kernel<2, 2>), dim3(nb), dim3(256), 0, stream, r, r, nb);
-    else if (npl == 3) hipLaunchKernelGGL((recall_rank_kernel<3, 3>), dim3(nb), dim3(256), 0, stream, r, r, nb);
-    else hipLaunchKernelGGL((recall_rank_kernel<4, 4>), dim3(nb), dim3(256), 0, stream, r, r, nb);
-  }
-  {
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    const int g = std::min(r.R, 1024);
-    hipLaunchKernelGGL(recall_rank_finish_kernel, dim3(g), dim3(64 * RK_FW), 0, stream, r, r, g);
-  }
-}
-
-static int fill_k(RankArgs &r, const int *k_vals, int nk) {
-  r.nk = nk; r.kmax = 0;
-  for (int i = 0; i < 4; ++i) r.k[i] = 0;
-  for (int i = 0; i < nk; ++i) { r.k[i] = k_vals[i]; r.kmax = std::max(r.kmax, k_vals[i]); }
-  return r.kmax;
-}
-
 extern "C" int vtc_l2_recall_planes(const int *k_vals, int nk, int n_total) {
-  int kmax = 0;
+  int kmax = 0;                                                // (a size query: no validation, the launches do that)
   for (int i = 0; k_vals && i < nk; ++i) kmax = std::max(kmax, k_vals[i]);
   return l2min_col_planes(recall_mode(kmax, n_total));       // (the planes that travel: the column direction's)
 }
@@ -1864,31 +1837,21 @@ extern "C" int vtc_l2_recall_shard_rows(const float *a_all, const float *b_local
   VTC_CHECK(a_all && b_local && k_vals && hits_b_from_a && col_planes && ws, "l2_recall_shard_rows: null argument");
   VTC_CHECK(vtc_l2_recall_shard_supported(n_total, n_local, d), "l2_recall_shard_rows: unsupported shape (n_total=%d n_local=%d d=%d)", n_total, n_local, d);
   VTC_CHECK(row_base >= 0 && row_base + n_local <= n_total, "l2_recall_shard_rows: rows [%d, %d) outside [0, %d)", row_base, row_base + n_local, n_total);
-  VTC_CHECK(nk >= 1 && nk <= 4, "l2_recall_shard_rows: nk=%d must be in 1..4", nk);
-  for (int i = 0; i < nk; ++i) VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= n_total, "l2_recall_shard_rows: k=%d must be in 1..%d", k_vals[i], n_total);
+  KList kl;
+  if (int rc = read_k(kl, "l2_recall_shard_rows", k_vals, nk, n_total)) return rc;
   Sweep2Ws s = plan2((char *)ws, n_total, n_local, d, false);
   VTC_CHECK(nblk_pad >= s.nblk_r, "l2_recall_shard_rows: nblk_pad=%d < %d row blocks", nblk_pad, s.nblk_r);
   VTC_CHECK(ws_bytes >= vtc_l2_sweep_shard_workspace_bytes(n_total, n_local, d), "l2_recall_shard_rows: workspace too small");
-  {
-    ProfScope prof(VTC_PROF_TOPK, (double)(n_total + n_local) * d * 6, stream);
-    const PrepSide A{b_local, s.qb, s.qn, s.qst, s.qmax, n_local}, B{a_all, s.gb, s.gn, s.gst, s.gmax, n_total};
-    launch_sweep_prep(A, B, d, s.pmax, stream, s.flags, nullptr);
-  }
+  sweep_prologue(s, b_local, n_local, a_all, n_total, d, true, stream, s.flags);
   VTC_LAUNCH_CHECK("l2_recall_shard_rows prologue");
-  int kmax = 0;
-  for (int i = 0; i < nk; ++i) kmax = std::max(kmax, k_vals[i]);
-  const int mode = recall_mode(kmax, n_total), npl = l2min_col_planes(mode);
+  const int mode = recall_mode(kl.kmax, n_total);
   GemmEpi e;
   e.mode = mode; e.out_dtype = VTC_F32; e.rown = s.qn; e.coln = s.gn;
   e.rowk = s.rowk; e.colk = col_planes; e.nblk_c = s.nblk_c; e.nblk_r = nblk_pad;
-  for (int pl = 0; pl < npl && nblk_pad > s.nblk_r; ++pl)     // blocks this rank has no rows for (shards differ by a row): +inf keys
-    (void)hipMemsetD32Async((hipDeviceptr_t)(col_planes + ((size_t)pl * nblk_pad + s.nblk_r) * n_total), 0x7F800000,
-                            (size_t)(nblk_pad - s.nblk_r) * n_total, stream);
+  fill_absent_row_blocks(col_planes, l2min_col_planes(mode), nblk_pad, s.nblk_r, n_total, stream);
   if (int rc = launch_gemm(s.qb, s.gb, nullptr, nullptr, n_local, n_total, d, VTC_BF16, e, stream)) return rc;
-  RankArgs r{s.rowk, n_local, s.nblk_c, 64, 1, nullptr, row_base, b_local, a_all, n_total, d, s.qn, s.qst, s.gmax, exact2_kappa(d), 0, nk, {0, 0, 0, 0},
-             (unsigned long long *)hits_b_from_a, s.flags, (int *)s.cand, s.cand_n, cdiv(n_local, RK_OW)};
-  fill_k(r, k_vals, nk);
-  launch_rank_one(r, l2min_row_planes(mode), stream);
+  const RankArgs r = rank_args(s, b_local, a_all, n_local, n_total, d, row_base, kl, (unsigned long long *)hits_b_from_a);
+  launch_rank(r, l2min_row_planes(mode), nullptr, 0, stream);
   VTC_LAUNCH_CHECK("l2_recall_shard_rows");
   return 0;
 }
@@ -1901,23 +1864,15 @@ extern "C" int vtc_l2_recall_shard_cols(const float *b_all, const float *a_local
   VTC_CHECK(vtc_l2_recall_shard_supported(n_total, n_local, d) && n_src >= 1 && nblk_pad >= 1,
             "l2_recall_shard_cols: unsupported shape (n_total=%d n_local=%d d=%d n_src=%d)", n_total, n_local, d, n_src);
   VTC_CHECK(row_base >= 0 && row_base + n_local <= n_total, "l2_recall_shard_cols: rows [%d, %d) outside [0, %d)", row_base, row_base + n_local, n_total);
-  VTC_CHECK(nk >= 1 && nk <= 4, "l2_recall_shard_cols: nk=%d must be in 1..4", nk);
-  for (int i = 0; i < nk; ++i) VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= n_total, "l2_recall_shard_cols: k=%d must be in 1..%d", k_vals[i], n_total);
+  KList kl;
+  if (int rc = read_k(kl, "l2_recall_shard_cols", k_vals, nk, n_total)) return rc;
   VTC_CHECK(ws_bytes >= vtc_l2_sweep_shard_workspace_bytes(n_total, n_local, d), "l2_recall_shard_cols: workspace too small");
   // owners = a_local (this rank's columns of every source's GEMM), the other side = b_all: the plan's areas fit as they are
   Sweep2Ws s = plan2((char *)ws, n_total, n_local, d, false);
-  {   // statistics only (the operands were rounded by the ranks that ran the GEMMs -- with this same rounding)
-    ProfScope prof(VTC_PROF_TOPK, (double)(n_total + n_local) * d * 4, stream);
-    const PrepSide A{a_local, nullptr, s.qn, s.qst, s.qmax, n_local}, B{b_all, nullptr, s.gn, s.gst, s.gmax, n_total};
-    launch_sweep_prep(A, B, d, s.pmax, stream, s.flags, nullptr);
-  }
-  int kmax_ = 0;
-  for (int i = 0; i < nk; ++i) kmax_ = std::max(kmax_, k_vals[i]);
-  const int npl = l2min_col_planes(recall_mode(kmax_, n_total));
-  RankArgs r{planes, n_local, nblk_pad, RB2, n_src, src_bounds, row_base, a_local, b_all, n_total, d, s.qn, s.qst, s.gmax,
-             exact2_kappa(d), 0, nk, {0, 0, 0, 0}, (unsigned long long *)hits_a_from_b, s.flags, (int *)s.cand, s.cand_n, cdiv(n_local, RK_OW)};
-  fill_k(r, k_vals, nk);
-  launch_rank_one(r, npl, stream);
+  sweep_prologue(s, a_local, n_local, b_all, n_total, d, false, stream, s.flags);
+  RankArgs r = rank_args(s, a_local, b_all, n_local, n_total, d, row_base, kl, (unsigned long long *)hits_a_from_b);
+  r.keys = planes; r.nblk = nblk_pad; r.bw = RB2; r.nsrc = n_src; r.bounds = src_bounds;      // every source's planes of this rank's columns
+  launch_rank(r, l2min_col_planes(recall_mode(kl.kmax, n_total)), nullptr, 0, stream);
   VTC_LAUNCH_CHECK("l2_recall_shard_cols");
   return 0;
 }
@@ -1927,98 +1882,6 @@ extern "C" size_t vtc_l2_topk_workspace_bytes(int n_gallery, int n_queries, int 
   if (precision == VTC_SWEEP_EXACT && exact2_enabled(n_gallery, n_queries, 1))
     return std::max(v1, plan2(nullptr, n_gallery, n_queries, d, false).total);     // the depth decides at call time
   return v1;
-}
-
-// col_ids != nullptr: also the transposed direction (for every gallery row its nearest query rows), read off the same
-// distance blocks by col_topk_kernel.
-static int l2_topk_impl(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int precision,
-                        int64_t *ids, float *dists, const SweepWs &s, hipStream_t stream, int64_t *col_ids = nullptr,
-                        float *col_dists = nullptr) {
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, stream, queries, s.qn, nq, d);
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(ng, 4)), dim3(256), 0, stream, gallery, s.gn, ng, d);
-  const int parts = precision == VTC_SWEEP_BF16X3 ? 3 : 1;
-  if (precision != VTC_SWEEP_F32) {
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)nq * d + 255) / 256)), dim3(256), 0, stream, queries, s.qb, nq, d, parts, 0);
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)ng * d + 255) / 256)), dim3(256), 0, stream, gallery, s.gb, ng, d, parts, 1);
-  }
-  VTC_LAUNCH_CHECK("l2_topk prologue");
-  for (int r0 = 0; r0 < nq; r0 += s.rows_per_block) {
-    const int rows = min(s.rows_per_block, nq - r0);
-    GemmEpi e;
-    e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
-    int rc;
-    if (precision == VTC_SWEEP_F32)
-      rc = launch_gemm(queries + (size_t)r0 * d, gallery, nullptr, s.dist, rows, ng, d, VTC_F32, e, stream);
-    else
-      rc = launch_gemm(s.qb + (size_t)r0 * d * parts, s.gb, nullptr, s.dist, rows, ng, d * parts, VTC_BF16, e, stream);
-    if (rc) return rc;
-    {
-      // enough (row, segment) waves to fill the chip (32 waves per CU)
-      // (every segment pays its own warm-up insertions, so segments are used only when rows alone cannot fill the chip)
-      int S = cdiv(8192, rows);
-      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
-      int seg_cols = cdiv(cdiv(ng, S), 1024) * 1024;
-      S = cdiv(ng, seg_cols);
-      ProfScope prof(VTC_PROF_TOPK, (double)rows * ng * 4, stream);
-      hipLaunchKernelGGL(row_topk_kernel, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, ng, rows, ng, depth, S, seg_cols, ids,
-                         dists, (size_t)r0, s.part_d, s.part_i);
-      if (S > 1)
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, s.part_d, s.part_i, rows, S, depth, ids, dists,
-                           (size_t)r0);
-    }
-    VTC_LAUNCH_CHECK("row_topk");
-    if (col_ids) {
-      const int seg_rows = cdiv(cdiv(rows, s.c_seg), 64) * 64;
-      ProfScope prof(VTC_PROF_TOPK, (double)rows * ng * 4, stream);
-      hipLaunchKernelGGL(col_topk_kernel, dim3(cdiv(ng, 64) * s.c_seg), dim3(256), 0, stream, s.dist, ng, rows, ng, depth, r0, s.c_seg,
-                         seg_rows, s.c_total, 0, r0 > 0 ? 1 : 0, s.cpart_d, s.cpart_i);
-      VTC_LAUNCH_CHECK("col_topk");
-    }
-  }
-  if (col_ids) {
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(cdiv(ng, 4)), dim3(256), 0, stream, s.cpart_d, s.cpart_i, ng, s.c_total, depth, col_ids,
-                       col_dists, (size_t)0);
-    VTC_LAUNCH_CHECK("col_topk merge");
-  }
-  return 0;
-}
-
-// EXACT tail: re-rank the candidate lists with fp64 distances, accept the rows whose list provably holds the true
-// top-k, recompute the others by fp64 brute force.  qn / gn: fp32 squared norms of the queries / gallery rows.
-static int exact_finish(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int cdepth, const int64_t *cand,
-                        const float *cand_d, const float *qn, const float *gn, float *gmax, int *flags, int64_t *ids, float *dists,
-                        hipStream_t stream, const int *cand_n, const FallbackWs *fb, const Rescan *rs) {
-  if (!cand_n) hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, stream, gn, ng, gmax);
-  // split-bf16 candidate lists (cand_n == nullptr): worst-case error of a split-bf16 distance, relative to |q|^2 + max|g|^2.
-  // With u = 2^-8 (bf16's unit roundoff): x = hi + lo + r, |lo| <= u |x|, |r| <= u^2 |x|; the GEMM forms hi.hi + hi.lo + lo.hi,
-  // so the product misses lo.lo (u^2 |q||g|) and the two residual terms (2 u^2 |q||g|): 3 u^2 |q||g| <= 3 u^2 (|q|^2 + |g|^2) / 2,
-  // twice that on the distance = 3 * 2^-16 (rounds 1-2 had 3 * 2^-18); fp32 accumulation of 3 d products (3 d * 2^-24), fp32 row
-  // norms (d * 2^-24), the epilogue's three roundings.  (Block-minima lists arrive certified.)
-  const float kappa = 3.0f / 65536.0f + 4.0f * d / 16777216.0f + 1e-6f;
-  (void)hipMemsetAsync(flags, 0, sizeof(int), stream);
-  const RerankArgs ra{queries, gallery, nq, ng, d, cand, cand_d, cdepth, depth, qn, gmax, kappa, ids, dists, flags, cand_n};
-  {   // (work = bytes gathered at ~2 x depth candidates per row: the lists' lengths live on the device)
-    ProfScope prof(VTC_PROF_TOPK, (double)nq * (2.0 * depth + 1.0) * d * 4, stream);
-    hipLaunchKernelGGL(exact_rerank_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, stream, ra, ra, cdiv(nq, 4));
-  }
-  int f_first = 0;
-  if (rs) {     // block-minima path: the uncertified owners are settled from their own planes (no pass over the gallery)
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    const RescanArgs rr{queries, gallery, ng, d, depth, flags, rs->keys, rs->R, rs->nblk, rs->bw, rs->nbs, rs->n_src, rs->src_base, rs->theta, ids, dists};
-    hipLaunchKernelGGL(block_rescan_kernel, dim3(std::min(nq, 2048)), dim3(256), 0, stream, rr, rr, std::min(nq, 2048));
-    VTC_LAUNCH_CHECK("l2_topk block rescan");
-    return 0;
-  }
-  if (fb) {     // the first FB_ROWS uncertified rows: every row spread over FB_CHUNKS workgroups
-    hipLaunchKernelGGL(exact_fallback_chunk_kernel, dim3(16, FB_CHUNKS), dim3(256), 0, stream, queries, gallery, ng, d, depth, flags, fb->part_d,
-                       fb->part_i);
-    hipLaunchKernelGGL(exact_fallback_merge_kernel, dim3(64), dim3(256), 0, stream, depth, flags, fb->part_d, fb->part_i, ids, dists);
-    f_first = FB_ROWS;
-  }
-  hipLaunchKernelGGL(exact_fallback_kernel, dim3(std::min(nq, 2048)), dim3(256), 0, stream, queries, gallery, ng, d, depth, flags, ids,
-                     dists, f_first);
-  VTC_LAUNCH_CHECK("l2_topk exact");
-  return 0;
 }
 
 extern "C" int vtc_l2_topk(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int precision,
@@ -2039,7 +1902,7 @@ extern "C" int vtc_l2_topk(const float *gallery, const float *queries, int ng, i
   // EXACT: BF16X3 candidate lists, fp64 re-rank, verified superset property, fp64 brute force for the rest
   const int cdepth = exact_cdepth(depth, ng);
   if (int rc = l2_topk_impl(gallery, queries, ng, nq, d, cdepth, VTC_SWEEP_BF16X3, s.cand, s.cand_d, s, stream)) return rc;
-  return exact_finish(gallery, queries, ng, nq, d, depth, cdepth, s.cand, s.cand_d, s.qn, s.gn, s.gmax, s.flags, ids, dists, stream, nullptr, nullptr);
+  return exact_finish_lists(gallery, queries, ng, nq, d, depth, cdepth, s.cand, s.cand_d, s.qn, s.gn, s.gmax, s.flags, ids, dists, stream);
 }
 
 // Both retrieval directions of RecallAtK (a -> b and b -> a, evaluation/eval.py:117-127) from ONE distance matrix
@@ -2073,23 +1936,18 @@ extern "C" int vtc_l2_topk_bidir(const float *a, const float *b, int n_a, int n_
   }
   const int cdepth = std::min(exact_cdepth(depth, n_a), exact_cdepth(depth, n_b));
   if (int rc = l2_topk_impl(a, b, n_a, n_b, d, cdepth, VTC_SWEEP_BF16X3, s.cand, s.cand_d, s, stream, s.cand2, s.cand2_d)) return rc;
-  if (int rc = exact_finish(a, b, n_a, n_b, d, depth, cdepth, s.cand, s.cand_d, s.qn, s.gn, s.gmax, s.flags, ids_b2a, dists_b2a, stream, nullptr, nullptr))
-    return rc;
-  return exact_finish(b, a, n_b, n_a, d, depth, cdepth, s.cand2, s.cand2_d, s.gn, s.qn, s.qmax, s.flags, ids_a2b, dists_a2b, stream, nullptr, nullptr);
+  if (int rc = exact_finish_lists(a, b, n_a, n_b, d, depth, cdepth, s.cand, s.cand_d, s.qn, s.gn, s.gmax, s.flags, ids_b2a, dists_b2a, stream)) return rc;
+  return exact_finish_lists(b, a, n_b, n_a, d, depth, cdepth, s.cand2, s.cand2_d, s.gn, s.qn, s.qmax, s.flags, ids_a2b, dists_a2b, stream);
 }
 
 extern "C" int vtc_recall_hits(const int64_t *ids, int nq, int depth, int64_t target_offset, const int *k_vals, int nk,
                                long long *hits, void *stream) {
-  VTC_CHECK(nk >= 1 && nk <= 4, "recall_hits: nk=%d must be in [1,4]", nk);
-  int k[4] = {0, 0, 0, 0};
-  for (int i = 0; i < nk; ++i) {
-    VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= depth, "recall_hits: k=%d outside [1, depth=%d]", k_vals[i], depth);
-    k[i] = k_vals[i];
-  }
+  KList kl;
+  if (int rc = read_k(kl, "recall_hits", k_vals, nk, depth)) return rc;
   {
     ProfScope prof(VTC_PROF_TOPK, (double)nq * depth * 8, (hipStream_t)stream);
     hipLaunchKernelGGL(recall_hits_kernel, dim3(cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, ids, nq, depth, target_offset,
-                       k[0], k[1], k[2], k[3], nk, (unsigned long long *)hits, (const int64_t *)nullptr, (unsigned long long *)nullptr);
+                       kl.k[0], kl.k[1], kl.k[2], kl.k[3], nk, (unsigned long long *)hits, (const int64_t *)nullptr, (unsigned long long *)nullptr);
   }
   VTC_LAUNCH_CHECK("recall_hits");
   return 0;
@@ -2098,16 +1956,12 @@ extern "C" int vtc_recall_hits(const int64_t *ids, int nq, int depth, int64_t ta
 extern "C" int vtc_recall_hits_pair(const int64_t *ids_a, const int64_t *ids_b, int nq, int depth, int64_t target_offset, const int *k_vals,
                                     int nk, long long *hits_a, long long *hits_b, void *stream) {
   VTC_CHECK(ids_a && ids_b && hits_a && hits_b, "recall_hits_pair: null argument");
-  VTC_CHECK(nk >= 1 && nk <= 4, "recall_hits_pair: nk=%d must be in [1,4]", nk);
-  int k[4] = {0, 0, 0, 0};
-  for (int i = 0; i < nk; ++i) {
-    VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= depth, "recall_hits_pair: k=%d outside [1, depth=%d]", k_vals[i], depth);
-    k[i] = k_vals[i];
-  }
+  KList kl;
+  if (int rc = read_k(kl, "recall_hits_pair", k_vals, nk, depth)) return rc;
   {
     ProfScope prof(VTC_PROF_TOPK, 2.0 * nq * depth * 8, (hipStream_t)stream);
     hipLaunchKernelGGL(recall_hits_kernel, dim3(2 * cdiv(nq, 256)), dim3(256), 0, (hipStream_t)stream, ids_a, nq, depth, target_offset,
-                       k[0], k[1], k[2], k[3], nk, (unsigned long long *)hits_a, ids_b, (unsigned long long *)hits_b);
+                       kl.k[0], kl.k[1], kl.k[2], kl.k[3], nk, (unsigned long long *)hits_a, ids_b, (unsigned long long *)hits_b);
   }
   VTC_LAUNCH_CHECK("recall_hits_pair");
   return 0;
@@ -2119,11 +1973,11 @@ extern "C" int vtc_l2_recall_bidir(const float *a, const float *b, int n, int d,
                                    long long *hits_a_from_b, void *ws, size_t ws_bytes, void *stream) {
   VTC_CHECK(a && b && hits_b_from_a && hits_a_from_b && k_vals, "l2_recall_bidir: null argument");
   VTC_CHECK(vtc_l2_recall_bidir_supported(n, d), "l2_recall_bidir: n=%d must be >= 1024 and d=%d a multiple of 64 (else: vtc_l2_topk + vtc_recall_hits)", n, d);
-  VTC_CHECK(nk >= 1 && nk <= 4, "l2_recall_bidir: nk=%d must be in [1,4]", nk);
-  for (int i = 0; i < nk; ++i) VTC_CHECK(k_vals[i] >= 1 && k_vals[i] <= n, "l2_recall_bidir: k=%d outside [1, n=%d]", k_vals[i], n);
+  KList kl;
+  if (int rc = read_k(kl, "l2_recall_bidir", k_vals, nk, n)) return rc;
   Sweep2Ws s = plan2((char *)ws, n, n, d, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_recall_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return recall_bidir_impl(a, b, n, d, k_vals, nk, (unsigned long long *)hits_b_from_a, (unsigned long long *)hits_a_from_b, s, (hipStream_t)stream);
+  return recall_bidir_impl(a, b, n, d, kl, (unsigned long long *)hits_b_from_a, (unsigned long long *)hits_a_from_b, s, (hipStream_t)stream);
 }
 
 extern "C" int vtc_similarity(const float *v, const float *t, int nv, int nt, int d, const float *logit_scale, float *sim,

@@ -23,11 +23,15 @@ single-GPU search, bit for bit.  Works with "gloo" on CPU tensors for the collec
 """
 from __future__ import annotations
 
+import enum
 import os
 from typing import Callable, Optional, Sequence
 
 import torch
 import torch.distributed as dist
+
+from . import _lib as L
+from . import ops
 
 
 def init_from_env(backend: Optional[str] = None):
@@ -105,45 +109,53 @@ def all_gather_rows(x: torch.Tensor, n_total: int, rank: int, world: int) -> tor
     return torch.cat([out[r * mx: r * mx + (hi - lo)] for r, (lo, hi) in enumerate(sizes)])
 
 
-RANK_PATH = os.environ.get("VTC_SWEEP_RANK", "1") != "0"      # world 1, EXACT: hit counters without sorted lists (as host/metric.py RecallAtK.rank_path)
-RANK_MIN_ROWS = 1024
-BIDIR_MIN_ROWS = 5120       # as host/metric.py RecallAtK.bidir_min_rows (tools/bidir_threshold.py: EXACT 6k 0.49 vs 0.6+, 10k 0.64 vs 0.79 ms)
-BIDIR_MIN_ROWS_F32 = 3000
+RANK_PATH = os.environ.get("VTC_SWEEP_RANK", "1") != "0"      # EXACT: hit counters without sorted lists (read at import; RecallAtK.rank_path's default)
+RANK_MIN_ROWS = 1024        # the library's recall-only sweep takes n >= 1024
+BIDIR_MIN_ROWS = 5120       # tools/bidir_threshold.py: one matrix wins from ~5k rows (EXACT 6k 0.49 vs 0.6+, 10k 0.64 vs 0.79 ms)
+BIDIR_MIN_ROWS_F32 = 3000   # SWEEP_F32: the fp32-MFMA GEMM it saves is the expensive part at every size
 
 
-def one_matrix_sharded(n_total: int, precision: int, world: int, depth: int) -> bool:
-    """True when world > 1 ranks take the one-GEMM-per-rank path (VTC_SWEEP_EXACT, shapes the block-minima sweep covers;
-    VTC_SWEEP_SHARD_TWO=1 forces the two-search path)."""
-    if world <= 1 or precision != 3 or os.environ.get("VTC_SWEEP_SHARD_TWO") == "1":
-        return False
-    from . import ops
-    return all(ops.sweep_shard_supported(n_total, hi - lo, depth)
-               for lo, hi in (shard_bounds(n_total, r, world) for r in range(world)))
+class SweepPath(enum.Enum):
+    """The five ways an N x N sweep of both directions runs; the value is the label that `phases["path"]` and bench.py print."""
+    RANK = "one distance matrix, ranks of the paired rows (no sorted lists)"
+    ONE_MATRIX = "one distance matrix, row + column top-k"
+    RANK_SHARDED = "one [N/G, N] distance GEMM per rank, column block minima exchanged (all-to-all), ranks of the paired rows (no sorted lists)"
+    ONE_MATRIX_SHARDED = "one [N/G, N] distance GEMM per rank, column block minima exchanged (all-to-all)"
+    TWO_SEARCHES = "two searches per rank ([N/G, N] blocks)"
 
 
-def rank_sharded(n_total: int, d: int, precision: int, world: int, nk: int = 3) -> bool:
-    """True when world > 1 ranks take the one-GEMM-per-rank path with the recall-only finish (hit counters from the ranks of the paired
-    rows: no sorted lists; VTC_SWEEP_RANK=0 or VTC_SWEEP_SHARD_TWO=1 turn it off)."""
-    if world <= 1 or precision != 3 or not RANK_PATH or nk > 4 or os.environ.get("VTC_SWEEP_SHARD_TWO") == "1":
-        return False
-    from . import ops
-    return all(ops.recall_shard_supported(n_total, hi - lo, d) for lo, hi in (shard_bounds(n_total, r, world) for r in range(world)))
+def choose_sweep_path(n_total: int, d: int, precision: int, world: int, nk: int = 3, depth: int = 11, *, paired: bool = True,
+                      rank_path: Optional[bool] = None, bidir_min_rows: Optional[int] = None, bidir_min_rows_f32: Optional[int] = None,
+                      rank_min_rows: Optional[int] = None) -> SweepPath:
+    """THE decision which sweep a call takes (sharded_recall, RecallAtK.compute_both and sweep_path all ask here).  No tensors, no
+    collectives, no GPU: world 1 needs no library at all, world > 1 asks its host-only `*_shard_supported` once per shard size.
+    ``paired``: both embedding sets have the same shape.  The thresholds default to the constants above (RecallAtK passes its own
+    attributes).  VTC_SWEEP_SHARD_TWO=1 (read at CALL time: bench.py sets it mid-process) forces two searches at world > 1."""
+    rank_ok = (precision == L.SWEEP_EXACT and (RANK_PATH if rank_path is None else rank_path) and nk <= 4 and paired)
+    if world <= 1:
+        if rank_ok and n_total >= (RANK_MIN_ROWS if rank_min_rows is None else rank_min_rows) and d % 64 == 0:
+            return SweepPath.RANK
+        if precision == L.SWEEP_F32:
+            one = n_total >= (BIDIR_MIN_ROWS_F32 if bidir_min_rows_f32 is None else bidir_min_rows_f32)
+        else:
+            one = n_total >= (BIDIR_MIN_ROWS if bidir_min_rows is None else bidir_min_rows)
+        return SweepPath.ONE_MATRIX if one else SweepPath.TWO_SEARCHES
+    if precision != L.SWEEP_EXACT or os.environ.get("VTC_SWEEP_SHARD_TWO") == "1":
+        return SweepPath.TWO_SEARCHES
+    shards = {hi - lo for lo, hi in (shard_bounds(n_total, r, world) for r in range(world))}      # at most two sizes
+    if rank_ok and all(ops.recall_shard_supported(n_total, n_r, d) for n_r in shards):
+        return SweepPath.RANK_SHARDED
+    if all(ops.sweep_shard_supported(n_total, n_r, depth) for n_r in shards):
+        return SweepPath.ONE_MATRIX_SHARDED
+    return SweepPath.TWO_SEARCHES
 
 
 def sweep_path(n_total: int, precision: int, world: int, depth: int = 11, d: int = 512) -> str:
-    if world > 1 and rank_sharded(n_total, d, precision, world):
-        return "one [N/G, N] distance GEMM per rank, column block minima exchanged (all-to-all), ranks of the paired rows (no sorted lists)"
-    if world > 1:
-        return ("one [N/G, N] distance GEMM per rank, column block minima exchanged (all-to-all)"
-                if one_matrix_sharded(n_total, precision, world, depth) else "two searches per rank ([N/G, N] blocks)")
-    if precision == 3 and RANK_PATH and n_total >= RANK_MIN_ROWS:
-        return "one distance matrix, ranks of the paired rows (no sorted lists)"
-    one = n_total >= (BIDIR_MIN_ROWS_F32 if precision == 0 else BIDIR_MIN_ROWS)
-    return "one distance matrix, row + column top-k" if one else "two searches per rank ([N/G, N] blocks)"
+    """The label of the path that paired embeddings of this shape take with the usual three k values."""
+    return choose_sweep_path(n_total, d, precision, world, depth=depth).value
 
 
 _A2A_SEND: dict = {}      # exchange_column_planes' padded send buffer / pinned host staging buffers, by shape
-A2A_MODE = os.environ.get("VTC_A2A", "single")     # "single": one all_to_all_single on a padded [G, 4, nblk, max shard] buffer; "list": all_to_all on per-rank slices
 
 
 def exchange_column_planes(planes: torch.Tensor, n_total: int, rank: int, world: int) -> torch.Tensor:
@@ -159,11 +171,6 @@ def exchange_column_planes(planes: torch.Tensor, n_total: int, rank: int, world:
         raise ValueError(f"exchange_column_planes: planes must be a contiguous [P, nblk_pad, n_total = {n_total}] tensor, got "
                          f"{tuple(planes.shape)} (contiguous: {planes.is_contiguous()})")
     nccl = dist.get_backend() == "nccl"
-    if A2A_MODE == "list" and nccl:
-        send = [planes[:, :, a:b].contiguous() for a, b in bounds]
-        recv = planes.new_empty(world, P, NB, hi - lo)
-        dist.all_to_all(list(recv.unbind(0)), send)
-        return recv
     if all(b - a == mx for a, b in bounds):
         send = planes.reshape(P, NB, world, mx).permute(2, 0, 1, 3).contiguous()
     else:
@@ -199,7 +206,6 @@ def exchange_column_planes(planes: torch.Tensor, n_total: int, rank: int, world:
 
 def sweep_workspace_bytes(n_total: int, n_local: int, d: int, precision: int, world: int) -> int:
     """Bytes of caller-owned workspace that sharded_recall needs for this shape (largest of the paths it may take)."""
-    from . import _lib as L
     lib = L.lib()
     need = lib.vtc_l2_topk_workspace_bytes(n_total, n_local, d, precision, 0)
     if world == 1:
@@ -233,8 +239,7 @@ class _PhaseClock:
 
 
 def _exchange_name() -> str:
-    return (f"all_to_all{'' if A2A_MODE == 'list' else '_single'} (RCCL)" if dist.get_backend() == "nccl"
-            else f"all_to_all_single through host memory ({dist.get_backend()})")
+    return "all_to_all_single (RCCL)" if dist.get_backend() == "nccl" else f"all_to_all_single through host memory ({dist.get_backend()})"
 
 
 def gather_both(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_total: int, rank: int, world: int):
@@ -250,7 +255,6 @@ def gather_both(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_tota
 def _flag_nonfinite(flag: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
     """flag (one int64 slot behind the hit counters, so it travels with their all-reduce and D2H) |= 1 / 2 when a / b hold a NaN or inf."""
     if a.is_cuda:
-        from . import ops
         ops.nonfinite_flag2(a, b, flag)
     else:
         flag[0] = int(not bool(torch.isfinite(a).all())) | 2 * int(not bool(torch.isfinite(b).all()))
@@ -260,14 +264,12 @@ def _flag_nonfinite(flag: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
 def _world1_rank_path(a_all, b_all, ks, hits, ws, clock):
     """One rank owns every pair, EXACT: the hit counters come straight from the distance GEMM's key planes (vtc_l2_recall_bidir: the
     rank of each query's own gallery row; no sorted lists) -- what RecallAtK.compute_both does on one GPU."""
-    from . import ops
     ops.recall_bidir(a_all, b_all, ks, ws=ws, hits=hits)
     clock.mark("bidir_gemm_rank")
 
 
 def _world1_one_matrix(a_all, b_all, depth, precision, ws, clock):
     """One rank owns the whole matrix: the sorted ids of both directions from one distance GEMM (vtc_l2_topk_bidir)."""
-    from . import ops
     i1, _, i2, _ = ops.l2_topk_bidir(a_all, b_all, depth, precision=precision, return_dists=False, ws=ws)
     clock.mark("bidir_gemm_select")
     return i1, i2
@@ -277,7 +279,6 @@ def _rank_sharded(a_all, b_all, a_local, b_local, n_total, lo, ks, hits, rank, w
     """One [N/G, N] GEMM per rank, recall-only finish: this rank's hit counters of the row direction come with the GEMM, the column
     block minima go to the column owners (one all-to-all), whose rank launch counts the other direction."""
     if rank_ops is None:
-        from . import ops
         rank_ops = (lambda a_, b_, base, ks_, nbp, h: ops.recall_shard_rows(a_, b_, base, ks_, nbp, h, ws=ws),
                     lambda b_, a_, base, ks_, pl, sb, h: ops.recall_shard_cols(b_, a_, base, ks_, pl, sb, h, ws=ws), ops.sweep_row_block())
     rows_fn, cols_fn, rb = rank_ops
@@ -295,7 +296,6 @@ def _rank_sharded(a_all, b_all, a_local, b_local, n_total, lo, ks, hits, rank, w
 def _one_matrix_sharded(a_all, b_all, a_local, b_local, n_total, depth, rank, world, shard_ops, ws, clock):
     """One [N/G, N] GEMM per rank, sorted ids: rows finished locally, column block minima to the column owners, who certify + re-rank."""
     if shard_ops is None:
-        from . import ops
         shard_ops = (lambda a_, b_, d_, nbp: ops.sweep_shard_rows(a_, b_, d_, nbp, ws=ws),
                      lambda b_, a_, d_, pl, sb: ops.sweep_shard_cols(b_, a_, d_, pl, sb, ws=ws), ops.sweep_row_block())
     rows_fn, cols_fn, rb = shard_ops
@@ -311,8 +311,11 @@ def _one_matrix_sharded(a_all, b_all, a_local, b_local, n_total, depth, rank, wo
     return i1, i2
 
 
-def _two_searches(a_all, b_all, a_local, b_local, depth, topk, clock):
+def _two_searches(a_all, b_all, a_local, b_local, depth, topk, precision, ws, clock):
     """compute(a, b): gallery a, queries b (model/metric.py:137-146) and the transposed search; this rank owns query rows [lo, hi)."""
+    if topk is None:
+        def topk(g, q, depth_):
+            return ops.l2_topk(g, q, depth_, precision=precision, return_dists=False, ws=ws)[0]
     i1 = topk(a_all, b_local, depth)
     clock.mark("search_b_from_a")
     i2 = topk(b_all, a_local, depth)
@@ -323,12 +326,10 @@ def _two_searches(a_all, b_all, a_local, b_local, depth, topk, clock):
 def _hits_from_ids(both, ks, lo, hi, hits):
     """hits[d, j] = #{ local query i : lo + i among the first ks[j] ids of its row } for the two id arrays."""
     if both[0].is_cuda and len(ks) <= 4 and both[0].shape == both[1].shape:
-        from . import ops
         ops.recall_hits_pair(both[0], both[1], ks, lo, hits)        # both directions: one launch
         return
     for d_, ids in enumerate(both):
         if ids.is_cuda and len(ks) <= 4:
-            from . import ops
             ops.recall_hits(ids, ks, target_offset=lo, hits=hits[d_])
         else:
             tgt = torch.arange(lo, hi, device=ids.device)[:, None]
@@ -356,9 +357,9 @@ def sharded_recall(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_t
     rows_gemm_select / alltoall / cols_select / search_a / search_b / hits / allreduce) and the path taken -- what a scaling run is
     read from.
 
-    The dispatcher only: one function per path above (world 1: rank path, one matrix; world > 1: rank-sharded, one-matrix sharded;
-    any world: two searches).  Non-finite embeddings on ANY rank raise ValueError on EVERY rank (the flag word rides behind the hit
-    counters through their all-reduce)."""
+    The dispatcher only: choose_sweep_path decides ONCE, one function per path above runs (world 1: rank path, one matrix; world > 1:
+    rank-sharded, one-matrix sharded; any world: two searches).  Injected stand-ins override the choice before it is made.  Non-finite
+    embeddings on ANY rank raise ValueError on EVERY rank (the flag word rides behind the hit counters through their all-reduce)."""
     lo, hi = shard_bounds(n_total, rank, world)
     clock = _PhaseClock(phases, feats_a_local.is_cuda)
     clock.mark("start")
@@ -367,40 +368,35 @@ def sharded_recall(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_t
     clock.mark("allgather")
     depth = min(int(max(k_vals)) + 1, n_total)
     ks = [min(int(k), depth) for k in k_vals]
-    d = feats_a_local.shape[1]
-    same_width = d == feats_b_local.shape[1]
     acc = torch.zeros(2 * len(ks) + 1, dtype=torch.int64, device=feats_a_local.device)        # hit counters + the non-finite word
     hits, flag = acc[: 2 * len(ks)].view(2, len(ks)), acc[2 * len(ks):]
-    hip_sweep = topk is None
+    if world > 1 and rank_ops is not None:
+        path, label = SweepPath.RANK_SHARDED, "injected rank ops"
+    elif world > 1 and shard_ops is not None:
+        path, label = SweepPath.ONE_MATRIX_SHARDED, "injected shard ops"
+    elif topk is not None:
+        path, label = SweepPath.TWO_SEARCHES, "injected top-k"
+    else:
+        path, label = choose_sweep_path(n_total, feats_a_local.shape[1], precision, world, len(ks), depth,
+                                        paired=feats_a_local.shape == feats_b_local.shape), None
     # the finite check: the recall-only HIP paths report NaN / inf rows inside their counters (VTC_RECALL_NONFINITE: no launch of its own);
     # every other path gets one flag launch over this rank's rows
-    rank_hip = hip_sweep and rank_ops is None and precision == 3 and RANK_PATH and len(ks) <= 4 and feats_a_local.is_cuda and same_width and (
-        (world == 1 and n_total >= RANK_MIN_ROWS and d % 64 == 0) or (world > 1 and shard_ops is None and rank_sharded(n_total, d, precision, world, len(ks))))
-    if not rank_hip:
+    marked = label is None and path in (SweepPath.RANK, SweepPath.RANK_SHARDED)
+    if not marked:
         _flag_nonfinite(flag, feats_a_local, feats_b_local)
-    if topk is None:
-        from . import ops
-
-        def topk(g, q, depth_):
-            return ops.l2_topk(g, q, depth_, precision=precision, return_dists=False, ws=ws)[0]
-
-    both, path, exchange = None, None, None
-    if (hip_sweep and world == 1 and precision == 3 and RANK_PATH and n_total >= RANK_MIN_ROWS and len(ks) <= 4
-            and feats_a_local.shape == feats_b_local.shape and d % 64 == 0):
+    both, exchange = None, None
+    if path is SweepPath.RANK:
         _world1_rank_path(a_all, b_all, ks, hits, ws, clock)
-        path = sweep_path(n_total, precision, world, depth, d)
-    elif hip_sweep and world == 1 and n_total >= (BIDIR_MIN_ROWS_F32 if precision == 0 else BIDIR_MIN_ROWS):
+    elif path is SweepPath.ONE_MATRIX:
         both = _world1_one_matrix(a_all, b_all, depth, precision, ws, clock)
-    elif world > 1 and (rank_ops is not None or (hip_sweep and shard_ops is None and same_width
-                                                 and rank_sharded(n_total, d, precision, world, len(ks)))):
-        path = sweep_path(n_total, precision, world, depth, d) if rank_ops is None else "injected rank ops"
+    elif path is SweepPath.RANK_SHARDED:
         _rank_sharded(a_all, b_all, feats_a_local, feats_b_local, n_total, lo, ks, hits, rank, world, rank_ops, ws, clock)
         exchange = _exchange_name()
-    elif world > 1 and (shard_ops is not None or (hip_sweep and one_matrix_sharded(n_total, precision, world, depth))):
+    elif path is SweepPath.ONE_MATRIX_SHARDED:
         both = _one_matrix_sharded(a_all, b_all, feats_a_local, feats_b_local, n_total, depth, rank, world, shard_ops, ws, clock)
         exchange = _exchange_name()
     else:
-        both = _two_searches(a_all, b_all, feats_a_local, feats_b_local, depth, topk, clock)
+        both = _two_searches(a_all, b_all, feats_a_local, feats_b_local, depth, topk, precision, ws, clock)
     if both is not None:
         _hits_from_ids(both, ks, lo, hi, hits)
         clock.mark("hits")
@@ -408,12 +404,11 @@ def sharded_recall(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_t
         dist.all_reduce(acc, op=dist.ReduceOp.SUM)
         clock.mark("allreduce")
     vals = acc.cpu().tolist()            # ONE D2H; plain Python integers from here (torch CPU ops cost microseconds each: the 10k sweep is 0.28 ms)
-    clock.close(path or (sweep_path(n_total, precision, world, depth, d) if hip_sweep else "injected top-k"), exchange)
+    clock.close(label or path.value, exchange)
     nh = 2 * len(ks)
-    marker = rank_hip and any(v >> 40 for v in vals[:nh])              # VTC_RECALL_NONFINITE, summed over the ranks
-    if vals[-1] != 0 or marker:
+    if vals[-1] != 0 or (marked and any(v >> 40 for v in vals[:nh])):              # VTC_RECALL_NONFINITE, summed over the ranks
         raise ValueError("sharded_recall: non-finite values in the embeddings of at least one rank -- the ranks of such rows are undefined "
                          "(vtc_amd.host.model.nonfinite_cause lists what this build knows can produce them)")
-    h = [v & ((1 << 40) - 1) for v in vals[:nh]] if rank_hip else vals[:nh]
+    h = [v & ((1 << 40) - 1) for v in vals[:nh]] if marked else vals[:nh]
     nk = len(ks)
     return ({k: h[j] / n_total for j, k in enumerate(k_vals)}, {k: h[nk + j] / n_total for j, k in enumerate(k_vals)})

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import dist as vdist
 from .. import ops
 
 __all__ = ["RecallAtK", "BaseMetric"]
@@ -119,13 +120,14 @@ class RecallAtK(BaseMetric):
     #: direction is read off the columns of the blocks the first direction wrote).  Measured one-matrix vs two searches,
     #: EXACT: 10k 1.54 vs 1.33 ms, 16k 2.46 vs 2.65, 25k 5.1 vs 6.0, 50k 15.4 vs 21.1 (the column pass is issue-bound
     #: and pays a list initialisation per segment; the GEMM it saves grows with N^2)
-    bidir_min_rows = 5120          # tools/bidir_threshold.py: one matrix wins from ~5k rows (EXACT 10k: 0.64 vs 0.79 ms)
-    bidir_min_rows_f32 = 3000      # SWEEP_F32: the fp32-MFMA GEMM it saves is the expensive part at every size
+    #: (the numbers live in vtc_amd.dist, whose choose_sweep_path decides with this object's attributes)
+    bidir_min_rows = vdist.BIDIR_MIN_ROWS
+    bidir_min_rows_f32 = vdist.BIDIR_MIN_ROWS_F32
     #: EXACT mode, paired rows: hit counters straight from the distance GEMM's key planes (the rank of each query's own gallery row),
     #: no sorted neighbour lists (round 5; the library takes n >= 1024)
-    #: (VTC_SWEEP_RANK=0, read at import as vtc_amd.dist.RANK_PATH is: sorted neighbour lists instead -- the A/B knob of INTEGRATION.md)
-    rank_path = __import__("os").environ.get("VTC_SWEEP_RANK", "1") != "0"
-    rank_min_rows = 1024
+    #: (VTC_SWEEP_RANK=0, read at import by vtc_amd.dist: sorted neighbour lists instead -- the A/B knob of INTEGRATION.md)
+    rank_path = vdist.RANK_PATH
+    rank_min_rows = vdist.RANK_MIN_ROWS
     #: inputs are checked for NaN / inf before the search (one tiny launch + a 4-byte D2H) and rejected: a non-finite row would be
     #: ranked arbitrarily
     check_finite = True
@@ -141,13 +143,18 @@ class RecallAtK(BaseMetric):
     def compute_both(self, features_a, features_b):
         """(compute(a, b), compute(b, a)) -- the two calls every caller of the reference makes back to back
         (metric.py:177-180, evaluation/eval.py:117-127, retrieval_evaluation.py:38-44)."""
-        min_rows = self.bidir_min_rows_f32 if self.precision == L.SWEEP_F32 else self.bidir_min_rows
-        if features_a.shape[0] != features_b.shape[0] or features_a.shape[0] < min(min_rows, self.rank_min_rows):
+        n = features_a.shape[0]
+        if n != features_b.shape[0]:
+            return self.compute(features_a, features_b), self.compute(features_b, features_a)
+        ks = [int(k) for k in self.k_vals]
+        d = features_a.shape[-1] + -features_a.shape[-1] % 64          # as _prep pads it
+        path = vdist.choose_sweep_path(n, d, self.precision, 1, len(ks), rank_path=self.rank_path and max(ks) <= n,
+                                       bidir_min_rows=self.bidir_min_rows, bidir_min_rows_f32=self.bidir_min_rows_f32,
+                                       rank_min_rows=self.rank_min_rows)
+        if path is vdist.SweepPath.TWO_SEARCHES:
             return self.compute(features_a, features_b), self.compute(features_b, features_a)
         a, b, depth = self._prep(features_a, features_b, check=False)
-        ks = [int(k) for k in self.k_vals]
-        if (self.precision == L.SWEEP_EXACT and self.rank_path and a.shape[0] >= self.rank_min_rows and len(ks) <= 4
-                and max(ks) <= a.shape[0] and ops.recall_bidir_supported(a.shape[0], a.shape[1])):
+        if path is vdist.SweepPath.RANK:
             # paired rows, parity mode: the reference asks only whether the query's own index is among the first k -- the RANK of one
             # gallery row -- so the sorted lists are never built (vtc_l2_recall_bidir; the same counters as the two-step form below).
             # The finite check rides in the counters (VTC_RECALL_NONFINITE): no launch, no D2H of its own.
@@ -156,10 +163,7 @@ class RecallAtK(BaseMetric):
             if bad and self.check_finite:
                 raise self._nonfinite_error(ops.nonfinite_bits(a, b) or 3)
             hits = hits.numpy()
-            n = a.shape[0]
             return ([(k, float(h) / n) for k, h in zip(self.k_vals, hits[0])], [(k, float(h) / n) for k, h in zip(self.k_vals, hits[1])])
-        if features_a.shape[0] < min_rows:
-            return self.compute(features_a, features_b), self.compute(features_b, features_a)
         if self.check_finite:
             bits = ops.nonfinite_bits(a, b)
             if bits:

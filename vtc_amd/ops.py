@@ -64,6 +64,16 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _ws_for(ws: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    """The caller's workspace when it is large enough and on ``device``, else a fresh one."""
+    return ws if ws is not None and ws.numel() >= need and ws.device == device else workspace(need, device)
+
+
+def _k_array(k_vals: Sequence[int]):
+    """The k values as the C ABI's ``const int *``."""
+    return (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+
+
 # ---- primitives ---------------------------------------------------------------------------
 @on_device
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = L.EPI_STORE,
@@ -260,9 +270,7 @@ def l2_topk(gallery: torch.Tensor, queries: torch.Tensor, depth: int, precision:
     gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
     ng, d = gallery.shape
     nq = queries.shape[0]
-    need = L.lib().vtc_l2_topk_workspace_bytes(ng, nq, d, precision, rows_per_block)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, gallery.device)
+    ws = _ws_for(ws, L.lib().vtc_l2_topk_workspace_bytes(ng, nq, d, precision, rows_per_block), gallery.device)
     ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     L.check(L.lib().vtc_l2_topk(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, precision, rows_per_block,
@@ -279,9 +287,7 @@ def l2_topk_bidir(a: torch.Tensor, b: torch.Tensor, depth: int, precision: int =
     a, b = _gpu(a, torch.float32, "a"), _gpu(b, torch.float32, "b")
     na, d = a.shape
     nb = b.shape[0]
-    need = L.lib().vtc_l2_topk_bidir_workspace_bytes(na, nb, d, precision, rows_per_block)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, a.device)
+    ws = _ws_for(ws, L.lib().vtc_l2_topk_bidir_workspace_bytes(na, nb, d, precision, rows_per_block), a.device)
     ids1 = torch.empty(nb, depth, dtype=torch.int64, device=a.device)
     ids2 = torch.empty(na, depth, dtype=torch.int64, device=a.device)
     d1 = torch.empty(nb, depth, dtype=torch.float32, device=a.device) if return_dists else None
@@ -308,9 +314,7 @@ def sweep_shard_rows(a_all: torch.Tensor, b_local: torch.Tensor, depth: int, nbl
     a_all, b_local = _gpu(a_all, torch.float32, "a_all"), _gpu(b_local, torch.float32, "b_local")
     n, d = a_all.shape
     nl = b_local.shape[0]
-    need = L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, a_all.device)
+    ws = _ws_for(ws, L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d), a_all.device)
     ids = torch.empty(nl, depth, dtype=torch.int64, device=a_all.device)
     planes = torch.empty(4, nblk_pad, n, dtype=torch.int32, device=a_all.device)
     L.check(L.lib().vtc_l2_sweep_shard_rows(a_all.data_ptr(), b_local.data_ptr(), n, nl, d, depth, ids.data_ptr(), None,
@@ -331,9 +335,7 @@ def sweep_shard_cols(b_all: torch.Tensor, a_local: torch.Tensor, depth: int, pla
     n_src, four, nblk_pad, nl2 = planes.shape
     if four != 4 or nl2 != nl or src_base.numel() != n_src:
         raise ValueError(f"sweep_shard_cols: planes {tuple(planes.shape)} / src_base {tuple(src_base.shape)} do not match n_local={nl}")
-    need = L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d)
-    if ws is None or ws.numel() < need:
-        ws = workspace(need, b_all.device)
+    ws = _ws_for(ws, L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d), b_all.device)
     ids = torch.empty(nl, depth, dtype=torch.int64, device=b_all.device)
     L.check(L.lib().vtc_l2_sweep_shard_cols(b_all.data_ptr(), a_local.data_ptr(), n, nl, d, depth, planes.data_ptr(), n_src,
                                             nblk_pad, src_base.data_ptr(), ids.data_ptr(), None, ws.data_ptr(), ws.numel(),
@@ -358,10 +360,8 @@ def recall_bidir(a: torch.Tensor, b: torch.Tensor, k_vals: Sequence[int], ws: Op
     if hits is None:
         hits = torch.zeros(2, len(k_vals), dtype=torch.int64, device=a.device)
     assert hits.shape == (2, len(k_vals)) and hits.is_contiguous() and hits.dtype == torch.int64
-    need = L.lib().vtc_l2_recall_bidir_workspace_bytes(n, d)
-    if ws is None or ws.numel() < need or ws.device != a.device:
-        ws = workspace(need, a.device)
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ws = _ws_for(ws, L.lib().vtc_l2_recall_bidir_workspace_bytes(n, d), a.device)
+    ks = _k_array(k_vals)
     L.check(L.lib().vtc_l2_recall_bidir(a.data_ptr(), b.data_ptr(), n, d, ks, len(k_vals), hits[0].data_ptr(), hits[1].data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_recall_bidir")
     return hits
@@ -376,7 +376,7 @@ def split_recall_counters(hits_host: torch.Tensor):
 
 def recall_planes(k_vals: Sequence[int], n_total: int) -> int:
     """Key planes per (column, block) that the recall-only sweep keeps for these k at this gallery size (vtc_l2_recall_planes): 2, 3 or 4."""
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ks = _k_array(k_vals)
     return int(L.lib().vtc_l2_recall_planes(ks, len(k_vals), int(n_total)))
 
 
@@ -393,10 +393,8 @@ def recall_shard_rows(a_all: torch.Tensor, b_local: torch.Tensor, row_base: int,
     n, d = a_all.shape
     nl = b_local.shape[0]
     assert hits.shape == (len(k_vals),) and hits.dtype == torch.int64 and hits.is_contiguous() and hits.device == a_all.device
-    need = L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d)
-    if ws is None or ws.numel() < need or ws.device != a_all.device:
-        ws = workspace(need, a_all.device)
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ws = _ws_for(ws, L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d), a_all.device)
+    ks = _k_array(k_vals)
     planes = torch.empty(L.lib().vtc_l2_recall_planes(ks, len(k_vals), n), nblk_pad, n, dtype=torch.int32, device=a_all.device)
     L.check(L.lib().vtc_l2_recall_shard_rows(a_all.data_ptr(), b_local.data_ptr(), n, nl, int(row_base), d, ks, len(k_vals), hits.data_ptr(),
                                              planes.data_ptr(), nblk_pad, ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_recall_shard_rows")
@@ -413,15 +411,12 @@ def recall_shard_cols(b_all: torch.Tensor, a_local: torch.Tensor, row_base: int,
     n, d = b_all.shape
     nl = a_local.shape[0]
     n_src, npl, nblk_pad, nl2 = planes.shape
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ks = _k_array(k_vals)
     if npl != L.lib().vtc_l2_recall_planes(ks, len(k_vals), n) or nl2 != nl or src_bounds.numel() != n_src + 1:
         raise ValueError(f"recall_shard_cols: planes {tuple(planes.shape)} / src_bounds {tuple(src_bounds.shape)} do not match n_local={nl}, "
                          f"k_vals={list(k_vals)}")
     assert hits.shape == (len(k_vals),) and hits.dtype == torch.int64 and hits.is_contiguous() and hits.device == b_all.device
-    need = L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d)
-    if ws is None or ws.numel() < need or ws.device != b_all.device:
-        ws = workspace(need, b_all.device)
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ws = _ws_for(ws, L.lib().vtc_l2_sweep_shard_workspace_bytes(n, nl, d), b_all.device)
     L.check(L.lib().vtc_l2_recall_shard_cols(b_all.data_ptr(), a_local.data_ptr(), n, nl, int(row_base), d, ks, len(k_vals), planes.data_ptr(),
                                              n_src, nblk_pad, src_bounds.data_ptr(), hits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
             "vtc_l2_recall_shard_cols")
@@ -434,7 +429,7 @@ def recall_hits_pair(ids_a: torch.Tensor, ids_b: torch.Tensor, k_vals: Sequence[
     ids_a, ids_b = _gpu(ids_a, torch.int64, "ids_a"), _gpu(ids_b, torch.int64, "ids_b")
     assert ids_a.shape == ids_b.shape and hits.shape[0] == 2 and hits.is_contiguous()
     nq, depth = ids_a.shape
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ks = _k_array(k_vals)
     L.check(L.lib().vtc_recall_hits_pair(ids_a.data_ptr(), ids_b.data_ptr(), nq, depth, int(target_offset), ks, len(k_vals),
                                          hits[0].data_ptr(), hits[1].data_ptr(), _stream()), "vtc_recall_hits_pair")
     return hits
@@ -447,7 +442,7 @@ def recall_hits(ids: torch.Tensor, k_vals: Sequence[int], target_offset: int = 0
     nq, depth = ids.shape
     if hits is None:
         hits = torch.zeros(len(k_vals), dtype=torch.int64, device=ids.device)
-    ks = (C.c_int * len(k_vals))(*[int(k) for k in k_vals])
+    ks = _k_array(k_vals)
     L.check(L.lib().vtc_recall_hits(ids.data_ptr(), nq, depth, int(target_offset), ks, len(k_vals), hits.data_ptr(), _stream()),
             "vtc_recall_hits")
     return hits
