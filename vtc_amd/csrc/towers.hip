@@ -18,6 +18,19 @@
 // where T is the compute dtype (bf16 or fp32).  The reference's ~10 rearrange/cat/repeat copies
 // per block (timesformer_clip_alt.py:143-173) do not exist here: the attention kernel addresses
 // tokens through an affine row map and the cls bookkeeping is two tiny kernels.
+//
+// The last block.  Behind it a tower reads ONE row per item (x[:, 0] into ln_post, model/timesformer_clip_alt.py:281 and
+// model/timesformer_clip.py:433; the EOT row into ln_final, upstream CLIP encode_text).  That block's attention still needs K and V
+// of every row, but its queries, its out_proj, its residual update and its whole MLP are per-row maps: on any other row they produce
+// values nothing ever reads.  So the n output rows are gathered into a compact fp32 stream and out_proj / ln_2 / c_fc / QuickGELU /
+// c_proj run on those n rows only (LayerNorm kernels, the reference's own order of operations).  Exact, not an approximation: every
+// value that can influence an embedding is computed as before.  Three paths (LastBlock, one switch per block loop):
+//   AllRows                   as every other block: VTC_TOWER_FULL_LAST_LAYER computes the dead rows anyway (or layers == 0)
+//   OutputRowsAfterAttention  variant-1 video tower (its cls query attends globally in a kernel of its own): every query attends,
+//                             then the output rows of the stream and of the attention output are gathered
+//   OneQueryPerSequence       every other tower: only the output rows' queries are projected (tail_query: LayerNorm kernel + the Q third of
+//                             in_proj on n rows), the all-rows projection computes the K and V thirds only (ln_proj's column window) and
+//                             the attention core runs one query per sequence (attention.hip, sq_attn_kernel)
 #include <stdarg.h>
 #include <string.h>
 
@@ -76,10 +89,9 @@ struct Bump {
 
 inline int esz(int dtype) { return dtype == VTC_F32 ? 4 : 2; }
 
-int gemm(const void *A, const void *W, const float *bias, void *out, int M, int N, int K, int dtype, int mode, int out_dtype,
-         int skip_mod, hipStream_t s) {
+int gemm(const void *A, const void *W, const float *bias, void *out, int M, int N, int K, int dtype, int mode, int out_dtype, hipStream_t s) {
   GemmEpi e;
-  e.mode = mode; e.out_dtype = out_dtype; e.skip_mod = skip_mod;
+  e.mode = mode; e.out_dtype = out_dtype;
   return launch_gemm(A, W, bias, out, M, N, K, dtype, e, s);
 }
 
@@ -99,7 +111,8 @@ struct Fold {
   float *stat = nullptr;    // [rows_pad] (mean, rstd)
   int rows_pad = 0;
   int fmt = -1;             // operand format (xb, xl) / stat currently hold (-1: the stream is the fp32 x)
-  float *splitk = nullptr;  // [SPLITK_MAX][rows_pad, W] fp32 partial products of a split-K c_proj (rows_pad <= SPLITK_MAX_ROWS; else NULL)
+  float *splitk = nullptr;  // [SPLITK_MAX][rows_pad, W] fp32 partial products of a split-K c_proj (NULL: rows_pad > SPLITK_MAX_ROWS, or
+                            // flags & VTC_TOWER_NO_SPLITK -- the c_proj is one GEMM)
 };
 // Split-K for the MLP's c_proj at batch 1 - 2: its 64 x 64 tiles are few (video, B = 1: 8 x 12 = 96) and each walks
 // K = 3072 alone -- 24 us of a 109 us layer.  Cut into K slices it is one round of ~4x the workgroups, and the pass that sums the slices
@@ -114,17 +127,16 @@ inline int splitk_slices(int rows_pad, int W, int K) {
     if (K % (64 * s) == 0 && K / s >= 256 && tiles * s <= 2L * vtcgemm::num_cus()) return s;
   return 1;
 }
-// the fp32 rows a final LayerNorm reads (rows i * row_mul, or row_index[i]) out of the pair
-int fold_merge_rows(Fold &f, float *x, int n, int W, const int *row_index, int row_mul, hipStream_t s) {
-  if (!f.on || f.fmt < 0) return 0;
-  return launch_split_merge_rows(f.xb, f.xl, x, n, W, row_index, row_mul, f.fmt, s);
-}
 inline int pad256(int rows) { return (rows + 255) / 256 * 256; }
-bool fold_usable(const vtc_block_w *blocks, int layers, int W, int dtype, bool timesformer, int flags) {
-  if ((flags & VTC_TOWER_NO_LN_FOLD) || dtype == VTC_F32 || W % 256 != 0) return false;
-  for (int l = 0; l < layers; ++l)
-    if (!blocks[l].qkv_wf || !blocks[l].fc_wf || (timesformer && !blocks[l].tqkv_wf)) return false;
-  return true;
+// the folded path's buffers behind a tower's own (16-bit formats only; rows already padded to 256)
+void plan_fold(Bump &b, Fold &f, size_t rows, int W, int dtype) {
+  if (dtype == VTC_F32) return;
+  f.rows_pad = (int)rows;
+  f.xb = b.take(rows * W * 2);
+  f.xl = b.take(rows * W * 2);
+  f.part = (float *)b.take((size_t)(W / 64 + 1) * rows * 8);
+  f.stat = (float *)b.take(rows * 8);
+  if (rows <= (size_t)SPLITK_MAX_ROWS) f.splitk = (float *)b.take((size_t)SPLITK_MAX * rows * W * 4);
 }
 
 // A row count: known to the host (dev == NULL), or living in device memory -- the ragged text tower of vtc_text_forward2, whose
@@ -138,110 +150,132 @@ struct Rows {
   const int *dev_pad() const { return dev ? dev + 1 : nullptr; }
 };
 
+// The activation buffers of one forward (the layout in the header comment) and what every stage needs to walk them.
+struct Act {
+  float *x = nullptr;
+  void *h = nullptr, *big = nullptr;
+  Fold fold;
+  Rows rows = 0;      // (rows, W, s: set by the planners; the ragged text tower adds the device-side count)
+  int W = 0;
+  hipStream_t s = nullptr;
+};
+// x, h, big: the first three pieces of every tower's workspace (rows already padded to 256)
+void plan_act(Bump &b, Act &a, size_t rows, int W, size_t big_elems, int dtype, hipStream_t s) {
+  a.W = W; a.s = s;
+  a.x = (float *)b.take(rows * W * 4);
+  a.h = b.take(rows * W * esz(dtype));
+  a.big = b.take(big_elems * esz(dtype));
+}
+// what the tower's flags and weights decide about the folded path, once per forward
+void fold_begin(Act &a, const vtc_block_w *blocks, int layers, int dtype, bool timesformer, int flags) {
+  if (flags & VTC_TOWER_NO_SPLITK) a.fold.splitk = nullptr;
+  a.fold.on = !(flags & VTC_TOWER_NO_LN_FOLD) && dtype != VTC_F32 && a.W % 256 == 0;
+  for (int l = 0; l < layers; ++l)
+    if (!blocks[l].qkv_wf || !blocks[l].fc_wf || (timesformer && !blocks[l].tqkv_wf)) a.fold.on = false;
+}
+
+// the fp32 rows a final LayerNorm reads (rows i * row_mul, or row_index[i]) out of the pair
+int fold_merge_rows(Act &a, int n, const int *row_index, int row_mul) {
+  if (!a.fold.on || a.fold.fmt < 0) return 0;
+  return launch_split_merge_rows(a.fold.xb, a.fold.xl, a.x, n, a.W, row_index, row_mul, a.fold.fmt, a.s);
+}
+
 // the stream as the pair (xb, xl) + row statistics in operand format `dtype` (no residual GEMM of this format in front: layer 0, or
 // a format boundary -- back through fp32)
-int fold_enter(Fold &f, const float *x, const Rows &rows, int W, int dtype, hipStream_t s) {
+int fold_enter(Act &a, int dtype) {
+  Fold &f = a.fold;
   if (f.fmt == dtype) return 0;
-  if (f.fmt >= 0) RUN(launch_split_merge_rows(f.xb, f.xl, const_cast<float *>(x), rows.n, W, nullptr, 1, f.fmt, s, rows.dev));
-  RUN(launch_cast_rowstats(x, f.xb, f.xl, f.stat, rows.n, W, dtype, s, rows.dev));
+  if (f.fmt >= 0) RUN(launch_split_merge_rows(f.xb, f.xl, a.x, a.rows.n, a.W, nullptr, 1, f.fmt, a.s, a.rows.dev));
+  RUN(launch_cast_rowstats(a.x, f.xb, f.xl, f.stat, a.rows.n, a.W, dtype, a.s, a.rows.dev));
   f.fmt = dtype;
   return 0;
 }
 
-// out = epi(LN(x; g, bt) w^T + bias)
+// One LayerNorm -> projection of a block, plain (g, bt; w, bias) and folded (wf = gamma . w, s = its row sums, c = bias + w beta).
+struct Proj { const float *g, *bt; const void *w; const float *bias; const void *wf; const float *s, *c; };
+inline Proj qkv_of(const vtc_block_w &b) { return {b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c}; }
+inline Proj tqkv_of(const vtc_block_w &b) { return {b.lnt_g, b.lnt_b, b.tqkv_w, b.tqkv_b, b.tqkv_wf, b.tqkv_s, b.tqkv_c}; }
+inline Proj fc_of(const vtc_block_w &b) { return {b.ln2_g, b.ln2_b, b.fc_w, b.fc_b, b.fc_wf, b.fc_s, b.fc_c}; }
+
+// big = epi(LN(x; g, bt) w^T + bias), N columns
 // (col0, ncols: only the output columns [col0, col0 + ncols) -- rows col0.. of the weight -- are computed, at their places in the
 // N-wide output: the K and V thirds of a QKV projection whose queries come from elsewhere; ncols == 0: all N)
-int ln_proj(Fold &f, const float *x, const float *g, const float *bt, const void *w, const float *bias, const void *wf, const float *fs,
-            const float *fc, void *h, void *out, const Rows &rows, int N, int W, int dtype, int mode, hipStream_t s, int col0 = 0,
-            int ncols = 0) {
-  const int ldo = N;
+int ln_proj(Act &a, Proj p, int N, int dtype, int mode, int col0 = 0, int ncols = 0) {
+  const int W = a.W;
+  void *out = a.big;
+  GemmEpi e;
+  e.mode = mode; e.out_dtype = dtype; e.ldo = N;
   if (ncols > 0) {
     const size_t wo = (size_t)col0 * W * esz(dtype);
-    w = (const char *)w + wo;
-    if (wf) wf = (const char *)wf + wo;
-    if (bias) bias += col0;
-    if (fs) fs += col0;
-    if (fc) fc += col0;
+    p.w = (const char *)p.w + wo;
+    if (p.wf) p.wf = (const char *)p.wf + wo;
+    if (p.bias) p.bias += col0;
+    if (p.s) p.s += col0;
+    if (p.c) p.c += col0;
     out = (char *)out + (size_t)col0 * esz(dtype);
     N = ncols;
   }
-  if (f.on) {
-    RUN(fold_enter(f, x, rows, W, dtype, s));
-    GemmEpi e;
-    e.mode = mode; e.out_dtype = dtype; e.fold_stat = f.stat; e.fold_s = fs; e.m_dev = rows.dev_pad(); e.ldo = ldo;
-    return launch_gemm(f.xb, wf, fc, out, f.rows_pad, N, W, dtype, e, s);
+  if (!a.fold.on) {
+    RUN(launch_layernorm(a.x, p.g, p.bt, a.h, a.rows.n, W, dtype, nullptr, 1, false, a.s, a.rows.dev));
+    e.m_dev = a.rows.dev;
+    return launch_gemm(a.h, p.w, p.bias, out, a.rows.n, N, W, dtype, e, a.s);
   }
-  RUN(launch_layernorm(x, g, bt, h, rows.n, W, dtype, nullptr, 1, false, s, rows.dev));
-  GemmEpi e;
-  e.mode = mode; e.out_dtype = dtype; e.m_dev = rows.dev; e.ldo = ldo;
-  return launch_gemm(h, w, bias, out, rows.n, N, W, dtype, e, s);
+  RUN(fold_enter(a, dtype));
+  e.fold_stat = a.fold.stat; e.fold_s = p.s; e.m_dev = a.rows.dev_pad();
+  return launch_gemm(a.fold.xb, p.wf, p.c, out, a.fold.rows_pad, N, W, dtype, e, a.s);
 }
 
 // x += A w^T + bias  (rows with m % skip_mod == 0 untouched)
 // center: this update also subtracts the rows' previous means (the stream stays centred; once per layer is enough -- a single
 // update moves a row's mean by a fraction of its spread)
-int resid_proj(Fold &f, const void *A, const void *w, const float *bias, float *x, const Rows &rows, int W, int K, int dtype, int skip_mod,
-               hipStream_t s, bool center = false, int flags = 0) {
-  if (f.on) {
-    GemmEpi e;
-    e.mode = VTC_EPI_RESID; e.out_dtype = VTC_F32; e.skip_mod = skip_mod; e.y16 = f.xb; e.y16lo = f.xl; e.fold_part = f.part;
-    e.m_dev = rows.dev_pad();
-    if (center) e.fold_stat = f.stat;       // the rows' means before this update: the stream is stored centred (gemm.hip, SPLIT)
-    if (f.fmt != dtype) {       // the stream is not a pair of this format yet (cannot happen behind ln_proj; kept for safety)
-      if (f.fmt >= 0) RUN(launch_split_merge_rows(f.xb, f.xl, x, rows.n, W, nullptr, 1, f.fmt, s, rows.dev));
-      RUN(launch_cast_rowstats(x, f.xb, f.xl, f.stat, rows.n, W, dtype, s, rows.dev));
-      f.fmt = dtype;
-    }
-    const int nsl = (center && skip_mod == 0 && f.splitk && !(flags & VTC_TOWER_NO_SPLITK)) ? splitk_slices(f.rows_pad, W, K) : 1;
-    if (nsl > 1) {
-      GemmEpi ek;
-      ek.mode = VTC_EPI_STORE; ek.out_dtype = VTC_F32; ek.m_dev = rows.dev_pad(); ek.ksplit = nsl; ek.split_stride = f.rows_pad * W;
-      RUN(launch_gemm(A, w, nullptr, f.splitk, f.rows_pad, W, K, dtype, ek, s));
-      return launch_splitk_resid_rows(f.splitk, nsl, f.rows_pad * W, bias, f.xb, f.xl, f.stat, f.rows_pad, W, dtype, s, rows.dev_pad());
-    }
-    RUN(launch_gemm(A, w, bias, x, f.rows_pad, W, K, dtype, e, s));
-    return launch_fold_stats(f.part, W / 64, f.rows_pad, f.stat, s, rows.dev_pad());
-  }
+int resid_proj(Act &a, const void *A, const void *w, const float *bias, int K, int dtype, int skip_mod, bool center = false) {
+  const int W = a.W;
+  Fold &f = a.fold;
+  const int *m_dev = f.on ? a.rows.dev_pad() : a.rows.dev;
   GemmEpi e;
-  e.mode = VTC_EPI_RESID; e.out_dtype = VTC_F32; e.skip_mod = skip_mod; e.m_dev = rows.dev;
-  return launch_gemm(A, w, bias, x, rows.n, W, K, dtype, e, s);
+  e.mode = VTC_EPI_RESID; e.out_dtype = VTC_F32; e.skip_mod = skip_mod; e.m_dev = m_dev;
+  if (!f.on) return launch_gemm(A, w, bias, a.x, a.rows.n, W, K, dtype, e, a.s);
+  RUN(fold_enter(a, dtype));      // (behind ln_proj the stream already is a pair of this format)
+  const int nsl = (center && skip_mod == 0 && f.splitk) ? splitk_slices(f.rows_pad, W, K) : 1;
+  if (nsl > 1) {
+    GemmEpi ek;
+    ek.mode = VTC_EPI_STORE; ek.out_dtype = VTC_F32; ek.m_dev = m_dev; ek.ksplit = nsl; ek.split_stride = f.rows_pad * W;
+    RUN(launch_gemm(A, w, nullptr, f.splitk, f.rows_pad, W, K, dtype, ek, a.s));
+    return launch_splitk_resid_rows(f.splitk, nsl, f.rows_pad * W, bias, f.xb, f.xl, f.stat, f.rows_pad, W, dtype, a.s, m_dev);
+  }
+  e.y16 = f.xb; e.y16lo = f.xl; e.fold_part = f.part;
+  if (center) e.fold_stat = f.stat;       // the rows' means before this update: the stream is stored centred (gemm.hip, SPLIT)
+  RUN(launch_gemm(A, w, bias, a.x, f.rows_pad, W, K, dtype, e, a.s));
+  return launch_fold_stats(f.part, W / 64, f.rows_pad, f.stat, a.s, m_dev);
 }
 
 // x += MLP(ln_2 x)   (timesformer_clip_alt.py:174 / upstream block)
-int mlp_part(Fold &f, const vtc_block_w &b, float *x, void *h, void *big, const Rows &rows, int W, int dtype, hipStream_t s, int flags = 0) {
+int mlp_part(Act &a, const vtc_block_w &b, int dtype) {
   ProfRegion region(VTC_PROF_REGION_MLP);
-  RUN(ln_proj(f, x, b.ln2_g, b.ln2_b, b.fc_w, b.fc_b, b.fc_wf, b.fc_s, b.fc_c, h, big, rows, 4 * W, W, dtype, VTC_EPI_GELU, s));
-  RUN(resid_proj(f, big, b.proj_w, b.proj_b, x, rows, W, 4 * W, dtype, 0, s, true, flags));
-  return 0;
+  RUN(ln_proj(a, fc_of(b), 4 * a.W, dtype, VTC_EPI_GELU));
+  return resid_proj(a, a.big, b.proj_w, b.proj_b, 4 * a.W, dtype, 0, true);
 }
 
-// x += MHA(ln_1 x) over n_seq contiguous sequences of L tokens
-// (tail_src: stop behind the attention core and say where its output lies -- the last block, whose out_proj runs on the output
-// rows only: last_block_tail)
-int attn_part_contig(Fold &f, const vtc_block_w &b, float *x, void *h, void *big, int n_seq, int L, int W, int heads, int causal,
-                     int dtype, int flags, hipStream_t s, const void **tail_src = nullptr) {
-  const int rows = n_seq * L;
+// x += MHA(ln_1 x) over n_seq contiguous sequences of L tokens (n_seq * L == a.rows.n)
+int attn_part_contig(Act &a, const vtc_block_w &b, int n_seq, int L, int heads, int causal, int dtype) {
+  const int W = a.W;
   ProfRegion region(VTC_PROF_REGION_ATTN);
-  RUN(ln_proj(f, x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, h, big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s));
+  RUN(ln_proj(a, qkv_of(b), 3 * W, dtype, VTC_EPI_STORE));
   if (W != heads * 64) {      // the CAM with head_dim != 64 (ViT-L/14's 768-d features at the reference's default n_heads = 8)
     VTC_CHECK(!causal && W % heads == 0, "attention: head_dim %d/%d", W, heads);
-    RUN(launch_attention_generic_small(big, h, n_seq, L, heads, W / heads, dtype, s));
+    RUN(launch_attention_generic_small(a.big, a.h, n_seq, L, heads, W / heads, dtype, a.s));
   } else {
-    RUN(launch_attention(big, h, nullptr, n_seq, L, heads, causal, 1, 0, L, 0, 0, 1, dtype, s));
+    RUN(launch_attention(a.big, a.h, nullptr, n_seq, L, heads, causal, 1, 0, L, 0, 0, 1, dtype, a.s));
   }
-  if (tail_src) { *tail_src = h; return 0; }
-  RUN(resid_proj(f, h, b.out_w, b.out_b, x, rows, W, W, dtype, 0, s));
-  return 0;
+  return resid_proj(a, a.h, b.out_w, b.out_b, W, dtype, 0);
 }
 
-// ---- the last block: only the rows that reach the output --------------------------------------------------------------------
-// Behind the last block a tower reads ONE row per item (x[:, 0] into ln_post, model/timesformer_clip_alt.py:281 and
-// model/timesformer_clip.py:433; the EOT row into ln_final, upstream CLIP encode_text).  That block's attention still needs K and V
-// of every row, but its out_proj, its residual update and its whole MLP are per-row maps: on any other row they produce values
-// nothing ever reads.  So after the last attention core the n output rows are gathered into a compact fp32 stream and
-// out_proj / ln_2 / c_fc / QuickGELU / c_proj run on those n rows only (LayerNorm kernels, the reference's own order of
-// operations).  Exact, not an approximation: every value that can influence an embedding is computed as before.
-// flags & VTC_TOWER_FULL_LAST_LAYER computes the dead rows anyway.
+// ---- the last block: only the rows that reach the output (the header comment); the path is chosen once per forward ------------
+enum class LastBlock { AllRows, OutputRowsAfterAttention, OneQueryPerSequence };
+inline LastBlock last_block_path(int flags, int layers, bool variant1) {
+  if ((flags & VTC_TOWER_FULL_LAST_LAYER) || layers == 0) return LastBlock::AllRows;
+  return variant1 ? LastBlock::OutputRowsAfterAttention : LastBlock::OneQueryPerSequence;
+}
 struct Tail {
   float *x = nullptr;      // [n, W] fp32: the output rows of the residual stream
   void *a = nullptr;       // [n, W] operand format: their attention outputs
@@ -256,111 +290,67 @@ void plan_tail(Bump &b, Tail &t, int n, int W) {      // sized for fp32 operands
   t.big = b.take((size_t)n * 4 * W * 4);
   t.sq = (float *)b.take((size_t)n * W * 4);
 }
-inline bool prune_last(int flags) { return (flags & VTC_TOWER_FULL_LAST_LAYER) == 0; }
-// ... and the last block's QUERIES are per-row maps too: only the output rows' queries are
-// projected (tail_query: LayerNorm kernel + the Q third of in_proj on n rows), the all-rows projection computes the K and V thirds
-// only (ln_proj's column window) and the attention core runs one query per sequence (attention.hip, sq_attn_kernel).
-inline bool prune_last_queries(int flags) { return prune_last(flags); }
-// the n output rows of the stream -> t.x (fp32, compact); their queries ln_1(x) Wq^T + bq -> t.big [n, W] (operand format)
-int tail_query(Fold &f, const vtc_block_w &b, float *x, Tail &t, int n, int W, const int *row_index, int row_mul, int dtype, hipStream_t s) {
-  RUN(fold_merge_rows(f, x, n, W, row_index, row_mul, s));
-  RUN(launch_gather_rows(x, t.x, n, W * 4, row_index, row_mul, s));
-  RUN(launch_layernorm(t.x, b.ln1_g, b.ln1_b, t.h, n, W, dtype, nullptr, 1, false, s));
-  return gemm(t.h, b.qkv_w, b.qkv_b, t.big, n, W, W, dtype, VTC_EPI_STORE, dtype, 0, s);
+// the n output rows of the stream (row_index[i], or i * row_mul) -> t.x (fp32, compact): (hi, lo) -> fp32 on those rows only, gather
+int gather_output_rows(Act &a, Tail &t, int n, const int *row_index, int row_mul) {
+  RUN(fold_merge_rows(a, n, row_index, row_mul));
+  return launch_gather_rows(a.x, t.x, n, a.W * 4, row_index, row_mul, a.s);
 }
-// t.x += out_proj(t.a) ; t.x += MLP(ln_2 t.x)      (t.a: the output rows' attention outputs, operand format)
+// ... and their queries ln_1(x) Wq^T + bq -> t.big [n, W] (operand format)
+int tail_query(Act &a, const vtc_block_w &b, Tail &t, int n, const int *row_index, int row_mul, int dtype) {
+  RUN(gather_output_rows(a, t, n, row_index, row_mul));
+  RUN(launch_layernorm(t.x, b.ln1_g, b.ln1_b, t.h, n, a.W, dtype, nullptr, 1, false, a.s));
+  return gemm(t.h, b.qkv_w, b.qkv_b, t.big, n, a.W, a.W, dtype, VTC_EPI_STORE, dtype, a.s);
+}
+// t.x += out_proj(t.a) ; t.x += MLP(ln_2 t.x)      (t.a: the output rows' attention outputs, operand format; inside the block's ATTN region)
 int tail_finish(const vtc_block_w &b, Tail &t, int n, int W, int dtype, hipStream_t s) {
-  {
-    ProfRegion region(VTC_PROF_REGION_ATTN);
-    RUN(gemm(t.a, b.out_w, b.out_b, t.x, n, W, W, dtype, VTC_EPI_RESID, VTC_F32, 0, s));
-  }
-  Fold nofold;
-  return mlp_part(nofold, b, t.x, t.h, t.big, Rows(n), W, dtype, s);
-}
-// attn_out: [rows, W] operand format, the attention core's output (cls rows already averaged over frames for the TimeSformer);
-// the output row of item i is row_index[i] (or i * row_mul) of the stream
-int last_block_tail(Fold &f, const vtc_block_w &b, float *x, const void *attn_out, Tail &t, int n, int W, const int *row_index, int row_mul,
-                    int dtype, hipStream_t s) {
-  {
-    ProfRegion region(VTC_PROF_REGION_ATTN);
-    RUN(fold_merge_rows(f, x, n, W, row_index, row_mul, s));      // (hi, lo) -> fp32, those rows only
-    RUN(launch_gather_rows(x, t.x, n, W * 4, row_index, row_mul, s));
-    RUN(launch_gather_rows(attn_out, t.a, n, W * esz(dtype), row_index, row_mul, s));
-    RUN(gemm(t.a, b.out_w, b.out_b, t.x, n, W, W, dtype, VTC_EPI_RESID, VTC_F32, 0, s));
-  }
-  Fold nofold;
-  return mlp_part(nofold, b, t.x, t.h, t.big, Rows(n), W, dtype, s);
-}
-
-// operand format of text block l: with dtype == VTC_BF16 the first half_layers blocks run on IEEE half
-inline int layer_dtype(const vtc_text_w *w, int l, int dtype) {
-  return (dtype == VTC_BF16 && l < w->half_layers) ? VTC_F16 : dtype;
+  RUN(gemm(t.a, b.out_w, b.out_b, t.x, n, W, W, dtype, VTC_EPI_RESID, VTC_F32, s));
+  Act ta{t.x, t.h, t.big, Fold(), n, W, s};      // the compact stream: n rows, never folded
+  return mlp_part(ta, b, dtype);
 }
 
 struct VisionWs {
-  float *x, *cls_tmp;
-  void *h, *big, *lnp;
-  Fold fold;
+  Act a;
+  float *cls_tmp;
+  void *lnp;
   Tail tail;
   size_t total;
 };
-
-VisionWs plan_vision(const vtc_vision_w *w, int n_items, int F, int dtype, void *ws) {
+VisionWs plan_vision(const vtc_vision_w *w, int n_items, int F, int dtype, void *ws, hipStream_t s = nullptr) {
   Bump b(ws);
   VisionWs v;
   const int P = w->grid * w->grid, T = 1 + P * F, W = w->width;
   const size_t rows = (size_t)pad256(n_items * T);      // padded: the folded-LayerNorm GEMMs run whole 256-row tiles
   const size_t patch_elems = (size_t)n_items * F * P * patch_k_padded(w->patch);
-  size_t big_elems = rows * 4 * W;
-  if (patch_elems > big_elems) big_elems = patch_elems;
-  v.x = (float *)b.take(rows * W * 4);
-  v.h = b.take(rows * W * esz(dtype));
-  v.big = b.take(big_elems * esz(dtype));
+  plan_act(b, v.a, rows, W, patch_elems > rows * 4 * W ? patch_elems : rows * 4 * W, dtype, s);
+  v.a.rows = n_items * T;
   v.cls_tmp = (float *)b.take((size_t)n_items * (F > P ? F : P) * W * 4);
   v.lnp = b.take((size_t)n_items * W * 4);
-  if (dtype != VTC_F32) {
-    v.fold.rows_pad = (int)rows;
-    v.fold.xb = b.take(rows * W * 2);
-    v.fold.xl = b.take(rows * W * 2);
-    v.fold.part = (float *)b.take((size_t)(W / 64 + 1) * rows * 8);
-    v.fold.stat = (float *)b.take(rows * 8);
-    if (rows <= (size_t)SPLITK_MAX_ROWS) v.fold.splitk = (float *)b.take((size_t)SPLITK_MAX * rows * W * 4);
-  }
+  plan_fold(b, v.a.fold, rows, W, dtype);
   plan_tail(b, v.tail, n_items, W);
   v.total = b.off;
   return v;
 }
 
 struct TextWs {
-  float *x;
-  void *h, *big, *lnp;
+  Act a;
+  void *lnp;
   int *eot;
   int *lens, *offs, *mdev;     // vtc_text_forward2, ragged: per-sequence lengths, their prefix sums, (rows, rows padded to 256)
-  Fold fold;
   Tail tail;
   size_t total;
 };
-
-TextWs plan_text(int rows_, int n_seq, int W, int dtype, void *ws) {
+TextWs plan_text(int rows_, int n_seq, int W, int dtype, void *ws, hipStream_t s = nullptr) {
   Bump b(ws);
   TextWs t;
   const size_t rows = (size_t)pad256(rows_);
-  t.x = (float *)b.take(rows * W * 4);
-  t.h = b.take(rows * W * esz(dtype));
-  t.big = b.take(rows * 4 * W * esz(dtype));
+  plan_act(b, t.a, rows, W, rows * 4 * W, dtype, s);
+  t.a.rows = rows_;
   t.lnp = b.take((size_t)n_seq * W * 4);
   t.eot = (int *)b.take((size_t)n_seq * 4);
   t.lens = (int *)b.take((size_t)n_seq * 4);
   t.offs = (int *)b.take((size_t)(n_seq + 1) * 4);
   t.mdev = (int *)b.take(16);
-  if (dtype != VTC_F32) {
-    t.fold.rows_pad = (int)rows;
-    t.fold.xb = b.take(rows * W * 2);
-    t.fold.xl = b.take(rows * W * 2);
-    t.fold.part = (float *)b.take((size_t)(W / 64 + 1) * rows * 8);
-    t.fold.stat = (float *)b.take(rows * 8);
-    if (rows <= (size_t)SPLITK_MAX_ROWS) t.fold.splitk = (float *)b.take((size_t)SPLITK_MAX * rows * W * 4);
-  }
+  plan_fold(b, t.a.fold, rows, W, dtype);
   plan_tail(b, t.tail, n_seq, W);
   t.total = b.off;
   return t;
@@ -379,7 +369,7 @@ extern "C" int vtc_vision_forward(const vtc_vision_w *w, const void *pixels, int
   VTC_CHECK(w && pixels && out && ws, "vision_forward: null argument");
   VTC_CHECK(dtype == VTC_F32 || dtype == VTC_BF16 || dtype == VTC_F16, "vision_forward: bad dtype %d", dtype);
   VTC_CHECK(n_items > 0 && F > 0, "vision_forward: n_items=%d frames=%d", n_items, F);
-  const bool tsf = w->nframes > 0;
+  const bool tsf = w->nframes > 0, v1 = w->variant == 1;
   VTC_CHECK(tsf || F == 1, "vision_forward: the image tower takes frames == 1 (got %d)", F);
   VTC_CHECK(!tsf || F <= w->nframes, "vision_forward: %d frames > temporal_embed rows %d", F, w->nframes);
   VTC_CHECK(w->width == w->heads * 64, "vision_forward: head_dim must be 64 (width %d, heads %d)", w->width, w->heads);
@@ -388,16 +378,17 @@ extern "C" int vtc_vision_forward(const vtc_vision_w *w, const void *pixels, int
   VTC_CHECK(w->variant == 0 || w->variant == 1, "vision_forward: unknown variant %d", w->variant);
   VTC_CHECK(!(w->variant == 1 && w->nframes == 0), "vision_forward: variant 1 (model/timesformer_clip.py) is a video tower: nframes must be > 0");
   const int rows = n_items * T, res = w->grid * w->patch;
-  VisionWs v = plan_vision(w, n_items, F, dtype, ws);
+  VisionWs v = plan_vision(w, n_items, F, dtype, ws, s);
   VTC_CHECK(ws_bytes >= v.total, "vision_forward: workspace too small (%zu < %zu)", ws_bytes, v.total);
+  Act &a = v.a;
 
   // patch embedding (+pos, +temporal) scattered into the reference's token order, cls rows, ln_pre
   VTC_CHECK(pixel_dtype == VTC_F32 || pixel_dtype == VTC_BF16 || pixel_dtype == VTC_U8 || pixel_dtype == VTC_F16, "vision_forward: bad pixel dtype %d", pixel_dtype);
   {
     GemmEpi e;
     e.mode = EPI_PATCH; e.out_dtype = VTC_F32; e.pos = w->pos; e.temporal = tsf ? w->temporal : nullptr;
-    e.P = P; e.F = F; e.T = T; e.ldo = W; e.frames_major = w->variant == 1;
-    const void *act = v.big;
+    e.P = P; e.F = F; e.T = T; e.ldo = W; e.frames_major = v1;
+    const void *act = a.big;
     // (few patches: the gather only exists on the 256 x 256 phased kernel, whose single tile would walk K = 3 072 alone -- 113 us
     // at B <= 8 videos; the im2row matrix + 64 x 64 / 128 x 128 tiles take 30-60 us there)
     const bool few = (long)n_items * F * P < 4096;
@@ -409,91 +400,97 @@ extern "C" int vtc_vision_forward(const vtc_vision_w *w, const void *pixels, int
       // raw uint8 frames (the loader's ToTensor + Normalize, dataset_loaders/dataset_loaders.py:40-49, as the
       // prologue of the patch GEMM): ONE pass turns them into normalised pixels in the operand format -- a quarter of the fp32
       // H2D bytes arrived, no im2row matrix is built -- and the GEMM gathers the patches from that tensor as above
-      RUN(launch_pixels_u8_to_operand(pixels, v.big, dtype, n_items * F, res, w->pix_mean, w->pix_std, s));
+      RUN(launch_pixels_u8_to_operand(pixels, a.big, dtype, n_items * F, res, w->pix_mean, w->pix_std, s));
       e.gather = 1; e.grid = w->grid; e.res = res; e.patch = w->patch;
     } else {
-      RUN(launch_im2row(pixels, pixel_dtype, v.big, dtype, n_items * F, w->grid, w->patch, res, w->pix_mean, w->pix_std, s));
+      RUN(launch_im2row(pixels, pixel_dtype, a.big, dtype, n_items * F, w->grid, w->patch, res, w->pix_mean, w->pix_std, s));
     }
-    RUN(launch_gemm(act, w->conv_w, nullptr, v.x, n_items * F * P, W, patch_k_padded(w->patch), dtype, e, s));
+    RUN(launch_gemm(act, w->conv_w, nullptr, a.x, n_items * F * P, W, patch_k_padded(w->patch), dtype, e, s));
   }
-  RUN(launch_cls_rows(v.x, w->class_embedding, w->pos, n_items, T, W, s));
-  Fold &fold = v.fold;
-  fold.on = fold_usable(w->blocks, w->layers, W, dtype, tsf, w->flags);
-  if (fold.on && w->layers > 0) {
+  RUN(launch_cls_rows(a.x, w->class_embedding, w->pos, n_items, T, W, s));
+  fold_begin(a, w->blocks, w->layers, dtype, tsf, w->flags);
+  if (a.fold.on && w->layers > 0) {
     // ln_pre and the entry into the (hi, lo) stream in one pass (round 6: the LayerNorm kernel + cast_rowstats moved the rows twice)
-    RUN(launch_ln_cast_rowstats(v.x, w->ln_pre_g, w->ln_pre_b, fold.xb, fold.xl, fold.stat, rows, W, dtype, s));
-    fold.fmt = dtype;
+    RUN(launch_ln_cast_rowstats(a.x, w->ln_pre_g, w->ln_pre_b, a.fold.xb, a.fold.xl, a.fold.stat, rows, W, dtype, s));
+    a.fold.fmt = dtype;
   } else {
-    RUN(launch_layernorm(v.x, w->ln_pre_g, w->ln_pre_b, v.x, rows, W, VTC_F32, nullptr, 1, false, s));
+    RUN(launch_layernorm(a.x, w->ln_pre_g, w->ln_pre_b, a.x, rows, W, VTC_F32, nullptr, 1, false, s));
   }
-  const bool prune = prune_last(w->flags);
-  const bool tail_q = prune_last_queries(w->flags) && !(tsf && w->variant == 1);   // ... and its queries (not on the v1 tower's global cls attention)
+
+  // The attention of a block up to (not including) the spatial out_proj: h = the attention output of every row.
+  // Variant 1, model/timesformer_clip.py:308-315: x += time(ln_time x); x += space(ln_1 x); x += mlp(ln_2 x).  Tokens are (frames
+  // patches): row item*T + 1 + t*P + n (:392).  In both attentions the cls query attends to every token (:81,:158) --
+  // cls_global_attention -- and a patch query to cls + its same-position frames (time, :161-185) or cls + its same-frame patches
+  // (space, :84-108): the generic kernel over [cls, ...] sequences whose own cls output is discarded into cls_tmp.
+  auto v1_attention = [&](const vtc_block_w &b) -> int {
+    RUN(ln_proj(a, tqkv_of(b), 3 * W, dtype, VTC_EPI_STORE));
+    RUN(launch_attention(a.big, a.h, v.cls_tmp, n_items * P, 1 + F, w->heads, 0, P, 0, T, 0, 1, P, dtype, s));
+    RUN(launch_cls_global_attention(a.big, a.h, n_items, T, w->heads, dtype, s));
+    RUN(resid_proj(a, a.h, b.tout_w, b.tout_b, W, dtype, 0));
+    RUN(ln_proj(a, qkv_of(b), 3 * W, dtype, VTC_EPI_STORE));
+    RUN(launch_attention(a.big, a.h, v.cls_tmp, n_items * F, 1 + P, w->heads, 0, F, 0, T, 0, P, 1, dtype, s));
+    return launch_cls_global_attention(a.big, a.h, n_items, T, w->heads, dtype, s);
+  };
+  // Variant 0, the temporal branch (timesformer_clip_alt.py:142-149): sequences = the F frames of one (item, patch)
+  auto time_branch = [&](const vtc_block_w &b) -> int {
+    RUN(ln_proj(a, tqkv_of(b), 3 * W, dtype, VTC_EPI_STORE));
+    RUN(launch_attention(a.big, a.h, nullptr, n_items * P, F, w->heads, 0, P, 1, T, F, 0, 1, dtype, s));
+    if (b.tout_w) {
+      RUN(gemm(a.h, b.tout_w, b.tout_b, a.big, a.fold.on ? a.fold.rows_pad : rows, W, W, dtype, VTC_EPI_STORE, dtype, s));
+      return resid_proj(a, a.big, b.tfc_w, b.tfc_b, W, dtype, T);
+    }
+    return resid_proj(a, a.h, b.tfc_w, b.tfc_b, W, dtype, T);      // temporal_fc o out_proj pre-multiplied on the host
+  };
+
+  const LastBlock last = last_block_path(w->flags, w->layers, v1);
   for (int l = 0; l < w->layers; ++l) {
     const vtc_block_w &b = w->blocks[l];
-    const bool tail = prune && l == w->layers - 1;      // out_proj + MLP of the last block: the cls rows only (last_block_tail)
-    const void *tail_src = v.h;                         // where the last attention core's output lies
-    {
-    ProfRegion region(VTC_PROF_REGION_ATTN);   // time + space branches: what BASELINE.md calls "TimeSformer attention"
-    if (tsf && w->variant == 1) {
-      // model/timesformer_clip.py:308-315: x += time(ln_time x); x += space(ln_1 x); x += mlp(ln_2 x).
-      // Tokens are (frames patches): row item*T + 1 + t*P + n (:392).  In both attentions the cls query
-      // attends to every token (:81,:158) -- cls_global_attention -- and a patch query to cls + its
-      // same-position frames (time, :161-185) or cls + its same-frame patches (space, :84-108): the
-      // generic kernel over [cls, ...] sequences whose own cls output is discarded into cls_tmp.
-      RUN(ln_proj(fold, v.x, b.lnt_g, b.lnt_b, b.tqkv_w, b.tqkv_b, b.tqkv_wf, b.tqkv_s, b.tqkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s));
-      RUN(launch_attention(v.big, v.h, v.cls_tmp, n_items * P, 1 + F, w->heads, 0, P, 0, T, 0, 1, P, dtype, s));
-      RUN(launch_cls_global_attention(v.big, v.h, n_items, T, w->heads, dtype, s));
-      RUN(resid_proj(fold, v.h, b.tout_w, b.tout_b, v.x, rows, W, W, dtype, 0, s));
-      RUN(ln_proj(fold, v.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s));
-      RUN(launch_attention(v.big, v.h, v.cls_tmp, n_items * F, 1 + P, w->heads, 0, F, 0, T, 0, P, 1, dtype, s));
-      RUN(launch_cls_global_attention(v.big, v.h, n_items, T, w->heads, dtype, s));
-      if (!tail) RUN(resid_proj(fold, v.h, b.out_w, b.out_b, v.x, rows, W, W, dtype, 0, s));
-    } else if (tsf) {
-      // temporal branch (timesformer_clip_alt.py:142-149): sequences = the F frames of one (item, patch)
-      RUN(ln_proj(fold, v.x, b.lnt_g, b.lnt_b, b.tqkv_w, b.tqkv_b, b.tqkv_wf, b.tqkv_s, b.tqkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s));
-      RUN(launch_attention(v.big, v.h, nullptr, n_items * P, F, w->heads, 0, P, 1, T, F, 0, 1, dtype, s));
-      if (b.tout_w) {
-        RUN(gemm(v.h, b.tout_w, b.tout_b, v.big, fold.on ? fold.rows_pad : rows, W, W, dtype, VTC_EPI_STORE, dtype, 0, s));
-        RUN(resid_proj(fold, v.big, b.tfc_w, b.tfc_b, v.x, rows, W, W, dtype, T, s));
-      } else {  // temporal_fc o out_proj pre-multiplied on the host
-        RUN(resid_proj(fold, v.h, b.tfc_w, b.tfc_b, v.x, rows, W, W, dtype, T, s));
-      }
-      // spatial branch (:152-168): sequences = (item, frame): [cls, the P patches of that frame]
-      if (tail && tail_q) {
-        // last block: the cls query only (one per item, the same in each of its F sequences), K and V of every row
-        RUN(tail_query(fold, b, v.x, v.tail, n_items, W, nullptr, T, dtype, s));
-        RUN(ln_proj(fold, v.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s, W, 2 * W));
-        RUN(launch_single_query_attention(v.big, v.tail.big, v.cls_tmp, n_items * F, 1 + P, w->heads, F, 0, T, 0, 1, F, nullptr, nullptr, 0, dtype, s));
-        RUN(launch_mean_cast(v.cls_tmp, v.tail.a, n_items, F, W, dtype, s));      // cls output = mean over the frames (:166-167)
-      } else {
-        RUN(ln_proj(fold, v.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s));
-        RUN(launch_attention(v.big, v.h, v.cls_tmp, n_items * F, 1 + P, w->heads, 0, F, 0, T, 0, 1, F, dtype, s));
-        RUN(launch_cls_mean(v.cls_tmp, v.h, dtype, n_items, F, T, W, s));
-        if (!tail) RUN(resid_proj(fold, v.h, b.out_w, b.out_b, v.x, rows, W, W, dtype, 0, s));
-      }
-    } else if (tail && tail_q) {
-      // image tower, last block: the cls query only
-      RUN(tail_query(fold, b, v.x, v.tail, n_items, W, nullptr, T, dtype, s));
-      RUN(ln_proj(fold, v.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, v.h, v.big, rows, 3 * W, W, dtype, VTC_EPI_STORE, s, W, 2 * W));
-      RUN(launch_single_query_attention(v.big, v.tail.big, v.cls_tmp, n_items, T, w->heads, 1, 0, T, 0, 0, 1, nullptr, nullptr, 0, dtype, s));
-      RUN(launch_mean_cast(v.cls_tmp, v.tail.a, n_items, 1, W, dtype, s));
-    } else {
-      RUN(attn_part_contig(fold, b, v.x, v.h, v.big, n_items, T, W, w->heads, 0, dtype, w->flags, s, tail ? &tail_src : nullptr));
+    // time + space branches: what BASELINE.md calls "TimeSformer attention" (everything of a block but mlp_part, which names its own)
+    ProfRegion region(VTC_PROF_REGION_ATTN);
+    switch (l == w->layers - 1 ? last : LastBlock::AllRows) {
+      case LastBlock::AllRows:
+        if (v1) {
+          RUN(v1_attention(b));
+          RUN(resid_proj(a, a.h, b.out_w, b.out_b, W, dtype, 0));
+        } else if (tsf) {
+          RUN(time_branch(b));
+          // spatial branch (:152-168): sequences = (item, frame): [cls, the P patches of that frame]
+          RUN(ln_proj(a, qkv_of(b), 3 * W, dtype, VTC_EPI_STORE));
+          RUN(launch_attention(a.big, a.h, v.cls_tmp, n_items * F, 1 + P, w->heads, 0, F, 0, T, 0, 1, F, dtype, s));
+          RUN(launch_cls_mean(v.cls_tmp, a.h, dtype, n_items, F, T, W, s));
+          RUN(resid_proj(a, a.h, b.out_w, b.out_b, W, dtype, 0));
+        } else {
+          RUN(attn_part_contig(a, b, n_items, T, w->heads, 0, dtype));
+        }
+        RUN(mlp_part(a, b, dtype));
+        break;
+      case LastBlock::OutputRowsAfterAttention:      // variant 1: the cls rows of the stream and of the attention output
+        RUN(v1_attention(b));
+        RUN(gather_output_rows(a, v.tail, n_items, nullptr, T));
+        RUN(launch_gather_rows(a.h, v.tail.a, n_items, W * esz(dtype), nullptr, T, s));
+        RUN(tail_finish(b, v.tail, n_items, W, dtype, s));
+        break;
+      case LastBlock::OneQueryPerSequence:
+        // the cls query only, K and V of every row: one query per item, the same in each of its F sequences [cls, the P patches of
+        // that frame]; the cls output is the mean over the frames (:166-167).  The image tower is F == 1 of that, without the map's frame stride
+        if (tsf) RUN(time_branch(b));
+        RUN(tail_query(a, b, v.tail, n_items, nullptr, T, dtype));
+        RUN(ln_proj(a, qkv_of(b), 3 * W, dtype, VTC_EPI_STORE, W, 2 * W));
+        RUN(launch_single_query_attention(a.big, v.tail.big, v.cls_tmp, n_items * F, 1 + P, w->heads, F, 0, T, 0, tsf ? 1 : 0, F, nullptr, nullptr, 0, dtype, s));
+        RUN(launch_mean_cast(v.cls_tmp, v.tail.a, n_items, F, W, dtype, s));
+        RUN(tail_finish(b, v.tail, n_items, W, dtype, s));
+        break;
     }
-    }
-    if (tail && tail_q && w->variant == 0) RUN(tail_finish(b, v.tail, n_items, W, dtype, s));
-    else if (tail) RUN(last_block_tail(fold, b, v.x, tail_src, v.tail, n_items, W, nullptr, T, dtype, s));
-    else RUN(mlp_part(fold, b, v.x, v.h, v.big, rows, W, dtype, s, w->flags));
   }
   // ln_post(x[:,0]) @ proj -- always fp32 (n_items rows only): the embedding the sweep ranks on
   // does not pick up a last bf16 rounding
-  if (prune && w->layers > 0) {
+  if (last != LastBlock::AllRows) {
     RUN(launch_layernorm(v.tail.x, w->ln_post_g, w->ln_post_b, v.lnp, n_items, W, VTC_F32, nullptr, 1, false, s));
   } else {
-    RUN(fold_merge_rows(fold, v.x, n_items, W, nullptr, T, s));
-    RUN(launch_layernorm(v.x, w->ln_post_g, w->ln_post_b, v.lnp, n_items, W, VTC_F32, nullptr, T, false, s));
+    RUN(fold_merge_rows(a, n_items, nullptr, T));
+    RUN(launch_layernorm(a.x, w->ln_post_g, w->ln_post_b, v.lnp, n_items, W, VTC_F32, nullptr, T, false, s));
   }
-  RUN(gemm(v.lnp, w->proj_t, nullptr, out, n_items, w->embed_dim, W, VTC_F32, VTC_EPI_STORE, VTC_F32, 0, s));
+  RUN(gemm(v.lnp, w->proj_t, nullptr, out, n_items, w->embed_dim, W, VTC_F32, VTC_EPI_STORE, VTC_F32, s));
   return 0;
 }
 
@@ -503,68 +500,70 @@ extern "C" size_t vtc_text_workspace_bytes(const vtc_text_w *w, int n_seq, int d
 }
 
 namespace {
-// The text tower over the sequences of `ids` (two arrays back to back).  mode 0: dense, all ctx positions of every sequence;
-// 1: ragged with host-known prefix sums (seq_offsets, total_rows); 2: ragged with NOTHING known to the host -- EOT positions,
-// prefix sums and the row count are computed on the device (embed.hip text_prep) and every kernel reads the count there.
+// Which rows of the text tower exist.  Dense: all ctx positions of every sequence; HostOffsets: ragged with host-known prefix sums
+// (seq_offsets, total_rows); DeviceOffsets: ragged with NOTHING known to the host -- EOT positions, prefix sums and the row count are
+// computed on the device (embed.hip text_prep) and every kernel reads the count there.
 // Ragged = only the rows [seq_offsets[s], seq_offsets[s+1]) = tokens 0..EOT of each sequence exist.  Identical outputs: under
 // the causal mask no token after EOT can influence the EOT feature, and every other op of the tower is per-row.
-int text_forward_impl(const vtc_text_w *w, const TextIds &ids, int mode, const int *seq_offsets, int total_rows, float *out, void *ws,
+enum class TextRows { Dense, HostOffsets, DeviceOffsets };
+// The text tower over the sequences of `ids` (two arrays back to back).
+int text_forward_impl(const vtc_text_w *w, const TextIds &ids, TextRows kind, const int *seq_offsets, int total_rows, float *out, void *ws,
                       size_t ws_bytes, int dtype, hipStream_t s, const char *who) {
-  const int n_seq = ids.n_a + ids.n_b;
+  const int n_seq = ids.n_a + ids.n_b, W = w->width;
   VTC_CHECK(dtype == VTC_F32 || dtype == VTC_BF16 || dtype == VTC_F16, "%s: bad dtype %d", who, dtype);
   VTC_CHECK(w->ctx <= 80, "%s: context %d > 80 unsupported", who, w->ctx);
   VTC_CHECK(w->width == w->heads * 64, "%s: head_dim must be 64", who);
-  const int W = w->width;
-  const int rows_host = mode == 1 ? total_rows : n_seq * w->ctx;          // exact (modes 0, 1) or the dense upper bound (mode 2)
-  TextWs t = plan_text(rows_host, n_seq, W, dtype, ws);
+  const int rows_host = kind == TextRows::HostOffsets ? total_rows : n_seq * w->ctx;      // exact, or (DeviceOffsets) the dense upper bound
+  TextWs t = plan_text(rows_host, n_seq, W, dtype, ws, s);
   VTC_CHECK(ws_bytes >= t.total, "%s: workspace too small (%zu < %zu)", who, ws_bytes, t.total);
+  Act &a = t.a;
   const int *offs = seq_offsets;
-  Rows rows(rows_host);
-  if (mode == 2) {
+  if (kind == TextRows::DeviceOffsets) {
     RUN(launch_text_prep(ids, n_seq, w->ctx, t.lens, t.offs, t.mdev, s));
     offs = t.offs;
-    rows = Rows(rows_host, t.mdev);
+    a.rows = Rows(rows_host, t.mdev);
   }
-  if (mode == 0) RUN(launch_text_embed(ids, w->tok_emb, w->pos, t.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
-  else RUN(launch_text_embed_ragged(ids, w->tok_emb, w->pos, offs, t.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
-  Fold &fold = t.fold;
-  fold.on = fold_usable(w->blocks, w->layers, W, dtype, false, w->flags);
+  if (kind == TextRows::Dense) RUN(launch_text_embed(ids, w->tok_emb, w->pos, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
+  else RUN(launch_text_embed_ragged(ids, w->tok_emb, w->pos, offs, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
+  fold_begin(a, w->blocks, w->layers, dtype, false, w->flags);
   // attention work of the ragged batch for the profiler (the lengths are not known here): rows x (mean length ~ ctx / 2)
   const double attn_flops_per_row = 4.0 * (0.5 * w->ctx) * 64 * w->heads;
-  const bool prune = prune_last(w->flags), tail_q = prune_last_queries(w->flags);
+  const LastBlock last = last_block_path(w->flags, w->layers, false);
   for (int l = 0; l < w->layers; ++l) {
     const vtc_block_w &b = w->blocks[l];
-    const int dl = layer_dtype(w, l, dtype);
-    const bool tail = prune && l == w->layers - 1;      // out_proj + MLP of the last block: the EOT rows only (last_block_tail)
-    const void *tail_src = t.h;
-    if (tail && tail_q) {
-      // last block: the EOT query only (it sees its whole causal prefix), K and V of every row
-      ProfRegion region(VTC_PROF_REGION_ATTN);
-      RUN(tail_query(fold, b, t.x, t.tail, n_seq, W, t.eot, 1, dl, s));
-      RUN(ln_proj(fold, t.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, t.h, t.big, rows, 3 * W, W, dl, VTC_EPI_STORE, s, W, 2 * W));
-      RUN(launch_single_query_attention(t.big, t.tail.big, t.tail.sq, n_seq, 0, w->heads, 1, 0, 0, 0, 0, 1, t.eot, mode == 0 ? nullptr : offs, w->ctx, dl, s));
-      RUN(launch_mean_cast(t.tail.sq, t.tail.a, n_seq, 1, W, dl, s));
-    } else if (mode == 0) {
-      RUN(attn_part_contig(fold, b, t.x, t.h, t.big, n_seq, w->ctx, W, w->heads, 1, dl, w->flags, s, tail ? &tail_src : nullptr));
-    } else {
-      ProfRegion region(VTC_PROF_REGION_ATTN);
-      RUN(ln_proj(fold, t.x, b.ln1_g, b.ln1_b, b.qkv_w, b.qkv_b, b.qkv_wf, b.qkv_s, b.qkv_c, t.h, t.big, rows, 3 * W, W, dl, VTC_EPI_STORE, s));
-      RUN(launch_attention_ragged(t.big, t.h, n_seq, w->ctx, w->heads, 1, offs, attn_flops_per_row * (rows.dev ? 1.0 : rows.n), rows.dev, dl, s));
-      if (!tail) RUN(resid_proj(fold, t.h, b.out_w, b.out_b, t.x, rows, W, W, dl, 0, s));
+    const int dl = (dtype == VTC_BF16 && l < w->half_layers) ? VTC_F16 : dtype;      // bf16 mode: the first half_layers blocks on IEEE half
+    ProfRegion region(VTC_PROF_REGION_ATTN);      // everything of a block but mlp_part, which names its own
+    switch (l == w->layers - 1 ? last : LastBlock::AllRows) {
+      case LastBlock::AllRows:
+        if (kind == TextRows::Dense) {
+          RUN(attn_part_contig(a, b, n_seq, w->ctx, w->heads, 1, dl));
+        } else {
+          RUN(ln_proj(a, qkv_of(b), 3 * W, dl, VTC_EPI_STORE));
+          RUN(launch_attention_ragged(a.big, a.h, n_seq, w->ctx, w->heads, 1, offs, attn_flops_per_row * (a.rows.dev ? 1.0 : a.rows.n), a.rows.dev, dl, s));
+          RUN(resid_proj(a, a.h, b.out_w, b.out_b, W, dl, 0));
+        }
+        RUN(mlp_part(a, b, dl));
+        break;
+      case LastBlock::OneQueryPerSequence:      // the EOT query only (it sees its whole causal prefix), K and V of every row
+        RUN(tail_query(a, b, t.tail, n_seq, t.eot, 1, dl));
+        RUN(ln_proj(a, qkv_of(b), 3 * W, dl, VTC_EPI_STORE, W, 2 * W));
+        RUN(launch_single_query_attention(a.big, t.tail.big, t.tail.sq, n_seq, 0, w->heads, 1, 0, 0, 0, 0, 1, t.eot,
+                                          kind == TextRows::Dense ? nullptr : offs, w->ctx, dl, s));
+        RUN(launch_mean_cast(t.tail.sq, t.tail.a, n_seq, 1, W, dl, s));
+        RUN(tail_finish(b, t.tail, n_seq, W, dl, s));
+        break;
+      case LastBlock::OutputRowsAfterAttention: VTC_CHECK(false, "%s: last_block_path() chose the variant-1 video tower's path", who);
     }
-    if (tail && tail_q) RUN(tail_finish(b, t.tail, n_seq, W, dl, s));
-    else if (tail) RUN(last_block_tail(fold, b, t.x, tail_src, t.tail, n_seq, W, t.eot, 1, dl, s));
-    else RUN(mlp_part(fold, b, t.x, t.h, t.big, rows, W, dl, s, w->flags));
   }
   // ln_final on the EOT row only (LayerNorm is per-row, so gathering first is identical), then @ text_projection
   // (always fp32, as for the vision tower)
-  if (prune && w->layers > 0) {
+  if (last != LastBlock::AllRows) {
     RUN(launch_layernorm(t.tail.x, w->ln_final_g, w->ln_final_b, t.lnp, n_seq, W, VTC_F32, nullptr, 1, false, s));
   } else {
-    RUN(fold_merge_rows(fold, t.x, n_seq, W, t.eot, 1, s));
-    RUN(launch_layernorm(t.x, w->ln_final_g, w->ln_final_b, t.lnp, n_seq, W, VTC_F32, t.eot, 1, false, s));
+    RUN(fold_merge_rows(a, n_seq, t.eot, 1));
+    RUN(launch_layernorm(a.x, w->ln_final_g, w->ln_final_b, t.lnp, n_seq, W, VTC_F32, t.eot, 1, false, s));
   }
-  RUN(gemm(t.lnp, w->proj_t, nullptr, out, n_seq, w->embed_dim, W, VTC_F32, VTC_EPI_STORE, VTC_F32, 0, s));
+  RUN(gemm(t.lnp, w->proj_t, nullptr, out, n_seq, w->embed_dim, W, VTC_F32, VTC_EPI_STORE, VTC_F32, s));
   return 0;
 }
 }  // namespace
@@ -573,15 +572,16 @@ extern "C" int vtc_text_forward(const vtc_text_w *w, const int64_t *ids, int n_s
                                 int dtype, void *stream_) {
   VTC_CHECK(w && ids && out && ws, "text_forward: null argument");
   VTC_CHECK(n_seq > 0, "text_forward: n_seq=%d", n_seq);
-  return text_forward_impl(w, TextIds{ids, nullptr, n_seq, 0}, 0, nullptr, 0, out, ws, ws_bytes, dtype, (hipStream_t)stream_, "text_forward");
+  return text_forward_impl(w, TextIds{ids, nullptr, n_seq, 0}, TextRows::Dense, nullptr, 0, out, ws, ws_bytes, dtype, (hipStream_t)stream_,
+                           "text_forward");
 }
 
 extern "C" int vtc_text_forward2(const vtc_text_w *w, const int64_t *ids_a, int n_a, const int64_t *ids_b, int n_b, int ragged,
                                  float *out, void *ws, size_t ws_bytes, int dtype, void *stream_) {
   VTC_CHECK(w && ids_a && out && ws && (ids_b || n_b == 0), "text_forward2: null argument");
   VTC_CHECK(n_a > 0 && n_b >= 0, "text_forward2: n_a=%d n_b=%d", n_a, n_b);
-  return text_forward_impl(w, TextIds{ids_a, ids_b, n_a, n_b}, ragged ? 2 : 0, nullptr, 0, out, ws, ws_bytes, dtype, (hipStream_t)stream_,
-                           "text_forward2");
+  return text_forward_impl(w, TextIds{ids_a, ids_b, n_a, n_b}, ragged ? TextRows::DeviceOffsets : TextRows::Dense, nullptr, 0, out, ws,
+                           ws_bytes, dtype, (hipStream_t)stream_, "text_forward2");
 }
 
 // Ragged variant with host-known prefix sums: only the rows [seq_offsets[s], seq_offsets[s+1]) are computed (total_rows of them).
@@ -593,8 +593,8 @@ extern "C" int vtc_text_forward_ragged(const vtc_text_w *w, const int64_t *ids, 
                                        float *out, void *ws, size_t ws_bytes, int dtype, void *stream_) {
   VTC_CHECK(w && ids && seq_offsets && out && ws, "text_forward_ragged: null argument");
   VTC_CHECK(n_seq > 0 && total_rows >= n_seq && total_rows <= n_seq * w->ctx, "text_forward_ragged: n_seq=%d total_rows=%d", n_seq, total_rows);
-  return text_forward_impl(w, TextIds{ids, nullptr, n_seq, 0}, 1, seq_offsets, total_rows, out, ws, ws_bytes, dtype, (hipStream_t)stream_,
-                           "text_forward_ragged");
+  return text_forward_impl(w, TextIds{ids, nullptr, n_seq, 0}, TextRows::HostOffsets, seq_offsets, total_rows, out, ws, ws_bytes, dtype,
+                           (hipStream_t)stream_, "text_forward_ragged");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -618,27 +618,26 @@ static int cam_forward_impl(const vtc_cam_w *w, const float *main_feats, const f
   const int D = w->width, Lc = 1 + nc + na, rows = B * Lc;
   VTC_CHECK(w->heads >= 1 && w->width % w->heads == 0 && (w->width == w->heads * 64 || (w->width / w->heads <= 128 && Lc <= 16)),
             "cam_forward: head_dim %d / %d: 64, or <= 128 with at most 16 tokens per item", w->width, w->heads);
-  TextWs t = plan_text(rows, B, D, dtype, ws);
+  TextWs t = plan_text(rows, B, D, dtype, ws, s);
+  Act &a = t.a;      // fold.on stays false -- B (1 + nc + na) tokens: the LayerNorm kernels
   float *lin = (float *)((char *)ws + t.total);
   VTC_CHECK(ws_bytes >= cam_ws_bytes(w, B, Lc, dtype), "cam_forward: workspace too small");
   // small batches: the whole module as one cooperative launch (cam.hip)
   if (cam_fused_supported(w, B, nc, na, dtype)) {
-    const int rc = launch_cam_fused(w, main_feats, comm_feats, comments, aux, ctx, B, nc, na, adapted, t.x, (float *)t.big, (float *)t.h,
+    const int rc = launch_cam_fused(w, main_feats, comm_feats, comments, aux, ctx, B, nc, na, adapted, a.x, (float *)a.big, (float *)a.h,
                                     (int *)((char *)ws + t.total + align_up((size_t)B * w->width * 4, 256)), s);
     if (rc >= 0) return rc;      // -1: another stream's cooperative launch may still be running: the multi-launch path below
   }
-  RUN(launch_cam_tokens(main_feats, comm_feats, comments, w->mask_embedding, aux, t.x, B, nc, na, ctx, D, s));
-  Fold nofold;      // B (1 + nc + na) tokens: the LayerNorm kernels
+  RUN(launch_cam_tokens(main_feats, comm_feats, comments, w->mask_embedding, aux, a.x, B, nc, na, ctx, D, s));
   for (int l = 0; l < w->layers; ++l) {
-    const vtc_block_w &b = w->blocks[l];
-    RUN(attn_part_contig(nofold, b, t.x, t.h, t.big, B, Lc, D, w->heads, 0, dtype, 0, s));
-    RUN(mlp_part(nofold, b, t.x, t.h, t.big, rows, D, dtype, s));
+    RUN(attn_part_contig(a, w->blocks[l], B, Lc, w->heads, 0, dtype));
+    RUN(mlp_part(a, w->blocks[l], dtype));
   }
   if (!w->init_from_avg) {  // comm_res = final_linear(comm_tfm[0])   model/model.py:161
-    RUN(launch_layernorm(t.x, nullptr, nullptr, t.lnp, B, D, dtype, nullptr, Lc, true, s));
-    RUN(gemm(t.lnp, w->final_linear, nullptr, lin, B, D, D, dtype, VTC_EPI_STORE, VTC_F32, 0, s));
+    RUN(launch_layernorm(a.x, nullptr, nullptr, t.lnp, B, D, dtype, nullptr, Lc, true, s));
+    RUN(gemm(t.lnp, w->final_linear, nullptr, lin, B, D, D, dtype, VTC_EPI_STORE, VTC_F32, s));
   }
-  RUN(launch_cam_finalize(t.x, lin, main_feats, adapted, B, Lc, D, w->init_from_avg, w->residual_activation, w->squash_scale, w->bn_mean, w->bn_var, s));
+  RUN(launch_cam_finalize(a.x, lin, main_feats, adapted, B, Lc, D, w->init_from_avg, w->residual_activation, w->squash_scale, w->bn_mean, w->bn_var, s));
   return 0;
 }
 

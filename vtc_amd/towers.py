@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
+import warnings
 from typing import Dict, List, Optional
 
 import torch
@@ -25,21 +27,21 @@ VISION_CHUNK = 0
 # sequences per text-tower launch; 0 = the whole batch in one pass.  A chunk whose activations
 # (x fp32 + h + qkv/hidden, ~8 KB per token at W = 512) stay inside the 256 MiB Infinity Cache turns the
 # HBM-bound stages (LayerNorm, attention, residual epilogues) into cache-bound ones.
-TEXT_CHUNK = int(__import__("os").environ.get("VTC_TEXT_CHUNK", "0"))
+TEXT_CHUNK = int(os.environ.get("VTC_TEXT_CHUNK", "0"))
 # Text tower on ragged batches: compute only tokens 0..EOT of every sequence.  Identical outputs: under the causal
 # mask no token after EOT can reach the EOT feature, and every other op of the tower is per-row
 # (tests/test_gpu_towers.py::test_ragged_text_tower_equals_dense).  On by default (VTC_TEXT_RAGGED=0: the dense path,
 # which computes all 77 positions of every sequence as the reference does).
-TEXT_RAGGED = __import__("os").environ.get("VTC_TEXT_RAGGED", "1") != "0"
+TEXT_RAGGED = os.environ.get("VTC_TEXT_RAGGED", "1") != "0"
 # bf16 mode of the TEXT tower: the first TEXT_HALF_LAYERS blocks run with IEEE-half operands instead of bf16 (same MFMA
 # rate, same bytes, 11 significant bits instead of 8; |values| up to 65504 -- the format upstream CLIP itself runs in
 # on a GPU).  The operand-rounding floor of an all-bf16 text tower is rms 3.2e-4 / max 1.1-1.4e-3 on the unit-norm
 # embedding (tests/bf16_floor_study.py), above BASELINE's 1e-3 budget; layer 0 alone is 42 % of that variance.
 # 0 = plain bf16 everywhere.
-TEXT_HALF_LAYERS = int(__import__("os").environ.get("VTC_TEXT_HALF_LAYERS", "12"))
+TEXT_HALF_LAYERS = int(os.environ.get("VTC_TEXT_HALF_LAYERS", "12"))
 # 16-bit modes: pack the gamma-scaled projection weights of the folded LayerNorm next to the plain ones (include/vtc_hip.h,
 # vtc_block_w *_wf / *_s / *_c); whether a forward uses them is the packed model's own `flags` (VTC_TOWER_*).
-LN_FOLD_PACK = __import__("os").environ.get("VTC_LN_FOLD_PACK", "1") != "0"
+LN_FOLD_PACK = os.environ.get("VTC_LN_FOLD_PACK", "1") != "0"
 
 
 def tower_flags(ln_fold: bool = True, full_last_layer: bool = False, splitk: bool = True) -> int:
@@ -51,9 +53,9 @@ def tower_flags(ln_fold: bool = True, full_last_layer: bool = False, splitk: boo
 
 
 # defaults of newly packed towers (env VTC_LN_FOLD=0 / VTC_FULL_LAST_LAYER=1: A/B runs); a packed tower's `w.flags` may be set per model
-DEFAULT_FLAGS = tower_flags(__import__("os").environ.get("VTC_LN_FOLD", "1") != "0",
-                            __import__("os").environ.get("VTC_FULL_LAST_LAYER", "0") == "1",
-                            __import__("os").environ.get("VTC_SPLITK", "1") != "0")
+DEFAULT_FLAGS = tower_flags(os.environ.get("VTC_LN_FOLD", "1") != "0",
+                            os.environ.get("VTC_FULL_LAST_LAYER", "0") == "1",
+                            os.environ.get("VTC_SPLITK", "1") != "0")
 _WS: Dict[tuple, torch.Tensor] = {}
 
 
@@ -172,21 +174,69 @@ def _pack_blocks(sd: SD, p: str, layers: int, dtype, keep: _Keep, timesformer: b
     return arr
 
 
-class PackedVision:
-    def __init__(self, sd: SD, prefix: str, dtype, fuse_temporal: bool = True):
-        self._src = (sd, prefix, fuse_temporal)          # references to the caller's tensors: the bf16 re-pack of the half mode's range guard
+class _HalfRangeGuard:
+    """Range guard of the IEEE-half operand modes: the vision tower under compute_dtype = torch.float16 and the text tower's half
+    blocks of the bf16 mode (the bf16 rounding floor of that tower is above 1e-3).  Half has 5 exponent bits: a
+    residual-stream or MLP-hidden value beyond +-65504 becomes inf and the embedding NaN.  Synthetic and typical CLIP weights stay
+    orders of magnitude inside (tests push the stream to 1e3-1e4), but nothing in a checkpoint promises it, so: every forward ends
+    with vtc_nonfinite_flag on the tower's output (one tiny launch) and an ASYNC copy of the flag to pinned host memory -- no sync.
+    The FIRST forward after packing (which synchronises anyway: the weights were just uploaded) checks the flag at once and, if
+    set, re-packs as bf16 (more range, the same speed, a higher rounding floor) and recomputes; later forwards read the pinned flag
+    on entry (the previous call's verdict) and do the same switch with a warning -- the overflowed call's NaN embeddings have been
+    returned by then and say so themselves (the wrappers' watchdog raises on them)."""
+
+    def __init__(self, active, rebuild, warning: str):
+        """active(): is the half mode on; rebuild(): the bf16 re-pack; warning: its text, with {why}."""
+        self._guard_active, self._guard_rebuild, self._range_warning = active, rebuild, warning
         self._flag_dev = self._flag_host = None
         self._calibrated = False
         self.range_fallbacks = 0
+
+    def _guard_on(self, dev=None) -> bool:
+        """dev: at the end of _build -- the flag word on the device and its pinned copy, once, when the half mode is on."""
+        if dev is not None and self._guard_active() and self._flag_dev is None:
+            self._flag_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        return self._flag_dev is not None and self._guard_active()
+
+    def _range_switch(self, why: str):
+        warnings.warn(self._range_warning.format(why=why), RuntimeWarning, stacklevel=4)
+        self.range_fallbacks += 1
+        self._flag_dev.zero_()
+        self._flag_host.zero_()
+        self._guard_rebuild()
+
+    def _guard_entry(self):
+        if self._guard_on() and int(self._flag_host[0]) != 0:
+            self._range_switch("an earlier forward")       # pinned host memory: no synchronisation
+
+    def _range_guard(self, out: torch.Tensor, run):
+        """out = run() of this forward; returns it, or run() again after the switch."""
+        if not self._guard_on():
+            return out
+        L.check(L.lib().vtc_nonfinite_flag(out.data_ptr(), out.numel(), self._flag_dev.data_ptr(), ops._stream()), "vtc_nonfinite_flag")
+        if not self._calibrated:
+            self._calibrated = True
+            if int(self._flag_dev.item()) != 0:            # first call after packing: synchronous
+                self._range_switch("first forward after packing")
+                return run()
+            return out
+        self._flag_host.copy_(self._flag_dev, non_blocking=True)
+        return out
+
+
+class PackedVision(_HalfRangeGuard):
+    def __init__(self, sd: SD, prefix: str, dtype, fuse_temporal: bool = True):
+        self._src = (sd, prefix, fuse_temporal)          # references to the caller's tensors: the bf16 re-pack of the half mode's range guard
+        super().__init__(lambda: self.dtype == torch.float16, lambda: self._build(torch.bfloat16),
+                         "vtc_amd vision tower: {why}: a value left the IEEE-half range (+-65504) in the half-operand mode; re-packing the "
+                         "tower as bf16 operands (wider range, 8 significant bits instead of 11)")
         self._build(dtype)
 
     def _build(self, dtype):
         sd, prefix, fuse_temporal = self._src
         sd, dev = _host_sd(sd, prefix)
         self.dtype, self.code, self.keep = dtype, ops.dtype_code(dtype), _Keep(dev)
-        if dtype == torch.float16 and self._flag_dev is None:
-            self._flag_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         k = self.keep
         conv = sd["conv1.weight"]
         w = L.VisionW()
@@ -216,38 +266,13 @@ class PackedVision:
         w.blocks = self.blocks
         self.w = w
         self.res = w.grid * w.patch
-
-    # ---- range guard of the IEEE-half mode (round 6; as PackedText's) ------------------------------------------------------------
-    # compute_dtype = torch.float16 runs the tower on half operands with a half (hi, lo) residual stream: 11 significant bits, range
-    # +-65504.  A checkpoint whose activations leave that range shows as inf / NaN in the output: the FIRST forward after packing checks
-    # synchronously, re-packs the tower as bf16 and recomputes; later forwards carry the flag to pinned memory asynchronously and the
-    # next call switches (that call's NaN rows have been returned by then -- the wrappers' watchdog raises on them).
-    def _range_switch(self, why: str):
-        import warnings
-        warnings.warn(f"vtc_amd vision tower: {why}: a value left the IEEE-half range (+-65504) in the half-operand mode; re-packing the "
-                      "tower as bf16 operands (wider range, 8 significant bits instead of 11)", RuntimeWarning, stacklevel=3)
-        self.range_fallbacks += 1
-        self._flag_dev.zero_()
-        self._flag_host.zero_()
-        self._build(torch.bfloat16)
+        self._guard_on(dev)
 
     @ops.on_device
     def forward(self, pixels: torch.Tensor) -> torch.Tensor:
         """pixels [N,3,H,W] (image tower) or [N,F,3,H,W] (TimeSformer), fp32 / bf16 / half / uint8 -> [N, embed] fp32."""
-        if self.dtype == torch.float16 and self._flag_host is not None and int(self._flag_host[0]) != 0:
-            self._range_switch("an earlier forward")         # pinned host memory: no synchronisation
-        out = self._forward(pixels)
-        if self.dtype != torch.float16:
-            return out
-        L.check(L.lib().vtc_nonfinite_flag(out.data_ptr(), out.numel(), self._flag_dev.data_ptr(), ops._stream()), "vtc_nonfinite_flag")
-        if not self._calibrated:
-            self._calibrated = True
-            if int(self._flag_dev.item()) != 0:               # first call after packing: synchronous
-                self._range_switch("first forward after packing")
-                return self._forward(pixels)
-            return out
-        self._flag_host.copy_(self._flag_dev, non_blocking=True)
-        return out
+        self._guard_entry()
+        return self._range_guard(self._forward(pixels), lambda: self._forward(pixels))
 
     def _forward(self, pixels: torch.Tensor) -> torch.Tensor:
         w = self.w
@@ -272,12 +297,13 @@ class PackedVision:
         return out
 
 
-class PackedText:
+class PackedText(_HalfRangeGuard):
     def __init__(self, sd: SD, prefix: str, dtype, heads: Optional[int] = None, half_layers: Optional[int] = None):
         self._src = (sd, prefix, dtype, heads)          # references to the caller's tensors: the bf16 re-pack of the range guard
-        self._flag_dev = self._flag_host = None
-        self._calibrated = False
-        self.range_fallbacks = 0
+        super().__init__(lambda: self.w.half_layers > 0, lambda: self._build(0),
+                         "vtc_amd text tower: {why}: a value left the IEEE-half range (+-65504) in the half-operand blocks; "
+                         "re-packing the text blocks as bf16 operands (VTC_TEXT_HALF_LAYERS=0 semantics: wider range, rounding floor "
+                         "~1e-3 instead of ~1.5e-4)")
         self._build(half_layers)
 
     def _build(self, half_layers):
@@ -300,41 +326,7 @@ class PackedText:
                                    fold_ln=LN_FOLD_PACK)
         w.blocks = self.blocks
         self.w = w
-        if w.half_layers > 0 and self._flag_dev is None:
-            self._flag_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-
-    # ---- range guard of the IEEE-half blocks ---------------------------------------------------------------------------------
-    # bf16 mode runs the text blocks on IEEE-half operands (the bf16 rounding floor of this tower is above 1e-3).
-    # Half has 5 exponent bits: a residual-stream or MLP-hidden value beyond +-65504 becomes inf and the embedding NaN.  Synthetic
-    # and typical CLIP weights stay orders of magnitude inside (tests push the stream to 1e3-1e4), but nothing in a checkpoint
-    # promises it, so: every forward ends with vtc_nonfinite_flag on the tower's output (one tiny launch) and an ASYNC copy of
-    # the flag to pinned host memory -- no sync.  The FIRST forward after packing (which synchronises anyway: the weights were
-    # just uploaded) checks the flag at once and, if set, re-packs the blocks as bf16 (more range, the same speed, a higher
-    # rounding floor) and recomputes; later forwards read the pinned flag on entry (the previous call's verdict) and do the
-    # same switch with a warning -- the overflowed call's NaN embeddings have been returned by then and say so themselves.
-    def _range_switch(self, why: str):
-        import warnings
-        warnings.warn(f"vtc_amd text tower: {why}: a value left the IEEE-half range (+-65504) in the half-operand blocks; "
-                      "re-packing the text blocks as bf16 operands (VTC_TEXT_HALF_LAYERS=0 semantics: wider range, rounding floor "
-                      "~1e-3 instead of ~1.5e-4)", RuntimeWarning, stacklevel=3)
-        self.range_fallbacks += 1
-        self._flag_dev.zero_()
-        self._flag_host.zero_()
-        self._build(0)
-
-    def _range_guard(self, out: torch.Tensor, run):
-        if self.w.half_layers <= 0 or self._flag_dev is None:
-            return out
-        L.check(L.lib().vtc_nonfinite_flag(out.data_ptr(), out.numel(), self._flag_dev.data_ptr(), ops._stream()), "vtc_nonfinite_flag")
-        if not self._calibrated:
-            self._calibrated = True
-            if int(self._flag_dev.item()) != 0:            # first call after packing: synchronous
-                self._range_switch("first forward after packing")
-                return run()
-            return out
-        self._flag_host.copy_(self._flag_dev, non_blocking=True)
-        return out
+        self._guard_on(dev)
 
     @ops.on_device
     def forward(self, ids: torch.Tensor, ragged: Optional[bool] = None, ids_b: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -347,8 +339,7 @@ class PackedText:
         tokens) -- and the 256-vs-128 tile choice of the GEMMs is made on that bound too (the kernels themselves read the true
         count on the device and walk only its tiles).  `forward_host_offsets` is the exact-size alternative at the price of one
         D2H sync; TEXT_CHUNK bounds the workspace of the DENSE path (both id arrays are walked in chunks), not of the ragged one."""
-        if self._flag_host is not None and self.w.half_layers > 0 and int(self._flag_host[0]) != 0:
-            self._range_switch("an earlier forward")       # pinned host memory: no synchronisation
+        self._guard_entry()
         w = self.w
         ids = ops._gpu(ids, torch.int64, "token ids")
         if ids.dim() != 2 or ids.shape[1] != w.ctx:
