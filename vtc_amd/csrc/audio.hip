@@ -132,8 +132,6 @@ __global__ __launch_bounds__(256, 2) void feature_mlp_kernel(const float *__rest
 
 }  // namespace
 
-namespace vtcgemm { int num_cus(); }
-
 // hidden split: grow S while the grid stays within half the CUs (the weights, not the rows, are the cost at small n)
 static int mlp_split(int n) {
   const int tiles = cdiv(n, 16);

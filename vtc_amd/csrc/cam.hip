@@ -477,8 +477,6 @@ __global__ __launch_bounds__(256, 1) void cam_fused_kernel(const CamFusedParams 
 
 }  // namespace
 
-namespace vtcgemm { int num_cus(); }
-
 // Largest token count B (1 + nc) the one-launch CAM takes: above it the GEMM launches of towers.hip fill the chip and win
 // (measured crossover).  A model opts out with VTC_CAM_NO_FUSED.
 constexpr int CAM_FUSED_MAX_ROWS = 512;

@@ -137,7 +137,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- per-device launch state ----------------------------------------------------------------
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE setting: a process that drives several GPUs (one
@@ -246,6 +246,7 @@ constexpr bool l2min_half_keys(int mode) { return mode == EPI_L2MIN2 || mode == 
 
 int launch_gemm(const void *A, const void *W, const float *bias, void *out, int M, int N, int K, int dtype,
                 const GemmEpi &epi, hipStream_t stream);
+namespace vtcgemm { int num_cus(); }   // CU count of the current device (gemm.hip): what the persistent grids are sized by
 bool gemm_resid_ln_supported(int M, int N, int K, int dtype);
 bool gemm_patch_gather_supported(int n_frames, int grid, int patch, int res, int pixel_dtype, int dtype);
 // rows_dev != NULL: the row count lives in device memory (*rows_dev <= rows, which then only sizes the grid)

@@ -6,16 +6,17 @@
 // model/timesformer_clip_alt.py:50,65,148,174 and upstream nn.MultiheadAttention / nn.Linear.
 //
 // gfx950 design
-//   * two tile configurations:
+//   * two tile configurations (choose_tile decides, once per launch):
 //       "big"   256x256 output tile (gemm_phased_kernel), 512 threads (8 waves as 2x4, 128x64 per wave), one workgroup
 //               per CU, 128 KiB LDS -- 131 FLOP per byte staged from L2, used when the problem
 //               has enough tiles to fill the chip;
-//       "small" 128x128 tile (gemm_kernel; 64x64 for the fewest tiles), 256 threads (4 waves as 2x2, 64x64 per wave), two workgroups per CU
+//       "small" 128x128 tile (gemm_kernel), 256 threads (4 waves as 2x2, 64x64 per wave), two workgroups per CU; for the fewest tiles
+//               64x64 (2 waves as 2x1, 32x64 per wave, three LDS stages)
 //               -- for the skinny problems (CAM, output projections, edge cases) and for fp32;
 //   * K is consumed in 128-byte rows (64 bf16 / 32 fp32 per step); both operands go L2 -> LDS with
 //     global_load_lds_dwordx4 (LDS-DMA, no VGPR round trip), double buffered, issued from inline
-//     asm so the compiler does not serialise the pipeline behind them; one s_waitcnt vmcnt(0) +
-//     barrier per K-step publishes the next buffer;
+//     asm so the compiler does not serialise the pipeline behind them; gemm_kernel: one s_waitcnt vmcnt + barrier per K-step
+//     publishes the next buffer; gemm_phased_kernel: a quarter of the next K-tile per phase, counted waits (its header);
 //   * LDS image is lane-linear (a DMA constraint); the XOR bank swizzle is applied on the per-lane
 //     SOURCE address and again on the ds_read_b128 address (guide rule 21): conflict-free reads;
 //   * bf16: v_mfma_f32_16x16x32_bf16; fp32: 4 x v_mfma_f32_16x16x4_f32 per 16-byte chunk (exact
@@ -37,14 +38,10 @@
 #include "gemm_common.h"
 #include "ln_row.h"
 
-// Production source: the ablation / timing-probe branches of rounds 1-2 (builds that gave WRONG results on purpose: stores,
-// LDS reads, DMA or waits removed, 32x32x16 MFMA probe) are gone from this file -- their measurements are in DESIGN.md 4.1 and
-// the code in the history (commit 3ac3430).  What remains are the cycle-stamp diagnostics (correct results, slower), kept out of
-// line in gemm_stamps.h and compiled only with -DVTC_GEMM_STAMPS / -DVTC_GEMM_PHASE_STAMPS.  The three alternative K-loop schedules
-// of round 4 (DEEP 2 / 3 / 4: bit-identical results, measured level or slower -- profiles/r04_experiments.txt 1, 14, 16) left the
-// product source in round 5 (commit 7fd3e13 has them); __graft_entry__.build() refuses every -DVTC_* flag.  The run-time environment
-// knobs (forced tile incl. the free-running 256 x 256 kernel, DEEP = 0 override, column groups / super-rows of the tile walk, start
-// stagger, CU budget, residual K threshold, im2row patch embedding) left after round 6 (commit dda8438 has them).
+// Production source: no build-time or run-time option selects anything in this file (__graft_entry__.build() refuses every -DVTC_*
+// flag).  The one instrument left is the cycle-stamp diagnostic build (correct results, slower), out of line in gemm_stamps.h and
+// compiled only with -DVTC_GEMM_STAMPS / -DVTC_GEMM_PHASE_STAMPS (tools/build_variant.sh).  The measurements behind the fixed choices
+// are in DESIGN.md 4.1 and profiles/r04_experiments.txt / r05_experiments.txt; the removed timing probes are refused by name:
 #if defined(VTC_ABLATE_STORES) || defined(VTC_ABLATE_DMA) || defined(VTC_ABLATE_HALF_DMA) || defined(VTC_ABLATE_DMA_EXEC1) || \
     defined(VTC_ABLATE_VMWAIT) || defined(VTC_ABLATE_LDSREAD) || defined(VTC_PROBE_MFMA32) || defined(VTC_PHASED_WAIT_FIRST) || \
     defined(VTC_PHASED_ONE_BARRIER) || defined(VTC_NO_RELAXED_FIRST) || defined(VTC_ROW_PANEL_PROBE)
@@ -52,14 +49,16 @@
 #endif
 #include "gemm_stamps.h"
 
-#ifndef VTC_MFMA_PRIO
-#define VTC_MFMA_PRIO 3      // s_setprio of a wave inside its MFMA cluster.  Round 5 A/B (tools/gemm_ab.py, 6 rounds x 30 reps, bit-identical): 3 against
-                             // round 4's 1: c_proj +1.2 %, QKV +1.0 %, c_fc / out-proj / text shapes +0.2 ... +0.8 % (profiles/r05_experiments.txt 5)
-#endif
-
 using namespace vtcgemm;
 
 namespace {
+
+// s_setprio of a wave inside its MFMA cluster.  A/B (tools/gemm_ab.py, 6 rounds x 30 reps, bit-identical): 3 against 1: c_proj +1.2 %,
+// QKV +1.0 %, c_fc / out-proj / text shapes +0.2 ... +0.8 % (profiles/r05_experiments.txt 5)
+constexpr int MFMA_PRIO = 3;
+// LDS stages of the 64 x 64 configuration: two K-steps of LDS-DMA in flight (these launches are one tile's serial K loop: B = 1 forward
+// 2.36 -> 1.98 ms from 2 to 3 stages; 5 stages: no further gain -- 1.83 against 1.78 - 1.80 ms, profiles/r05_experiments.txt 8)
+constexpr int SMALL_NSTAGE = 3;
 
 // x of the lane the DPP control selects (row-local permutations: quad_perm, row_half_mirror 0x141, row_mirror 0x140)
 template <int CTRL>
@@ -82,22 +81,6 @@ __device__ __forceinline__ void store16(void *o, float4 v) {
   store16<NT>(o, make_uint4(__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)));
 }
 
-// The number of 16-byte stores a wave issues LAST in tile_epilogue's interior fast paths (bf16 / f16 outputs: TM x 2, fp32 outputs:
-// TM x 4, one per (fragment row, k) of the pass loops -- the static_asserts inside the paths hold them to it): gemm_phased_kernel's
-// relaxed first-K-tile waits leave exactly this many vector-memory operations in flight (one definition, not a restated
-// constant).  A fast path that issued FEWER trailing stores would make those waits under-wait and race the LDS-DMA.
-template <typename OutT, int TM>
-constexpr int fast_epilogue_trailing_stores() { return TM * (sizeof(OutT) == 2 ? 2 : 4); }
-
-// ---- epilogue (shared by both kernels).  CONTRACT with gemm_phased_kernel's relaxed first-K-tile waits: on an interior
-// tile a wave issues AT LEAST TM * 2 (bf16 out) or TM * 4 (fp32 out) vector-memory operations here (its 16-byte stores;
-// the residual mode's x loads come on top), so the NST youngest operations before the next tile's first LDS-DMA piece
-// all belong to this epilogue -- none of them is a DMA piece the K loop still has to wait for.
-// The wave's TM x TN accumulator fragments -> out, through a scratch
-// area of the dynamic LDS (byte offset scratch_off, >= 6 KiB per wave) that no DMA targets and nobody reads until
-// the caller's next barrier.  (The area is named by OFFSET and re-based on the extern array here: handed over as
-// a generic pointer, hipcc guards every LDS read behind the preceding global stores -- vmcnt waits that
-// serialise the store stream; measured -20 % on the residual shapes.)
 // ---- block-minima epilogue of the retrieval sweep (EPI_L2MIN): the distance matrix is never written ----------------------
 // A key is a NON-NEGATIVE fp32 distance (negative rounding results clamp to zero) whose low 7 mantissa bits are replaced
 // by an index inside the block: unsigned-integer order = distance order, ties by index, and min / max / med3 on the keys
@@ -314,6 +297,21 @@ __device__ __forceinline__ void l2min_epilogue(f32x4 (&acc)[TM][TN], const GemmP
   }
 }
 
+// ---- epilogue (shared by both kernels): the wave's TM x TN accumulator fragments -> out ------------------------------------------
+// Interior tiles go through a scratch area of the dynamic LDS (byte offset scratch_off, >= 6 KiB per wave) that no DMA targets and
+// nobody reads until the caller's next barrier.  (The area is named by OFFSET and re-based on the extern array here: handed over
+// as a generic pointer, hipcc guards every LDS read behind the preceding global stores -- vmcnt waits that serialise the store
+// stream; measured -20 % on the residual shapes.)
+//
+// TRAILING STORES, the contract of the two interior fast paths with gemm_phased_kernel's relaxed first-K-tile waits: on an interior
+// tile a wave issues AT LEAST this many vector-memory operations LAST (its 16-byte stores: TM x 2 for 16-bit outputs, TM x 4 for fp32
+// ones, one per (fragment row, k) of the pass loops -- the static_asserts inside the paths hold them to it; the residual mode's x
+// loads come on top), so the NST youngest operations before the next tile's first LDS-DMA piece all belong to this epilogue -- none
+// of them is a DMA piece the K loop still has to wait for.  The relaxed waits leave exactly this many operations in flight (one
+// definition, not a restated constant): a fast path that issued FEWER trailing stores would make them under-wait and race the LDS-DMA.
+template <typename OutT, int TM>
+constexpr int fast_epilogue_trailing_stores() { return TM * (sizeof(OutT) == 2 ? 2 : 4); }
+
 // REJOIN (the phased kernel): waves 0 .. WN-1 run one barrier ahead of the others and wait for them here -- AFTER the tile's small
 // vectors (bias, folded-LayerNorm statistics, first residual rows) have been requested, BEFORE the LDS scratch is touched (it is the
 // stage the lagging half reads last).  Every path executes the barrier exactly once.
@@ -349,11 +347,8 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
   // in-order vmcnt queue, so the K loop restarts only once they are acknowledged.  The distance matrix (256 KiB of
   // fp32 per tile, read back once by the top-k pass): -27 % on the 50k x 50k distance GEMM; the towers' bf16
   // outputs: -1.6 % per config-2 step; the fp32 residual stream (re-read by the LayerNorm that follows): neutral,
-  // kept on the default policy.  Mask bits: 0 distance, 1 bf16 outputs, 2 residual, 3 other fp32 (A/B builds).
-#ifndef VTC_NT_MASK
-#define VTC_NT_MASK 3
-#endif
-  constexpr bool nt_out = (VTC_NT_MASK >> (MODE == EPI_L2DIST ? 0 : (MODE == VTC_EPI_RESID || MODE == EPI_RESID_LN) ? 2 : sizeof(OutT) == 2 ? 1 : 3)) & 1;
+  // kept on the default policy, as are the other fp32 outputs.
+  constexpr bool nt_out = MODE == EPI_L2DIST || (sizeof(OutT) == 2 && MODE != VTC_EPI_RESID && MODE != EPI_RESID_LN);
   // Interior tiles (every tile of the towers) take the transposed fast epilogue; edge tiles the generic one.
   const bool interior = (m0 + BM <= p.M) && (n0 + BN <= p.N) && vec_ok;
   // ---- epilogue: lane holds out[m][n..n+3], m = m0 + 16 (wr TM + i) + (lane & 15),
@@ -490,7 +485,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
     out_rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float *>(p.out) + (size_t)m0u * ldo, 0,
                                                  (int)(rem < 0xFFFFFFF0u ? rem : 0xFFFFFFF0u), 0x00020000);
   }
-  if (interior) {
+  if (sizeof(OutT) == 4 && interior) {      // (16-bit outputs: interior tiles have returned above)
     // Fast path (every tile of the towers).  The write path of a CU retires roughly one distinct
     // cache line per 5-8 cycles whatever its fill, so storing straight from the MFMA layout
     // (16 rows x 32..64 B per instruction) made the epilogue cost as much as 5 K-steps.  Instead
@@ -498,8 +493,9 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
     // (the other stage already holds the next tile's first slab) and writes whole rows: every
     // store instruction covers 4 (fp32) or 8 (bf16) full 256 / 128-byte row segments.
     constexpr int TS = 68;                                   // padded row stride (floats): conflict-free b128 writes
-    // A pass moves 16 rows x 64 columns: the wave's TN * 16 columns are H = TN / 4 column halves (H = 2 for the
-    // 128 x 512 row-panel tiles), pass pp = (fragment row i, half hh)
+    // A pass moves 16 rows x 64 columns: the wave's TN * 16 columns are H = TN / 4 column halves, pass pp = (fragment row i, half hh).
+    // (TN = 4 in every instantiation, so H = 1 and hh = 0; the arithmetic and cadd's eight slots stay as written because hipcc's
+    //  schedule of the store loop depends on them -- profiles/r09_gemm_refactor.md, "what could not go")
     constexpr int H = TN / 4, NP = TM * H;
     static_assert(TN % 4 == 0 && (H == 1 || sizeof(OutT) == 4), "wide wave tiles: fp32 outputs only");
     static_assert(sizeof(OutT) == 2 || fast_epilogue_trailing_stores<OutT, TM>() <= NP * 4, "fp32 fast path: NP passes x 4 stores (>= the count the K loop's relaxed waits assume)");
@@ -514,17 +510,10 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
 #pragma unroll
       for (int e = 0; e < 8; ++e) cadd[hh][e] = 0.f;
     if (colv) {
-      if constexpr (sizeof(OutT) == 4) {
 #pragma unroll
-        for (int hh = 0; hh < H; ++hh) {
-          const float4 c4 = *reinterpret_cast<const float4 *>(colv + ncol0 + 64 * hh + l15 * 4);
-          cadd[hh][0] = c4.x; cadd[hh][1] = c4.y; cadd[hh][2] = c4.z; cadd[hh][3] = c4.w;
-        }
-      } else {
-        const float4 c0 = *reinterpret_cast<const float4 *>(colv + ncol0 + (lane & 7) * 8);
-        const float4 c1 = *reinterpret_cast<const float4 *>(colv + ncol0 + (lane & 7) * 8 + 4);
-        cadd[0][0] = c0.x; cadd[0][1] = c0.y; cadd[0][2] = c0.z; cadd[0][3] = c0.w;
-        cadd[0][4] = c1.x; cadd[0][5] = c1.y; cadd[0][6] = c1.z; cadd[0][7] = c1.w;
+      for (int hh = 0; hh < H; ++hh) {
+        const float4 c4 = *reinterpret_cast<const float4 *>(colv + ncol0 + 64 * hh + l15 * 4);
+        cadd[hh][0] = c4.x; cadd[hh][1] = c4.y; cadd[hh][2] = c4.z; cadd[hh][3] = c4.w;
       }
     }
     auto fin = [&](float a, float add) -> float {
@@ -538,16 +527,10 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
       const int m = m0 + (wr * TM + pp / H) * 16 + (lane >> 4) + 4 * k;
       return reinterpret_cast<float *>(p.out) + (size_t)m * ldo + ncol0 + 64 * (pp % H) + l15 * 4;
     };
-#ifndef VTC_RESID_AUX
-#define VTC_RESID_AUX 16    // cache policy of the residual stores: 16 = sc1 (write-through)
-#endif
-#ifndef VTC_RESID_DEPTH
-#define VTC_RESID_DEPTH 2
-#endif
     // x rows of the next XD - 1 passes in flight.  Depth 2 (one pass ahead) is enough: these loads queue behind the
     // previous passes' stores in the in-order vmcnt queue, and the N = 512 residual GEMMs move their 605 MB at
     // 4.35 TB/s -- the copy rate of the chip -- at depth 2, 3 and 4 alike (3 = +14 VGPRs, 4 spills)
-    constexpr int XD = VTC_RESID_DEPTH;
+    constexpr int XD = 2;
     float4 xr[XD][4];
     // folded LayerNorm: the residual row is the 16-bit pair (hi, lo) of GemmEpi::y16 / y16lo -- fetched as two 8-byte loads
     // into the same four registers the fp32 row would take: (hi.x, hi.y, lo.x, lo.y)
@@ -651,112 +634,83 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[TM][TN], const GemmPa
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       // 2. LDS -> global, row-contiguous
       const int mrow0 = m0 + (wr * TM + i) * 16;
-      if constexpr (sizeof(OutT) == 4) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int r = (lane >> 4) + 4 * k, cc = l15 * 4;
-          float4 v = *reinterpret_cast<const float4 *>(tr + r * TS + cc);
-          const int m = mrow0 + r;
-          v.x = fin(v.x, cadd[hh][0]); v.y = fin(v.y, cadd[hh][1]); v.z = fin(v.z, cadd[hh][2]); v.w = fin(v.w, cadd[hh][3]);
-          size_t orow = (size_t)m;
-          bool live = true;
-          if constexpr (MODE == VTC_EPI_RESID || MODE == EPI_RESID_LN) {
-            if (hh == 0) {                                       // row (i, k): next in this lane's walk
-              live_k[k] = skip_rem != 0;
-              skip_rem += skip_step;
-              skip_rem = min(skip_rem, skip_rem - skip_m);       // unsigned: the wrapped difference loses unless skip_rem >= skip_m
-            }
-            live = live_k[k];
+      for (int k = 0; k < 4; ++k) {
+        const int r = (lane >> 4) + 4 * k, cc = l15 * 4;
+        float4 v = *reinterpret_cast<const float4 *>(tr + r * TS + cc);
+        const int m = mrow0 + r;
+        v.x = fin(v.x, cadd[hh][0]); v.y = fin(v.y, cadd[hh][1]); v.z = fin(v.z, cadd[hh][2]); v.w = fin(v.w, cadd[hh][3]);
+        size_t orow = (size_t)m;
+        bool live = true;
+        if constexpr (MODE == VTC_EPI_RESID || MODE == EPI_RESID_LN) {
+          if (hh == 0) {                                       // row (i, k): next in this lane's walk
+            live_k[k] = skip_rem != 0;
+            skip_rem += skip_step;
+            skip_rem = min(skip_rem, skip_rem - skip_m);       // unsigned: the wrapped difference loses unless skip_rem >= skip_m
           }
-          if (MODE == EPI_PATCH) {
-            const int np = m % p.epi.P, ft = m / p.epi.P;
-            const int tt = ft % p.epi.F, item = ft / p.epi.F;
-            orow = p.epi.frames_major ? (size_t)item * p.epi.T + 1 + (size_t)tt * p.epi.P + np
-                                      : (size_t)item * p.epi.T + 1 + (size_t)np * p.epi.F + tt;
-            const float4 p4 = *reinterpret_cast<const float4 *>(p.epi.pos + (size_t)(1 + np) * p.N + ncolh + cc);
-            v.x += p4.x; v.y += p4.y; v.z += p4.z; v.w += p4.w;
-            if (p.epi.temporal) {
-              const float4 t4 = *reinterpret_cast<const float4 *>(p.epi.temporal + (size_t)tt * p.N + ncolh + cc);
-              v.x += t4.x; v.y += t4.y; v.z += t4.z; v.w += t4.w;
-            }
-          }
-          float *o = reinterpret_cast<float *>(p.out) + orow * ldo + ncolh + cc;
-          if (MODE == EPI_RESID_LN || MODE == VTC_EPI_RESID) {
-            // skipped rows are written back unchanged (a select, not a branch: an exec-masked store makes hipcc
-            // re-wait on the x prefetch after every store, which throttles the store stream).  The stores are
-            // WRITE-THROUGH (sc1) buffer stores: measured 8-10 % faster than plain global stores on the residual GEMMs of
-            // the towers (tools/resid_ln_bench.py), and what makes the rows visible to the column tile that
-            // completes the row block in EPI_RESID_LN without a release fence (MI355X_MICROARCH "Valid forms",
-            // cdna_hip_programming Guideline 16 R1)
-            float4 x = xr[pp % XD][k];
-            if constexpr (SPLIT) {
-              const unsigned h0 = __float_as_uint(x.x), h1 = __float_as_uint(x.y), l0 = __float_as_uint(x.z), l1 = __float_as_uint(x.w);
-              float mu = 0.0f;
-              if constexpr (CENTER) mu = mean_prev[i * 16 + r];
-              x = make_float4((up16<T>((unsigned short)(h0 & 0xFFFFu)) - mu) + up16<T>((unsigned short)(l0 & 0xFFFFu)),
-                              (up16<T>((unsigned short)(h0 >> 16)) - mu) + up16<T>((unsigned short)(l0 >> 16)),
-                              (up16<T>((unsigned short)(h1 & 0xFFFFu)) - mu) + up16<T>((unsigned short)(l1 & 0xFFFFu)),
-                              (up16<T>((unsigned short)(h1 >> 16)) - mu) + up16<T>((unsigned short)(l1 >> 16)));
-            }
-            typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-            const float4 y = make_float4(live ? x.x + v.x : x.x, live ? x.y + v.y : x.y, live ? x.z + v.z : x.z, live ? x.w + v.w : x.w);
-            if constexpr (!SPLIT) {
-              const v4u_t yy = {__float_as_uint(y.x), __float_as_uint(y.y), __float_as_uint(y.z), __float_as_uint(y.w)};
-              __builtin_amdgcn_raw_buffer_store_b128(yy, out_rsrc, (int)((((size_t)m - m0u) * ldo + ncolh + cc) * 4), 0,
-                                                     MODE == EPI_RESID_LN ? 16 : VTC_RESID_AUX);
-            } else {
-              // producer side of the folded LayerNorm: the updated row as (hi, lo) + this wave's partial statistics
-              uint2 pk, pl;
-              pk.x = pack16<T>(y.x, y.y);
-              pk.y = pack16<T>(y.z, y.w);
-              pl.x = pack16<T>(y.x - up16<T>((unsigned short)(pk.x & 0xFFFFu)), y.y - up16<T>((unsigned short)(pk.x >> 16)));
-              pl.y = pack16<T>(y.z - up16<T>((unsigned short)(pk.y & 0xFFFFu)), y.w - up16<T>((unsigned short)(pk.y >> 16)));
-              // cache policy of the (hi, lo) stores: the wave's next x loads sit behind them in the in-order vmcnt queue, so how
-              // soon a store is ACKNOWLEDGED sets the pace of the pass loop (0 plain, 1 nt; measured: DESIGN 4.1)
-#ifndef VTC_SPLIT_ST
-#define VTC_SPLIT_ST 0
-#endif
-              v2u_t *ph = reinterpret_cast<v2u_t *>(hi_base + split_off(pp, k));
-              v2u_t *pq = reinterpret_cast<v2u_t *>(lo_base + split_off(pp, k));
-              if constexpr (VTC_SPLIT_ST == 1) {
-                __builtin_nontemporal_store((v2u_t){pk.x, pk.y}, ph);
-                __builtin_nontemporal_store((v2u_t){pl.x, pl.y}, pq);
-              } else {
-                *ph = (v2u_t){pk.x, pk.y};
-                *pq = (v2u_t){pl.x, pl.y};
-              }
-              // (sum, sum of squared deviations from the 64-column mean): merged exactly like a two-pass variance
-              // (fold_stats_kernel).  Over the 16 lanes of the row: xor 1, 2 in the quad, then half-row and row mirrors.
-              float s1 = (y.x + y.y) + (y.z + y.w);
-              s1 += dpp_f<0xB1>(s1); s1 += dpp_f<0x4E>(s1); s1 += dpp_f<0x141>(s1); s1 += dpp_f<0x140>(s1);
-              const float mp = s1 * (1.0f / 64.0f);
-              const float d0 = y.x - mp, d1 = y.y - mp, d2 = y.z - mp, d3 = y.w - mp;
-              float q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-              q += dpp_f<0xB1>(q); q += dpp_f<0x4E>(q); q += dpp_f<0x141>(q); q += dpp_f<0x140>(q);
-              if (l15 == 0) {
-                if constexpr (H == 1) stat_buf[i * 16 + r] = make_float2(s1, q);
-                else *reinterpret_cast<float2 *>(p.epi.fold_part + 2 * ((size_t)(ncolh >> 6) * p.M + m)) = make_float2(s1, q);
-              }
-            }
-          } else {
-            store16<nt_out>(o, v);
+          live = live_k[k];
+        }
+        if (MODE == EPI_PATCH) {
+          const int np = m % p.epi.P, ft = m / p.epi.P;
+          const int tt = ft % p.epi.F, item = ft / p.epi.F;
+          orow = p.epi.frames_major ? (size_t)item * p.epi.T + 1 + (size_t)tt * p.epi.P + np
+                                    : (size_t)item * p.epi.T + 1 + (size_t)np * p.epi.F + tt;
+          const float4 p4 = *reinterpret_cast<const float4 *>(p.epi.pos + (size_t)(1 + np) * p.N + ncolh + cc);
+          v.x += p4.x; v.y += p4.y; v.z += p4.z; v.w += p4.w;
+          if (p.epi.temporal) {
+            const float4 t4 = *reinterpret_cast<const float4 *>(p.epi.temporal + (size_t)tt * p.N + ncolh + cc);
+            v.x += t4.x; v.y += t4.y; v.z += t4.z; v.w += t4.w;
           }
         }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int r = (lane >> 3) + 8 * k, cc = (lane & 7) * 8;
-          float4 v0 = *reinterpret_cast<const float4 *>(tr + r * TS + cc);
-          float4 v1 = *reinterpret_cast<const float4 *>(tr + r * TS + cc + 4);
-          v0.x = fin(v0.x, cadd[0][0]); v0.y = fin(v0.y, cadd[0][1]); v0.z = fin(v0.z, cadd[0][2]); v0.w = fin(v0.w, cadd[0][3]);
-          v1.x = fin(v1.x, cadd[0][4]); v1.y = fin(v1.y, cadd[0][5]); v1.z = fin(v1.z, cadd[0][6]); v1.w = fin(v1.w, cadd[0][7]);
-          uint4 pk;
-          pk.x = (unsigned)cvt16<OutT>(v0.x) | ((unsigned)cvt16<OutT>(v0.y) << 16);
-          pk.y = (unsigned)cvt16<OutT>(v0.z) | ((unsigned)cvt16<OutT>(v0.w) << 16);
-          pk.z = (unsigned)cvt16<OutT>(v1.x) | ((unsigned)cvt16<OutT>(v1.y) << 16);
-          pk.w = (unsigned)cvt16<OutT>(v1.z) | ((unsigned)cvt16<OutT>(v1.w) << 16);
-          unsigned short *o = reinterpret_cast<unsigned short *>(p.out) + (size_t)(mrow0 + r) * ldo + ncol0 + cc;
-          *reinterpret_cast<uint4 *>(o) = pk;
+        float *o = reinterpret_cast<float *>(p.out) + orow * ldo + ncolh + cc;
+        if (MODE == EPI_RESID_LN || MODE == VTC_EPI_RESID) {
+          // skipped rows are written back unchanged (a select, not a branch: an exec-masked store makes hipcc
+          // re-wait on the x prefetch after every store, which throttles the store stream).  The stores are
+          // WRITE-THROUGH (sc1) buffer stores: measured 8-10 % faster than plain global stores on the residual GEMMs of
+          // the towers (tools/resid_ln_bench.py), and what makes the rows visible to the column tile that
+          // completes the row block in EPI_RESID_LN without a release fence (MI355X_MICROARCH "Valid forms",
+          // cdna_hip_programming Guideline 16 R1)
+          float4 x = xr[pp % XD][k];
+          if constexpr (SPLIT) {
+            const unsigned h0 = __float_as_uint(x.x), h1 = __float_as_uint(x.y), l0 = __float_as_uint(x.z), l1 = __float_as_uint(x.w);
+            float mu = 0.0f;
+            if constexpr (CENTER) mu = mean_prev[i * 16 + r];
+            x = make_float4((up16<T>((unsigned short)(h0 & 0xFFFFu)) - mu) + up16<T>((unsigned short)(l0 & 0xFFFFu)),
+                            (up16<T>((unsigned short)(h0 >> 16)) - mu) + up16<T>((unsigned short)(l0 >> 16)),
+                            (up16<T>((unsigned short)(h1 & 0xFFFFu)) - mu) + up16<T>((unsigned short)(l1 & 0xFFFFu)),
+                            (up16<T>((unsigned short)(h1 >> 16)) - mu) + up16<T>((unsigned short)(l1 >> 16)));
+          }
+          typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+          const float4 y = make_float4(live ? x.x + v.x : x.x, live ? x.y + v.y : x.y, live ? x.z + v.z : x.z, live ? x.w + v.w : x.w);
+          if constexpr (!SPLIT) {
+            const v4u_t yy = {__float_as_uint(y.x), __float_as_uint(y.y), __float_as_uint(y.z), __float_as_uint(y.w)};
+            __builtin_amdgcn_raw_buffer_store_b128(yy, out_rsrc, (int)((((size_t)m - m0u) * ldo + ncolh + cc) * 4), 0, 16);   // aux 16 = sc1
+          } else {
+            // producer side of the folded LayerNorm: the updated row as (hi, lo) + this wave's partial statistics
+            uint2 pk, pl;
+            pk.x = pack16<T>(y.x, y.y);
+            pk.y = pack16<T>(y.z, y.w);
+            pl.x = pack16<T>(y.x - up16<T>((unsigned short)(pk.x & 0xFFFFu)), y.y - up16<T>((unsigned short)(pk.x >> 16)));
+            pl.y = pack16<T>(y.z - up16<T>((unsigned short)(pk.y & 0xFFFFu)), y.w - up16<T>((unsigned short)(pk.y >> 16)));
+            // cache policy of the (hi, lo) stores: the wave's next x loads sit behind them in the in-order vmcnt queue, so how
+            // soon a store is ACKNOWLEDGED sets the pace of the pass loop: plain stores (other cache policies: no gain)
+            *reinterpret_cast<v2u_t *>(hi_base + split_off(pp, k)) = (v2u_t){pk.x, pk.y};
+            *reinterpret_cast<v2u_t *>(lo_base + split_off(pp, k)) = (v2u_t){pl.x, pl.y};
+            // (sum, sum of squared deviations from the 64-column mean): merged exactly like a two-pass variance
+            // (fold_stats_kernel).  Over the 16 lanes of the row: xor 1, 2 in the quad, then half-row and row mirrors.
+            float s1 = (y.x + y.y) + (y.z + y.w);
+            s1 += dpp_f<0xB1>(s1); s1 += dpp_f<0x4E>(s1); s1 += dpp_f<0x141>(s1); s1 += dpp_f<0x140>(s1);
+            const float mp = s1 * (1.0f / 64.0f);
+            const float d0 = y.x - mp, d1 = y.y - mp, d2 = y.z - mp, d3 = y.w - mp;
+            float q = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+            q += dpp_f<0xB1>(q); q += dpp_f<0x4E>(q); q += dpp_f<0x141>(q); q += dpp_f<0x140>(q);
+            if (l15 == 0) {
+              if constexpr (H == 1) stat_buf[i * 16 + r] = make_float2(s1, q);
+              else *reinterpret_cast<float2 *>(p.epi.fold_part + 2 * ((size_t)(ncolh >> 6) * p.M + m)) = make_float2(s1, q);
+            }
+          }
+        } else {
+          store16<nt_out>(o, v);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -832,30 +786,17 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
   constexpr bool STAGGER = NW == 8;                     // two waves per SIMD inside one workgroup
   constexpr int A_BYTES = BM * ROWB, W_BYTES = BN * ROWB, STAGE = A_BYTES + W_BYTES;
   constexpr int AG = BM / 8 / NW, WG = BN / 8 / NW;
-  constexpr int SUPER = SUPER_ROWS / BM;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WN, wc = wave % WN;
   const int g = lane >> 4;
 
-  // ---- persistent, XCD-aware tile walk ----------------------------------------------------
-  // (split-K, GemmEpi::ksplit: the walk runs over (tile, K slice) pairs, slice-minor; every workgroup has exactly one)
+  // ---- persistent, XCD-aware tile walk (split-K, GemmEpi::ksplit: over (tile, K slice) pairs; every workgroup has exactly one) ----
   const int S = p.epi.ksplit > 1 ? p.epi.ksplit : 1;
-  const int ntiles = p.MT * p.NT * S, nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3;
-  const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);                 // workgroups sharing this XCD label
-  const int nt_x = (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);           // tiles given to this XCD label
-  const int start_x = xcd * (ntiles >> 3) + min(xcd, ntiles & 7);
-  auto decode = [&](int logical, int &m0, int &n0) {
-    if (S > 1) logical /= S;
-    const int per_super = SUPER * p.NT;
-    const int sr = logical / per_super, rem = logical - sr * per_super;
-    const int gsz = min(SUPER, p.MT - sr * SUPER);
-    const int nt = rem / gsz;
-    m0 = (sr * SUPER + (rem - nt * gsz)) * BM;
-    n0 = nt * BN;
-  };
-  int li = slot;
+  const XcdRange rng = xcd_range(p.MT * p.NT * S);
+  const int nb_x = rng.nb_x, nt_x = rng.nt_x, start_x = rng.start_x;
+  auto decode = [&](int logical, int &m0, int &n0) { decode_tile<BM, BN>(logical, S, p.MT, p.NT, m0, n0); };
+  int li = rng.slot;
   if (li >= nt_x) return;                      // uniform for the whole workgroup
   int m0, n0;
   decode(start_x + li, m0, n0);
@@ -873,8 +814,6 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
   const int swz = (lane >> 1) & 7;
   const int arow = (wr * TM * 16 + (lane & 15)) * ROWB;
   const int wrow = (wc * TN * 16 + (lane & 15)) * ROWB;
-  const int ldo = p.ldo;
-  const bool vec_ok = (ldo & 3) == 0;
 
   int cur = 0;                                   // LDS buffer of the slab being multiplied
   // both operands addressable with 32-bit byte offsets (true for every tower shape)?
@@ -908,26 +847,14 @@ __global__ __launch_bounds__(WM *WN * 64, 2) void gemm_kernel(GemmParams p) {
   };
   // `ahead` = slabs in flight or landed BEHIND the one being multiplied (<= NSTAGE - 1).  A wait that must be sure of the next slab may
   // leave the ahead - 1 slabs issued after it in flight (vmcnt is in order): NSTAGE - 2 slabs of LDS-DMA cover the L2 / HBM round trip
-  // of these launches, whose time is one tile's serial K loop (2 - 5 stages; the 64 x 64 configuration runs 3).
+  // of these launches, whose time is one tile's serial K loop (the 64 x 64 configuration runs 3 stages).
   auto wait_all_but = [&](int slabs) {       // uniform; slabs <= NSTAGE - 2
-    if constexpr (NSTAGE >= 3) {
-      if (slabs >= 1) {
-        if constexpr (NSTAGE >= 4) {
-          if (slabs >= 2) {
-            if constexpr (NSTAGE >= 5) {
-              if (slabs >= 3) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * G) : "memory"); return; }
-            }
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
-            return;
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-        return;
-      }
+    if constexpr (NSTAGE == 3) {
+      if (slabs >= 1) { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory"); return; }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-  static_assert(NSTAGE >= 2 && NSTAGE <= 5 && 3 * G <= 63, "stages / counted waits");
+  static_assert((NSTAGE == 2 || NSTAGE == 3) && G <= 63, "stages / counted waits");
   int ahead = -1;
 #pragma unroll
   for (int d = 0; d < NSTAGE - 1; ++d)
@@ -1092,28 +1019,17 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
     p.MT = (p.M + BM - 1) / BM;
   }
   constexpr int A_BYTES = BM * ROWB, STAGE = (BM + BN) * ROWB;
-  constexpr int SUPER = SUPER_ROWS / BM;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
   const int g = lane >> 4;
 
-  // ---- persistent, XCD-aware tile walk (as gemm_kernel) ----
-  const int ntiles = p.MT * p.NT, nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, slot = bid >> 3;
-  const int nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
-  const int nt_x = (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
-  const int start_x = xcd * (ntiles >> 3) + min(xcd, ntiles & 7);
-  // Logical order: super-rows of SUPER row blocks, inside a super-row column by column (as gemm_kernel).
-  auto decode = [&](int logical, int &m0, int &n0) {
-    const int per_super = SUPER * p.NT;
-    const int sr = logical / per_super, rem = logical - sr * per_super;
-    const int gsz = min(SUPER, p.MT - sr * SUPER);
-    const int nt = rem / gsz;
-    m0 = (sr * SUPER + (rem - nt * gsz)) * BM;
-    n0 = nt * BN;
-  };
-  int li = slot;
+  // ---- persistent, XCD-aware tile walk ----
+  [[maybe_unused]] const int bid = blockIdx.x;     // (the stamps build, gemm_stamps.h, files its records by it)
+  const XcdRange rng = xcd_range(p.MT * p.NT);
+  const int nb_x = rng.nb_x, nt_x = rng.nt_x, start_x = rng.start_x;
+  auto decode = [&](int logical, int &m0, int &n0) { decode_tile<BM, BN>(logical, 1, p.MT, p.NT, m0, n0); };
+  int li = rng.slot;
   if (li >= nt_x) return;                      // uniform for the whole workgroup
   int m0, n0;
   decode(start_x + li, m0, n0);
@@ -1209,15 +1125,17 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
     const int c = k / pp, i = (k - c * pp) / p.epi.patch;
     return ((size_t)c * p.epi.res + i) * p.epi.res * 2;
   };
-  // quarter qi (0 = A0, 1 = W0, 2 = W1, 3 = A1) of K-tile kk of the tile at (sm, sn) into stage st
+  // quarter qi of K-tile kk of the tile at (sm, sn) into stage st.  The quarters in the order the next K-tile's phases need them (the
+  // one-quarter-in-flight loop issues quarter ph in phase ph):
+  enum { Q_A0 = 0, Q_W0 = 1, Q_W1 = 2, Q_A1 = 3 };
   auto stage_quarter = [&](int qi, int sm, int sn, int kk, unsigned st, bool fastA, bool fastW, const char *ta, const char *tw) __attribute__((always_inline)) {
-    if (qi == 0 || qi == 3) {
-      const int grp = ga0 + (qi == 3 ? 8 : 0);
+    if (qi == Q_A0 || qi == Q_A1) {
+      const int grp = ga0 + (qi == Q_A1 ? 8 : 0);
       if constexpr (CAN_GATHER) {
         if (gather) {
           const char *sb0 = reinterpret_cast<const char *>(p.A) + gather_kbase(kk);
           const char *sb1 = sb0 - 1024;
-          const int h = qi == 3 ? 1 : 0;
+          const int h = qi == Q_A1 ? 1 : 0;
           asm volatile(
               "s_mov_b32 m0, %4\n\t"
               "s_nop 0\n\t"
@@ -1229,10 +1147,10 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
           return;
         }
       }
-      stage2(p.A, ta, qi == 3 ? offA1 : offA0, sm, p.M, p.lda_bytes, a_vo, a_vo2, grp, kk * ROWB, st + grp * 1024, fastA);
+      stage2(p.A, ta, qi == Q_A1 ? offA1 : offA0, sm, p.M, p.lda_bytes, a_vo, a_vo2, grp, kk * ROWB, st + grp * 1024, fastA);
     } else {
-      const int grp = gw0 + (qi == 2 ? 4 : 0);
-      stage2(p.W, tw, qi == 2 ? offW1 : offW0, sn, p.N, p.ldw_bytes, w_vo, w_vo2, grp, kk * ROWB, st + A_BYTES + grp * 1024, fastW);
+      const int grp = gw0 + (qi == Q_W1 ? 4 : 0);
+      stage2(p.W, tw, qi == Q_W1 ? offW1 : offW0, sn, p.N, p.ldw_bytes, w_vo, w_vo2, grp, kk * ROWB, st + A_BYTES + grp * 1024, fastW);
     }
   };
 
@@ -1247,7 +1165,6 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
   }
 
   u32x4 aS[4][2], wS[2][2];     // register subtile: 4 activation x 2 weight fragments x 2 K halves
-  [[maybe_unused]] u32x4 wD[1][2][2];   // the deep loop's weight fragments
   bool relax_first = false;     // the previous tile's epilogue issued exactly NST stores last (see the phase-end wait)
   // EPI_L2MIN2: -(norms) / 2 of a tile's 256 rows and 256 columns travel through 2 KiB of LDS behind the two stages -- one value per thread,
   // requested before the previous tile's epilogue and written behind it (held in registers across the epilogue, 24 per lane, they cost 4 spills)
@@ -1326,7 +1243,7 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
           __builtin_amdgcn_s_barrier();
           lgkm_wait_subtile(aS, wS);
           // (d) the MFMA cluster
-          __builtin_amdgcn_s_setprio(VTC_MFMA_PRIO);
+          __builtin_amdgcn_s_setprio(MFMA_PRIO);
   #pragma unroll
           for (int ks = 0; ks < 2; ++ks)
   #pragma unroll
@@ -1353,7 +1270,6 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
         });
       } else {
         // ---- deep pipeline (see the kernel's header comment) ----
-        constexpr int QA = 1, QB = 2;                                     // quarter ids: 0 = A0, 1 = W0, 2 = W1, 3 = A1
         constexpr int NST = fast_epilogue_trailing_stores<OutT, TM>();             // 16-byte stores per wave in tile_epilogue's fast paths (its LAST vm ops)
         const bool first = t == 0, last = t == ksteps - 1;                // of this tile (ksteps >= 2: never both)
         // K-tile t+1 (-> st_nxt): of this tile, or K-tile 0 of the next tile (no next tile: K-tile 0 of this one again, into a stage
@@ -1370,13 +1286,12 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
         static_for<4>([&](auto ph_c) __attribute__((always_inline)) {
           constexpr int ph = decltype(ph_c)::value;
           constexpr int qm = ph >> 1, qn = (ph == 1 || ph == 2) ? 1 : 0;
-          constexpr int wreg = 0;
           // (a) this quadrant's new fragments
           if constexpr (ph == 0 || ph == 1 || ph == 3) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-              lds_read16(wD[wreg][j][0], rw0, (qn * 2 + j) * 16 * ROWB);
-              lds_read16(wD[wreg][j][1], rw1, (qn * 2 + j) * 16 * ROWB);
+              lds_read16(wS[j][0], rw0, (qn * 2 + j) * 16 * ROWB);
+              lds_read16(wS[j][1], rw1, (qn * 2 + j) * 16 * ROWB);
             }
           }
           if constexpr (ph == 0 || ph == 2) {
@@ -1388,11 +1303,11 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
           }
           // (b) this phase's quarter(s); (c) the counted waits, BEFORE the phase's first barrier (their data is read in a later phase)
           if constexpr (ph == 0) {
-            stage_quarter(QA, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);
-            if (first) stage_quarter(0, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);        // A0 of K-tile 1: the previous tile's ph2 did not issue it
+            stage_quarter(Q_W0, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);
+            if (first) stage_quarter(Q_A0, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);     // A0 of K-tile 1: the previous tile's ph2 did not issue it
           } else if constexpr (ph == 1) {
-            if (first) stage_quarter(QB, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);       // ... nor QB in its ph3 (QB before A1: ph3's count)
-            stage_quarter(3, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);
+            if (first) stage_quarter(Q_W1, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);     // ... nor W1 in its ph3 (W1 before A1: ph3's count)
+            stage_quarter(Q_A1, sm1, sn1, kk1, st_nxt, fA1, fW1, ta1, tw1);
             // A1 of THIS K-tile (issued four quarters ago) has landed.  First K-tile after an interior epilogue: its NST stores sit
             // between A1 and this K-tile's quarters in the in-order queue, and nothing younger than them is needed yet.
             if (first && relax_first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 + NST) : "memory");
@@ -1402,26 +1317,26 @@ __global__ __launch_bounds__(512, 2) void gemm_phased_kernel(GemmParams p) {
               if constexpr (CAN_GATHER) {
                 if (gather && nx2 && t + 2 == ksteps) gather_offsets(m0n);       // every activation quarter from here on is the next tile's
               }
-              stage_quarter(0, sm2, sn2, kk2, st_cur, fA2, fW2, ta2, tw2);
+              stage_quarter(Q_A0, sm2, sn2, kk2, st_cur, fA2, fW2, ta2, tw2);
             }
           } else {
-            if (!last) stage_quarter(QB, sm2, sn2, kk2, st_cur, fA2, fW2, ta2, tw2);
-            lgkm_wait_w4(wD[0]);                                                  // W0's second read retired before the barrier: re-filled next phase
-            // A0, QA, QB of K-tile t+1 have landed (A1 and this K-tile's two quarters stay in flight)
+            if (!last) stage_quarter(Q_W1, sm2, sn2, kk2, st_cur, fA2, fW2, ta2, tw2);
+            lgkm_wait_w4(wS);                                                  // W0's second read retired before the barrier: re-filled next phase
+            // A0, W0, W1 of K-tile t+1 have landed (A1 and this K-tile's two quarters stay in flight)
             if (last) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
           }
           __builtin_amdgcn_s_barrier();
-          lgkm_wait_subtile(aS, wD[0]);
+          lgkm_wait_subtile(aS, wS);
           VTC_PHASE_STAMP(1);
           // (d) the MFMA cluster
-          __builtin_amdgcn_s_setprio(VTC_MFMA_PRIO);
+          __builtin_amdgcn_s_setprio(MFMA_PRIO);
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-              for (int j = 0; j < 2; ++j) Mma<T>::run(wD[wreg][j][ks], aS[i][ks], acc[qm * 4 + i][qn * 2 + j]);
+              for (int j = 0; j < 2; ++j) Mma<T>::run(wS[j][ks], aS[i][ks], acc[qm * 4 + i][qn * 2 + j]);
           __builtin_amdgcn_s_setprio(0);
           VTC_PHASE_STAMP(0);
           __builtin_amdgcn_s_barrier();
@@ -1541,27 +1456,51 @@ int run_phased(const GemmParams &p, hipStream_t stream) {
   return run_phased_d<MODE, OutT, T, 0>(p, stream);
 }
 
-template <typename T, int MODE, typename OutT>
-int run_cfg(const GemmParams &p, hipStream_t stream) {
-  if constexpr (sizeof(T) == 2) {
-    // Tile choice by estimated rounds: a round of 256x256 tiles (one per CU) costs ~1.0, a round of 128x128 tiles
-    // (two per CU) ~0.65 of that (calibrated on the vision-tower shapes, tools/gemm_tile_choice.py of commit dda8438: 150 big tiles
-    // -> big, 297 -> small, 75 -> small, 256 -> big, 450 and more -> big).
-    const long tb = (long)cdiv(p.M, 256) * cdiv(p.N, 256), ts = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
-    const long rb = (tb + num_cus() - 1) / num_cus(), rs = (ts + 2 * num_cus() - 1) / (2 * num_cus());
-    if (rb * 100 <= rs * 65) return run_phased<MODE, OutT, T>(p, stream);
+// ---- the tile configuration: decided here and nowhere else ----------------------------------------------------------------
+enum class Tile { Phased256, Small128, Small64 };
+struct TileChoice {
+  Tile tile;
+  int nstage;      // LDS stages of the 64 x 64 K loop (the other two configurations run two)
+};
+// (modes that only the phased kernel implements -- the patch gather, EPI_L2MIN*, EPI_RESID_LN -- do not ask: they call run_phased)
+constexpr TileChoice choose_tile(int M, int N, int K, int elem_bytes, int ksplit, int cus) {
+  // 64 x 64: the slabs staged ahead may reach into the NEXT tile but not beyond it: a K loop of ksteps slabs carries at most ksteps + 1 stages
+  const int ksteps = K / (ksplit > 1 ? ksplit : 1) / (ROWB / elem_bytes);
+  const TileChoice small64 = {Tile::Small64, ksteps >= SMALL_NSTAGE - 1 ? SMALL_NSTAGE : 2};
+  if (ksplit > 1) return small64;      // split-K (launch_gemm checked: 16-bit operands, fp32 partial planes): one workgroup per (tile, slice)
+  if (elem_bytes == 2) {
+    // Estimated rounds: a round of 256x256 tiles (one per CU) costs ~1.0, a round of 128x128 tiles (two per CU) ~0.65 of that
+    // (calibrated on the vision-tower shapes; the calibration points are the static_asserts below).
+    const long tb = (long)cdiv(M, 256) * cdiv(N, 256), ts = (long)cdiv(M, 128) * cdiv(N, 128);
+    const long rb = (tb + cus - 1) / cus, rs = (ts + 2 * cus - 1) / (2 * cus);
+    if (rb * 100 <= rs * 65) return {Tile::Phased256, 2};
   }
   // few 128x128 tiles (CAM: 1536 x 512, the output projections): 64x64 tiles, two waves, put 4x the workgroups
   // on the chip -- these launches are bounded by one tile's serial K loop, not by throughput
-  const long ts128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
-#ifndef VTC_SMALL_NSTAGE
-#define VTC_SMALL_NSTAGE 3      // LDS stages of the 64 x 64 configuration: two K-steps of LDS-DMA in flight (these launches are one tile's serial K loop: B = 1 forward 2.36 -> 1.98 ms from 2 to 3 stages in round 2; 5 stages, round 5: no further gain -- 1.83 against 1.78 - 1.80 ms, profiles/r05_experiments.txt 8)
-#endif
-  if (ts128 * 2 <= num_cus()) {
-    // the slabs staged ahead may reach into the NEXT tile but not beyond it: a K loop of ksteps slabs carries at most ksteps + 1 stages
-    const int ksteps = p.K / Mma<T>::KPR;
-    if (ksteps >= VTC_SMALL_NSTAGE - 1) return run<T, MODE, OutT, 2, 1, 2, 4, VTC_SMALL_NSTAGE>(p, stream);
-    if (ksteps >= 2) return run<T, MODE, OutT, 2, 1, 2, 4, 3>(p, stream);
+  const long ts128 = (long)cdiv(M, 128) * cdiv(N, 128);
+  if (ts128 * 2 <= cus) return small64;
+  return {Tile::Small128, 2};
+}
+constexpr Tile tile_at_256_cus(int M, int N, int elem_bytes = 2) { return choose_tile(M, N, 768, elem_bytes, 0, 256).tile; }
+static_assert(tile_at_256_cus(12800, 768) == Tile::Phased256, "150 big tiles: big");
+static_assert(tile_at_256_cus(25344, 768) == Tile::Small128, "297 big tiles: small");
+static_assert(tile_at_256_cus(6400, 768) == Tile::Small128, "75 big tiles: small");
+static_assert(tile_at_256_cus(32768, 512) == Tile::Phased256, "256 big tiles: big");
+static_assert(tile_at_256_cus(38400, 768) == Tile::Phased256, "450 big tiles: big");
+static_assert(tile_at_256_cus(12800, 768, 4) != Tile::Phased256 && tile_at_256_cus(32768, 512, 4) != Tile::Phased256, "fp32 operands: never the phased kernel");
+static_assert(tile_at_256_cus(1024, 2048) == Tile::Small64 && tile_at_256_cus(1024 + 128, 2048) == Tile::Small128, "64 x 64 while tiles128 * 2 <= cus");
+static_assert(choose_tile(128, 128, 64, 2, 0, 256).nstage == 2 && choose_tile(128, 128, 128, 2, 0, 256).nstage == SMALL_NSTAGE &&
+                  choose_tile(128, 128, 192, 2, 0, 256).nstage == SMALL_NSTAGE && choose_tile(128, 128, 256, 2, 4, 256).nstage == 2,
+              "64 x 64 stages: 2 for one K-step (of a slice), 3 from two K-steps on");
+
+template <typename T, int MODE, typename OutT>
+int run_cfg(const GemmParams &p, hipStream_t stream) {
+  const TileChoice c = choose_tile(p.M, p.N, p.K, sizeof(T), p.epi.ksplit, num_cus());
+  if constexpr (sizeof(T) == 2) {
+    if (c.tile == Tile::Phased256) return run_phased<MODE, OutT, T>(p, stream);
+  }
+  if (c.tile == Tile::Small64) {
+    if (c.nstage == SMALL_NSTAGE) return run<T, MODE, OutT, 2, 1, 2, 4, SMALL_NSTAGE>(p, stream);
     return run<T, MODE, OutT, 2, 1, 2, 4, 2>(p, stream);
   }
   return run<T, MODE, OutT, 2, 2, 4, 4, 2>(p, stream);
@@ -1583,13 +1522,7 @@ int dispatch(GemmParams p, hipStream_t stream) {
   using Out16 = std::conditional_t<sizeof(T) == 2, T, bf16_t>;   // 16-bit outputs are in the operand format (fp32 operands: bf16)
   switch (p.epi.mode) {
     case VTC_EPI_STORE:
-      if constexpr (sizeof(T) == 2) {
-        if (p.epi.ksplit > 1) {      // (launch_gemm checked: fp32 partial planes, 64 x 64 tiles, one workgroup per (tile, slice))
-          if (p.K / p.epi.ksplit / Mma<T>::KPR >= VTC_SMALL_NSTAGE - 1) return run<T, VTC_EPI_STORE, float, 2, 1, 2, 4, VTC_SMALL_NSTAGE>(p, stream);
-          return run<T, VTC_EPI_STORE, float, 2, 1, 2, 4, 2>(p, stream);
-        }
-      }
-      if (out_f32) return run_cfg<T, VTC_EPI_STORE, float>(p, stream);
+      if (out_f32) return run_cfg<T, VTC_EPI_STORE, float>(p, stream);     // (split-K comes this way: fp32 partial planes, and choose_tile gives it 64 x 64 tiles)
       if constexpr (sizeof(T) == 2) {
         if (p.epi.fold_stat) return run_cfg<T, EPI_STORE_FOLD, Out16>(p, stream);
       }
@@ -1645,9 +1578,7 @@ bool gemm_resid_ln_supported(int M, int N, int K, int dtype) {
   if (dtype != VTC_BF16 && dtype != VTC_F16) return false;
   if (N % 256 != 0 || N > 512 * LN_MAXV || K % 64 != 0) return false;
   if ((size_t)M * N * 4 >= ((size_t)1 << 32)) return false;
-  const long tb = (long)cdiv(M, 256) * cdiv(N, 256), ts = (long)cdiv(M, 128) * cdiv(N, 128);
-  const long rb = (tb + num_cus() - 1) / num_cus(), rs = (ts + 2 * num_cus() - 1) / (2 * num_cus());
-  return rb * 100 <= rs * 65;          // the tile heuristic of run_cfg picks the phased kernel
+  return choose_tile(M, N, K, 2, 0, num_cus()).tile == Tile::Phased256;
 }
 
 int launch_gemm(const void *A, const void *W, const float *bias, void *out, int M, int N, int K, int dtype,

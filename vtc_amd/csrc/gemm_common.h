@@ -9,41 +9,30 @@ namespace vtcgemm {
 constexpr int ROWB = 128;          // bytes of K per LDS row
 constexpr int SUPER_ROWS = 1024;   // output rows per L2 super-row
 
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // one 128-bit register tuple (asm "v" operand)
+
+// one 16-byte chunk of K: weight fragment w x activation fragment a -> acc
 template <typename T> struct Mma;
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 template <> struct Mma<bf16_t> {
   static constexpr int KPR = 64;  // K elements per 128-byte row
-  __device__ static __forceinline__ void run(const u32x4v &w, const u32x4v &a, f32x4 &acc) {
+  __device__ static __forceinline__ void run(const u32x4 &w, const u32x4 &a, f32x4 &acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ void run(const uint4 &w, const uint4 &a, f32x4 &acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, a), acc,
-                                                  0, 0, 0);
   }
 };
 template <> struct Mma<f16_t> {
   static constexpr int KPR = 64;
-  __device__ static __forceinline__ void run(const u32x4v &w, const u32x4v &a, f32x4 &acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, a), acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ void run(const uint4 &w, const uint4 &a, f32x4 &acc) {
+  __device__ static __forceinline__ void run(const u32x4 &w, const u32x4 &a, f32x4 &acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, a), acc, 0, 0, 0);
   }
 };
 template <> struct Mma<float> {
   static constexpr int KPR = 32;
-  __device__ static __forceinline__ void run(const u32x4v &w, const u32x4v &a, f32x4 &acc) {
+  __device__ static __forceinline__ void run(const u32x4 &w, const u32x4 &a, f32x4 &acc) {
     const f32x4 wv = __builtin_bit_cast(f32x4, w), av = __builtin_bit_cast(f32x4, a);   // whole-tuple casts
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[0], av[0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[1], av[1], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[2], av[2], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[3], av[3], acc, 0, 0, 0);
-  }
-  __device__ static __forceinline__ void run(const uint4 &w, const uint4 &a, f32x4 &acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, w.x), __builtin_bit_cast(float, a.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, w.y), __builtin_bit_cast(float, a.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, w.z), __builtin_bit_cast(float, a.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__builtin_bit_cast(float, w.w), __builtin_bit_cast(float, a.w), acc, 0, 0, 0);
   }
 };
 
@@ -85,7 +74,6 @@ __device__ __forceinline__ void glds16(const char *gsrc, unsigned lds_dst) {
 // 16-byte LDS read the compiler does not schedule or count: `addr` is the 32-bit LDS byte address,
 // OFF an immediate (< 65536).  The data is valid only after a matching lgkm_wait (LDS reads of one
 // wave return in order; every wait names the registers it guards so no consumer can move above it).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // one 128-bit register tuple (asm "v" operand)
 __device__ __forceinline__ void lds_read16(u32x4 &dst, unsigned addr, int off) {
   // "memory": keeps the read below the barrier that publishes the buffer and above the one that recycles it
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory");
@@ -94,16 +82,9 @@ template <int N>
 __device__ __forceinline__ void lgkm_wait(u32x4 &x) {
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "n"(N));
 }
-template <int N, int TN>
-__device__ __forceinline__ void lgkm_wait_frags(u32x4 &x, u32x4 (&w)[TN]) {
-  static_assert(TN == 4 || TN == 8, "four or eight weight fragments per wave");
-  if constexpr (TN == 4) {
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(x), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N));
-  } else {
-    asm volatile("s_waitcnt lgkmcnt(%9)"
-                 : "+v"(x), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7])
-                 : "n"(N));
-  }
+template <int N>
+__device__ __forceinline__ void lgkm_wait_frags(u32x4 &x, u32x4 (&w)[4]) {      // ... and the wave's four weight fragments
+  asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(x), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N));
 }
 
 // all twelve fragments of the phased kernel's register subtile (whatever subset was just re-read) have landed
@@ -179,6 +160,36 @@ __device__ __forceinline__ void stage_tile(const char *base, int row0, int nrows
   }
 }
 
+// ---- the persistent, XCD-aware tile walk of both kernels ----
+// Workgroups with equal (id mod 8) share an XCD (observed dispatch; used for speed only).  Each XCD label gets a contiguous range
+// of the logical tile order -- nt_x tiles from start_x on -- which its nb_x workgroups walk with stride nb_x from their slot.
+struct XcdRange {
+  int slot, nb_x, nt_x, start_x;
+};
+__device__ __forceinline__ XcdRange xcd_range(int ntiles) {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int xcd = bid & 7;
+  XcdRange r;
+  r.slot = bid >> 3;
+  r.nb_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0);
+  r.nt_x = (ntiles >> 3) + (xcd < (ntiles & 7) ? 1 : 0);
+  r.start_x = xcd * (ntiles >> 3) + min(xcd, ntiles & 7);
+  return r;
+}
+// Logical order: super-rows of SUPER row blocks, inside a super-row column by column; with split-K (S > 1 slices) over (tile,
+// K slice) pairs, slice-minor.  -> first row and column of the tile.
+template <int BM, int BN>
+__device__ __forceinline__ void decode_tile(int logical, int S, int MT, int NT, int &m0, int &n0) {
+  constexpr int SUPER = SUPER_ROWS / BM;
+  if (S > 1) logical /= S;
+  const int per_super = SUPER * NT;
+  const int sr = logical / per_super, rem = logical - sr * per_super;
+  const int gsz = min(SUPER, MT - sr * SUPER);
+  const int nt = rem / gsz;
+  m0 = (sr * SUPER + (rem - nt * gsz)) * BM;
+  n0 = nt * BN;
+}
+
 // QuickGELU x * sigmoid(1.702 x) (model/timesformer_clip_alt.py:31-33).  fp32 mode: IEEE division and
 // expf; bf16 mode: v_exp_f32 + v_rcp_f32 (1 ulp each, far below the bf16 rounding of the result) --
 // the IEEE division sequence alone cost ~25 % of a K = 512 tile.
@@ -196,7 +207,5 @@ __device__ __forceinline__ gelu_f2_t quick_gelu2(gelu_f2_t x) {
   const gelu_f2_t d = (gelu_f2_t){__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)} + (gelu_f2_t){1.0f, 1.0f};
   return x * (gelu_f2_t){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
 }
-
-int num_cus();
 
 }  // namespace vtcgemm

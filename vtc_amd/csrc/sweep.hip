@@ -23,8 +23,6 @@
 
 #include <algorithm>
 
-namespace vtcgemm { int num_cus(); }   // gemm.hip
-
 namespace {
 
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict__ x, float *__restrict__ out, int n, int d) {

@@ -35,7 +35,6 @@
 #include <string.h>
 
 #include "common.h"
-namespace vtcgemm { int num_cus(); }
 
 static thread_local char g_err[512] = "";
 void vtc_set_error(const char *fmt, ...) {
