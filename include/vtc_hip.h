@@ -311,6 +311,24 @@ int vtc_l2_recall_bidir_supported(int n, int d);
 size_t vtc_l2_recall_bidir_workspace_bytes(int n, int d);
 int vtc_l2_recall_bidir(const float *a, const float *b, int n, int d, const int *k_vals_host, int nk, long long *hits_b_from_a,
                         long long *hits_a_from_b, void *ws, size_t ws_bytes, void *stream);
+/* FULL ranks of both directions of n PAIRED rows (a_i <-> b_i), for median / mean rank, MRR and recall at ANY k:
+ *   rank_a[i] = #{ j : (|b_i - a_j|^2, j) < (|b_i - a_i|^2, i) }   gallery a, query b_i   (the direction of RecallAtK.compute(a, b))
+ *   rank_b[i] = #{ j : (|a_i - b_j|^2, j) < (|a_i - b_i|^2, i) }   gallery b, query a_i   (the direction of RecallAtK.compute(b, a))
+ * 0-based int64 (device, n each); pairs compare lexicographically on the fp64 distances sum_k (q_k - g_k)^2 of the fp32 inputs, so exact
+ * ties go to the lower index and  #{ i : rank[i] < k }  are the counters of vtc_l2_recall_bidir, bit for bit, for every k.
+ * The sweep COUNTS instead of selecting: the split-bf16 distance GEMM of VTC_SWEEP_BF16X3 writes row blocks (rows_per_block as in
+ * vtc_l2_topk; 0 = as many rows as fit 2 GiB), a row pass and a column pass over each block count the entries that are closer than the
+ * target by more than the BF16X3 error bound  eps = kappa (|q|^2 + max|g|^2),  kappa = the value vtc_l2_rank_kappa returns for d,  and
+ * put the pairs within eps of it into a reach pool of reach_capacity pairs per direction (0 = the default, 512 n) that is settled in fp64.
+ * An owner whose pairs did not fit is counted again by fp64 brute force: the ranks do not depend on the capacity.
+ * A gallery row with a non-finite distance is never closer; a pair whose own distance |a_i - b_i|^2 is not finite (NaN / inf anywhere in
+ * a_i or b_i) gets rank n in both directions: a miss at every k.  nonfinite[0] (int32, device) = 1 if a holds a NaN / inf, | 2 if b does.
+ * n >= 1, d % 64 == 0.  After the call the first eight 64-bit words of the workspace hold the sweep's statistics, (direction a, direction
+ * b) each: pairs in reach, the largest number of them for one owner, owners counted by brute force; then two unused words. */
+float vtc_l2_rank_kappa(int d);
+size_t vtc_l2_rank_bidir_workspace_bytes(int n, int d, int rows_per_block, int reach_capacity);
+int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per_block, int reach_capacity, int64_t *rank_a,
+                      int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* The sharded sweep (above) with the recall-only finish: rank r holds rows [row_base, row_base + n_local) of both sets and the gathered
  * sets, runs ONE [n_local, n_total] distance GEMM and adds its PARTIAL counters (the host all-reduces them: model/metric.py:148-160 counted
  * over this rank's queries):

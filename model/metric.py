@@ -1,1 +1,1 @@
-from vtc_amd.host.metric import BaseMetric, RecallAtK  # noqa: F401
+from vtc_amd.host.metric import BaseMetric, RecallAtK, rank_statistics  # noqa: F401

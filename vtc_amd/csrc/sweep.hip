@@ -2,6 +2,8 @@
 //   vtc_l2_topk     exact squared-L2 k-NN: replaces faiss.GpuIndexFlatL2.add/search in
 //                   RecallAtK.compute (model/metric.py:137-146)
 //   vtc_recall_hits `target in rp[:k]` counting (model/metric.py:148-160)
+//   vtc_l2_rank_bidir  the exact rank of EVERY pair's target in both directions (median / mean rank, MRR, recall at any k): a counting
+//                   sweep over the BF16X3 distance blocks, fp64 for the entries within the error bound of a target (end of this file)
 //   vtc_similarity  exp(logit_scale) * V @ T^T (model/model.py:369,478,504,621)
 //   vtc_clip_loss   0.5 (CE(sim, arange) + CE(sim^T, arange)) (model/loss.py:18-22)
 //
@@ -652,14 +654,19 @@ static void launch_minsel(const MinselArgs &A, const MinselArgs *B, hipStream_t 
 }
 
 // ---- VTC_SWEEP_EXACT ------------------------------------------------------------------------------------
+// One step of every fp64 squared distance of this file: four coordinates of a (query, gallery) pair.  ALL the kernels that form
+// sum_k (q_k - g_k)^2 -- the re-rank, the rescan, the recall-only finish, the full-rank sweep -- add these steps in the same order (a lane's
+// chunks in ascending k, then the xor butterfly), so a distance has the same bits whichever kernel forms it and exact ties stay ties.
+__device__ __forceinline__ double dist64_step(const float4 a, const float4 b) {
+  const double e0 = (double)a.x - (double)b.x, e1 = (double)a.y - (double)b.y, e2 = (double)a.z - (double)b.z, e3 = (double)a.w - (double)b.w;
+  return e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+}
 // fp64 squared distance sum_k (q_k - g_k)^2 of one (query, gallery) pair by the whole wave (lanes stride over k)
 __device__ __forceinline__ double wave_dist64(const float *__restrict__ q, const float *__restrict__ g, int d, int lane) {
   double s = 0.0;
   for (int c = lane * 4; c < d; c += 256) {
     const float4 a = *reinterpret_cast<const float4 *>(q + c), b = *reinterpret_cast<const float4 *>(g + c);
-    const double e0 = (double)a.x - (double)b.x, e1 = (double)a.y - (double)b.y, e2 = (double)a.z - (double)b.z,
-                 e3 = (double)a.w - (double)b.w;
-    s += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+    s += dist64_step(a, b);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);   // xor butterfly: every lane ends with the same bits
@@ -725,9 +732,7 @@ __global__ __launch_bounds__(256) void exact_rerank_kernel(const RerankArgs PA, 
         b[u] = *reinterpret_cast<const float4 *>(gallery + (size_t)(jj[u] < 0 ? 0 : jj[u]) * d + c);
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
-        const double e0 = (double)a.x - (double)b[u].x, e1 = (double)a.y - (double)b[u].y, e2 = (double)a.z - (double)b[u].z,
-                     e3 = (double)a.w - (double)b[u].w;
-        sacc[u] += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+        sacc[u] += dist64_step(a, b[u]);
       }
     }
 #pragma unroll
@@ -903,9 +908,7 @@ __global__ __launch_bounds__(256) void block_rescan_kernel(const RescanArgs PA, 
           for (int u = 0; u < 4; ++u) b[u] = *reinterpret_cast<const float4 *>(gallery + (size_t)jj[u] * d + c);
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const double e0 = (double)a.x - (double)b[u].x, e1 = (double)a.y - (double)b[u].y, e2 = (double)a.z - (double)b[u].z,
-                         e3 = (double)a.w - (double)b[u].w;
-            sacc[u] += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+            sacc[u] += dist64_step(a, b[u]);
           }
         }
 #pragma unroll
@@ -1272,9 +1275,7 @@ __device__ __forceinline__ void wave_dist64_x8(const float *__restrict__ q, cons
     for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const float4 *>(gallery + (size_t)(jj[u] < 0 ? 0 : jj[u]) * d + c);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const double e0 = (double)a.x - (double)b[u].x, e1 = (double)a.y - (double)b[u].y, e2 = (double)a.z - (double)b[u].z,
-                   e3 = (double)a.w - (double)b[u].w;
-      sacc[u] += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+      sacc[u] += dist64_step(a, b[u]);
     }
   }
 #pragma unroll
@@ -1329,9 +1330,7 @@ __device__ __forceinline__ void recall_rank_body(const RankArgs &P, int bid, Sha
       }
 #pragma unroll
       for (int cc = 0; cc < OPW; ++cc) {
-        const double e0 = (double)qa[cc].x - (double)gb[cc].x, e1 = (double)qa[cc].y - (double)gb[cc].y, e2 = (double)qa[cc].z - (double)gb[cc].z,
-                     e3 = (double)qa[cc].w - (double)gb[cc].w;
-        dt[cc] += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+        dt[cc] += dist64_step(qa[cc], gb[cc]);
       }
     }
 #pragma unroll
@@ -1766,6 +1765,506 @@ int recall_bidir_impl(const float *a, const float *b, int n, int d, const KList 
   VTC_LAUNCH_CHECK("l2_recall_bidir");
   return 0;
 }
+// ---- full-rank sweep (vtc_l2_rank_bidir): COUNT instead of select ------------------------------------------------------------------
+// rank_i = #{ j : (|q_i - g_j|^2, j) < (|q_i - g_t|^2, t) } for EVERY query, wherever its target landed (median / mean rank, MRR, recall at
+// any k), in both directions of n paired rows from the blocks of ONE split-bf16 distance matrix D[i][j] ~ |b_i - a_j|^2 (the BF16X3 GEMM of
+// l2_topk_impl).  With d_t the target's fp64 distance and eps = kappa (|q|^2 + max|g|^2) the bound that certifies the BF16X3 lists
+// (exact_finish_lists), an entry v of the query's row (gallery a) or column (gallery b) is
+//   v < lo = rd(d_t - eps)   closer for certain: counted;     v > hi = ru(d_t + eps)   farther for certain: dropped;
+//   else (a NaN entry too)   in reach: the pair (owner, other) goes to the direction's reach pool and fp64 decides (rank_settle_kernel).
+// An owner whose pairs did not fit the pool is flagged and counted again by fp64 brute force over the whole other side
+// (rank_brute_kernel), so the ranks do not depend on the pool's capacity.  A pair whose target distance is not finite gets rank n.
+constexpr int RS_STATS = 8;           // 64-bit words at the head of the workspace (include/vtc_hip.h, vtc_l2_rank_bidir)
+constexpr int RS_NB = 8;              // fp64 distances a wave forms at once
+float rank_kappa(int d) { return 3.0f / 65536.0f + 4.0f * d / 16777216.0f + 1e-6f; }      // = exact_finish_lists' kappa
+
+// fp64 |q_u - g_u|^2 of RS_NB pairs at once: per pair the arithmetic and order of wave_dist64.  EVERY distance the rank sweep compares
+// (targets, pooled pairs, brute force) is formed by this one function, so exact ties are bit-equal.
+__device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, const float *__restrict__ gs, const int (&qi)[RS_NB],
+                                                  const int (&gi)[RS_NB], int d, int lane, double (&out)[RS_NB]) {
+  double sacc[RS_NB];
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) sacc[u] = 0.0;
+  for (int c = lane * 4; c < d; c += 256) {
+    float4 a[RS_NB], b[RS_NB];
+#pragma unroll
+    for (int u = 0; u < RS_NB; ++u) {
+      a[u] = *reinterpret_cast<const float4 *>(qs + (size_t)qi[u] * d + c);
+      b[u] = *reinterpret_cast<const float4 *>(gs + (size_t)gi[u] * d + c);
+    }
+#pragma unroll
+    for (int u = 0; u < RS_NB; ++u) {
+      sacc[u] += dist64_step(a[u], b[u]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int u = 0; u < RS_NB; ++u) sacc[u] += __shfl_xor(sacc[u], o, 64);
+  }
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) out[u] = sacc[u];
+}
+
+// max of the FINITE squared norms of each side (a non-finite row's entries are NaN / inf whatever the bound says; with it in the maximum
+// every query of the direction would have the whole gallery in reach)
+__global__ __launch_bounds__(256) void rank_max_kernel(const float *__restrict__ xa, const float *__restrict__ xb, int n, float *__restrict__ out_a,
+                                                       float *__restrict__ out_b) {
+  __shared__ float part[4];
+  const float *x = blockIdx.x ? xb : xa;
+  float m = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float v = x[i];
+    m = v < INFINITY ? fmaxf(m, v) : m;
+  }
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) *(blockIdx.x ? out_b : out_a) = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+
+// per-direction state of the counting sweep
+struct RankDir {
+  const float *own, *other;      // [n, d] fp32: the direction's queries and its gallery
+  const float *lo, *hi;          // [n] thresholds of the owner's row / column of D (hi = -inf: the owner's target distance is not finite)
+  int *cnt;                      // [n] entries closer than the target
+  int *reach;                    // [n] entries in reach of the target (statistics)
+  int *ovf;                      // [n] != 0: the owner's pairs did not fit the pool
+  int2 *pool;                    // [cap] (owner, other)
+  unsigned long long *pool_n;    // pairs offered to the pool (may exceed cap)
+  unsigned long long cap;
+};
+
+// One wave per 8 pairs: the targets' fp64 distances, both directions' thresholds, and the counters' zeroes.
+__global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, int n, int d,
+                                                        const float *__restrict__ an2, const float *__restrict__ bn2,
+                                                        const float *__restrict__ amax, const float *__restrict__ bmax, float kappa,
+                                                        double *__restrict__ dt, float *__restrict__ lo_r, float *__restrict__ hi_r,
+                                                        float *__restrict__ lo_c, float *__restrict__ hi_c, int *__restrict__ zero, int n_zero) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  for (int i = t; i < n_zero; i += gridDim.x * 256) zero[i] = 0;
+  const int lane = threadIdx.x & 63;
+  const int i0 = (t >> 6) * RS_NB;
+  if (i0 >= n) return;                                  // wave-uniform
+  int ii[RS_NB];
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) ii[u] = min(i0 + u, n - 1);
+  double dd[RS_NB];
+  wave_dist64_pairs(b, a, ii, ii, d, lane, dd);
+  double mine = 0.0;
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
+  const int i = i0 + lane;
+  if (lane < RS_NB && i < n) {
+    dt[i] = mine;
+    const bool ok = mine < (double)INFINITY;            // false for NaN too
+    // rows of D: query b_i against the a's; columns: query a_i against the b's
+    const float eps_r = kappa * (bn2[i] + *amax), eps_c = kappa * (an2[i] + *bmax);
+    lo_r[i] = ok ? __double2float_rd(mine - (double)eps_r) : -INFINITY;
+    hi_r[i] = ok ? __double2float_ru(mine + (double)eps_r) : -INFINITY;
+    lo_c[i] = ok ? __double2float_rd(mine - (double)eps_c) : -INFINITY;
+    hi_c[i] = ok ? __double2float_ru(mine + (double)eps_c) : -INFINITY;
+  }
+}
+
+// Wave-wide append of the lanes' in-reach pairs: `m` has a bit per candidate slot of the lane, other(q) its index on the other side,
+// owner(q) its owner.  ONE atomic per wave reserves the room; a pair past the capacity flags its owner instead.
+template <int NSLOT, typename OwnerFn, typename OtherFn>
+__device__ __forceinline__ void rank_pool_append(const RankDir &P, unsigned m, int lane, OwnerFn owner, OtherFn other) {
+  const int nr = __popc(m);
+  int incl = nr;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    incl += lane >= o ? up : 0;
+  }
+  const int total = __shfl(incl, 63, 64);
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(P.pool_n, (unsigned long long)total);
+  base = __shfl(base, 0, 64);
+  unsigned long long pos = base + (unsigned long long)(incl - nr);
+#pragma unroll
+  for (int q = 0; q < NSLOT; ++q) {
+    if ((m >> q) & 1u) {
+      if (pos < P.cap) P.pool[pos] = make_int2(owner(q), other(q));
+      else P.ovf[owner(q)] = 1;
+      ++pos;
+    }
+  }
+}
+
+// The same through a wave-private staging buffer in LDS (RS_STAGE pairs): the atomic that reserves room in the pool returns a value the wave
+// has to wait for, and with a pair or two in reach in most steps of a scan that wait was the scan (10k: 0.34 of the row pass's ms).  Staged,
+// a wave pays it once per RS_STAGE pairs and once at its end (rank_stage_flush).  A step with more pairs than the buffer holds goes direct.
+constexpr int RS_STAGE = 256;
+__device__ __forceinline__ void rank_stage_flush(const RankDir &P, const int2 *stage, int &n_st, int lane) {
+  if (n_st == 0) return;                                   // wave-uniform
+  __builtin_amdgcn_wave_barrier();
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(P.pool_n, (unsigned long long)n_st);
+  base = __shfl(base, 0, 64);
+  for (int i = lane; i < n_st; i += 64) {
+    const int2 e = stage[i];
+    if (base + (unsigned long long)i < P.cap) P.pool[base + (unsigned long long)i] = e;
+    else P.ovf[e.x] = 1;
+  }
+  __builtin_amdgcn_wave_barrier();
+  n_st = 0;
+}
+template <int NSLOT, typename OwnerFn, typename OtherFn>
+__device__ __forceinline__ void rank_stage_append(const RankDir &P, int2 *stage, int &n_st, unsigned m, int lane, OwnerFn owner, OtherFn other) {
+  const int nr = __popc(m);
+  int incl = nr;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    incl += lane >= o ? up : 0;
+  }
+  const int total = __shfl(incl, 63, 64);
+  if (n_st + total > RS_STAGE) rank_stage_flush(P, stage, n_st, lane);       // wave-uniform
+  if (total > RS_STAGE) {                                                    // wave-uniform: a dense step (duplicates, clusters)
+    rank_pool_append<NSLOT>(P, m, lane, owner, other);
+    return;
+  }
+  int pos = n_st + incl - nr;
+#pragma unroll
+  for (int q = 0; q < NSLOT; ++q) {
+    if ((m >> q) & 1u) stage[pos++] = make_int2(owner(q), other(q));
+  }
+  n_st += total;
+}
+
+// Row direction: one wave per (row of the block, column segment), streaming as row_topk_kernel does (1024 columns per step, four 16-byte
+// loads per lane, two steps in flight behind the one being counted).  Per value two compares; one atomic per wave at the end.
+__global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row0, int S,
+                                                             int seg_cols, const RankDir P) {
+  __shared__ int2 stage_all[4][RS_STAGE];
+  const int lane = threadIdx.x & 63;
+  int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
+  int n_st = 0;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n_rows * S) return;
+  const int r = w / S, seg = w - r * S;
+  const int gr = row0 + r;                                // the owner, and the column of its target
+  const float lo = P.lo[gr], hi = P.hi[gr];
+  if (hi == -INFINITY) return;                            // wave-uniform: target distance not finite, rank n
+  const float *row = dist + (size_t)r * ld;
+  const int c_lo = seg * seg_cols, c_hi = min(n_cols, c_lo + seg_cols);
+  const bool vec = (ld & 3) == 0;
+  auto load_step = [&](int base, float (&v)[16]) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const int c = base + 256 * h + lane * 4;
+      if (vec && c + 3 < c_hi) {
+        typedef float v4f_t __attribute__((ext_vector_type(4)));
+        const v4f_t t = __builtin_nontemporal_load(reinterpret_cast<const v4f_t *>(row + c));
+        v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[4 * h + e] = c + e < c_hi ? row[c + e] : INFINITY;
+      }
+    }
+  };
+  float cur[16], nxt[16], nx2[16];
+  load_step(c_lo, cur);
+  if (c_lo + 1024 < c_hi) load_step(c_lo + 1024, nxt);
+  int closer = 0, n_reach = 0;
+  for (int base = c_lo; base < c_hi; base += 1024) {
+    if (base + 2048 < c_hi) load_step(base + 2048, nx2);
+    unsigned m = 0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int idx = base + 256 * (q >> 2) + lane * 4 + (q & 3);
+      const bool ok = idx < c_hi && idx != gr;
+      const bool lt = cur[q] < lo;
+      closer += (ok && lt) ? 1 : 0;
+      m |= (ok && !lt && !(cur[q] > hi)) ? (1u << q) : 0u;
+    }
+    if (__ballot(m != 0) != 0ull) {                       // wave-uniform, rare: entries within eps of the target's distance
+      n_reach += __popc(m);
+      rank_stage_append<16>(P, stage, n_st, m, lane, [&](int) { return gr; }, [&](int q) { return base + 256 * (q >> 2) + lane * 4 + (q & 3); });
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) { cur[q] = nxt[q]; nxt[q] = nx2[q]; }
+  }
+  rank_stage_flush(P, stage, n_st, lane);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { closer += __shfl_xor(closer, o, 64); n_reach += __shfl_xor(n_reach, o, 64); }
+  if (lane == 0) {
+    if (closer) atomicAdd(&P.cnt[gr], closer);
+    if (n_reach) atomicAdd(&P.reach[gr], n_reach);
+  }
+}
+
+// Column direction of the same block: one wave per (strip of 64 columns, row segment).  V = 4 (rows 16-byte aligned): a lane owns four
+// adjacent columns and every fourth row -- a load instruction of the wave is four 256-byte row pieces; V = 1: a lane owns one column.
+// Eight loads per lane in flight; the lanes' counts are folded over the wave once, behind the scan: one atomic per column and wave.
+// The counts are CARRIED from one block of rows to the next in P.cnt (global row ids: row_id0 + row).
+template <int V>
+__global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row_id0,
+                                                             int n_strips, int S, int seg_rows, const RankDir P) {
+  constexpr int U = 8, RPL = V;                           // loads in flight per lane; rows per load instruction of the wave
+  __shared__ int2 stage_all[4][RS_STAGE];
+  int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
+  int n_st = 0;
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n_strips * S) return;
+  const int seg = w / n_strips, strip = w - seg * n_strips;   // neighbouring waves: neighbouring strips of the same rows
+  const int c = strip * 64 + (V == 4 ? 4 * (lane & 15) : lane);
+  const int sub = V == 4 ? lane >> 4 : 0;
+  const int r_lo = seg * seg_rows, r_hi = min(n_rows, r_lo + seg_rows);
+  const bool live = c < n_cols;                           // (V = 4: n_cols % 4 == 0, the lane's four columns are in or out together)
+  float lo[V], hi[V];
+  int cnt[V], reach[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    lo[e] = live ? P.lo[c + e] : -INFINITY;
+    hi[e] = live ? P.hi[c + e] : -INFINITY;                // -inf: a column past the matrix, or an owner whose target distance is not finite
+    cnt[e] = 0; reach[e] = 0;
+  }
+  for (int rb = r_lo; rb < r_hi; rb += RPL * U) {
+    float v[U][V];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int row = rb + u * RPL + sub;
+      const float *src = dist + (size_t)min(row, r_hi - 1) * ld + (live ? c : 0);      // branch-free: all loads of a lane in flight together
+      if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(src);
+        v[u][0] = t.x; v[u][1 % V] = t.y; v[u][2 % V] = t.z; v[u][3 % V] = t.w;
+      } else {
+        v[u][0] = *src;
+      }
+    }
+    unsigned m = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int row = rb + u * RPL + sub;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const bool ok = row < r_hi && hi[e] != -INFINITY && row_id0 + row != c + e;
+        const bool lt = v[u][e] < lo[e];
+        cnt[e] += (ok && lt) ? 1 : 0;
+        const bool in = ok && !lt && !(v[u][e] > hi[e]);
+        reach[e] += in ? 1 : 0;
+        m |= in ? (1u << (u * V + e)) : 0u;
+      }
+    }
+    if (__ballot(m != 0) != 0ull)                          // wave-uniform, rare
+      rank_stage_append<U * V>(P, stage, n_st, m, lane, [&](int q) { return c + q % V; }, [&](int q) { return row_id0 + rb + (q / V) * RPL + sub; });
+  }
+  rank_stage_flush(P, stage, n_st, lane);
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    if (V == 4) {
+      cnt[e] += __shfl_xor(cnt[e], 16, 64); cnt[e] += __shfl_xor(cnt[e], 32, 64);
+      reach[e] += __shfl_xor(reach[e], 16, 64); reach[e] += __shfl_xor(reach[e], 32, 64);
+    }
+    if (live && sub == 0) {
+      if (cnt[e]) atomicAdd(&P.cnt[c + e], cnt[e]);
+      if (reach[e]) atomicAdd(&P.reach[c + e], reach[e]);
+    }
+  }
+}
+
+// The pooled pairs of both directions, eight per wave and step: fp64 distances (wave_dist64_pairs), compared as (d, other) < (d_t, owner).
+__global__ __launch_bounds__(256) void rank_settle_kernel(const RankDir PA, const RankDir PB, int nblocks_a, const double *__restrict__ dt, int d) {
+  const bool second = (int)blockIdx.x >= nblocks_a;
+  const RankDir &P = second ? PB : PA;
+  const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
+  const int nbl = second ? (int)gridDim.x - nblocks_a : nblocks_a;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long offered = *P.pool_n;
+  const long long n_e = (long long)(offered < P.cap ? offered : P.cap);
+  for (long long e0 = ((long long)bid * 4 + (threadIdx.x >> 6)) * RS_NB; e0 < n_e; e0 += (long long)nbl * 4 * RS_NB) {
+    const bool have = lane < RS_NB && e0 + lane < n_e;
+    const int2 pr = have ? P.pool[e0 + lane] : make_int2(0, 0);
+    int qi[RS_NB], gi[RS_NB];
+#pragma unroll
+    for (int u = 0; u < RS_NB; ++u) { qi[u] = __shfl(pr.x, u, 64); gi[u] = __shfl(pr.y, u, 64); }
+    double dd[RS_NB];
+    wave_dist64_pairs(P.own, P.other, qi, gi, d, lane, dd);
+    double mine = 0.0;
+#pragma unroll
+    for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
+    if (have) {                                            // (a flagged owner's count is overwritten by rank_brute_kernel, later in the stream)
+      const double t = dt[pr.x];
+      if (mine < t || (mine == t && pr.y < pr.x)) atomicAdd(&P.cnt[pr.x], 1);
+    }
+  }
+}
+
+// Flagged owners (their pairs overflowed the pool): the count again, by fp64 brute force over the whole other side; one workgroup of
+// eight waves per owner.  Also the statistics: owners sent here, the largest in-reach count of an owner.
+__global__ __launch_bounds__(512) void rank_brute_kernel(const RankDir PA, const RankDir PB, int nblocks_a, const double *__restrict__ dt, int n, int d,
+                                                         unsigned long long *__restrict__ stats) {
+  const bool second = (int)blockIdx.x >= nblocks_a;
+  const RankDir &P = second ? PB : PA;
+  const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
+  const int nbl = second ? (int)gridDim.x - nblocks_a : nblocks_a;
+  __shared__ int part[8];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int mx = 0;
+  for (int o = bid; o < n; o += nbl) {                     // uniform for the workgroup
+    mx = max(mx, P.reach[o]);
+    if (!P.ovf[o]) continue;
+    const double t = dt[o];
+    int cnt = 0;
+    for (int j0 = RS_NB * w; j0 < n; j0 += RS_NB * 8) {
+      int qi[RS_NB], gi[RS_NB];
+#pragma unroll
+      for (int u = 0; u < RS_NB; ++u) { qi[u] = o; gi[u] = min(j0 + u, n - 1); }
+      double dd[RS_NB];
+      wave_dist64_pairs(P.own, P.other, qi, gi, d, lane, dd);
+#pragma unroll
+      for (int u = 0; u < RS_NB; ++u) {
+        const int j = j0 + u;
+        if (j < n && j != o && (dd[u] < t || (dd[u] == t && j < o))) ++cnt;
+      }
+    }
+    if (lane == 0) part[w] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+#pragma unroll
+      for (int ww = 0; ww < 8; ++ww) total += part[ww];
+      P.cnt[o] = total;
+      atomicAdd(&stats[4 + (second ? 1 : 0)], 1ull);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && mx) atomicMax(&stats[2 + (second ? 1 : 0)], (unsigned long long)mx);
+}
+
+__global__ __launch_bounds__(256) void rank_write_kernel(const double *__restrict__ dt, const int *__restrict__ cnt_r, const int *__restrict__ cnt_c,
+                                                         int n, int64_t *__restrict__ rank_a, int64_t *__restrict__ rank_b) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool ok = dt[i] < (double)INFINITY;
+  rank_a[i] = ok ? (int64_t)cnt_r[i] : (int64_t)n;
+  rank_b[i] = ok ? (int64_t)cnt_c[i] : (int64_t)n;
+}
+
+struct RankWs {
+  unsigned long long *stats;       // [RS_STATS]
+  float *qn, *gn, *qmax, *gmax;    // queries = b (rows of D), gallery = a (columns)
+  bf16_t *qb, *gb;
+  float *dist;
+  int rows_per_block;
+  double *dt;
+  float *lo_r, *hi_r, *lo_c, *hi_c;
+  int *zero;                       // cnt_r, cnt_c, reach_r, reach_c, ovf_r, ovf_c: [6][n], zeroed by rank_prep_kernel
+  int2 *pool_r, *pool_c;
+  size_t cap;
+  size_t total;
+};
+// default pool: 512 pairs per owner and direction (8 bytes each).  Measured (profiles/r10_rank_sweep.md): an owner in the bulk of unrelated
+// unit vectors at d = 512 has 0.216 % of the other side in reach (108 pairs at 50k, at most 203), one whose target leads almost none.
+size_t rank_default_capacity(int n) { return std::max<size_t>(4096, (size_t)512 * n); }
+RankWs rank_plan(char *ws, int n, int d, int rows_per_block, int reach_capacity) {
+  RankWs s;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
+  s.stats = (unsigned long long *)take(RS_STATS * 8);
+  s.qn = (float *)take((size_t)n * 4);
+  s.gn = (float *)take((size_t)n * 4);
+  s.qmax = (float *)take(4);
+  s.gmax = (float *)take(4);
+  s.qb = (bf16_t *)take((size_t)n * d * 3 * 2);
+  s.gb = (bf16_t *)take((size_t)n * d * 3 * 2);
+  int rpb = rows_per_block;
+  if (rpb <= 0) {                                          // as plan(): as many rows as fit a 2 GiB block
+    rpb = (int)std::min<size_t>(((size_t)2 << 30) / ((size_t)n * 4), (size_t)1 << 20);
+    rpb = rpb / 256 * 256;
+    if (rpb < 256) rpb = 256;
+  }
+  if (rpb > n) rpb = n;
+  s.rows_per_block = rpb;
+  s.dist = (float *)take((size_t)rpb * n * 4);
+  s.dt = (double *)take((size_t)n * 8);
+  s.lo_r = (float *)take((size_t)n * 4);
+  s.hi_r = (float *)take((size_t)n * 4);
+  s.lo_c = (float *)take((size_t)n * 4);
+  s.hi_c = (float *)take((size_t)n * 4);
+  s.zero = (int *)take((size_t)6 * n * 4);
+  s.cap = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(n);
+  s.pool_r = (int2 *)take(s.cap * 8);
+  s.pool_c = (int2 *)take(s.cap * 8);
+  s.total = off;
+  return s;
+}
+
+int rank_bidir_impl(const float *a, const float *b, int n, int d, int64_t *rank_a, int64_t *rank_b, int *nonfinite, const RankWs &s,
+                    hipStream_t stream) {
+  int *cnt_r = s.zero, *cnt_c = s.zero + n, *reach_r = s.zero + 2 * (size_t)n, *reach_c = s.zero + 3 * (size_t)n, *ovf_r = s.zero + 4 * (size_t)n,
+      *ovf_c = s.zero + 5 * (size_t)n;
+  // gallery a, query b_i: the rows of D;  gallery b, query a_i: its columns
+  const RankDir R{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap};
+  const RankDir Cd{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap};
+  (void)hipMemsetAsync(s.stats, 0, RS_STATS * 8, stream);
+  (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
+  if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)n * d, nonfinite, stream)) return rc;
+  {
+    ProfScope prof(VTC_PROF_TOPK, (double)n * d * 2 * (4 + 6 + 4), stream);
+    prof.tag(101, n, d);
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, b, s.qn, n, d);
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, a, s.gn, n, d);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, b, s.qb, n, d, 3, 0);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, a, s.gb, n, d, 3, 1);
+    hipLaunchKernelGGL(rank_max_kernel, dim3(2), dim3(256), 0, stream, s.gn, s.qn, n, s.gmax, s.qmax);
+    hipLaunchKernelGGL(rank_prep_kernel, dim3(cdiv(cdiv(n, RS_NB), 4)), dim3(256), 0, stream, a, b, n, d, s.gn, s.qn, s.gmax, s.qmax, rank_kappa(d),
+                       s.dt, s.lo_r, s.hi_r, s.lo_c, s.hi_c, s.zero, 6 * n);
+  }
+  VTC_LAUNCH_CHECK("l2_rank_bidir prologue");
+  const int V = (n & 3) == 0 ? 4 : 1;
+  const int n_strips = cdiv(n, 64);
+  for (int r0 = 0; r0 < n; r0 += s.rows_per_block) {
+    const int rows = min(s.rows_per_block, n - r0);
+    GemmEpi e;
+    e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
+    if (int rc = launch_gemm(s.qb + (size_t)r0 * d * 3, s.gb, nullptr, s.dist, rows, n, d * 3, VTC_BF16, e, stream)) return rc;
+    {
+      // enough (row, segment) waves to fill the chip, as row_topk_kernel's launch
+      int S = cdiv(8192, rows);
+      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
+      const int seg_cols = cdiv(cdiv(n, S), 1024) * 1024;
+      S = cdiv(n, seg_cols);
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
+      prof.tag(102, rows, n);
+      hipLaunchKernelGGL(rank_row_count_kernel, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, S, seg_cols, R);
+    }
+    {
+      // (strip, segment) waves: ~32 per CU; a segment is a whole number of the wave's 8-load steps
+      const int step = 8 * V;
+      int S = std::max(1, cdiv(32 * vtcgemm::num_cus(), n_strips));
+      const int seg_rows = cdiv(cdiv(rows, S), step) * step;
+      S = cdiv(rows, seg_rows);
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
+      prof.tag(103, rows, n);
+      if (V == 4)
+        hipLaunchKernelGGL(rank_col_count_kernel<4>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
+      else
+        hipLaunchKernelGGL(rank_col_count_kernel<1>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
+    }
+    VTC_LAUNCH_CHECK("l2_rank_bidir count");
+  }
+  {
+    // eight pairs per wave and step; the pools' fill lives on the device, so the grid is sized for a full pool and strides
+    const int g = (int)std::min<size_t>(2048, (s.cap + 4 * RS_NB - 1) / (4 * RS_NB));
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    prof.tag(104, n, d);
+    hipLaunchKernelGGL(rank_settle_kernel, dim3(2 * g), dim3(256), 0, stream, R, Cd, g, s.dt, d);
+  }
+  {
+    const int g = std::min(n, 1024);
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    prof.tag(105, n, d);
+    hipLaunchKernelGGL(rank_brute_kernel, dim3(2 * g), dim3(512), 0, stream, R, Cd, g, s.dt, n, d, s.stats);
+  }
+  hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, s.dt, cnt_r, cnt_c, n, rank_a, rank_b);
+  VTC_LAUNCH_CHECK("l2_rank_bidir finish");
+  return 0;
+}
 }  // namespace
 
 // ---- sharded sweep: ONE [N/G, N] distance GEMM per rank for both directions (include/vtc_hip.h) ---------------------------
@@ -1976,6 +2475,23 @@ extern "C" int vtc_l2_recall_bidir(const float *a, const float *b, int n, int d,
   Sweep2Ws s = plan2((char *)ws, n, n, d, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_recall_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
   return recall_bidir_impl(a, b, n, d, kl, (unsigned long long *)hits_b_from_a, (unsigned long long *)hits_a_from_b, s, (hipStream_t)stream);
+}
+
+// ---- full ranks of both directions (median / mean rank, MRR, recall at any k): include/vtc_hip.h ----------------------------
+extern "C" float vtc_l2_rank_kappa(int d) { return rank_kappa(d); }
+extern "C" size_t vtc_l2_rank_bidir_workspace_bytes(int n, int d, int rows_per_block, int reach_capacity) {
+  if (n < 1 || d < 1) return 0;
+  return rank_plan(nullptr, n, d, rows_per_block, reach_capacity).total;
+}
+extern "C" int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per_block, int reach_capacity, int64_t *rank_a,
+                                 int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream) {
+  VTC_CHECK(a && b && rank_a && rank_b && nonfinite, "l2_rank_bidir: null argument");
+  VTC_CHECK(n >= 1, "l2_rank_bidir: n=%d must be >= 1", n);
+  VTC_CHECK(d > 0 && d % 64 == 0, "l2_rank_bidir: d=%d must be a positive multiple of 64", d);
+  VTC_CHECK(reach_capacity >= 0, "l2_rank_bidir: reach_capacity=%d must be >= 0 (0: the default)", reach_capacity);
+  const RankWs s = rank_plan((char *)ws, n, d, rows_per_block, reach_capacity);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  return rank_bidir_impl(a, b, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
 }
 
 extern "C" int vtc_similarity(const float *v, const float *t, int nv, int nt, int d, const float *logit_scale, float *sim,

@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader
 
 from . import datasets as module_data
 from . import model as module_arch
-from .metric import RecallAtK
+from .metric import RecallAtK, rank_statistics
 from .parse_config import ConfigParser
 
 
@@ -57,6 +57,11 @@ def main(config: ConfigParser, args, checkpoint_path=None, device="cuda"):
     counters); rank 0 writes the reference's JSON.  The towers and the CAM are per-item functions and the sharded sweep returns the
     single-GPU counters, so the JSON equals the one-process run's (tests/test_gpu_eval_entry.py, world 2 and 3 on one card)."""
     rank, world = 0, int(os.environ.get("WORLD_SIZE", "1"))
+    rank_stats = bool(getattr(args, "rank_stats", False))
+    if rank_stats and world > 1:
+        # refused before anything is encoded: the counting sweep (vtc_l2_rank_bidir) runs on one GPU
+        raise NotImplementedError("--rank-stats under WORLD_SIZE > 1: the sharded counting sweep is not built; run the rank statistics "
+                                  "in one process")
     if world > 1:
         from .. import dist as vdist
         rank, local, world = vdist.init_from_env()
@@ -135,6 +140,12 @@ def main(config: ConfigParser, args, checkpoint_path=None, device="cuda"):
         t_from_i, i_from_t = RecallAtK("images", "titles", [1, 5, 10]).compute_both(res_vis, res_text)
     out = {"R1_title_from_im": t_from_i[0][1], "R5_title_from_im": t_from_i[1][1], "R10_title_from_im": t_from_i[2][1],
            "R1_im_from_title": i_from_t[0][1], "R5_im_from_title": i_from_t[1][1], "R10_im_from_title": i_from_t[2][1]}
+    if rank_stats:
+        # --rank-stats: where every target landed, not only whether it made the first k (median / mean rank 1-based, MRR)
+        rank_t_from_i, rank_i_from_t = RecallAtK("images", "titles", [1, 5, 10]).ranks(res_vis, res_text)
+        for name, r in (("title_from_im", rank_t_from_i), ("im_from_title", rank_i_from_t)):
+            st = rank_statistics(r, ())
+            out[f"MedR_{name}"], out[f"MeanR_{name}"], out[f"MRR_{name}"] = st["median_rank"], st["mean_rank"], st["mrr"]
     if getattr(dataset, "synthetic", False):
         # beside the reference's six keys (evaluation/eval.py:131-138): the numbers are on synthetic stand-in data
         out["synthetic"] = True
@@ -145,7 +156,7 @@ def main(config: ConfigParser, args, checkpoint_path=None, device="cuda"):
     return out, res_vis, res_text
 
 
-def cli(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="VTC eval (MI355X)")
     ap.add_argument("-c", "--config", default="configs/pretrained_clip.jsonc", type=str)
     ap.add_argument("-r", "--resume", default=None, type=str)
@@ -161,7 +172,13 @@ def cli(argv=None):
     ap.add_argument("--n_pairs", type=int, default=None, help="synthetic datasets only: number of pairs")
     ap.add_argument("--dtype", type=str, default=None, choices=["bf16", "f16", "f32"],
                     help="operand arithmetic of the towers (default: VTC_COMPUTE_DTYPE, else bf16; the reference is fp32)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--rank-stats", dest="rank_stats", action="store_true",
+                    help="also MedR_* / MeanR_* / MRR_* of both directions (exact full ranks; one process only)")
+    return ap
+
+
+def cli(argv=None):
+    args = build_parser().parse_args(argv)
     mods = {"batch_size": args.bs, "arch;args;branch_to_adapt_val": args.bv, "dataset;args;num_comms": args.nc,
             "arch;args;comment_fusion": args.am, "dataset;args;add_comments": args.ac, "dataset;args;n_pairs": args.n_pairs}
     config = ConfigParser.from_file(args.config, resume=args.resume, modification=mods)

@@ -16,7 +16,7 @@ from .. import _lib as L
 from .. import dist as vdist
 from .. import ops
 
-__all__ = ["RecallAtK", "BaseMetric"]
+__all__ = ["RecallAtK", "BaseMetric", "rank_statistics"]
 
 
 class BaseMetric:
@@ -28,6 +28,18 @@ class BaseMetric:
 
     def set_writer(self, writer):
         self.writer = writer
+
+
+def rank_statistics(ranks, k_vals=(1, 5, 10)) -> dict:
+    """The retrieval-table figures of one direction's 0-based ranks (RecallAtK.ranks): recall at every k (target hit at k <=> rank < k,
+    any number of k), and median rank, mean rank and mean reciprocal rank on the 1-BASED ranks, in fp64 on the host (one D2H of n int64)."""
+    r = ranks.detach().cpu().numpy() if isinstance(ranks, torch.Tensor) else np.asarray(ranks)
+    r = r.astype(np.int64).reshape(-1)
+    if r.size == 0:
+        raise ValueError("rank_statistics: no ranks")
+    r1 = r.astype(np.float64) + 1.0
+    return {"recall_at_k": {int(k): float(np.count_nonzero(r < int(k))) / r.size for k in k_vals},
+            "median_rank": float(np.median(r1)), "mean_rank": float(r1.mean()), "mrr": float((1.0 / r1).mean())}
 
 
 class RecallAtK(BaseMetric):
@@ -74,9 +86,9 @@ class RecallAtK(BaseMetric):
                           "of such rows are undefined (faiss would return arbitrary ids for them); fix the embeddings "
                           "(vtc_amd.host.model.nonfinite_cause lists what this build knows can produce them)")
 
-    def _prep(self, features_a, features_b, check=True):
+    def _padded(self, features_a, features_b):
         """fp32 [N, D] on the GPU; D zero-padded to the sweep's granule of 64 (squared L2 distances are unchanged;
-        faiss.IndexFlatL2 takes any D), depth = max(k) + 1 (metric.py:145) capped by the gallery size."""
+        faiss.IndexFlatL2 takes any D)."""
         a = torch.as_tensor(features_a, dtype=torch.float32).to(self._dev())
         b = torch.as_tensor(features_b, dtype=torch.float32).to(self._dev())
         if a.dim() != 2 or b.dim() != 2:
@@ -86,6 +98,11 @@ class RecallAtK(BaseMetric):
         pad = -a.shape[1] % 64
         if pad:
             a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
+        return a, b
+
+    def _prep(self, features_a, features_b, check=True):
+        """_padded + the finite check + depth = max(k) + 1 (metric.py:145) capped by the gallery size."""
+        a, b = self._padded(features_a, features_b)
         if self.check_finite and check:
             bits = ops.nonfinite_bits(a, b)
             if bits:
@@ -171,6 +188,37 @@ class RecallAtK(BaseMetric):
         ids_b2a, _, ids_a2b, _ = ops.l2_topk_bidir(a, b, depth, precision=self.precision, return_dists=False, ws=self._workspace(
             L.lib().vtc_l2_topk_bidir_workspace_bytes(a.shape[0], b.shape[0], a.shape[1], self.precision, 0), a.device))
         return self._hits_to_recall(ids_b2a, a.shape[0]), self._hits_to_recall(ids_a2b, b.shape[0])
+
+    def ranks(self, features_a, features_b):
+        """(rank_a, rank_b): the 0-based rank of every pair's target in both directions, int64 [N] on the GPU -- rank_a[i] the rank of a_i
+        among the a's for query b_i (the direction of compute(a, b)), rank_b[i] of b_i among the b's for query a_i.  ``(rank < k).sum()``
+        are compute_both's hit counts for every k; rank_statistics() turns them into MedR / MeanR / MRR.  Exact (fp64-settled) only."""
+        if features_a.shape[0] != features_b.shape[0]:
+            raise ValueError(f"RecallAtK.ranks expects paired rows ({features_a.shape[0]} vs {features_b.shape[0]})")
+        a, b = self._padded(features_a, features_b)
+        rank_a, rank_b, bits = ops.rank_bidir(a, b, ws=self._workspace(
+            L.lib().vtc_l2_rank_bidir_workspace_bytes(a.shape[0], a.shape[1], 0, 0), a.device))
+        if self.check_finite:                     # the word rides with the sweep: one 4-byte D2H, no launch of its own
+            bad = int(bits.item())
+            if bad:
+                raise self._nonfinite_error(bad)
+        return rank_a, rank_b
+
+    def rank_result(self):
+        """result()'s analogue for the rank figures of the accumulated update() features: median_rank, mean_rank and mrr of both
+        directions under result()'s key prefixes."""
+        fa, fb = torch.cat(self.features_a_list), torch.cat(self.features_b_list)
+        assert self.insert_index == len(fa)
+        rank_a, rank_b = self.ranks(fa, fb)
+        res = {}
+        for prefix, r in ((f"{self.name_b}_from_{self.name_a}", rank_a), (f"{self.name_a}_from_{self.name_b}", rank_b)):
+            st = rank_statistics(r, ())
+            for key in ("median_rank", "mean_rank", "mrr"):
+                res[f"{prefix}-{key}"] = st[key]
+        if self.writer:
+            for name, r in res.items():
+                self.writer.add_scalar(name, r)
+        return res
 
     def avg(self):
         return None

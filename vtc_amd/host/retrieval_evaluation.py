@@ -41,7 +41,7 @@ import torch
 from .. import ops
 from . import datasets as module_data
 from . import model as module_arch
-from .metric import RecallAtK
+from .metric import RecallAtK, rank_statistics
 
 SOT, EOT = 49406, 49407
 
@@ -98,6 +98,30 @@ def compute_recall(tensor_v, tensor_t, split: str = "full-test", dataset_name: s
     tvr = np.array(r_t2v)[:, 1] * 100.0
     df = pd.DataFrame({f"{dataset_name} {split} split Video to Text": tvr,
                        f"{dataset_name} {split} split Text to Video": vtr}, index=[f"R@{i}" for i in recall_range])
+    logging.info(df)
+    return df
+
+
+def compute_rank_table(tensor_v, tensor_t, split: str = "full-test", dataset_name: str = "MSRVTT"):
+    """compute_recall's table with the rank figures under it: rows R@1 / R@5 / R@10 (percent, equal to compute_recall's), MedR, MeanR
+    (1-based ranks) and MRR, in compute_recall's two columns.  From the exact full ranks (RecallAtK.ranks); an extension of the
+    reference's module, whose own compute_recall is unchanged."""
+    import pandas as pd
+    tv, tt = torch.as_tensor(tensor_v), torch.as_tensor(tensor_t)
+    if tt.dim() == 3 and tt.shape[1] == 1:
+        tt = tt[:, 0]
+    if tv.dim() != 2 or tt.dim() != 2:
+        raise ValueError("compute_rank_table: one caption per video only; "
+                         f"got video {tuple(tv.shape)}, captions {tuple(tt.shape)}")
+    recall_range = [1, 5, 10]
+    rank_v2t, rank_t2v = RecallAtK("videos", "titles", recall_range).ranks(tv, tt)    # the directions of compute(video, caption), compute(caption, video)
+
+    def column(ranks):
+        st = rank_statistics(ranks, recall_range)
+        return [st["recall_at_k"][k] * 100.0 for k in recall_range] + [st["median_rank"], st["mean_rank"], st["mrr"]]
+    df = pd.DataFrame({f"{dataset_name} {split} split Video to Text": column(rank_t2v),         # compute_recall's pairing (tvr / vtr)
+                       f"{dataset_name} {split} split Text to Video": column(rank_v2t)},
+                      index=[f"R@{i}" for i in recall_range] + ["MedR", "MeanR", "MRR"])
     logging.info(df)
     return df
 
@@ -244,9 +268,8 @@ def retrieval_evaluation(model, datasetname, split: str = "full-test", device="c
     return (outdf, video_emb, caption_emb) if return_embeddings else outdf
 
 
-def cli(argv=None):
-    """The reference's flags (:271-360)."""
-    global args
+def build_parser() -> argparse.ArgumentParser:
+    """The reference's flags (:271-360), and --rank-stats."""
     ap = argparse.ArgumentParser(description="VTC video retrieval evaluation (MI355X)")
     ap.add_argument("-c", "--dataset", default="MSRVTT_videos", choices=list(_DATASETS), type=str, help="dataset to load")
     ap.add_argument("-r", "--checkpoint", default=None, type=str, help="path to checkpoint (default: None)")
@@ -260,9 +283,19 @@ def cli(argv=None):
     ap.add_argument("--frame_stride", default=16, type=int, help="Video frame stride")
     ap.add_argument("--first_frame_only", action="store_true", help="Use only the first frame of a video, as if it were an image")
     ap.add_argument("--first_chunk_only", action="store_true", help="Use only the first 8-frame chunk of a video")
-    args = ap.parse_args(argv)
+    ap.add_argument("--rank-stats", dest="rank_stats", action="store_true",
+                    help="also log compute_rank_table: R@K with median / mean rank and MRR under it")
+    return ap
+
+
+def cli(argv=None):
+    global args
+    args = build_parser().parse_args(argv)
     model = load_model(args.checkpoint, args.device, model_type=args.model_type)
-    df = retrieval_evaluation(model, args.dataset, args.split, args.device, out_csv=args.out_csv, frame_stride=args.frame_stride,
-                              first_frame_only=args.first_frame_only, first_chunk_only=args.first_chunk_only)
+    df, video_emb, caption_emb = retrieval_evaluation(model, args.dataset, args.split, args.device, out_csv=args.out_csv,
+                                                      frame_stride=args.frame_stride, first_frame_only=args.first_frame_only,
+                                                      first_chunk_only=args.first_chunk_only, return_embeddings=True)
     print(df)
+    if args.rank_stats:
+        print(compute_rank_table(video_emb, caption_emb, split=args.split, dataset_name=args.dataset))
     return df

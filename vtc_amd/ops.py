@@ -367,6 +367,37 @@ def recall_bidir(a: torch.Tensor, b: torch.Tensor, k_vals: Sequence[int], ws: Op
     return hits
 
 
+@on_device
+def rank_bidir(a: torch.Tensor, b: torch.Tensor, rows_per_block: int = 0, reach_capacity: int = 0, ws: Optional[torch.Tensor] = None):
+    """Full 0-based ranks of both directions of n paired rows (vtc_l2_rank_bidir): (rank_a [n] int64 = the rank of a_i among the a's for
+    query b_i, the direction of RecallAtK.compute(a, b); rank_b [n] the transposed direction; nonfinite_bits, a device int32 [1] with the
+    meaning of nonfinite_bits(): 1 = a holds a NaN / inf, 2 = b does).  ``(rank < k).sum()`` are recall_bidir's counters for every k; a
+    pair with a non-finite distance has rank n.  The ranks do not depend on reach_capacity (0: the default pool)."""
+    a, b = _gpu(a, torch.float32, "a"), _gpu(b, torch.float32, "b")
+    n, d = a.shape
+    if b.shape != (n, d):
+        raise ValueError(f"rank_bidir: paired rows expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    ws = _ws_for(ws, L.lib().vtc_l2_rank_bidir_workspace_bytes(n, d, rows_per_block, reach_capacity), a.device)
+    rank_a = torch.empty(n, dtype=torch.int64, device=a.device)
+    rank_b = torch.empty(n, dtype=torch.int64, device=a.device)
+    bits = torch.empty(1, dtype=torch.int32, device=a.device)
+    L.check(L.lib().vtc_l2_rank_bidir(a.data_ptr(), b.data_ptr(), n, d, rows_per_block, reach_capacity, rank_a.data_ptr(), rank_b.data_ptr(),
+                                      bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_rank_bidir")
+    return rank_a, rank_b, bits
+
+
+def rank_kappa(d: int) -> float:
+    """kappa of the rank sweep's error bound eps = kappa (|q|^2 + max|g|^2) at feature width d."""
+    return float(L.lib().vtc_l2_rank_kappa(int(d)))
+
+
+def rank_sweep_stats(ws: torch.Tensor) -> dict:
+    """What the last rank_bidir call on workspace ``ws`` left in its first words (include/vtc_hip.h): per direction the pairs in reach
+    of their target, the largest number of them for one owner, and the owners counted by fp64 brute force."""
+    w = ws[:64].view(torch.int64).cpu().tolist()
+    return {"in_reach": (w[0], w[1]), "in_reach_max": (w[2], w[3]), "brute_force_owners": (w[4], w[5])}
+
+
 def split_recall_counters(hits_host: torch.Tensor):
     """(counters, nonfinite) of a HOST copy of the recall-only sweeps' hit counters: the NaN / inf marker (bit 40 and above of the first
     counter of a direction, summed over ranks) taken off."""
