@@ -6,7 +6,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vtc_amd.host.retrieval_evaluation import (  # noqa: E402,F401
-    cli, compute_rank_table, compute_recall, image_models, load_model, models_needing_comments, retrieval_evaluation, video_models)
+    cli, compute_multi_caption_table, compute_rank_table, compute_recall, image_models, load_model, models_needing_comments,
+    retrieval_evaluation, video_models)
 
 if __name__ == "__main__":
     cli(sys.argv[1:])

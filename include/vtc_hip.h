@@ -329,6 +329,26 @@ float vtc_l2_rank_kappa(int d);
 size_t vtc_l2_rank_bidir_workspace_bytes(int n, int d, int rows_per_block, int reach_capacity);
 int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per_block, int reach_capacity, int64_t *rank_a,
                       int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* The same ranks for videos with SEVERAL captions each (MSR-VTT: 20 per video, MSVD: about 40).  a [n, d]: one row per video; b [m, d]: the
+ * captions, those of one video contiguous and in video order; off [n + 1] (device int32): non-decreasing, off[0] = 0, off[n] = m.  Caption c
+ * belongs to video g(c), the v with off[v] <= c < off[v + 1].  With D(c, j) the fp64 value sum_k (b_c[k] - a_j[k])^2 of the fp32 inputs
+ * (formed by the one device function of the paired sweep, so exact ties are bit-equal) and pairs compared lexicographically:
+ *   rank_a[c] = #{ j in [0, n) : (D(c, j), j) < (D(c, g(c)), g(c)) }    c in [0, m)   text -> video: the caption queries the videos
+ *   rank_b[v] = #{ c in [0, m) : (D(c, v), c) < (D(c*, v), c*) }        v in [0, n)   video -> text: the video queries ALL captions;
+ *               c* = the own caption (off[v] <= c < off[v + 1], D finite) with the smallest (D(c, v), c)
+ * rank_b is the CAPTION-LEVEL convention of the image-text literature: the best rank any own caption reaches in the list of all m
+ * captions.  No own caption can precede c*, so rank_b[v] counts captions of other videos.  (The video-unit convention -- the number of
+ * other videos that have a closer caption -- needs a segmented minimum over the matrix and is not built.)
+ * An entry with a non-finite distance is never closer; a caption whose own distance is not finite gets rank_a = n and is no candidate
+ * for c*; a video without a finite own caption (an empty group too) gets rank_b = m; nonfinite[0] as above.  With m = n and
+ * off = 0, 1, ..., n both outputs are those of the paired entry point, element for element.
+ * The sweep is the paired one made rectangular (D is [m, n], rows_per_block caption rows per block), the owner's target taken from a table;
+ * the reach pool of a direction holds reach_capacity pairs (0 = the default, 512 per owner: 512 m for the captions, 512 n for the
+ * videos, at least 4096).  Everything is on the device, off included: no host sync, no allocation.  n >= 1, m >= 1, d % 64 == 0.  The
+ * statistics words at the head of the workspace are the paired entry point's (direction a = the captions' row direction). */
+size_t vtc_l2_rank_grouped_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity);
+int vtc_l2_rank_grouped(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block, int reach_capacity,
+                        int64_t *rank_a /* [m] */, int64_t *rank_b /* [n] */, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* The sharded sweep (above) with the recall-only finish: rank r holds rows [row_base, row_base + n_local) of both sets and the gathered
  * sets, runs ONE [n_local, n_total] distance GEMM and adds its PARTIAL counters (the host all-reduces them: model/metric.py:148-160 counted
  * over this rank's queries):

@@ -4,6 +4,7 @@
 //   vtc_recall_hits `target in rp[:k]` counting (model/metric.py:148-160)
 //   vtc_l2_rank_bidir  the exact rank of EVERY pair's target in both directions (median / mean rank, MRR, recall at any k): a counting
 //                   sweep over the BF16X3 distance blocks, fp64 for the entries within the error bound of a target (end of this file)
+//   vtc_l2_rank_grouped  the same for videos with several captions each: the sweep made rectangular, the target taken from a table
 //   vtc_similarity  exp(logit_scale) * V @ T^T (model/model.py:369,478,504,621)
 //   vtc_clip_loss   0.5 (CE(sim, arange) + CE(sim^T, arange)) (model/loss.py:18-22)
 //
@@ -24,6 +25,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -1834,6 +1836,14 @@ struct RankDir {
   unsigned long long *pool_n;    // pairs offered to the pool (may exceed cap)
   unsigned long long cap;
 };
+// The grouped form (vtc_l2_rank_grouped): the owner's target comes from a table, each direction has its own target distances, and the two
+// sides differ in size.  The kernels below take either form as a compile-time policy; with RankDir they are the paired sweep as it was.
+struct RankDirG : RankDir {
+  const int *tgt;                // [n_own] the owner's target on the other side (never excluded when hi = -inf)
+  const double *dt;              // [n_own] fp64 distance of the owner to its target
+  int n_own, n_other;
+};
+template <typename Dir> constexpr bool rank_has_table = std::is_same<Dir, RankDirG>::value;
 
 // One wave per 8 pairs: the targets' fp64 distances, both directions' thresholds, and the counters' zeroes.
 __global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, int n, int d,
@@ -1936,8 +1946,9 @@ __device__ __forceinline__ void rank_stage_append(const RankDir &P, int2 *stage,
 
 // Row direction: one wave per (row of the block, column segment), streaming as row_topk_kernel does (1024 columns per step, four 16-byte
 // loads per lane, two steps in flight behind the one being counted).  Per value two compares; one atomic per wave at the end.
+template <typename Dir>
 __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row0, int S,
-                                                             int seg_cols, const RankDir P) {
+                                                             int seg_cols, const Dir P) {
   __shared__ int2 stage_all[4][RS_STAGE];
   const int lane = threadIdx.x & 63;
   int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
@@ -1945,9 +1956,11 @@ __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__rest
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_rows * S) return;
   const int r = w / S, seg = w - r * S;
-  const int gr = row0 + r;                                // the owner, and the column of its target
+  const int gr = row0 + r;                                // the owner (paired: also the column of its target)
   const float lo = P.lo[gr], hi = P.hi[gr];
   if (hi == -INFINITY) return;                            // wave-uniform: target distance not finite, rank n
+  int tg = gr;                                            // the column of its target
+  if constexpr (rank_has_table<Dir>) tg = P.tgt[gr];
   const float *row = dist + (size_t)r * ld;
   const int c_lo = seg * seg_cols, c_hi = min(n_cols, c_lo + seg_cols);
   const bool vec = (ld & 3) == 0;
@@ -1975,7 +1988,7 @@ __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__rest
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int idx = base + 256 * (q >> 2) + lane * 4 + (q & 3);
-      const bool ok = idx < c_hi && idx != gr;
+      const bool ok = idx < c_hi && idx != tg;
       const bool lt = cur[q] < lo;
       closer += (ok && lt) ? 1 : 0;
       m |= (ok && !lt && !(cur[q] > hi)) ? (1u << q) : 0u;
@@ -2000,9 +2013,9 @@ __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__rest
 // adjacent columns and every fourth row -- a load instruction of the wave is four 256-byte row pieces; V = 1: a lane owns one column.
 // Eight loads per lane in flight; the lanes' counts are folded over the wave once, behind the scan: one atomic per column and wave.
 // The counts are CARRIED from one block of rows to the next in P.cnt (global row ids: row_id0 + row).
-template <int V>
+template <int V, typename Dir>
 __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row_id0,
-                                                             int n_strips, int S, int seg_rows, const RankDir P) {
+                                                             int n_strips, int S, int seg_rows, const Dir P) {
   constexpr int U = 8, RPL = V;                           // loads in flight per lane; rows per load instruction of the wave
   __shared__ int2 stage_all[4][RS_STAGE];
   int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
@@ -2016,11 +2029,13 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
   const int r_lo = seg * seg_rows, r_hi = min(n_rows, r_lo + seg_rows);
   const bool live = c < n_cols;                           // (V = 4: n_cols % 4 == 0, the lane's four columns are in or out together)
   float lo[V], hi[V];
-  int cnt[V], reach[V];
+  constexpr bool kTable = rank_has_table<Dir>;
+  int cnt[V], reach[V], tg[kTable ? V : 1];               // tg: the row (global id) of the column's target, where it comes from a table
 #pragma unroll
   for (int e = 0; e < V; ++e) {
     lo[e] = live ? P.lo[c + e] : -INFINITY;
     hi[e] = live ? P.hi[c + e] : -INFINITY;                // -inf: a column past the matrix, or an owner whose target distance is not finite
+    if constexpr (kTable) tg[e] = live ? P.tgt[c + e] : -1;
     cnt[e] = 0; reach[e] = 0;
   }
   for (int rb = r_lo; rb < r_hi; rb += RPL * U) {
@@ -2042,7 +2057,9 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
       const int row = rb + u * RPL + sub;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        const bool ok = row < r_hi && hi[e] != -INFINITY && row_id0 + row != c + e;
+        int t = c + e;                                     // paired: the column's own index
+        if constexpr (kTable) t = tg[e];
+        const bool ok = row < r_hi && hi[e] != -INFINITY && row_id0 + row != t;
         const bool lt = v[u][e] < lo[e];
         cnt[e] += (ok && lt) ? 1 : 0;
         const bool in = ok && !lt && !(v[u][e] > hi[e]);
@@ -2067,10 +2084,11 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
   }
 }
 
-// The pooled pairs of both directions, eight per wave and step: fp64 distances (wave_dist64_pairs), compared as (d, other) < (d_t, owner).
-__global__ __launch_bounds__(256) void rank_settle_kernel(const RankDir PA, const RankDir PB, int nblocks_a, const double *__restrict__ dt, int d) {
+// The pooled pairs of both directions, eight per wave and step: fp64 distances (wave_dist64_pairs), compared as (d, other) < (d_t, target).
+template <typename Dir>
+__global__ __launch_bounds__(256) void rank_settle_kernel(const Dir PA, const Dir PB, int nblocks_a, const double *__restrict__ dt, int d) {
   const bool second = (int)blockIdx.x >= nblocks_a;
-  const RankDir &P = second ? PB : PA;
+  const Dir &P = second ? PB : PA;
   const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
   const int nbl = second ? (int)gridDim.x - nblocks_a : nblocks_a;
   const int lane = threadIdx.x & 63;
@@ -2088,38 +2106,45 @@ __global__ __launch_bounds__(256) void rank_settle_kernel(const RankDir PA, cons
 #pragma unroll
     for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
     if (have) {                                            // (a flagged owner's count is overwritten by rank_brute_kernel, later in the stream)
-      const double t = dt[pr.x];
-      if (mine < t || (mine == t && pr.y < pr.x)) atomicAdd(&P.cnt[pr.x], 1);
+      double t;
+      int tg = pr.x;
+      if constexpr (rank_has_table<Dir>) { t = P.dt[pr.x]; tg = P.tgt[pr.x]; } else { t = dt[pr.x]; }
+      if (mine < t || (mine == t && pr.y < tg)) atomicAdd(&P.cnt[pr.x], 1);
     }
   }
 }
 
 // Flagged owners (their pairs overflowed the pool): the count again, by fp64 brute force over the whole other side; one workgroup of
 // eight waves per owner.  Also the statistics: owners sent here, the largest in-reach count of an owner.
-__global__ __launch_bounds__(512) void rank_brute_kernel(const RankDir PA, const RankDir PB, int nblocks_a, const double *__restrict__ dt, int n, int d,
+template <typename Dir>
+__global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir PB, int nblocks_a, const double *__restrict__ dt, int n, int d,
                                                          unsigned long long *__restrict__ stats) {
   const bool second = (int)blockIdx.x >= nblocks_a;
-  const RankDir &P = second ? PB : PA;
+  const Dir &P = second ? PB : PA;
   const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
   const int nbl = second ? (int)gridDim.x - nblocks_a : nblocks_a;
   __shared__ int part[8];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int mx = 0;
-  for (int o = bid; o < n; o += nbl) {                     // uniform for the workgroup
+  int n_own = n, n_oth = n;
+  if constexpr (rank_has_table<Dir>) { n_own = P.n_own; n_oth = P.n_other; }
+  for (int o = bid; o < n_own; o += nbl) {                 // uniform for the workgroup
     mx = max(mx, P.reach[o]);
     if (!P.ovf[o]) continue;
-    const double t = dt[o];
+    double t;
+    int tg = o;
+    if constexpr (rank_has_table<Dir>) { t = P.dt[o]; tg = P.tgt[o]; } else { t = dt[o]; }
     int cnt = 0;
-    for (int j0 = RS_NB * w; j0 < n; j0 += RS_NB * 8) {
+    for (int j0 = RS_NB * w; j0 < n_oth; j0 += RS_NB * 8) {
       int qi[RS_NB], gi[RS_NB];
 #pragma unroll
-      for (int u = 0; u < RS_NB; ++u) { qi[u] = o; gi[u] = min(j0 + u, n - 1); }
+      for (int u = 0; u < RS_NB; ++u) { qi[u] = o; gi[u] = min(j0 + u, n_oth - 1); }
       double dd[RS_NB];
       wave_dist64_pairs(P.own, P.other, qi, gi, d, lane, dd);
 #pragma unroll
       for (int u = 0; u < RS_NB; ++u) {
         const int j = j0 + u;
-        if (j < n && j != o && (dd[u] < t || (dd[u] == t && j < o))) ++cnt;
+        if (j < n_oth && j != tg && (dd[u] < t || (dd[u] == t && j < tg))) ++cnt;
       }
     }
     if (lane == 0) part[w] = cnt;
@@ -2231,7 +2256,7 @@ int rank_bidir_impl(const float *a, const float *b, int n, int d, int64_t *rank_
       S = cdiv(n, seg_cols);
       ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
       prof.tag(102, rows, n);
-      hipLaunchKernelGGL(rank_row_count_kernel, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, S, seg_cols, R);
+      hipLaunchKernelGGL(rank_row_count_kernel<RankDir>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, S, seg_cols, R);
     }
     {
       // (strip, segment) waves: ~32 per CU; a segment is a whole number of the wave's 8-load steps
@@ -2242,9 +2267,9 @@ int rank_bidir_impl(const float *a, const float *b, int n, int d, int64_t *rank_
       ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
       prof.tag(103, rows, n);
       if (V == 4)
-        hipLaunchKernelGGL(rank_col_count_kernel<4>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
+        hipLaunchKernelGGL((rank_col_count_kernel<4, RankDir>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
       else
-        hipLaunchKernelGGL(rank_col_count_kernel<1>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
+        hipLaunchKernelGGL((rank_col_count_kernel<1, RankDir>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
     }
     VTC_LAUNCH_CHECK("l2_rank_bidir count");
   }
@@ -2253,16 +2278,234 @@ int rank_bidir_impl(const float *a, const float *b, int n, int d, int64_t *rank_
     const int g = (int)std::min<size_t>(2048, (s.cap + 4 * RS_NB - 1) / (4 * RS_NB));
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     prof.tag(104, n, d);
-    hipLaunchKernelGGL(rank_settle_kernel, dim3(2 * g), dim3(256), 0, stream, R, Cd, g, s.dt, d);
+    hipLaunchKernelGGL(rank_settle_kernel<RankDir>, dim3(2 * g), dim3(256), 0, stream, R, Cd, g, s.dt, d);
   }
   {
     const int g = std::min(n, 1024);
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     prof.tag(105, n, d);
-    hipLaunchKernelGGL(rank_brute_kernel, dim3(2 * g), dim3(512), 0, stream, R, Cd, g, s.dt, n, d, s.stats);
+    hipLaunchKernelGGL(rank_brute_kernel<RankDir>, dim3(2 * g), dim3(512), 0, stream, R, Cd, g, s.dt, n, d, s.stats);
   }
   hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, s.dt, cnt_r, cnt_c, n, rank_a, rank_b);
   VTC_LAUNCH_CHECK("l2_rank_bidir finish");
+  return 0;
+}
+
+// ---- grouped rank sweep (vtc_l2_rank_grouped): several captions per video ------------------------------------------------------------
+// a [n, d] videos, b [m, d] captions, off [n + 1]: the captions of video v are the rows off[v] .. off[v + 1] of b.  The counting sweep above
+// made rectangular (D is [m, n]: a caption per row), with the owner's target taken from a table:
+//   row direction     owner = caption c, target = its video g(c), d_t = D(c, g(c))                    -> rank_a [m]
+//   column direction  owner = video v, target = c* = its own caption with the smallest (D(c, v), c),  -> rank_b [n]
+//                     so d_t[v] is the segmented lexicographic minimum of the row direction's d_t over the video's captions
+// (include/vtc_hip.h has the definition).  The prologue below is new; the passes, the settle and the brute force are the kernels above
+// instantiated with RankDirG.
+
+// g(c) of every caption: the last v with off[v] <= c (an empty group is never the answer: its successor starts at the same caption).
+// Whatever `off` holds, the result lies in [0, n).
+__global__ __launch_bounds__(256) void rank_group_id_kernel(const int *__restrict__ off, int n, int m, int *__restrict__ gid) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= m) return;
+  int lo = 0, hi = n - 1;                                   // invariant: the answer is in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= c) lo = mid; else hi = mid - 1;
+  }
+  gid[c] = lo;
+}
+
+// One wave per 8 captions: the fp64 distance to the caption's own video, the row direction's thresholds, and the counters' zeroes.
+__global__ __launch_bounds__(256) void rank_grouped_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, const int *__restrict__ gid,
+                                                                int m, int d, const float *__restrict__ bn2, const float *__restrict__ amax,
+                                                                float kappa, double *__restrict__ dt_r, float *__restrict__ lo_r,
+                                                                float *__restrict__ hi_r, int *__restrict__ zero, int n_zero) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  for (int i = t; i < n_zero; i += gridDim.x * 256) zero[i] = 0;
+  const int lane = threadIdx.x & 63;
+  const int i0 = (t >> 6) * RS_NB;
+  if (i0 >= m) return;                                  // wave-uniform
+  int ci[RS_NB], gi[RS_NB];
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) { ci[u] = min(i0 + u, m - 1); gi[u] = gid[ci[u]]; }
+  double dd[RS_NB];
+  wave_dist64_pairs(b, a, ci, gi, d, lane, dd);
+  double mine = 0.0;
+#pragma unroll
+  for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
+  const int i = i0 + lane;
+  if (lane < RS_NB && i < m) {
+    dt_r[i] = mine;
+    const bool ok = mine < (double)INFINITY;            // false for NaN too
+    const float eps_r = kappa * (bn2[i] + *amax);
+    lo_r[i] = ok ? __double2float_rd(mine - (double)eps_r) : -INFINITY;
+    hi_r[i] = ok ? __double2float_ru(mine + (double)eps_r) : -INFINITY;
+  }
+}
+
+// One thread per video: c* = its own caption with the smallest finite (d_t, c), and the column direction's thresholds.  A video without a
+// finite own caption (an empty group too) gets d_t = inf and hi = -inf: rank m.  The columns [n, n_ld) that pad the matrix's rows to
+// 16 bytes get hi = -inf too: the column pass neither counts nor pools them.
+__global__ __launch_bounds__(256) void rank_grouped_target_kernel(const int *__restrict__ off, int n, int n_ld, int m, const double *__restrict__ dt_r,
+                                                                  const float *__restrict__ an2, const float *__restrict__ bmax, float kappa,
+                                                                  double *__restrict__ dt_c, int *__restrict__ tgt_c, float *__restrict__ lo_c,
+                                                                  float *__restrict__ hi_c) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n_ld) return;
+  if (v >= n) {
+    dt_c[v] = (double)INFINITY; tgt_c[v] = -1; lo_c[v] = -INFINITY; hi_c[v] = -INFINITY;
+    return;
+  }
+  const int c0 = max(off[v], 0), c1 = min(off[v + 1], m);
+  double best = (double)INFINITY;
+  int arg = -1;
+  for (int c = c0; c < c1; ++c) {
+    const double x = dt_r[c];
+    if (x < best) { best = x; arg = c; }                // strict: the lower index keeps an exact tie; NaN and inf never enter
+  }
+  dt_c[v] = best;
+  tgt_c[v] = arg;                                       // -1: no row is excluded (and none is counted: hi = -inf)
+  const bool ok = arg >= 0;
+  const float eps_c = kappa * (an2[v] + *bmax);
+  lo_c[v] = ok ? __double2float_rd(best - (double)eps_c) : -INFINITY;
+  hi_c[v] = ok ? __double2float_ru(best + (double)eps_c) : -INFINITY;
+}
+
+__global__ __launch_bounds__(256) void rank_grouped_write_kernel(const double *__restrict__ dt_r, const double *__restrict__ dt_c,
+                                                                 const int *__restrict__ cnt_r, const int *__restrict__ cnt_c, int n, int m,
+                                                                 int64_t *__restrict__ rank_a, int64_t *__restrict__ rank_b) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < m) rank_a[i] = dt_r[i] < (double)INFINITY ? (int64_t)cnt_r[i] : (int64_t)n;
+  if (i < n) rank_b[i] = dt_c[i] < (double)INFINITY ? (int64_t)cnt_c[i] : (int64_t)m;
+}
+
+struct RankGroupedWs {
+  unsigned long long *stats;       // [RS_STATS]
+  float *qn, *gn, *qmax, *gmax;    // queries = b (m rows of D), gallery = a (n columns)
+  bf16_t *qb, *gb;
+  float *dist;
+  int rows_per_block;
+  int n_ld;                        // columns of a row of D: n rounded up to 4 (rows 16-byte aligned whatever n is; the column-side arrays have n_ld entries)
+  int *gid, *tgt_c;                // [m] g(c); [n_ld] c*
+  double *dt_r, *dt_c;             // [m], [n_ld]
+  float *lo_r, *hi_r, *lo_c, *hi_c;
+  int *zero;                       // cnt_r, reach_r, ovf_r: [3][m], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_grouped_prep_kernel
+  int2 *pool_r, *pool_c;
+  size_t cap_r, cap_c;
+  size_t total;
+};
+RankGroupedWs rank_grouped_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity) {
+  RankGroupedWs s;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
+  s.stats = (unsigned long long *)take(RS_STATS * 8);
+  const int n_ld = (n + 3) & ~3;
+  s.n_ld = n_ld;
+  s.qn = (float *)take((size_t)m * 4);
+  s.gn = (float *)take((size_t)n_ld * 4);
+  s.qmax = (float *)take(4);
+  s.gmax = (float *)take(4);
+  s.qb = (bf16_t *)take((size_t)m * d * 3 * 2);
+  s.gb = (bf16_t *)take((size_t)n_ld * d * 3 * 2);
+  int rpb = rows_per_block;
+  if (rpb <= 0) {                                          // as rank_plan(): as many rows as fit a 2 GiB block
+    rpb = (int)std::min<size_t>(((size_t)2 << 30) / ((size_t)n_ld * 4), (size_t)1 << 20);
+    rpb = rpb / 256 * 256;
+    if (rpb < 256) rpb = 256;
+  }
+  if (rpb > m) rpb = m;
+  s.rows_per_block = rpb;
+  s.dist = (float *)take((size_t)rpb * n_ld * 4);
+  s.gid = (int *)take((size_t)m * 4);
+  s.tgt_c = (int *)take((size_t)n_ld * 4);
+  s.dt_r = (double *)take((size_t)m * 8);
+  s.dt_c = (double *)take((size_t)n_ld * 8);
+  s.lo_r = (float *)take((size_t)m * 4);
+  s.hi_r = (float *)take((size_t)m * 4);
+  s.lo_c = (float *)take((size_t)n_ld * 4);
+  s.hi_c = (float *)take((size_t)n_ld * 4);
+  s.zero = (int *)take(((size_t)3 * m + (size_t)3 * n_ld) * 4);
+  s.cap_r = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(m);      // per direction: 512 pairs per OWNER
+  s.cap_c = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(n);
+  s.pool_r = (int2 *)take(s.cap_r * 8);
+  s.pool_c = (int2 *)take(s.cap_c * 8);
+  s.total = off;
+  return s;
+}
+
+int rank_grouped_impl(const float *a, const float *b, const int *off, int n, int m, int d, int64_t *rank_a, int64_t *rank_b, int *nonfinite,
+                      const RankGroupedWs &s, hipStream_t stream) {
+  int *cnt_r = s.zero, *reach_r = s.zero + (size_t)m, *ovf_r = s.zero + 2 * (size_t)m;
+  const int n_ld = s.n_ld;
+  int *cnt_c = s.zero + 3 * (size_t)m, *reach_c = cnt_c + (size_t)n_ld, *ovf_c = cnt_c + 2 * (size_t)n_ld;
+  // gallery a, query b_c: the rows of D (m owners, n others);  gallery b, query a_v: its columns (n owners, m others)
+  const RankDirG R{{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r}, s.gid, s.dt_r, m, n};
+  const RankDirG Cd{{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c}, s.tgt_c, s.dt_c, n, m};
+  (void)hipMemsetAsync(s.stats, 0, RS_STATS * 8, stream);
+  (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
+  if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)m * d, nonfinite, stream)) return rc;
+  if (n_ld != n) {                                         // the padding columns' operands: zero rows, zero norms (their entries are never counted)
+    (void)hipMemsetAsync(s.gb + (size_t)n * d * 3, 0, (size_t)(n_ld - n) * d * 3 * 2, stream);
+    (void)hipMemsetAsync(s.gn + n, 0, (size_t)(n_ld - n) * 4, stream);
+  }
+  {
+    ProfScope prof(VTC_PROF_TOPK, (double)(n + m) * d * (4 + 6 + 4), stream);
+    prof.tag(101, m, d);
+    const float kappa = rank_kappa(d);
+    hipLaunchKernelGGL(rank_group_id_kernel, dim3(cdiv(m, 256)), dim3(256), 0, stream, off, n, m, s.gid);
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(m, 4)), dim3(256), 0, stream, b, s.qn, m, d);
+    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, a, s.gn, n, d);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)m * d + 255) / 256)), dim3(256), 0, stream, b, s.qb, m, d, 3, 0);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, a, s.gb, n, d, 3, 1);
+    hipLaunchKernelGGL(rank_max_kernel, dim3(1), dim3(256), 0, stream, s.gn, s.gn, n, s.gmax, s.gmax);      // (one side per launch: the sides differ in size)
+    hipLaunchKernelGGL(rank_max_kernel, dim3(1), dim3(256), 0, stream, s.qn, s.qn, m, s.qmax, s.qmax);
+    hipLaunchKernelGGL(rank_grouped_prep_kernel, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, a, b, s.gid, m, d, s.qn, s.gmax, kappa, s.dt_r,
+                       s.lo_r, s.hi_r, s.zero, 3 * m + 3 * n_ld);
+    hipLaunchKernelGGL(rank_grouped_target_kernel, dim3(cdiv(n_ld, 256)), dim3(256), 0, stream, off, n, n_ld, m, s.dt_r, s.gn, s.qmax, kappa, s.dt_c, s.tgt_c,
+                       s.lo_c, s.hi_c);
+  }
+  VTC_LAUNCH_CHECK("l2_rank_grouped prologue");
+  // D is [rows, n_ld]: the GEMM writes, and both passes read, 16-byte aligned rows at every n.  The row pass scans the n real columns; the
+  // column pass takes all n_ld (a lane owns four adjacent columns; the padding columns have hi = -inf).
+  const int n_strips = cdiv(n_ld, 64);
+  for (int r0 = 0; r0 < m; r0 += s.rows_per_block) {
+    const int rows = min(s.rows_per_block, m - r0);
+    GemmEpi e;
+    e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
+    if (int rc = launch_gemm(s.qb + (size_t)r0 * d * 3, s.gb, nullptr, s.dist, rows, n_ld, d * 3, VTC_BF16, e, stream)) return rc;
+    {
+      int S = cdiv(8192, rows);                            // as rank_bidir_impl
+      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
+      const int seg_cols = cdiv(cdiv(n, S), 1024) * 1024;
+      S = cdiv(n, seg_cols);
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
+      prof.tag(102, rows, n);
+      hipLaunchKernelGGL(rank_row_count_kernel<RankDirG>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n, r0, S, seg_cols, R);
+    }
+    {
+      const int step = 8 * 4;
+      int S = std::max(1, cdiv(32 * vtcgemm::num_cus(), n_strips));
+      const int seg_rows = cdiv(cdiv(rows, S), step) * step;
+      S = cdiv(rows, seg_rows);
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
+      prof.tag(103, rows, n);
+      hipLaunchKernelGGL((rank_col_count_kernel<4, RankDirG>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n_ld, r0, n_strips, S, seg_rows, Cd);
+    }
+    VTC_LAUNCH_CHECK("l2_rank_grouped count");
+  }
+  {
+    const int ga = (int)std::min<size_t>(2048, (s.cap_r + 4 * RS_NB - 1) / (4 * RS_NB));
+    const int gb = (int)std::min<size_t>(2048, (s.cap_c + 4 * RS_NB - 1) / (4 * RS_NB));
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    prof.tag(104, m, d);
+    hipLaunchKernelGGL(rank_settle_kernel<RankDirG>, dim3(ga + gb), dim3(256), 0, stream, R, Cd, ga, (const double *)nullptr, d);
+  }
+  {
+    const int ga = std::min(m, 1024), gb = std::min(n, 1024);
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    prof.tag(105, m, d);
+    hipLaunchKernelGGL(rank_brute_kernel<RankDirG>, dim3(ga + gb), dim3(512), 0, stream, R, Cd, ga, (const double *)nullptr, 0, d, s.stats);
+  }
+  hipLaunchKernelGGL(rank_grouped_write_kernel, dim3(cdiv(std::max(n, m), 256)), dim3(256), 0, stream, s.dt_r, s.dt_c, cnt_r, cnt_c, n, m, rank_a, rank_b);
+  VTC_LAUNCH_CHECK("l2_rank_grouped finish");
   return 0;
 }
 }  // namespace
@@ -2492,6 +2735,22 @@ extern "C" int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, i
   const RankWs s = rank_plan((char *)ws, n, d, rows_per_block, reach_capacity);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
   return rank_bidir_impl(a, b, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+}
+
+extern "C" size_t vtc_l2_rank_grouped_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity) {
+  if (n < 1 || m < 1 || d <= 0 || reach_capacity < 0) return 0;
+  return rank_grouped_plan(nullptr, n, m, d, rows_per_block, reach_capacity).total;
+}
+extern "C" int vtc_l2_rank_grouped(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block, int reach_capacity,
+                                   int64_t *rank_a, int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream) {
+  VTC_CHECK(a && b && off && rank_a && rank_b && nonfinite, "l2_rank_grouped: null argument");
+  VTC_CHECK(n >= 1, "l2_rank_grouped: n=%d must be >= 1", n);
+  VTC_CHECK(m >= 1, "l2_rank_grouped: m=%d must be >= 1", m);
+  VTC_CHECK(d > 0 && d % 64 == 0, "l2_rank_grouped: d=%d must be a positive multiple of 64", d);
+  VTC_CHECK(reach_capacity >= 0, "l2_rank_grouped: reach_capacity=%d must be >= 0 (0: the default)", reach_capacity);
+  const RankGroupedWs s = rank_grouped_plan((char *)ws, n, m, d, rows_per_block, reach_capacity);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  return rank_grouped_impl(a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
 }
 
 extern "C" int vtc_similarity(const float *v, const float *t, int nv, int nt, int d, const float *logit_scale, float *sim,

@@ -26,8 +26,9 @@ and a segment-mean kernel (vtc_segment_mean) reduces the ragged chunk groups; em
 The towers and the CAM are per-item functions, so the embeddings equal the per-video loop's
 (tests/test_gpu_retrieval_eval.py holds them to the oracle's batch-1 loop).  The dataset names resolve to
 synthetic stand-ins of the same tensor contract (vtc_amd/host/datasets.py), as ``eval.py`` does for
-``ImTextDataset``.  Only the one-caption-per-video case is defined (with several captions the
-reference hands a 3-D array to faiss).
+``ImTextDataset``.  compute_recall / compute_rank_table and the default path of retrieval_evaluation take one caption per
+video (with several captions the reference hands a 3-D array to faiss); several captions per video go through
+``multi_caption=True`` and compute_multi_caption_table (the exact grouped ranks, RecallAtK.grouped_ranks), an extension.
 """
 from __future__ import annotations
 
@@ -126,6 +127,49 @@ def compute_rank_table(tensor_v, tensor_t, split: str = "full-test", dataset_nam
     return df
 
 
+def padded_captions_to_offsets(tensor_t):
+    """The reference's padded caption tensor [N, C, D] (:238-260: every video's captions padded with -inf rows up to the largest caption
+    count) -> (flat [M, D] captions in video order, offsets [N + 1] int64 on the host).  A row that is entirely -inf is padding."""
+    tt = torch.as_tensor(tensor_t)
+    if tt.dim() != 3:
+        raise ValueError(f"padded captions [N, C, D] expected, got {tuple(tt.shape)}")
+    keep = ~(tt == float("-inf")).all(dim=-1)                                  # [N, C]
+    counts = keep.sum(dim=1).cpu().numpy().astype(np.int64)
+    return tt[keep], np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def compute_multi_caption_table(tensor_v, tensor_t, split: str = "full-test", dataset_name: str = "MSRVTT", offsets=None):
+    """compute_rank_table for videos with SEVERAL captions each: rows R@1 / R@5 / R@10 (percent), MedR, MeanR (1-based ranks) and MRR in
+    compute_recall's two columns.  ``tensor_t`` is the reference's own padded tensor [N, C, D] (:238-260; all -inf rows are padding and
+    are dropped) when ``offsets`` is None, else the flat [M, D] captions with ``offsets`` [N + 1] (the captions of video v are rows
+    offsets[v]:offsets[v + 1]).
+      "Text to Video": over the M captions, the rank of the caption's own video among the N videos;
+      "Video to Text": over the N videos, the best rank one of the video's own captions reaches among all M captions -- the caption-level
+      convention of the image-text literature (not the video-unit one, which counts other VIDEOS with a closer caption).
+    Exact ranks (RecallAtK.grouped_ranks).  With one caption per video the frame equals compute_rank_table's."""
+    import pandas as pd
+    tv, tt = torch.as_tensor(tensor_v), torch.as_tensor(tensor_t)
+    if offsets is None:
+        if tt.dim() != 3:
+            raise ValueError(f"compute_multi_caption_table: without offsets the padded captions [N, C, D] are expected, got {tuple(tt.shape)}")
+        tt, offsets = padded_captions_to_offsets(tt)
+    elif tt.dim() != 2:
+        raise ValueError(f"compute_multi_caption_table: with offsets the captions are flat [M, D], got {tuple(tt.shape)}")
+    if tv.dim() != 2:
+        raise ValueError(f"compute_multi_caption_table: videos [N, D] expected, got {tuple(tv.shape)}")
+    recall_range = [1, 5, 10]
+    rank_t2v, rank_v2t = RecallAtK("videos", "titles", recall_range).grouped_ranks(tv, tt, offsets)
+
+    def column(ranks):
+        st = rank_statistics(ranks, recall_range)
+        return [st["recall_at_k"][k] * 100.0 for k in recall_range] + [st["median_rank"], st["mean_rank"], st["mrr"]]
+    df = pd.DataFrame({f"{dataset_name} {split} split Video to Text": column(rank_v2t),
+                       f"{dataset_name} {split} split Text to Video": column(rank_t2v)},
+                      index=[f"R@{i}" for i in recall_range] + ["MedR", "MeanR", "MRR"])
+    logging.info(df)
+    return df
+
+
 def load_model(checkpoint_path: Optional[str], device: str, model_type: str, branch_to_adapt: Optional[str] = None,
                residual_activation: Optional[str] = None):
     """load_model (:65-105).  ``branch_to_adapt`` / ``residual_activation`` default to the CLI's parsed flags (the
@@ -156,9 +200,10 @@ def load_model(checkpoint_path: Optional[str], device: str, model_type: str, bra
     return model
 
 
-def _item_parts(item):
+def _item_parts(item, multi_caption: bool = False):
     """A dataset item as the reference's loaders return it: (frames, captions, id) or (frames, captions, comments, id)
-    (:144-150; the DataLoader's batch dimension of one is not added here).  captions: [77] or [1, 77]."""
+    (:144-150; the DataLoader's batch dimension of one is not added here).  captions: [77] or [1, 77]; with ``multi_caption``
+    [C, 77], C >= 1 (or [77]), returned as [C, 77]."""
     if len(item) == 3 and not torch.is_tensor(item[2]) and item[2] is not None:
         fr, cap, com = item[0], item[1], None
     elif len(item) == 3:                                          # (frames, caption, comments | None): the list form of the tests
@@ -167,6 +212,10 @@ def _item_parts(item):
         fr, cap, com = item[0], item[1], item[2]
     else:
         fr, cap, com = item[0], item[1], None
+    if multi_caption:
+        cap = cap[None] if cap.dim() == 1 else cap
+        assert fr.dim() == 4 and fr.shape[1] == 3 and cap.dim() == 2 and cap.shape[0] >= 1, "frames [T,3,H,W], captions [C,77] with C >= 1"
+        return fr, cap, com
     if cap.dim() == 2:
         assert cap.shape[0] == 1, "one caption per video (SURVEY 3.3: several captions reach faiss as a 3-D array in the reference)"
         cap = cap[0]
@@ -176,9 +225,11 @@ def _item_parts(item):
 
 @torch.no_grad()
 def encode_videos(model, videos: Sequence[Tuple], device, frame_stride: int = 16, first_chunk_only: bool = False,
-                  max_chunks_per_call: int = 256, first_frame_only: bool = False):
+                  max_chunks_per_call: int = 256, first_frame_only: bool = False, multi_caption: bool = False):
     """videos: sequence of dataset items (see _item_parts).  Returns (video_emb [N,D] = mean of the video's chunk
-    embeddings, caption_emb [N,D]) on the GPU -- the two tensors the reference stacks at :254-260."""
+    embeddings, caption_emb [N,D]) on the GPU -- the two tensors the reference stacks at :254-260.
+    ``multi_caption``: an item's captions may be [C_i, 77]; all captions are encoded in one call, on the CAM's text branch the video's
+    comment set is used once per caption (:207-229), and the result is (video_emb [N,D], caption_emb [M,D], caption counts [N])."""
     model.eval()
     if not isinstance(model, video_models):
         raise Exception("Unknown model_type")                      # :200-201
@@ -191,15 +242,16 @@ def encode_videos(model, videos: Sequence[Tuple], device, frame_stride: int = 16
                              "[B,F,3,H,W] only (model/timesformer_clip_alt.py:253 unpacks five dimensions)")
     chunks, captions, comments, counts = [], [], [], []
     for item in videos:
-        fr, cap, com = _item_parts(item)
+        fr, cap, com = _item_parts(item, multi_caption)
         ch = fr[0:1] if first_frame_only else chunk_frames(fr, frame_stride, 8, first_chunk_only)   # [1,3,H,W] | [C,8,3,H,W]
         chunks.append(ch)
         counts.append(ch.shape[0])
         captions.append(cap)
         if cam:
-            comments.append(com[:5] if com is not None else empty_comments(1, 5, cap.shape[0])[0])
+            comments.append(com[:5] if com is not None else empty_comments(1, 5, cap.shape[-1])[0])
     offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=device)
-    caps = torch.stack(captions).to(device)
+    caps = (torch.cat(captions) if multi_caption else torch.stack(captions)).to(device)
+    cap_counts = [c.shape[0] for c in captions] if multi_caption else None
     all_chunks = torch.cat(chunks)
     tower = model._pack()["visual"]
     if timesformer or first_frame_only:
@@ -218,6 +270,10 @@ def encode_videos(model, videos: Sequence[Tuple], device, frame_stride: int = 16
         packed = model._pack()["cam"]
         if model.branch_to_adapt_val == "text":                                   # one comment set per caption (:207-210)
             fc = model.encode_text(comm.reshape(-1, comm.shape[-1]))
+            if multi_caption:                                                    # the video's comment set, once per caption
+                rep = torch.repeat_interleave(torch.arange(len(cap_counts), device=device), torch.tensor(cap_counts, device=device))
+                fc = fc.reshape(len(cap_counts), comm.shape[1], -1)[rep].reshape(-1, fc.shape[-1]).contiguous()
+                comm = comm[rep].contiguous()
             ft = packed.forward(ft, fc, comm)
         elif model.branch_to_adapt_val == "image":                                # per chunk (:207-208)
             rep = torch.repeat_interleave(torch.arange(len(counts), device=device), torch.tensor(counts, device=device))
@@ -229,7 +285,7 @@ def encode_videos(model, videos: Sequence[Tuple], device, frame_stride: int = 16
     fv, ft = ops.normalize_rows(fv), ops.normalize_rows(ft)                        # forward()'s final normalize
     v_emb = ops.segment_mean(fv, offsets)
     module_arch.raise_if_nonfinite("retrieval_evaluation", v_emb, ft)
-    return v_emb, ft
+    return (v_emb, ft, cap_counts) if multi_caption else (v_emb, ft)
 
 
 def _resolve_dataset(datasetname, split):
@@ -243,12 +299,17 @@ def _resolve_dataset(datasetname, split):
 @torch.no_grad()
 def retrieval_evaluation(model, datasetname, split: str = "full-test", device="cuda", out_csv: Optional[str] = None,
                          frame_stride: int = 16, first_frame_only: bool = False, first_chunk_only: bool = False,
-                         videos_per_batch: int = 64, return_embeddings: bool = False):
+                         videos_per_batch: int = 64, return_embeddings: bool = False, multi_caption: bool = False):
     """retrieval_evaluation (:108-268) with the reference's positional arguments; returns its DataFrame.
     ``datasetname`` may also be a Dataset or a list of items (frames, captions[, comments], id).
     ``videos_per_batch`` bounds how many videos are decoded before their chunks are encoded (host memory);
-    ``return_embeddings``: also the two stacked embedding tensors of :254-260 (GPU)."""
+    ``return_embeddings``: also the two stacked embedding tensors of :254-260 (GPU).
+    ``multi_caption``: an item's captions may be [C_i, 77] with C_i >= 1; the result is compute_multi_caption_table's frame (R@K, MedR,
+    MeanR, MRR) and ``return_embeddings`` adds (video_emb [N, D], caption_emb [M, D], offsets [N + 1] int64 on the host)."""
     dataset, name = _resolve_dataset(datasetname, split)
+    if multi_caption:
+        return _retrieval_evaluation_multi(model, dataset, name, split, device, out_csv, frame_stride, first_frame_only, first_chunk_only,
+                                           videos_per_batch, return_embeddings)
     v_parts, c_parts = [], []
     batch = []
     n = len(dataset)
@@ -266,6 +327,30 @@ def retrieval_evaluation(model, datasetname, split: str = "full-test", device="c
     if out_csv is not None:
         outdf.to_csv(out_csv)
     return (outdf, video_emb, caption_emb) if return_embeddings else outdf
+
+
+def _retrieval_evaluation_multi(model, dataset, name, split, device, out_csv, frame_stride, first_frame_only, first_chunk_only,
+                                videos_per_batch, return_embeddings):
+    v_parts, c_parts, counts = [], [], []
+    batch = []
+    n = len(dataset)
+    for i in range(n):
+        batch.append(dataset[i])
+        if len(batch) == videos_per_batch or i == n - 1:
+            v, c, cnt = encode_videos(model, batch, device, frame_stride, first_chunk_only, first_frame_only=first_frame_only,
+                                      multi_caption=True)
+            v_parts.append(v)
+            c_parts.append(c)
+            counts += cnt
+            batch = []
+    video_emb, caption_emb = torch.cat(v_parts), torch.cat(c_parts)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    outdf = compute_multi_caption_table(video_emb, caption_emb, split=split, dataset_name=name, offsets=offsets)
+    if getattr(dataset, "synthetic", False):
+        outdf.attrs["synthetic"] = True
+    if out_csv is not None:
+        outdf.to_csv(out_csv)
+    return (outdf, video_emb, caption_emb, offsets) if return_embeddings else outdf
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -386,6 +386,58 @@ def rank_bidir(a: torch.Tensor, b: torch.Tensor, rows_per_block: int = 0, reach_
     return rank_a, rank_b, bits
 
 
+def check_offsets(offsets, n: int, m: int, allow_empty: bool = True):
+    """The caption offsets of rank_grouped as a host int64 array, validated (ValueError): length n + 1, offsets[0] = 0, offsets[n] = m,
+    non-decreasing (allow_empty=False: increasing -- no video without a caption).  Touches no device."""
+    import numpy as np
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.detach().cpu().numpy()
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.shape[0] != n + 1:
+        raise ValueError(f"offsets: expected {n + 1} entries for {n} videos, got shape {tuple(off.shape)}")
+    if off.dtype.kind not in "iu":
+        if off.dtype.kind != "f" or not np.array_equal(off, np.floor(off)):
+            raise ValueError(f"offsets: integers expected, got dtype {off.dtype}")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != m:
+        raise ValueError(f"offsets: must start at 0 and end at the number of captions {m}, got {int(off[0])} .. {int(off[-1])}")
+    steps = np.diff(off)
+    if (steps < 0).any():
+        raise ValueError(f"offsets: must be non-decreasing (first descent after video {int(np.flatnonzero(steps < 0)[0])})")
+    if not allow_empty and (steps == 0).any():
+        raise ValueError(f"offsets: video {int(np.flatnonzero(steps == 0)[0])} has no caption")
+    return off
+
+
+def rank_grouped(a: torch.Tensor, b: torch.Tensor, offsets, rows_per_block: int = 0, reach_capacity: int = 0,
+                 ws: Optional[torch.Tensor] = None):
+    """Full 0-based ranks for videos with several captions each (vtc_l2_rank_grouped): a [n, d] videos, b [m, d] captions (those of a video
+    contiguous, in video order), offsets [n + 1] (host sequence or tensor; validated on the host BEFORE anything is launched, ValueError;
+    uploaded as int32): the captions of video v are b[offsets[v]:offsets[v + 1]].  Returns (rank_a [m] int64 = the rank of the caption's own
+    video among the n videos, rank_b [n] int64 = the best rank one of the video's own captions reaches among all m captions -- the
+    caption-level convention, include/vtc_hip.h --, nonfinite_bits as rank_bidir).  A caption with a non-finite own distance has
+    rank_a = n, a video without a finite own caption (an empty group too) rank_b = m."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[0] < 1 or b.shape[0] < 1:
+        raise ValueError(f"rank_grouped: a [n, d] and b [m, d] expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    off = check_offsets(offsets, a.shape[0], b.shape[0])
+    return _rank_grouped(a, b, off, rows_per_block, reach_capacity, ws)
+
+
+@on_device
+def _rank_grouped(a, b, off, rows_per_block, reach_capacity, ws):
+    a, b = _gpu(a, torch.float32, "a"), _gpu(b, torch.float32, "b")
+    (n, d), m = a.shape, b.shape[0]
+    off_dev = torch.from_numpy(off.astype("int32")).to(a.device)
+    ws = _ws_for(ws, L.lib().vtc_l2_rank_grouped_workspace_bytes(n, m, d, rows_per_block, reach_capacity), a.device)
+    rank_a = torch.empty(m, dtype=torch.int64, device=a.device)
+    rank_b = torch.empty(n, dtype=torch.int64, device=a.device)
+    bits = torch.empty(1, dtype=torch.int32, device=a.device)
+    L.check(L.lib().vtc_l2_rank_grouped(a.data_ptr(), b.data_ptr(), off_dev.data_ptr(), n, m, d, rows_per_block, reach_capacity,
+                                        rank_a.data_ptr(), rank_b.data_ptr(), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            "vtc_l2_rank_grouped")
+    return rank_a, rank_b, bits
+
+
 def rank_kappa(d: int) -> float:
     """kappa of the rank sweep's error bound eps = kappa (|q|^2 + max|g|^2) at feature width d."""
     return float(L.lib().vtc_l2_rank_kappa(int(d)))
