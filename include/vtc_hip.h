@@ -317,7 +317,8 @@ int vtc_l2_recall_bidir(const float *a, const float *b, int n, int d, const int 
  * 0-based int64 (device, n each); pairs compare lexicographically on the fp64 distances sum_k (q_k - g_k)^2 of the fp32 inputs, so exact
  * ties go to the lower index and  #{ i : rank[i] < k }  are the counters of vtc_l2_recall_bidir, bit for bit, for every k.
  * The sweep COUNTS instead of selecting: the split-bf16 distance GEMM of VTC_SWEEP_BF16X3 writes row blocks (rows_per_block as in
- * vtc_l2_topk; 0 = as many rows as fit 2 GiB), a row pass and a column pass over each block count the entries that are closer than the
+ * vtc_l2_topk; 0 = as many rows as fit 2 GiB; a row holds n rounded up to 4 columns, so rows are 16-byte aligned at every n and the padding
+ * columns are never counted), a row pass and a column pass over each block count the entries that are closer than the
  * target by more than the BF16X3 error bound  eps = kappa (|q|^2 + max|g|^2),  kappa = the value vtc_l2_rank_kappa returns for d,  and
  * put the pairs within eps of it into a reach pool of reach_capacity pairs per direction (0 = the default, 512 n) that is settled in fp64.
  * An owner whose pairs did not fit is counted again by fp64 brute force: the ranks do not depend on the capacity.
@@ -342,7 +343,7 @@ int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per
  * An entry with a non-finite distance is never closer; a caption whose own distance is not finite gets rank_a = n and is no candidate
  * for c*; a video without a finite own caption (an empty group too) gets rank_b = m; nonfinite[0] as above.  With m = n and
  * off = 0, 1, ..., n both outputs are those of the paired entry point, element for element.
- * The sweep is the paired one made rectangular (D is [m, n], rows_per_block caption rows per block), the owner's target taken from a table;
+ * The sweep is the paired one made rectangular (D is [m, n], rows padded alike, rows_per_block caption rows per block), the owner's target taken from a table;
  * the reach pool of a direction holds reach_capacity pairs (0 = the default, 512 per owner: 512 m for the captions, 512 n for the
  * videos, at least 4096).  Everything is on the device, off included: no host sync, no allocation.  n >= 1, m >= 1, d % 64 == 0.  The
  * statistics words at the head of the workspace are the paired entry point's (direction a = the captions' row direction). */

@@ -93,9 +93,11 @@ def test_bulk_equals_the_fp64_reference(kind, n, d, rpb, b_frac):
     _check(got_b, want_b, "rank_b")
 
 
-@pytest.mark.parametrize("n,d", [(65, 64), (700, 128)])
+@pytest.mark.parametrize("n,d", [(65, 64), (700, 128), (1027, 64)])
 def test_identity_offsets_are_the_paired_sweep(n, d):
-    """off = 0, 1, ..., n with m = n: both outputs equal ops.rank_bidir's on the same tensors (and the paired reference)."""
+    """off = 0, 1, ..., n with m = n: both outputs equal ops.rank_bidir's on the same tensors (and the paired reference), and so do the sweep's
+    statistics -- the two entry points run the same passes over the same matrix.  (1027, 64): five blocks of 256 rows, one padding column."""
+    from vtc_amd import _lib as L
     from vtc_amd import ops
     a, b = RR.spread_pairs(n, d, 10 + n)
     want_a, want_b, gap = RR.reference_ranks(a, b)
@@ -103,10 +105,14 @@ def test_identity_offsets_are_the_paired_sweep(n, d):
     RR.assert_not_degenerate(want_a, n)
     RR.assert_not_degenerate(want_b, n)
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
-    pa, pb, _ = ops.rank_bidir(ta, tb, rows_per_block=256)
-    ga, gb, bits = ops.rank_grouped(ta, tb, np.arange(n + 1), rows_per_block=256)
+    ws_p = ops.workspace(L.lib().vtc_l2_rank_bidir_workspace_bytes(n, d, 256, 0), ta.device)
+    ws_g = ops.workspace(L.lib().vtc_l2_rank_grouped_workspace_bytes(n, n, d, 256, 0), ta.device)
+    pa, pb, _ = ops.rank_bidir(ta, tb, rows_per_block=256, ws=ws_p)
+    ga, gb, bits = ops.rank_grouped(ta, tb, np.arange(n + 1), rows_per_block=256, ws=ws_g)
     assert int(bits.item()) == 0
     assert torch.equal(ga, pa) and torch.equal(gb, pb)
+    st_p, st_g = ops.rank_sweep_stats(ws_p), ops.rank_sweep_stats(ws_g)
+    assert all(st_p[k] == st_g[k] for k in ("in_reach", "in_reach_max", "brute_force_owners")), (st_p, st_g)
     _check(ga.cpu().numpy(), want_a, "rank_a")
     _check(gb.cpu().numpy(), want_b, "rank_b")
 

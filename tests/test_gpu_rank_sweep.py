@@ -49,7 +49,8 @@ def _check(got, want, what):
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 257])
 def test_edge_sizes(n):
     """One row, two rows, one short of / exactly / one past a 64-column strip, and 257 with 256-row blocks: a second block of ONE row, whose
-    column counts are carried over from the first.  Odd n takes the scalar loads of both passes."""
+    column counts are carried over from the first.  n % 4 != 0: the rows of the matrix are padded to 16 bytes, the row pass ends in its scalar
+    tail and the column pass meets 3 / 2 / 1 / 3 / 3 padding columns (n = 1 .. 257), which it must neither count nor pool."""
     a, b, want_a, want_b = _case("spread", n, 64, 10 + n)
     if n >= 63:
         RR.assert_not_degenerate(want_a, n)
@@ -62,7 +63,8 @@ def test_edge_sizes(n):
 
 @pytest.mark.parametrize("n,d,seed,rpb", [(1027, 64, 2, 256), (700, 128, 3, 0), (1500, 512, 1, 0), (600, 768, 4, 0)])
 def test_spread_data_equals_the_fp64_reference(n, d, seed, rpb):
-    """(1027, 64) in five blocks of 256 rows (odd n: scalar loads); 16-byte loads at 700 / 1500 / 600 rows in one block; d = 64 .. 768."""
+    """(1027, 64) in five blocks of 256 rows (rows padded to 1028 columns: scalar tail in the row pass, one padding column in the column pass);
+    no padding at 700 / 1500 / 600 rows in one block; d = 64 .. 768."""
     a, b, want_a, want_b = _case("spread", n, d, seed)
     RR.assert_not_degenerate(want_a, n)
     RR.assert_not_degenerate(want_b, n)

@@ -43,6 +43,16 @@ void vtc_set_error(const char *fmt, ...);
     }                                                                           \
   } while (0)
 
+// the same for a driver shared by several entry points: "<entry point> <stage>"
+#define VTC_LAUNCH_CHECK2(fn, stage)                                                          \
+  do {                                                                                        \
+    hipError_t e_ = hipGetLastError();                                                        \
+    if (e_ != hipSuccess) {                                                                   \
+      vtc_set_error("%s %s: launch failed: %s", fn, stage, hipGetErrorString(e_));            \
+      return 1;                                                                               \
+    }                                                                                         \
+  } while (0)
+
 // float -> bf16 (round to nearest even; NaN stays NaN via the hardware convert).
 __device__ __forceinline__ bf16_t f2bf(float f) {
   __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32 on gfx950

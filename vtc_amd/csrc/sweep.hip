@@ -1021,6 +1021,27 @@ struct SweepWs {
 constexpr int MAX_SEG = 16;
 constexpr int MAX_CSEG = 8;
 
+// rows_per_block = 0: as many rows of `cols` fp32 distances as fit a 2 GiB block, a multiple of 256.
+// Big blocks: a block's top-k pass costs one list warm-up per (row, segment) wave, and the GEMM a fill/drain
+// per launch, so FEWER, LARGER blocks win over Infinity-Cache residency (measured at 50k x 50k, F32 /
+// BF16X3, one direction: 128 MiB blocks 27.5 / 19.6 ms, 2 GiB blocks 21.4 / 10.4 ms; top-k 1.5 -> 5.0 TB/s).
+int default_rows_per_block(int cols) {
+  const size_t budget = (size_t)2 << 30;
+  const int rpb = (int)std::min<size_t>(budget / ((size_t)cols * 4), (size_t)1 << 20) / 256 * 256;
+  return rpb < 256 ? 256 : rpb;
+}
+
+// A row pass over a [rows, cols] block: enough (row, segment) waves to fill the chip (32 waves per CU), in segments of whole 1024-column
+// steps (every segment pays its own warm-up insertions, so segments are used only when rows alone cannot fill the chip).
+struct RowSegments {
+  int S, seg_cols;
+};
+RowSegments row_segments(int rows, int cols) {
+  const int S = std::min(MAX_SEG, cdiv(8192, rows));
+  const int seg_cols = cdiv(cdiv(cols, S), 1024) * 1024;
+  return {cdiv(cols, seg_cols), seg_cols};
+}
+
 // candidate list depth of the EXACT mode: 21 spare ranks behind the requested ones, at least 32, at most 64 / n_gallery
 int exact_cdepth(int depth, int ng) { return std::min(std::min(64, ng), std::max(32, depth + 21)); }
 
@@ -1036,15 +1057,7 @@ SweepWs plan(char *ws, int ng, int nq, int d, int precision, int rows_per_block,
   s.qb = (bf16_t *)take((size_t)nq * d * parts * 2);
   s.gb = (bf16_t *)take((size_t)ng * d * parts * 2);
   int rpb = rows_per_block;
-  if (rpb <= 0) {
-    // Big blocks: a block's top-k pass costs one list warm-up per (row, segment) wave, and the GEMM a fill/drain
-    // per launch, so FEWER, LARGER blocks win over Infinity-Cache residency (measured at 50k x 50k, F32 /
-    // BF16X3, one direction: 128 MiB blocks 27.5 / 19.6 ms, 2 GiB blocks 21.4 / 10.4 ms; top-k 1.5 -> 5.0 TB/s).
-    const size_t budget = (size_t)2 << 30;
-    rpb = (int)std::min<size_t>(budget / ((size_t)ng * 4), (size_t)1 << 20);
-    rpb = rpb / 256 * 256;
-    if (rpb < 256) rpb = 256;
-  }
+  if (rpb <= 0) rpb = default_rows_per_block(ng);
   if (rpb > nq) rpb = nq;
   s.rows_per_block = rpb;
   s.dist = (float *)take((size_t)rpb * ng * 4);
@@ -1104,12 +1117,7 @@ static int l2_topk_impl(const float *gallery, const float *queries, int ng, int 
       rc = launch_gemm(s.qb + (size_t)r0 * d * parts, s.gb, nullptr, s.dist, rows, ng, d * parts, VTC_BF16, e, stream);
     if (rc) return rc;
     {
-      // enough (row, segment) waves to fill the chip (32 waves per CU)
-      // (every segment pays its own warm-up insertions, so segments are used only when rows alone cannot fill the chip)
-      int S = cdiv(8192, rows);
-      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
-      int seg_cols = cdiv(cdiv(ng, S), 1024) * 1024;
-      S = cdiv(ng, seg_cols);
+      const auto [S, seg_cols] = row_segments(rows, ng);
       ProfScope prof(VTC_PROF_TOPK, (double)rows * ng * 4, stream);
       hipLaunchKernelGGL(row_topk_kernel, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, ng, rows, ng, depth, S, seg_cols, ids,
                          dists, (size_t)r0, s.part_d, s.part_i);
@@ -1810,10 +1818,11 @@ __device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, 
 
 // max of the FINITE squared norms of each side (a non-finite row's entries are NaN / inf whatever the bound says; with it in the maximum
 // every query of the direction would have the whole gallery in reach)
-__global__ __launch_bounds__(256) void rank_max_kernel(const float *__restrict__ xa, const float *__restrict__ xb, int n, float *__restrict__ out_a,
-                                                       float *__restrict__ out_b) {
+__global__ __launch_bounds__(256) void rank_max_kernel(const float *__restrict__ xa, int na, const float *__restrict__ xb, int nb,
+                                                       float *__restrict__ out_a, float *__restrict__ out_b) {
   __shared__ float part[4];
   const float *x = blockIdx.x ? xb : xa;
+  const int n = blockIdx.x ? nb : na;
   float m = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
     const float v = x[i];
@@ -1827,53 +1836,71 @@ __global__ __launch_bounds__(256) void rank_max_kernel(const float *__restrict__
 
 // per-direction state of the counting sweep
 struct RankDir {
-  const float *own, *other;      // [n, d] fp32: the direction's queries and its gallery
-  const float *lo, *hi;          // [n] thresholds of the owner's row / column of D (hi = -inf: the owner's target distance is not finite)
-  int *cnt;                      // [n] entries closer than the target
-  int *reach;                    // [n] entries in reach of the target (statistics)
-  int *ovf;                      // [n] != 0: the owner's pairs did not fit the pool
+  const float *own, *other;      // [n_own, d], [n_other, d] fp32: the direction's queries and its gallery
+  const float *lo, *hi;          // [n_own] thresholds of the owner's row / column of D (hi = -inf: the owner's target distance is not finite)
+  int *cnt;                      // [n_own] entries closer than the target
+  int *reach;                    // [n_own] entries in reach of the target (statistics)
+  int *ovf;                      // [n_own] != 0: the owner's pairs did not fit the pool
   int2 *pool;                    // [cap] (owner, other)
   unsigned long long *pool_n;    // pairs offered to the pool (may exceed cap)
   unsigned long long cap;
-};
-// The grouped form (vtc_l2_rank_grouped): the owner's target comes from a table, each direction has its own target distances, and the two
-// sides differ in size.  The kernels below take either form as a compile-time policy; with RankDir they are the paired sweep as it was.
-struct RankDirG : RankDir {
-  const int *tgt;                // [n_own] the owner's target on the other side (never excluded when hi = -inf)
-  const double *dt;              // [n_own] fp64 distance of the owner to its target
+  const double *dt;              // [n_own] fp64 distance of the owner to its target (paired: one array for both directions)
   int n_own, n_other;
 };
+// The kernels below take the direction as a compile-time policy that says ONE thing, where an owner's target is: its own index (RankDir,
+// vtc_l2_rank_bidir) or an entry of a table (RankDirG, vtc_l2_rank_grouped).
+struct RankDirG : RankDir {
+  const int *tgt;                // [n_own] the owner's target on the other side (-1: none, and hi = -inf)
+};
 template <typename Dir> constexpr bool rank_has_table = std::is_same<Dir, RankDirG>::value;
+template <typename Dir>
+__device__ __forceinline__ int rank_target(const Dir &P, int owner) {
+  if constexpr (rank_has_table<Dir>) return P.tgt[owner];
+  else return owner;
+}
 
-// One wave per 8 pairs: the targets' fp64 distances, both directions' thresholds, and the counters' zeroes.
-__global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, int n, int d,
-                                                        const float *__restrict__ an2, const float *__restrict__ bn2,
-                                                        const float *__restrict__ amax, const float *__restrict__ bmax, float kappa,
-                                                        double *__restrict__ dt, float *__restrict__ lo_r, float *__restrict__ hi_r,
-                                                        float *__restrict__ lo_c, float *__restrict__ hi_c, int *__restrict__ zero, int n_zero) {
+// What the prologue writes for a direction: the owners' target distances and thresholds, from their norms and the other side's maximum.
+struct RankThresholds {
+  const float *n2, *other_max;   // [n_own] |q|^2; max |g|^2 over the finite rows of the other side
+  double *dt;
+  float *lo, *hi;
+};
+__device__ __forceinline__ void rank_set_thresholds(const RankThresholds &T, int i, double dt, float kappa) {
+  const bool ok = dt < (double)INFINITY;                // false for NaN too
+  const float eps = kappa * (T.n2[i] + *T.other_max);
+  T.lo[i] = ok ? __double2float_rd(dt - (double)eps) : -INFINITY;
+  T.hi[i] = ok ? __double2float_ru(dt + (double)eps) : -INFINITY;
+}
+
+// One wave per 8 owners of the row direction: the fp64 distance to the owner's target, the direction's thresholds, and the counters' zeroes.
+// Paired: the column direction's owner i has the same target distance, so its thresholds are written here too (TC.dt == TR.dt), and the
+// columns [n, n_ld) that pad the matrix's rows to 16 bytes get lo = hi = -inf: the column pass neither counts nor pools them.  Grouped:
+// rank_grouped_target_kernel writes the column direction (TC is not read).
+template <typename Dir>
+__global__ __launch_bounds__(256) void rank_prep_kernel(const Dir R, const RankThresholds TR, const RankThresholds TC, int n_ld, int d, float kappa,
+                                                        int *__restrict__ zero, int n_zero) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   for (int i = t; i < n_zero; i += gridDim.x * 256) zero[i] = 0;
+  const int n = R.n_own;
+  if constexpr (!rank_has_table<Dir>) {
+    if (t < n_ld - n) TC.lo[n + t] = TC.hi[n + t] = -INFINITY;
+  }
   const int lane = threadIdx.x & 63;
   const int i0 = (t >> 6) * RS_NB;
   if (i0 >= n) return;                                  // wave-uniform
-  int ii[RS_NB];
+  int qi[RS_NB], gi[RS_NB];
 #pragma unroll
-  for (int u = 0; u < RS_NB; ++u) ii[u] = min(i0 + u, n - 1);
+  for (int u = 0; u < RS_NB; ++u) { qi[u] = min(i0 + u, n - 1); gi[u] = rank_target(R, qi[u]); }
   double dd[RS_NB];
-  wave_dist64_pairs(b, a, ii, ii, d, lane, dd);
+  wave_dist64_pairs(R.own, R.other, qi, gi, d, lane, dd);
   double mine = 0.0;
 #pragma unroll
   for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
   const int i = i0 + lane;
   if (lane < RS_NB && i < n) {
-    dt[i] = mine;
-    const bool ok = mine < (double)INFINITY;            // false for NaN too
-    // rows of D: query b_i against the a's; columns: query a_i against the b's
-    const float eps_r = kappa * (bn2[i] + *amax), eps_c = kappa * (an2[i] + *bmax);
-    lo_r[i] = ok ? __double2float_rd(mine - (double)eps_r) : -INFINITY;
-    hi_r[i] = ok ? __double2float_ru(mine + (double)eps_r) : -INFINITY;
-    lo_c[i] = ok ? __double2float_rd(mine - (double)eps_c) : -INFINITY;
-    hi_c[i] = ok ? __double2float_ru(mine + (double)eps_c) : -INFINITY;
+    TR.dt[i] = mine;
+    rank_set_thresholds(TR, i, mine, kappa);            // rows of D: query b_i against the a's
+    if constexpr (!rank_has_table<Dir>) rank_set_thresholds(TC, i, mine, kappa);      // columns: query a_i against the b's
   }
 }
 
@@ -1945,7 +1972,8 @@ __device__ __forceinline__ void rank_stage_append(const RankDir &P, int2 *stage,
 }
 
 // Row direction: one wave per (row of the block, column segment), streaming as row_topk_kernel does (1024 columns per step, four 16-byte
-// loads per lane, two steps in flight behind the one being counted).  Per value two compares; one atomic per wave at the end.
+// loads per lane, two steps in flight behind the one being counted; the last columns of a row whose n_cols is no multiple of four are loaded
+// one by one).  Per value two compares; one atomic per wave at the end.
 template <typename Dir>
 __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row0, int S,
                                                              int seg_cols, const Dir P) {
@@ -1956,19 +1984,17 @@ __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__rest
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_rows * S) return;
   const int r = w / S, seg = w - r * S;
-  const int gr = row0 + r;                                // the owner (paired: also the column of its target)
+  const int gr = row0 + r;                                // the owner
   const float lo = P.lo[gr], hi = P.hi[gr];
   if (hi == -INFINITY) return;                            // wave-uniform: target distance not finite, rank n
-  int tg = gr;                                            // the column of its target
-  if constexpr (rank_has_table<Dir>) tg = P.tgt[gr];
-  const float *row = dist + (size_t)r * ld;
+  const int tg = rank_target(P, gr);                      // the column of its target
+  const float *row = dist + (size_t)r * ld;               // (ld % 4 == 0: 16-byte aligned at every multiple of four columns)
   const int c_lo = seg * seg_cols, c_hi = min(n_cols, c_lo + seg_cols);
-  const bool vec = (ld & 3) == 0;
   auto load_step = [&](int base, float (&v)[16]) {
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       const int c = base + 256 * h + lane * 4;
-      if (vec && c + 3 < c_hi) {
+      if (c + 3 < c_hi) {
         typedef float v4f_t __attribute__((ext_vector_type(4)));
         const v4f_t t = __builtin_nontemporal_load(reinterpret_cast<const v4f_t *>(row + c));
         v[4 * h] = t.x; v[4 * h + 1] = t.y; v[4 * h + 2] = t.z; v[4 * h + 3] = t.w;
@@ -2009,14 +2035,15 @@ __global__ __launch_bounds__(256) void rank_row_count_kernel(const float *__rest
   }
 }
 
-// Column direction of the same block: one wave per (strip of 64 columns, row segment).  V = 4 (rows 16-byte aligned): a lane owns four
-// adjacent columns and every fourth row -- a load instruction of the wave is four 256-byte row pieces; V = 1: a lane owns one column.
-// Eight loads per lane in flight; the lanes' counts are folded over the wave once, behind the scan: one atomic per column and wave.
-// The counts are CARRIED from one block of rows to the next in P.cnt (global row ids: row_id0 + row).
-template <int V, typename Dir>
+// Column direction of the same block: one wave per (strip of 64 columns, row segment).  The rows are 16-byte aligned (ld % 4 == 0 and
+// n_cols = ld: the padding columns are scanned, their hi = -inf): a lane owns four adjacent columns and every fourth row -- a load
+// instruction of the wave is four 256-byte row pieces.  Eight loads per lane in flight; the lanes' counts are folded over the wave once,
+// behind the scan: one atomic per column and wave.  The counts are CARRIED from one block of rows to the next in P.cnt (global row ids:
+// row_id0 + row).
+template <typename Dir>
 __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row_id0,
                                                              int n_strips, int S, int seg_rows, const Dir P) {
-  constexpr int U = 8, RPL = V;                           // loads in flight per lane; rows per load instruction of the wave
+  constexpr int U = 8, V = 4;                             // loads in flight per lane; columns per lane = rows per load instruction of the wave
   __shared__ int2 stage_all[4][RS_STAGE];
   int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
   int n_st = 0;
@@ -2024,42 +2051,35 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_strips * S) return;
   const int seg = w / n_strips, strip = w - seg * n_strips;   // neighbouring waves: neighbouring strips of the same rows
-  const int c = strip * 64 + (V == 4 ? 4 * (lane & 15) : lane);
-  const int sub = V == 4 ? lane >> 4 : 0;
+  const int c_strip = strip * 64 + 4 * (lane & 15);
+  const bool live = c_strip < n_cols;                     // (n_cols % 4 == 0: the lane's four columns are in or out together)
+  const int c = live ? c_strip : 0;                       // a lane past the matrix reads column 0 and counts nothing
+  const int sub = lane >> 4;
   const int r_lo = seg * seg_rows, r_hi = min(n_rows, r_lo + seg_rows);
-  const bool live = c < n_cols;                           // (V = 4: n_cols % 4 == 0, the lane's four columns are in or out together)
   float lo[V], hi[V];
-  constexpr bool kTable = rank_has_table<Dir>;
-  int cnt[V], reach[V], tg[kTable ? V : 1];               // tg: the row (global id) of the column's target, where it comes from a table
+  int cnt[V], reach[V], tg[V];                            // tg: the row (global id) of the column's target
 #pragma unroll
   for (int e = 0; e < V; ++e) {
     lo[e] = live ? P.lo[c + e] : -INFINITY;
     hi[e] = live ? P.hi[c + e] : -INFINITY;                // -inf: a column past the matrix, or an owner whose target distance is not finite
-    if constexpr (kTable) tg[e] = live ? P.tgt[c + e] : -1;
+    tg[e] = rank_target(P, c + e);                         // (table form: tgt has n_cols >= 4 entries, the padding ones written too; a lane past it reads tgt[0 .. 3])
     cnt[e] = 0; reach[e] = 0;
   }
-  for (int rb = r_lo; rb < r_hi; rb += RPL * U) {
+  for (int rb = r_lo; rb < r_hi; rb += V * U) {
     float v[U][V];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int row = rb + u * RPL + sub;
-      const float *src = dist + (size_t)min(row, r_hi - 1) * ld + (live ? c : 0);      // branch-free: all loads of a lane in flight together
-      if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4 *>(src);
-        v[u][0] = t.x; v[u][1 % V] = t.y; v[u][2 % V] = t.z; v[u][3 % V] = t.w;
-      } else {
-        v[u][0] = *src;
-      }
+      const int row = rb + u * V + sub;
+      const float4 t = *reinterpret_cast<const float4 *>(dist + (size_t)min(row, r_hi - 1) * ld + c);      // branch-free: all loads of a lane in flight together
+      v[u][0] = t.x; v[u][1] = t.y; v[u][2] = t.z; v[u][3] = t.w;
     }
     unsigned m = 0;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int row = rb + u * RPL + sub;
+      const int row = rb + u * V + sub;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        int t = c + e;                                     // paired: the column's own index
-        if constexpr (kTable) t = tg[e];
-        const bool ok = row < r_hi && hi[e] != -INFINITY && row_id0 + row != t;
+        const bool ok = row < r_hi && hi[e] != -INFINITY && row_id0 + row != tg[e];
         const bool lt = v[u][e] < lo[e];
         cnt[e] += (ok && lt) ? 1 : 0;
         const bool in = ok && !lt && !(v[u][e] > hi[e]);
@@ -2068,15 +2088,13 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
       }
     }
     if (__ballot(m != 0) != 0ull)                          // wave-uniform, rare
-      rank_stage_append<U * V>(P, stage, n_st, m, lane, [&](int q) { return c + q % V; }, [&](int q) { return row_id0 + rb + (q / V) * RPL + sub; });
+      rank_stage_append<U * V>(P, stage, n_st, m, lane, [&](int q) { return c + q % V; }, [&](int q) { return row_id0 + rb + (q / V) * V + sub; });
   }
   rank_stage_flush(P, stage, n_st, lane);
 #pragma unroll
   for (int e = 0; e < V; ++e) {
-    if (V == 4) {
-      cnt[e] += __shfl_xor(cnt[e], 16, 64); cnt[e] += __shfl_xor(cnt[e], 32, 64);
-      reach[e] += __shfl_xor(reach[e], 16, 64); reach[e] += __shfl_xor(reach[e], 32, 64);
-    }
+    cnt[e] += __shfl_xor(cnt[e], 16, 64); cnt[e] += __shfl_xor(cnt[e], 32, 64);
+    reach[e] += __shfl_xor(reach[e], 16, 64); reach[e] += __shfl_xor(reach[e], 32, 64);
     if (live && sub == 0) {
       if (cnt[e]) atomicAdd(&P.cnt[c + e], cnt[e]);
       if (reach[e]) atomicAdd(&P.reach[c + e], reach[e]);
@@ -2086,7 +2104,7 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
 
 // The pooled pairs of both directions, eight per wave and step: fp64 distances (wave_dist64_pairs), compared as (d, other) < (d_t, target).
 template <typename Dir>
-__global__ __launch_bounds__(256) void rank_settle_kernel(const Dir PA, const Dir PB, int nblocks_a, const double *__restrict__ dt, int d) {
+__global__ __launch_bounds__(256) void rank_settle_kernel(const Dir PA, const Dir PB, int nblocks_a, int d) {
   const bool second = (int)blockIdx.x >= nblocks_a;
   const Dir &P = second ? PB : PA;
   const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
@@ -2106,9 +2124,8 @@ __global__ __launch_bounds__(256) void rank_settle_kernel(const Dir PA, const Di
 #pragma unroll
     for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
     if (have) {                                            // (a flagged owner's count is overwritten by rank_brute_kernel, later in the stream)
-      double t;
-      int tg = pr.x;
-      if constexpr (rank_has_table<Dir>) { t = P.dt[pr.x]; tg = P.tgt[pr.x]; } else { t = dt[pr.x]; }
+      const double t = P.dt[pr.x];
+      const int tg = rank_target(P, pr.x);
       if (mine < t || (mine == t && pr.y < tg)) atomicAdd(&P.cnt[pr.x], 1);
     }
   }
@@ -2117,8 +2134,7 @@ __global__ __launch_bounds__(256) void rank_settle_kernel(const Dir PA, const Di
 // Flagged owners (their pairs overflowed the pool): the count again, by fp64 brute force over the whole other side; one workgroup of
 // eight waves per owner.  Also the statistics: owners sent here, the largest in-reach count of an owner.
 template <typename Dir>
-__global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir PB, int nblocks_a, const double *__restrict__ dt, int n, int d,
-                                                         unsigned long long *__restrict__ stats) {
+__global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir PB, int nblocks_a, int d, unsigned long long *__restrict__ stats) {
   const bool second = (int)blockIdx.x >= nblocks_a;
   const Dir &P = second ? PB : PA;
   const int bid = second ? (int)blockIdx.x - nblocks_a : (int)blockIdx.x;
@@ -2126,14 +2142,14 @@ __global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir
   __shared__ int part[8];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int mx = 0;
-  int n_own = n, n_oth = n;
-  if constexpr (rank_has_table<Dir>) { n_own = P.n_own; n_oth = P.n_other; }
-  for (int o = bid; o < n_own; o += nbl) {                 // uniform for the workgroup
+  // PB is PA transposed (its owners are PA's others): both sizes come from PA, beside nblocks_a in the argument block.  Read through P, the
+  // loop bound waits for one more scalar load, behind the one that selects P (+0.002 ms at 10k: a CU runs its workgroups one after another).
+  const int n_own = second ? PA.n_other : PA.n_own, n_oth = second ? PA.n_own : PA.n_other;
+  for (int o = bid; o < n_own; o += nbl) {                   // uniform for the workgroup
     mx = max(mx, P.reach[o]);
     if (!P.ovf[o]) continue;
-    double t;
-    int tg = o;
-    if constexpr (rank_has_table<Dir>) { t = P.dt[o]; tg = P.tgt[o]; } else { t = dt[o]; }
+    const double t = P.dt[o];
+    const int tg = rank_target(P, o);
     int cnt = 0;
     for (int j0 = RS_NB * w; j0 < n_oth; j0 += RS_NB * 8) {
       int qi[RS_NB], gi[RS_NB];
@@ -2161,144 +2177,13 @@ __global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir
   if (threadIdx.x == 0 && mx) atomicMax(&stats[2 + (second ? 1 : 0)], (unsigned long long)mx);
 }
 
-__global__ __launch_bounds__(256) void rank_write_kernel(const double *__restrict__ dt, const int *__restrict__ cnt_r, const int *__restrict__ cnt_c,
-                                                         int n, int64_t *__restrict__ rank_a, int64_t *__restrict__ rank_b) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const bool ok = dt[i] < (double)INFINITY;
-  rank_a[i] = ok ? (int64_t)cnt_r[i] : (int64_t)n;
-  rank_b[i] = ok ? (int64_t)cnt_c[i] : (int64_t)n;
-}
-
-struct RankWs {
-  unsigned long long *stats;       // [RS_STATS]
-  float *qn, *gn, *qmax, *gmax;    // queries = b (rows of D), gallery = a (columns)
-  bf16_t *qb, *gb;
-  float *dist;
-  int rows_per_block;
-  double *dt;
-  float *lo_r, *hi_r, *lo_c, *hi_c;
-  int *zero;                       // cnt_r, cnt_c, reach_r, reach_c, ovf_r, ovf_c: [6][n], zeroed by rank_prep_kernel
-  int2 *pool_r, *pool_c;
-  size_t cap;
-  size_t total;
-};
-// default pool: 512 pairs per owner and direction (8 bytes each).  Measured (profiles/r10_rank_sweep.md): an owner in the bulk of unrelated
-// unit vectors at d = 512 has 0.216 % of the other side in reach (108 pairs at 50k, at most 203), one whose target leads almost none.
-size_t rank_default_capacity(int n) { return std::max<size_t>(4096, (size_t)512 * n); }
-RankWs rank_plan(char *ws, int n, int d, int rows_per_block, int reach_capacity) {
-  RankWs s;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
-  s.stats = (unsigned long long *)take(RS_STATS * 8);
-  s.qn = (float *)take((size_t)n * 4);
-  s.gn = (float *)take((size_t)n * 4);
-  s.qmax = (float *)take(4);
-  s.gmax = (float *)take(4);
-  s.qb = (bf16_t *)take((size_t)n * d * 3 * 2);
-  s.gb = (bf16_t *)take((size_t)n * d * 3 * 2);
-  int rpb = rows_per_block;
-  if (rpb <= 0) {                                          // as plan(): as many rows as fit a 2 GiB block
-    rpb = (int)std::min<size_t>(((size_t)2 << 30) / ((size_t)n * 4), (size_t)1 << 20);
-    rpb = rpb / 256 * 256;
-    if (rpb < 256) rpb = 256;
-  }
-  if (rpb > n) rpb = n;
-  s.rows_per_block = rpb;
-  s.dist = (float *)take((size_t)rpb * n * 4);
-  s.dt = (double *)take((size_t)n * 8);
-  s.lo_r = (float *)take((size_t)n * 4);
-  s.hi_r = (float *)take((size_t)n * 4);
-  s.lo_c = (float *)take((size_t)n * 4);
-  s.hi_c = (float *)take((size_t)n * 4);
-  s.zero = (int *)take((size_t)6 * n * 4);
-  s.cap = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(n);
-  s.pool_r = (int2 *)take(s.cap * 8);
-  s.pool_c = (int2 *)take(s.cap * 8);
-  s.total = off;
-  return s;
-}
-
-int rank_bidir_impl(const float *a, const float *b, int n, int d, int64_t *rank_a, int64_t *rank_b, int *nonfinite, const RankWs &s,
-                    hipStream_t stream) {
-  int *cnt_r = s.zero, *cnt_c = s.zero + n, *reach_r = s.zero + 2 * (size_t)n, *reach_c = s.zero + 3 * (size_t)n, *ovf_r = s.zero + 4 * (size_t)n,
-      *ovf_c = s.zero + 5 * (size_t)n;
-  // gallery a, query b_i: the rows of D;  gallery b, query a_i: its columns
-  const RankDir R{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap};
-  const RankDir Cd{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap};
-  (void)hipMemsetAsync(s.stats, 0, RS_STATS * 8, stream);
-  (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
-  if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)n * d, nonfinite, stream)) return rc;
-  {
-    ProfScope prof(VTC_PROF_TOPK, (double)n * d * 2 * (4 + 6 + 4), stream);
-    prof.tag(101, n, d);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, b, s.qn, n, d);
-    hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, a, s.gn, n, d);
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, b, s.qb, n, d, 3, 0);
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, a, s.gb, n, d, 3, 1);
-    hipLaunchKernelGGL(rank_max_kernel, dim3(2), dim3(256), 0, stream, s.gn, s.qn, n, s.gmax, s.qmax);
-    hipLaunchKernelGGL(rank_prep_kernel, dim3(cdiv(cdiv(n, RS_NB), 4)), dim3(256), 0, stream, a, b, n, d, s.gn, s.qn, s.gmax, s.qmax, rank_kappa(d),
-                       s.dt, s.lo_r, s.hi_r, s.lo_c, s.hi_c, s.zero, 6 * n);
-  }
-  VTC_LAUNCH_CHECK("l2_rank_bidir prologue");
-  const int V = (n & 3) == 0 ? 4 : 1;
-  const int n_strips = cdiv(n, 64);
-  for (int r0 = 0; r0 < n; r0 += s.rows_per_block) {
-    const int rows = min(s.rows_per_block, n - r0);
-    GemmEpi e;
-    e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
-    if (int rc = launch_gemm(s.qb + (size_t)r0 * d * 3, s.gb, nullptr, s.dist, rows, n, d * 3, VTC_BF16, e, stream)) return rc;
-    {
-      // enough (row, segment) waves to fill the chip, as row_topk_kernel's launch
-      int S = cdiv(8192, rows);
-      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
-      const int seg_cols = cdiv(cdiv(n, S), 1024) * 1024;
-      S = cdiv(n, seg_cols);
-      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
-      prof.tag(102, rows, n);
-      hipLaunchKernelGGL(rank_row_count_kernel<RankDir>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, S, seg_cols, R);
-    }
-    {
-      // (strip, segment) waves: ~32 per CU; a segment is a whole number of the wave's 8-load steps
-      const int step = 8 * V;
-      int S = std::max(1, cdiv(32 * vtcgemm::num_cus(), n_strips));
-      const int seg_rows = cdiv(cdiv(rows, S), step) * step;
-      S = cdiv(rows, seg_rows);
-      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
-      prof.tag(103, rows, n);
-      if (V == 4)
-        hipLaunchKernelGGL((rank_col_count_kernel<4, RankDir>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
-      else
-        hipLaunchKernelGGL((rank_col_count_kernel<1, RankDir>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n, rows, n, r0, n_strips, S, seg_rows, Cd);
-    }
-    VTC_LAUNCH_CHECK("l2_rank_bidir count");
-  }
-  {
-    // eight pairs per wave and step; the pools' fill lives on the device, so the grid is sized for a full pool and strides
-    const int g = (int)std::min<size_t>(2048, (s.cap + 4 * RS_NB - 1) / (4 * RS_NB));
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    prof.tag(104, n, d);
-    hipLaunchKernelGGL(rank_settle_kernel<RankDir>, dim3(2 * g), dim3(256), 0, stream, R, Cd, g, s.dt, d);
-  }
-  {
-    const int g = std::min(n, 1024);
-    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
-    prof.tag(105, n, d);
-    hipLaunchKernelGGL(rank_brute_kernel<RankDir>, dim3(2 * g), dim3(512), 0, stream, R, Cd, g, s.dt, n, d, s.stats);
-  }
-  hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, s.dt, cnt_r, cnt_c, n, rank_a, rank_b);
-  VTC_LAUNCH_CHECK("l2_rank_bidir finish");
-  return 0;
-}
-
 // ---- grouped rank sweep (vtc_l2_rank_grouped): several captions per video ------------------------------------------------------------
 // a [n, d] videos, b [m, d] captions, off [n + 1]: the captions of video v are the rows off[v] .. off[v + 1] of b.  The counting sweep above
 // made rectangular (D is [m, n]: a caption per row), with the owner's target taken from a table:
 //   row direction     owner = caption c, target = its video g(c), d_t = D(c, g(c))                    -> rank_a [m]
 //   column direction  owner = video v, target = c* = its own caption with the smallest (D(c, v), c),  -> rank_b [n]
 //                     so d_t[v] is the segmented lexicographic minimum of the row direction's d_t over the video's captions
-// (include/vtc_hip.h has the definition).  The prologue below is new; the passes, the settle and the brute force are the kernels above
-// instantiated with RankDirG.
+// (include/vtc_hip.h has the definition).  The two kernels below are its own; everything else is the sweep above instantiated with RankDirG.
 
 // g(c) of every caption: the last v with off[v] <= c (an empty group is never the answer: its successor starts at the same caption).
 // Whatever `off` holds, the result lies in [0, n).
@@ -2311,34 +2196,6 @@ __global__ __launch_bounds__(256) void rank_group_id_kernel(const int *__restric
     if (off[mid] <= c) lo = mid; else hi = mid - 1;
   }
   gid[c] = lo;
-}
-
-// One wave per 8 captions: the fp64 distance to the caption's own video, the row direction's thresholds, and the counters' zeroes.
-__global__ __launch_bounds__(256) void rank_grouped_prep_kernel(const float *__restrict__ a, const float *__restrict__ b, const int *__restrict__ gid,
-                                                                int m, int d, const float *__restrict__ bn2, const float *__restrict__ amax,
-                                                                float kappa, double *__restrict__ dt_r, float *__restrict__ lo_r,
-                                                                float *__restrict__ hi_r, int *__restrict__ zero, int n_zero) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  for (int i = t; i < n_zero; i += gridDim.x * 256) zero[i] = 0;
-  const int lane = threadIdx.x & 63;
-  const int i0 = (t >> 6) * RS_NB;
-  if (i0 >= m) return;                                  // wave-uniform
-  int ci[RS_NB], gi[RS_NB];
-#pragma unroll
-  for (int u = 0; u < RS_NB; ++u) { ci[u] = min(i0 + u, m - 1); gi[u] = gid[ci[u]]; }
-  double dd[RS_NB];
-  wave_dist64_pairs(b, a, ci, gi, d, lane, dd);
-  double mine = 0.0;
-#pragma unroll
-  for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
-  const int i = i0 + lane;
-  if (lane < RS_NB && i < m) {
-    dt_r[i] = mine;
-    const bool ok = mine < (double)INFINITY;            // false for NaN too
-    const float eps_r = kappa * (bn2[i] + *amax);
-    lo_r[i] = ok ? __double2float_rd(mine - (double)eps_r) : -INFINITY;
-    hi_r[i] = ok ? __double2float_ru(mine + (double)eps_r) : -INFINITY;
-  }
 }
 
 // One thread per video: c* = its own caption with the smallest finite (d_t, c), and the column direction's thresholds.  A video without a
@@ -2369,31 +2226,38 @@ __global__ __launch_bounds__(256) void rank_grouped_target_kernel(const int *__r
   hi_c[v] = ok ? __double2float_ru(best + (double)eps_c) : -INFINITY;
 }
 
-__global__ __launch_bounds__(256) void rank_grouped_write_kernel(const double *__restrict__ dt_r, const double *__restrict__ dt_c,
-                                                                 const int *__restrict__ cnt_r, const int *__restrict__ cnt_c, int n, int m,
-                                                                 int64_t *__restrict__ rank_a, int64_t *__restrict__ rank_b) {
+// ---- both forms: the finish, the workspace and the driver -----------------------------------------------------------------------------
+// A caption (row direction, m owners) without a finite target distance ranks behind all n videos, a video (column direction) behind all m captions.
+__global__ __launch_bounds__(256) void rank_write_kernel(const double *__restrict__ dt_r, const double *__restrict__ dt_c, const int *__restrict__ cnt_r,
+                                                         const int *__restrict__ cnt_c, int n, int m, int64_t *__restrict__ rank_a,
+                                                         int64_t *__restrict__ rank_b) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < m) rank_a[i] = dt_r[i] < (double)INFINITY ? (int64_t)cnt_r[i] : (int64_t)n;
   if (i < n) rank_b[i] = dt_c[i] < (double)INFINITY ? (int64_t)cnt_c[i] : (int64_t)m;
 }
 
-struct RankGroupedWs {
+// The workspace of both forms: a [n, d] (the columns of D), b [m, d] (its rows; paired: m = n).  A row of D has n_ld = n rounded up to 4
+// columns, so the GEMM writes and both passes read 16-byte aligned rows at every n (measured with ld = n at 2 990 x 20: 1.70 against
+// 1.44 ms, profiles/r11_grouped_rank.md); the column-side arrays have n_ld entries, the padding columns zero operands and hi = -inf.
+struct RankWs {
   unsigned long long *stats;       // [RS_STATS]
   float *qn, *gn, *qmax, *gmax;    // queries = b (m rows of D), gallery = a (n columns)
   bf16_t *qb, *gb;
   float *dist;
-  int rows_per_block;
-  int n_ld;                        // columns of a row of D: n rounded up to 4 (rows 16-byte aligned whatever n is; the column-side arrays have n_ld entries)
-  int *gid, *tgt_c;                // [m] g(c); [n_ld] c*
-  double *dt_r, *dt_c;             // [m], [n_ld]
+  int rows_per_block, n_ld;
+  int *gid, *tgt_c;                // table form only: [m] g(c); [n_ld] c*
+  double *dt_r, *dt_c;             // [m]; table form: [n_ld]; paired: dt_c = dt_r, the pair's distance -- n entries, none for the padding columns
   float *lo_r, *hi_r, *lo_c, *hi_c;
-  int *zero;                       // cnt_r, reach_r, ovf_r: [3][m], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_grouped_prep_kernel
+  int *zero;                       // cnt_r, reach_r, ovf_r: [3][m], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_prep_kernel
   int2 *pool_r, *pool_c;
   size_t cap_r, cap_c;
   size_t total;
 };
-RankGroupedWs rank_grouped_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity) {
-  RankGroupedWs s;
+// default pool: 512 pairs per owner and direction (8 bytes each).  Measured (profiles/r10_rank_sweep.md): an owner in the bulk of unrelated
+// unit vectors at d = 512 has 0.216 % of the other side in reach (108 pairs at 50k, at most 203), one whose target leads almost none.
+size_t rank_default_capacity(int n) { return std::max<size_t>(4096, (size_t)512 * n); }
+RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity, bool table) {
+  RankWs s;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
   s.stats = (unsigned long long *)take(RS_STATS * 8);
@@ -2405,19 +2269,12 @@ RankGroupedWs rank_grouped_plan(char *ws, int n, int m, int d, int rows_per_bloc
   s.gmax = (float *)take(4);
   s.qb = (bf16_t *)take((size_t)m * d * 3 * 2);
   s.gb = (bf16_t *)take((size_t)n_ld * d * 3 * 2);
-  int rpb = rows_per_block;
-  if (rpb <= 0) {                                          // as rank_plan(): as many rows as fit a 2 GiB block
-    rpb = (int)std::min<size_t>(((size_t)2 << 30) / ((size_t)n_ld * 4), (size_t)1 << 20);
-    rpb = rpb / 256 * 256;
-    if (rpb < 256) rpb = 256;
-  }
-  if (rpb > m) rpb = m;
-  s.rows_per_block = rpb;
-  s.dist = (float *)take((size_t)rpb * n_ld * 4);
-  s.gid = (int *)take((size_t)m * 4);
-  s.tgt_c = (int *)take((size_t)n_ld * 4);
+  s.rows_per_block = std::min(m, rows_per_block > 0 ? rows_per_block : default_rows_per_block(n_ld));
+  s.dist = (float *)take((size_t)s.rows_per_block * n_ld * 4);
+  s.gid = table ? (int *)take((size_t)m * 4) : nullptr;
+  s.tgt_c = table ? (int *)take((size_t)n_ld * 4) : nullptr;
   s.dt_r = (double *)take((size_t)m * 8);
-  s.dt_c = (double *)take((size_t)n_ld * 8);
+  s.dt_c = table ? (double *)take((size_t)n_ld * 8) : s.dt_r;
   s.lo_r = (float *)take((size_t)m * 4);
   s.hi_r = (float *)take((size_t)m * 4);
   s.lo_c = (float *)take((size_t)n_ld * 4);
@@ -2431,14 +2288,22 @@ RankGroupedWs rank_grouped_plan(char *ws, int n, int m, int d, int rows_per_bloc
   return s;
 }
 
-int rank_grouped_impl(const float *a, const float *b, const int *off, int n, int m, int d, int64_t *rank_a, int64_t *rank_b, int *nonfinite,
-                      const RankGroupedWs &s, hipStream_t stream) {
-  int *cnt_r = s.zero, *reach_r = s.zero + (size_t)m, *ovf_r = s.zero + 2 * (size_t)m;
+// Both entry points: Dir = RankDir (off == nullptr, m == n) or RankDirG.  The policy decides the prologue's target step and nothing after it.
+template <typename Dir>
+int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *off, int n, int m, int d, int64_t *rank_a, int64_t *rank_b,
+                    int *nonfinite, const RankWs &s, hipStream_t stream) {
+  constexpr bool table = rank_has_table<Dir>;
   const int n_ld = s.n_ld;
+  int *cnt_r = s.zero, *reach_r = s.zero + (size_t)m, *ovf_r = s.zero + 2 * (size_t)m;
   int *cnt_c = s.zero + 3 * (size_t)m, *reach_c = cnt_c + (size_t)n_ld, *ovf_c = cnt_c + 2 * (size_t)n_ld;
+  auto dir = [](const RankDir &p, const int *tgt) {
+    if constexpr (table) return RankDirG{p, tgt};
+    else return p;
+  };
   // gallery a, query b_c: the rows of D (m owners, n others);  gallery b, query a_v: its columns (n owners, m others)
-  const RankDirG R{{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r}, s.gid, s.dt_r, m, n};
-  const RankDirG Cd{{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c}, s.tgt_c, s.dt_c, n, m};
+  const RankDir r{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r, s.dt_r, m, n};
+  const RankDir c{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c, s.dt_c, n, m};
+  const Dir R = dir(r, s.gid), Cd = dir(c, s.tgt_c);
   (void)hipMemsetAsync(s.stats, 0, RS_STATS * 8, stream);
   (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
   if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)m * d, nonfinite, stream)) return rc;
@@ -2450,21 +2315,20 @@ int rank_grouped_impl(const float *a, const float *b, const int *off, int n, int
     ProfScope prof(VTC_PROF_TOPK, (double)(n + m) * d * (4 + 6 + 4), stream);
     prof.tag(101, m, d);
     const float kappa = rank_kappa(d);
-    hipLaunchKernelGGL(rank_group_id_kernel, dim3(cdiv(m, 256)), dim3(256), 0, stream, off, n, m, s.gid);
+    const RankThresholds tr{s.qn, s.gmax, s.dt_r, s.lo_r, s.hi_r}, tc{s.gn, s.qmax, s.dt_c, s.lo_c, s.hi_c};
+    if constexpr (table) hipLaunchKernelGGL(rank_group_id_kernel, dim3(cdiv(m, 256)), dim3(256), 0, stream, off, n, m, s.gid);
     hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(m, 4)), dim3(256), 0, stream, b, s.qn, m, d);
     hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, a, s.gn, n, d);
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)m * d + 255) / 256)), dim3(256), 0, stream, b, s.qb, m, d, 3, 0);
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, a, s.gb, n, d, 3, 1);
-    hipLaunchKernelGGL(rank_max_kernel, dim3(1), dim3(256), 0, stream, s.gn, s.gn, n, s.gmax, s.gmax);      // (one side per launch: the sides differ in size)
-    hipLaunchKernelGGL(rank_max_kernel, dim3(1), dim3(256), 0, stream, s.qn, s.qn, m, s.qmax, s.qmax);
-    hipLaunchKernelGGL(rank_grouped_prep_kernel, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, a, b, s.gid, m, d, s.qn, s.gmax, kappa, s.dt_r,
-                       s.lo_r, s.hi_r, s.zero, 3 * m + 3 * n_ld);
-    hipLaunchKernelGGL(rank_grouped_target_kernel, dim3(cdiv(n_ld, 256)), dim3(256), 0, stream, off, n, n_ld, m, s.dt_r, s.gn, s.qmax, kappa, s.dt_c, s.tgt_c,
-                       s.lo_c, s.hi_c);
+    hipLaunchKernelGGL(rank_max_kernel, dim3(2), dim3(256), 0, stream, s.gn, n, s.qn, m, s.gmax, s.qmax);
+    hipLaunchKernelGGL(rank_prep_kernel<Dir>, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, R, tr, tc, n_ld, d, kappa, s.zero, 3 * m + 3 * n_ld);
+    if constexpr (table)
+      hipLaunchKernelGGL(rank_grouped_target_kernel, dim3(cdiv(n_ld, 256)), dim3(256), 0, stream, off, n, n_ld, m, s.dt_r, s.gn, s.qmax, kappa, s.dt_c,
+                         s.tgt_c, s.lo_c, s.hi_c);
   }
-  VTC_LAUNCH_CHECK("l2_rank_grouped prologue");
-  // D is [rows, n_ld]: the GEMM writes, and both passes read, 16-byte aligned rows at every n.  The row pass scans the n real columns; the
-  // column pass takes all n_ld (a lane owns four adjacent columns; the padding columns have hi = -inf).
+  VTC_LAUNCH_CHECK2(fn, "prologue");
+  // D is [rows, n_ld].  The row pass scans the n real columns; the column pass takes all n_ld.
   const int n_strips = cdiv(n_ld, 64);
   for (int r0 = 0; r0 < m; r0 += s.rows_per_block) {
     const int rows = min(s.rows_per_block, m - r0);
@@ -2472,40 +2336,37 @@ int rank_grouped_impl(const float *a, const float *b, const int *off, int n, int
     e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
     if (int rc = launch_gemm(s.qb + (size_t)r0 * d * 3, s.gb, nullptr, s.dist, rows, n_ld, d * 3, VTC_BF16, e, stream)) return rc;
     {
-      int S = cdiv(8192, rows);                            // as rank_bidir_impl
-      S = S < 1 ? 1 : (S > MAX_SEG ? MAX_SEG : S);
-      const int seg_cols = cdiv(cdiv(n, S), 1024) * 1024;
-      S = cdiv(n, seg_cols);
+      const auto [S, seg_cols] = row_segments(rows, n);
       ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
       prof.tag(102, rows, n);
-      hipLaunchKernelGGL(rank_row_count_kernel<RankDirG>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n, r0, S, seg_cols, R);
+      hipLaunchKernelGGL(rank_row_count_kernel<Dir>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n, r0, S, seg_cols, R);
     }
     {
-      const int step = 8 * 4;
-      int S = std::max(1, cdiv(32 * vtcgemm::num_cus(), n_strips));
-      const int seg_rows = cdiv(cdiv(rows, S), step) * step;
-      S = cdiv(rows, seg_rows);
+      // (strip, segment) waves: ~32 per CU; a segment is a whole number of the wave's steps of 8 loads x 4 rows
+      const int seg_rows = cdiv(cdiv(rows, std::max(1, cdiv(32 * vtcgemm::num_cus(), n_strips))), 32) * 32;
+      const int S = cdiv(rows, seg_rows);
       ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
       prof.tag(103, rows, n);
-      hipLaunchKernelGGL((rank_col_count_kernel<4, RankDirG>), dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n_ld, r0, n_strips, S, seg_rows, Cd);
+      hipLaunchKernelGGL(rank_col_count_kernel<Dir>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n_ld, r0, n_strips, S, seg_rows, Cd);
     }
-    VTC_LAUNCH_CHECK("l2_rank_grouped count");
+    VTC_LAUNCH_CHECK2(fn, "count");
   }
   {
+    // eight pairs per wave and step; the pools' fill lives on the device, so the grid is sized for a full pool and strides
     const int ga = (int)std::min<size_t>(2048, (s.cap_r + 4 * RS_NB - 1) / (4 * RS_NB));
     const int gb = (int)std::min<size_t>(2048, (s.cap_c + 4 * RS_NB - 1) / (4 * RS_NB));
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     prof.tag(104, m, d);
-    hipLaunchKernelGGL(rank_settle_kernel<RankDirG>, dim3(ga + gb), dim3(256), 0, stream, R, Cd, ga, (const double *)nullptr, d);
+    hipLaunchKernelGGL(rank_settle_kernel<Dir>, dim3(ga + gb), dim3(256), 0, stream, R, Cd, ga, d);
   }
   {
     const int ga = std::min(m, 1024), gb = std::min(n, 1024);
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     prof.tag(105, m, d);
-    hipLaunchKernelGGL(rank_brute_kernel<RankDirG>, dim3(ga + gb), dim3(512), 0, stream, R, Cd, ga, (const double *)nullptr, 0, d, s.stats);
+    hipLaunchKernelGGL(rank_brute_kernel<Dir>, dim3(ga + gb), dim3(512), 0, stream, R, Cd, ga, d, s.stats);
   }
-  hipLaunchKernelGGL(rank_grouped_write_kernel, dim3(cdiv(std::max(n, m), 256)), dim3(256), 0, stream, s.dt_r, s.dt_c, cnt_r, cnt_c, n, m, rank_a, rank_b);
-  VTC_LAUNCH_CHECK("l2_rank_grouped finish");
+  hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(std::max(n, m), 256)), dim3(256), 0, stream, s.dt_r, s.dt_c, cnt_r, cnt_c, n, m, rank_a, rank_b);
+  VTC_LAUNCH_CHECK2(fn, "finish");
   return 0;
 }
 }  // namespace
@@ -2724,7 +2585,7 @@ extern "C" int vtc_l2_recall_bidir(const float *a, const float *b, int n, int d,
 extern "C" float vtc_l2_rank_kappa(int d) { return rank_kappa(d); }
 extern "C" size_t vtc_l2_rank_bidir_workspace_bytes(int n, int d, int rows_per_block, int reach_capacity) {
   if (n < 1 || d < 1) return 0;
-  return rank_plan(nullptr, n, d, rows_per_block, reach_capacity).total;
+  return rank_plan(nullptr, n, n, d, rows_per_block, reach_capacity, false).total;
 }
 extern "C" int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per_block, int reach_capacity, int64_t *rank_a,
                                  int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream) {
@@ -2732,14 +2593,14 @@ extern "C" int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, i
   VTC_CHECK(n >= 1, "l2_rank_bidir: n=%d must be >= 1", n);
   VTC_CHECK(d > 0 && d % 64 == 0, "l2_rank_bidir: d=%d must be a positive multiple of 64", d);
   VTC_CHECK(reach_capacity >= 0, "l2_rank_bidir: reach_capacity=%d must be >= 0 (0: the default)", reach_capacity);
-  const RankWs s = rank_plan((char *)ws, n, d, rows_per_block, reach_capacity);
+  const RankWs s = rank_plan((char *)ws, n, n, d, rows_per_block, reach_capacity, false);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return rank_bidir_impl(a, b, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+  return rank_sweep_impl<RankDir>("l2_rank_bidir", a, b, nullptr, n, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
 }
 
 extern "C" size_t vtc_l2_rank_grouped_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity) {
   if (n < 1 || m < 1 || d <= 0 || reach_capacity < 0) return 0;
-  return rank_grouped_plan(nullptr, n, m, d, rows_per_block, reach_capacity).total;
+  return rank_plan(nullptr, n, m, d, rows_per_block, reach_capacity, true).total;
 }
 extern "C" int vtc_l2_rank_grouped(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block, int reach_capacity,
                                    int64_t *rank_a, int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream) {
@@ -2748,9 +2609,9 @@ extern "C" int vtc_l2_rank_grouped(const float *a, const float *b, const int *of
   VTC_CHECK(m >= 1, "l2_rank_grouped: m=%d must be >= 1", m);
   VTC_CHECK(d > 0 && d % 64 == 0, "l2_rank_grouped: d=%d must be a positive multiple of 64", d);
   VTC_CHECK(reach_capacity >= 0, "l2_rank_grouped: reach_capacity=%d must be >= 0 (0: the default)", reach_capacity);
-  const RankGroupedWs s = rank_grouped_plan((char *)ws, n, m, d, rows_per_block, reach_capacity);
+  const RankWs s = rank_plan((char *)ws, n, m, d, rows_per_block, reach_capacity, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return rank_grouped_impl(a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+  return rank_sweep_impl<RankDirG>("l2_rank_grouped", a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
 }
 
 extern "C" int vtc_similarity(const float *v, const float *t, int nv, int nt, int d, const float *logit_scale, float *sim,

@@ -196,8 +196,11 @@ class RecallAtK(BaseMetric):
         if features_a.shape[0] != features_b.shape[0]:
             raise ValueError(f"RecallAtK.ranks expects paired rows ({features_a.shape[0]} vs {features_b.shape[0]})")
         a, b = self._padded(features_a, features_b)
-        rank_a, rank_b, bits = ops.rank_bidir(a, b, ws=self._workspace(
-            L.lib().vtc_l2_rank_bidir_workspace_bytes(a.shape[0], a.shape[1], 0, 0), a.device))
+        return self._finite_ranks(*ops.rank_bidir(a, b, ws=self._workspace(
+            L.lib().vtc_l2_rank_bidir_workspace_bytes(a.shape[0], a.shape[1], 0, 0), a.device)))
+
+    def _finite_ranks(self, rank_a, rank_b, bits):
+        """The ranks of a rank sweep, once its non-finite word says the inputs were clean."""
         if self.check_finite:                     # the word rides with the sweep: one 4-byte D2H, no launch of its own
             bad = int(bits.item())
             if bad:
@@ -216,13 +219,8 @@ class RecallAtK(BaseMetric):
                              f"{tuple(features_b.shape)}")
         off = ops.check_offsets(offsets, features_a.shape[0], features_b.shape[0], allow_empty=False)
         a, b = self._padded(features_a, features_b)
-        rank_a, rank_b, bits = ops.rank_grouped(a, b, off, ws=self._workspace(
-            L.lib().vtc_l2_rank_grouped_workspace_bytes(a.shape[0], b.shape[0], a.shape[1], 0, 0), a.device))
-        if self.check_finite:
-            bad = int(bits.item())
-            if bad:
-                raise self._nonfinite_error(bad)
-        return rank_a, rank_b
+        return self._finite_ranks(*ops.rank_grouped(a, b, off, ws=self._workspace(
+            L.lib().vtc_l2_rank_grouped_workspace_bytes(a.shape[0], b.shape[0], a.shape[1], 0, 0), a.device)))
 
     def rank_result(self):
         """result()'s analogue for the rank figures of the accumulated update() features: median_rank, mean_rank and mrr of both

@@ -367,6 +367,20 @@ def recall_bidir(a: torch.Tensor, b: torch.Tensor, k_vals: Sequence[int], ws: Op
     return hits
 
 
+def _rank_call(name, head, size_args, n_a, n_b, device, rows_per_block, reach_capacity, ws):
+    """What both rank entry points do around the C call ``name(*head, rows_per_block, reach_capacity, outputs, workspace, stream)``: size the
+    workspace (``name_workspace_bytes(*size_args, rows_per_block, reach_capacity)``), allocate rank_a [n_a], rank_b [n_b] and the non-finite
+    word, call, return the three."""
+    lib = L.lib()
+    ws = _ws_for(ws, getattr(lib, name + "_workspace_bytes")(*size_args, rows_per_block, reach_capacity), device)
+    rank_a = torch.empty(n_a, dtype=torch.int64, device=device)
+    rank_b = torch.empty(n_b, dtype=torch.int64, device=device)
+    bits = torch.empty(1, dtype=torch.int32, device=device)
+    L.check(getattr(lib, name)(*head, rows_per_block, reach_capacity, rank_a.data_ptr(), rank_b.data_ptr(), bits.data_ptr(), ws.data_ptr(),
+                               ws.numel(), _stream()), name)
+    return rank_a, rank_b, bits
+
+
 @on_device
 def rank_bidir(a: torch.Tensor, b: torch.Tensor, rows_per_block: int = 0, reach_capacity: int = 0, ws: Optional[torch.Tensor] = None):
     """Full 0-based ranks of both directions of n paired rows (vtc_l2_rank_bidir): (rank_a [n] int64 = the rank of a_i among the a's for
@@ -377,13 +391,7 @@ def rank_bidir(a: torch.Tensor, b: torch.Tensor, rows_per_block: int = 0, reach_
     n, d = a.shape
     if b.shape != (n, d):
         raise ValueError(f"rank_bidir: paired rows expected, got {tuple(a.shape)} and {tuple(b.shape)}")
-    ws = _ws_for(ws, L.lib().vtc_l2_rank_bidir_workspace_bytes(n, d, rows_per_block, reach_capacity), a.device)
-    rank_a = torch.empty(n, dtype=torch.int64, device=a.device)
-    rank_b = torch.empty(n, dtype=torch.int64, device=a.device)
-    bits = torch.empty(1, dtype=torch.int32, device=a.device)
-    L.check(L.lib().vtc_l2_rank_bidir(a.data_ptr(), b.data_ptr(), n, d, rows_per_block, reach_capacity, rank_a.data_ptr(), rank_b.data_ptr(),
-                                      bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_rank_bidir")
-    return rank_a, rank_b, bits
+    return _rank_call("vtc_l2_rank_bidir", (a.data_ptr(), b.data_ptr(), n, d), (n, d), n, n, a.device, rows_per_block, reach_capacity, ws)
 
 
 def check_offsets(offsets, n: int, m: int, allow_empty: bool = True):
@@ -428,14 +436,8 @@ def _rank_grouped(a, b, off, rows_per_block, reach_capacity, ws):
     a, b = _gpu(a, torch.float32, "a"), _gpu(b, torch.float32, "b")
     (n, d), m = a.shape, b.shape[0]
     off_dev = torch.from_numpy(off.astype("int32")).to(a.device)
-    ws = _ws_for(ws, L.lib().vtc_l2_rank_grouped_workspace_bytes(n, m, d, rows_per_block, reach_capacity), a.device)
-    rank_a = torch.empty(m, dtype=torch.int64, device=a.device)
-    rank_b = torch.empty(n, dtype=torch.int64, device=a.device)
-    bits = torch.empty(1, dtype=torch.int32, device=a.device)
-    L.check(L.lib().vtc_l2_rank_grouped(a.data_ptr(), b.data_ptr(), off_dev.data_ptr(), n, m, d, rows_per_block, reach_capacity,
-                                        rank_a.data_ptr(), rank_b.data_ptr(), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-            "vtc_l2_rank_grouped")
-    return rank_a, rank_b, bits
+    return _rank_call("vtc_l2_rank_grouped", (a.data_ptr(), b.data_ptr(), off_dev.data_ptr(), n, m, d), (n, m, d), m, n, a.device,
+                      rows_per_block, reach_capacity, ws)
 
 
 def rank_kappa(d: int) -> float:
