@@ -86,7 +86,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NT <= 4) ? 4 : 1) void attn
   // sequence is clamped to the last row and zeroed afterwards, not skipped -- a branch per load made hipcc wait for each load in
   // turn (`if (tok < L) raw = load` x 8: nine dependent global round trips per (sequence, head) with the K fragments behind them,
   // ~10 of the ~17 us an item took; profiles/r04_experiments.txt 19).
-  uint4 kf[NT][KS];
+  // The first query tile's fragments are requested with them: one trip to memory before the barrier, not a second one behind it.
+  const char *qbase = p.qkv + (size_t)(h * 64) * SZ;
+  auto load_q = [&](int qt, uint4 (&q)[KS]) {
+    const char *r = qbase + (size_t)row_of(min(qt * 16 + c16, L - 1)) * ld;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) q[ks] = *reinterpret_cast<const uint4 *>(r + (4 * ks + g) * 16);
+  };
+  uint4 kf[NT][KS], qf[KS], qn[KS];
   {
     const char *vbase = p.qkv + (size_t)(2 * p.W + h * 64) * SZ;
     const char *kbase = p.qkv + (size_t)(p.W + h * 64) * SZ;
@@ -109,6 +116,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NT <= 4) ? 4 : 1) void attn
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) kf[kt][ks] = *reinterpret_cast<const uint4 *>(r + (4 * ks + g) * 16);
         }
+        load_q(0, qf);
       }
 #pragma unroll
       for (int u = 0; u < VB; ++u) {
@@ -124,16 +132,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NT <= 4) ? 4 : 1) void attn
   }
   __syncthreads();  // Vt visible to every lane of the wave (waves do not share LDS regions)
 
-  const char *qbase = p.qkv + (size_t)(h * 64) * SZ;
-  // query fragments are fetched one tile ahead: the loads of tile qt + 1 are in flight while tile qt is multiplied,
+  // the later query fragments are fetched one tile ahead: the loads of tile qt + 1 are in flight while tile qt is multiplied,
   // soft-maxed and stored (the compiler cannot hoist them itself across the stores to p.out)
-  auto load_q = [&](int qt, uint4 (&q)[KS]) {
-    const char *r = qbase + (size_t)row_of(min(qt * 16 + c16, L - 1)) * ld;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) q[ks] = *reinterpret_cast<const uint4 *>(r + (4 * ks + g) * 16);
-  };
-  uint4 qf[KS], qn[KS];
-  load_q(0, qf);
   for (int qt = 0; qt < NT; ++qt) {
     if (qt * 16 >= L) break;
     const int qtok = qt * 16 + c16;
@@ -213,12 +213,35 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && NT <= 4) ? 4 : 1) void attn
     }
 
     // ---- store: lane holds O[query = qtok][d = 16 dt + 4 g .. +3] ---------------------------
+    // 16-bit formats: the lanes g and g ^ 1 (16 apart, same query) hold adjacent 8 bytes of a row.  One v_permlane16_swap per
+    // register pair (dt, dt + 1) leaves every lane with 16 contiguous bytes -- even g: its own and its partner's dt in {0, 2}, odd g:
+    // dt in {1, 3} -- so a query tile leaves as two 16-byte stores per lane instead of four 8-byte ones (same bytes, same addresses).
+    // (The swaps run with every lane on: outside the predicate.)
+    uint4 st[2];
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        unsigned w[2][2];
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          const f32x4 &ov = o[2 * j + d];
+          w[d][0] = (unsigned)cvt16<T>(ov[0] * inv) | ((unsigned)cvt16<T>(ov[1] * inv) << 16);
+          w[d][1] = (unsigned)cvt16<T>(ov[2] * inv) | ((unsigned)cvt16<T>(ov[3] * inv) << 16);
+        }
+        const auto a = permlane16_swap(w[0][0], w[1][0]), b = permlane16_swap(w[0][1], w[1][1]);
+        st[j] = make_uint4(a[0], b[0], a[1], b[1]);
+      }
+    }
     if (active && qtok < L) {
       if (p.cls_out && qtok == 0) {
         float *dst = p.cls_out + (size_t)s * p.W + h * 64 + g * 4;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
           *reinterpret_cast<float4 *>(dst + dt * 16) = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
+      } else if constexpr (sizeof(T) == 2) {
+        T *dst = reinterpret_cast<T *>(p.out) + (size_t)row_of(qtok) * p.W + h * 64 + (g & 2) * 4 + (g & 1) * 16;
+        *reinterpret_cast<uint4 *>(dst) = st[0];
+        *reinterpret_cast<uint4 *>(dst + 32) = st[1];
       } else {
         T *dst = reinterpret_cast<T *>(p.out) + (size_t)row_of(qtok) * p.W + h * 64 + g * 4;
 #pragma unroll

@@ -146,6 +146,21 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// v_permlane16_swap (gfx950): the odd 16-lane rows of `a` and the even rows of `b` change places -- r[0] = a with its odd rows <- b's
+// even row below, r[1] = b with its even rows <- a's odd row above.  Lanes 16 apart trade a register without an LDS round trip
+// (ds_bpermute, which __shfl_xor compiles to): the sweep's key merges (gemm.hip) and the attention cores' paired stores.
+__device__ __forceinline__ auto permlane16_swap(unsigned a, unsigned b) { return __builtin_amdgcn_permlane16_swap(a, b, false, false); }
+// the value the lane 16 / 32 away holds (lane ^ 16, lane ^ 32): a swap of a register with itself leaves the partner half's value in
+// one of the two results
+__device__ __forceinline__ unsigned xor32_of(unsigned x, bool upper) {
+  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);     // r[0]: lanes 32-63 <- x[0-31];  r[1]: lanes 0-31 <- x[32-63]
+  return upper ? r[0] : r[1];
+}
+__device__ __forceinline__ unsigned xor16_of(unsigned x, bool odd_row) {
+  const auto r = permlane16_swap(x, x);
+  return odd_row ? r[0] : r[1];
+}
+
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 

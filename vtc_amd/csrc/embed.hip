@@ -7,6 +7,7 @@
 //                   ids.argmax(-1)                                  (upstream CLIP.encode_text)
 //   cam_tokens / cam_finalize   Context Adapter Module glue         (model/model.py:150-151,157-159,203,208-212)
 #include "common.h"
+#include "ln_row.h"
 
 namespace {
 
@@ -162,6 +163,39 @@ __global__ __launch_bounds__(256) void text_embed_ragged_kernel(const TextIds id
     const float4 a = *reinterpret_cast<const float4 *>(tr + c), b = *reinterpret_cast<const float4 *>(pr + c);
     *reinterpret_cast<float4 *>(xr + c) = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
   }
+}
+
+// The same rows, entering the folded scheme directly (round 13): row = tok + pos is built in registers in the column layout of
+// ln_row.h and leaves as the centred (hi, lo) pair + rstd -- what cast_rowstats_kernel makes of the fp32 row, which is then never
+// written (nor read back): one pass over the rows instead of two.
+template <typename OutT>
+__global__ __launch_bounds__(256) void text_embed_ragged_pair_kernel(const TextIds ids, const float *__restrict__ tok,
+                                                                     const float *__restrict__ pos, const int *__restrict__ seq_offsets,
+                                                                     OutT *__restrict__ y, OutT *__restrict__ ylo, float2 *__restrict__ stat,
+                                                                     int n_seq, int ctx, int W, int vocab) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);          // dense (s, p) index
+  if (r >= n_seq * ctx) return;
+  const int s = r / ctx, p = r - s * ctx;
+  const int lo = seq_offsets[s], len = seq_offsets[s + 1] - lo;
+  if (p >= len) return;
+  long id = ids.row(s, ctx)[p];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const float *tr = tok + (size_t)id * W, *pr = pos + (size_t)p * W;
+  float4 v[LN_MAXV][2];
+#pragma unroll
+  for (int i = 0; i < LN_MAXV; ++i) {
+    const int c = (lane + 64 * i) * 8;
+    if (c < W) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float4 a = *reinterpret_cast<const float4 *>(tr + c + 4 * h), b = *reinterpret_cast<const float4 *>(pr + c + 4 * h);
+        v[i][h] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+      }
+    }
+  }
+  const size_t row = (size_t)(lo + p);
+  pair_row_store<OutT>(v, y + row * W, ylo + row * W, stat + row, W, lane);
 }
 
 __global__ __launch_bounds__(256) void last_row_kernel(const int *__restrict__ seq_offsets, int *__restrict__ rows, int n_seq) {
@@ -512,6 +546,23 @@ int launch_text_embed_ragged(const TextIds &ids, const float *tok, const float *
                      ctx, W, vocab);
   hipLaunchKernelGGL(last_row_kernel, dim3(cdiv(n_seq, 256)), dim3(256), 0, stream, seq_offsets, eot_row, n_seq);
   VTC_LAUNCH_CHECK("text_embed_ragged");
+  return 0;
+}
+
+// ... into the (hi, lo) pair + row statistics of operand format `dtype` instead of the fp32 stream (text_embed_ragged_pair_kernel)
+int launch_text_embed_ragged_pair(const TextIds &ids, const float *tok, const float *pos, const int *seq_offsets, void *y16, void *y16lo,
+                                  float *stat, int *eot_row, int n_seq, int ctx, int W, int vocab, int dtype, hipStream_t stream) {
+  VTC_CHECK(W % 8 == 0 && W <= 512 * LN_MAXV && (dtype == VTC_BF16 || dtype == VTC_F16), "text_embed (pair): width=%d dtype=%d", W, dtype);
+  ProfScope prof(VTC_PROF_EMBED, (double)n_seq * ctx * W * 6, stream);
+  const dim3 grid(cdiv(n_seq * ctx, 4));
+  if (dtype == VTC_F16)
+    hipLaunchKernelGGL((text_embed_ragged_pair_kernel<f16_t>), grid, dim3(256), 0, stream, ids, tok, pos, seq_offsets, (f16_t *)y16,
+                       (f16_t *)y16lo, (float2 *)stat, n_seq, ctx, W, vocab);
+  else
+    hipLaunchKernelGGL((text_embed_ragged_pair_kernel<bf16_t>), grid, dim3(256), 0, stream, ids, tok, pos, seq_offsets, (bf16_t *)y16,
+                       (bf16_t *)y16lo, (float2 *)stat, n_seq, ctx, W, vocab);
+  hipLaunchKernelGGL(last_row_kernel, dim3(cdiv(n_seq, 256)), dim3(256), 0, stream, seq_offsets, eot_row, n_seq);
+  VTC_LAUNCH_CHECK("text_embed_ragged_pair");
   return 0;
 }
 

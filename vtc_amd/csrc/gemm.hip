@@ -97,16 +97,6 @@ __device__ __forceinline__ unsigned key_bfi(unsigned mask, unsigned idx, unsigne
   asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(mask), "v"(idx), "v"(bits));
   return r;
 }
-// the value the lane 16 / 32 away holds (lane ^ 16, lane ^ 32): v_permlane16_swap / v_permlane32_swap of a register with itself leave
-// the partner half's value in one of the two results -- no LDS round trip (ds_bpermute) as __shfl_xor compiles to
-__device__ __forceinline__ unsigned xor32_of(unsigned x, bool upper) {
-  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);     // r[0]: lanes 32-63 <- x[0-31];  r[1]: lanes 0-31 <- x[32-63]
-  return upper ? r[0] : r[1];
-}
-__device__ __forceinline__ unsigned xor16_of(unsigned x, bool odd_row) {
-  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);     // r[0]: odd 16-lane rows <- the even row below;  r[1]: even rows <- the odd row above
-  return odd_row ? r[0] : r[1];
-}
 // The NPL smallest keys seen, sorted (NPL = 4: three keys + the fourth as a bound; NPL = 2, round 5: the smallest + the second as a bound --
 // half the vector instructions per value and half the plane bytes, for the recall-only sweep at small k, whose rank kernel sends a block
 // to fp64 whenever its bound is in reach of the target's distance).

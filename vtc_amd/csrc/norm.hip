@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void fold_stats_kernel(const float2 *__restric
   stat[r] = make_float2(mean, 1.0f / sqrtf(m2 / (64.0f * nb) + 1e-5f));
 }
 
-// Layer 0 has no residual GEMM in front of it: y16 = x in the operand format, stat = (mean, rstd) as LayerNorm computes them.
+// Layer 0 has no residual GEMM in front of it: y16 = x in the operand format, stat = (mean, rstd) as LayerNorm computes them
+// (ln_row.h pair_row_store: the ragged text tower's embedding enters the pair with the same arithmetic, embed.hip).
 template <typename OutT>
 __global__ __launch_bounds__(256) void cast_rowstats_kernel(const float *__restrict__ x, OutT *__restrict__ y, OutT *__restrict__ ylo,
                                                             float2 *__restrict__ stat, int rows, int width,
@@ -67,49 +68,15 @@ __global__ __launch_bounds__(256) void cast_rowstats_kernel(const float *__restr
   if (r >= rows) return;
   const float *xr = x + (size_t)r * width;
   float4 v[LN_MAXV][2];
-  float s = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = (lane + 64 * i) * 8;
     if (c < width) {
       v[i][0] = *reinterpret_cast<const float4 *>(xr + c);
       v[i][1] = *reinterpret_cast<const float4 *>(xr + c + 4);
-      s += ((v[i][0].x + v[i][0].y) + (v[i][0].z + v[i][0].w)) + ((v[i][1].x + v[i][1].y) + (v[i][1].z + v[i][1].w));
     }
   }
-  const float mean = wave_sum(s) / width;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXV; ++i) {
-    const int c = (lane + 64 * i) * 8;
-    if (c < width) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const float a = v[i][h].x - mean, b = v[i][h].y - mean, cc = v[i][h].z - mean, d = v[i][h].w - mean;
-        q += (a * a + b * b) + (cc * cc + d * d);
-      }
-      // the stream is stored CENTRED (x - mean): its only readers are LayerNorms (gemm.hip, SPLIT)
-      const float o[8] = {v[i][0].x - mean, v[i][0].y - mean, v[i][0].z - mean, v[i][0].w - mean,
-                          v[i][1].x - mean, v[i][1].y - mean, v[i][1].z - mean, v[i][1].w - mean};
-      uint4 pk;
-      pk.x = (unsigned)cvt16<OutT>(o[0]) | ((unsigned)cvt16<OutT>(o[1]) << 16);
-      pk.y = (unsigned)cvt16<OutT>(o[2]) | ((unsigned)cvt16<OutT>(o[3]) << 16);
-      pk.z = (unsigned)cvt16<OutT>(o[4]) | ((unsigned)cvt16<OutT>(o[5]) << 16);
-      pk.w = (unsigned)cvt16<OutT>(o[6]) | ((unsigned)cvt16<OutT>(o[7]) << 16);
-      *reinterpret_cast<uint4 *>(y + (size_t)r * width + c) = pk;
-      // lo = fmt(x - hi): the pair carries the row to 2^-17 (bf16) / 2^-22 (half) relative
-      const unsigned hw[4] = {pk.x, pk.y, pk.z, pk.w};
-      unsigned lw[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float l0 = o[2 * e] - up16<OutT>((unsigned short)(hw[e] & 0xFFFFu)), l1 = o[2 * e + 1] - up16<OutT>((unsigned short)(hw[e] >> 16));
-        lw[e] = (unsigned)cvt16<OutT>(l0) | ((unsigned)cvt16<OutT>(l1) << 16);
-      }
-      *reinterpret_cast<uint4 *>(ylo + (size_t)r * width + c) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / width + 1e-5f);
-  if (lane == 0) stat[r] = make_float2(0.0f, rstd);       // the mean of the stored (centred) row
+  pair_row_store<OutT>(v, y + (size_t)r * width, ylo + (size_t)r * width, stat + r, width, lane);
 }
 
 // ln_pre + the entry into the folded scheme in ONE pass over the rows (round 6): z = LayerNorm(x; gamma, beta) -- the arithmetic of

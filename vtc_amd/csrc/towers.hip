@@ -53,6 +53,7 @@ int launch_cls_mean(const float *cls_tmp, void *out, int dtype, int n_items, int
 int launch_text_prep(const TextIds &ids, int n_seq, int ctx, int *lens, int *offsets, int *m_dev, hipStream_t stream);
 int launch_text_embed(const TextIds &ids, const float *tok, const float *pos, float *x, int *eot_row, int n_seq, int ctx, int W, int vocab, hipStream_t stream);
 int launch_text_embed_ragged(const TextIds &ids, const float *tok, const float *pos, const int *seq_offsets, float *x, int *eot_row, int n_seq, int ctx, int W, int vocab, hipStream_t stream);
+int launch_text_embed_ragged_pair(const TextIds &ids, const float *tok, const float *pos, const int *seq_offsets, void *y16, void *y16lo, float *stat, int *eot_row, int n_seq, int ctx, int W, int vocab, int dtype, hipStream_t stream);
 int launch_attention_ragged(const void *qkv, void *out, int n_seq, int max_L, int heads, int causal, const int *seq_offsets, double flops, const int *rows_dev, int dtype, hipStream_t stream);
 int launch_attention_generic_small(const void *qkv, void *out, int n_seq, int L, int heads, int hd, int dtype, hipStream_t stream);
 int launch_cam_tokens(const float *main_f, const float *comm, const int64_t *comments, const float *mask_emb, const float *aux, float *X, int B, int nc, int na, int ctx, int D, hipStream_t stream);
@@ -522,12 +523,23 @@ int text_forward_impl(const vtc_text_w *w, const TextIds &ids, TextRows kind, co
     offs = t.offs;
     a.rows = Rows(rows_host, t.mdev);
   }
-  if (kind == TextRows::Dense) RUN(launch_text_embed(ids, w->tok_emb, w->pos, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
-  else RUN(launch_text_embed_ragged(ids, w->tok_emb, w->pos, offs, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
   fold_begin(a, w->blocks, w->layers, dtype, false, w->flags);
+  const LastBlock last = last_block_path(w->flags, w->layers, false);
+  const bool ragged = kind != TextRows::Dense;
+  const int dl0 = (dtype == VTC_BF16 && w->half_layers > 0) ? VTC_F16 : dtype;      // the first block's operand format (see `dl` below)
+  if (!ragged) {
+    RUN(launch_text_embed(ids, w->tok_emb, w->pos, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
+  } else if (a.fold.on && (w->layers > 1 || (w->layers == 1 && last == LastBlock::AllRows))) {
+    // the embedding enters the (hi, lo) stream of the first block's format in one pass (the text twin of the video tower's
+    // launch_ln_cast_rowstats): the fp32 x is stale from the start, as it is behind layer 0 anyway -- its first reader is the
+    // fold_merge_rows in front of the last block's query / ln_final
+    RUN(launch_text_embed_ragged_pair(ids, w->tok_emb, w->pos, offs, a.fold.xb, a.fold.xl, a.fold.stat, t.eot, n_seq, w->ctx, W, w->vocab, dl0, s));
+    a.fold.fmt = dl0;
+  } else {
+    RUN(launch_text_embed_ragged(ids, w->tok_emb, w->pos, offs, a.x, t.eot, n_seq, w->ctx, W, w->vocab, s));
+  }
   // attention work of the ragged batch for the profiler (the lengths are not known here): rows x (mean length ~ ctx / 2)
   const double attn_flops_per_row = 4.0 * (0.5 * w->ctx) * 64 * w->heads;
-  const LastBlock last = last_block_path(w->flags, w->layers, false);
   for (int l = 0; l < w->layers; ++l) {
     const vtc_block_w &b = w->blocks[l];
     const int dl = (dtype == VTC_BF16 && l < w->half_layers) ? VTC_F16 : dtype;      // bf16 mode: the first half_layers blocks on IEEE half
