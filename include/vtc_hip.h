@@ -339,7 +339,7 @@ int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per
  *               c* = the own caption (off[v] <= c < off[v + 1], D finite) with the smallest (D(c, v), c)
  * rank_b is the CAPTION-LEVEL convention of the image-text literature: the best rank any own caption reaches in the list of all m
  * captions.  No own caption can precede c*, so rank_b[v] counts captions of other videos.  (The video-unit convention -- the number of
- * other videos that have a closer caption -- needs a segmented minimum over the matrix and is not built.)
+ * other videos that have a closer caption -- is vtc_l2_rank_grouped_vunit, below.)
  * An entry with a non-finite distance is never closer; a caption whose own distance is not finite gets rank_a = n and is no candidate
  * for c*; a video without a finite own caption (an empty group too) gets rank_b = m; nonfinite[0] as above.  With m = n and
  * off = 0, 1, ..., n both outputs are those of the paired entry point, element for element.
@@ -350,6 +350,28 @@ int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per
 size_t vtc_l2_rank_grouped_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity);
 int vtc_l2_rank_grouped(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block, int reach_capacity,
                         int64_t *rank_a /* [m] */, int64_t *rank_b /* [n] */, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* The same sweep with a third output, video -> text in the VIDEO-UNIT convention of the video-retrieval literature (multi-sentence
+ * evaluation): the [caption, video] distances are first reduced to one best caption per (video, video) pair, then the video's own group
+ * is ranked among the n groups.  With the notation above:
+ *   E(u, v)   = min { D(c, v) : off[u] <= c < off[u + 1], D(c, v) finite }      (+inf if there is none)
+ *   rank_v[v] = #{ u in [0, n), u != v : (E(u, v), u) < (E(v, v), v) }           if E(v, v) is finite
+ *             = n                                                                otherwise (no finite own caption, an empty group too)
+ * E(v, v) = D(c*, v), the target distance of rank_b.  A group without a finite distance to v (an empty group, a NaN video row, all of its
+ * captions NaN) is never closer; an exact tie goes to the lower VIDEO index.  rank_v[v] <= rank_b[v], rank_v[v] == 0 exactly when
+ * rank_b[v] == 0, and with m = n, off = 0, 1, ..., n rank_v is rank_b of the paired entry point, element for element.
+ * rank_a and rank_b are those of vtc_l2_rank_grouped on the same inputs, element for element: one sweep, three outputs, all required.
+ * A third pass over each distance block takes the smallest key of every (group, video) -- groups that lie across row blocks are joined
+ * through a per-column carry before they are classified --, counts the groups below the video's lo, and puts those in reach of its
+ * target into a pool of (video, group) pairs of the column direction's capacity, settled in fp64 over the group's captions; a video whose
+ * pairs did not fit is counted again by fp64 brute force over all m captions, group by group: the ranks do not depend on the capacity.
+ * Beyond the distance block nothing of size m x n or n x n is resident: the direction adds O(n) words and its pool to the workspace.
+ * Whatever off holds, nothing is read or written out of bounds; results are defined for valid offsets only.
+ * The first eight statistics words of the workspace keep their meaning; words 8, 9, 10 hold the video-unit direction's: (video, group)
+ * pairs in reach, the largest number of them for one video, videos counted by brute force; then five unused words. */
+size_t vtc_l2_rank_grouped_vunit_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity);
+int vtc_l2_rank_grouped_vunit(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block, int reach_capacity,
+                              int64_t *rank_a /* [m] */, int64_t *rank_b /* [n] */, int64_t *rank_v /* [n] */, int *nonfinite, void *ws,
+                              size_t ws_bytes, void *stream);
 /* The sharded sweep (above) with the recall-only finish: rank r holds rows [row_base, row_base + n_local) of both sets and the gathered
  * sets, runs ONE [n_local, n_total] distance GEMM and adds its PARTIAL counters (the host all-reduces them: model/metric.py:148-160 counted
  * over this rank's queries):

@@ -10,7 +10,11 @@ line per comparison: both times (HIP events around each call, median / min / max
 target per owner and the owners that went to the fp64 brute force per direction (a = the captions' row direction, b = the videos' column
 direction), and the per-kernel split of one sweep of each from the library's own launch records (tags 101 .. 105 = prologue, row count,
 column count, settle, brute force).  Data: the generator of tests/grouped_rank_refs.py (a per-video noise scale, log-uniform in
-[0.5, 60], times a per-caption jitter), drawn on the GPU.  profiles/r11_grouped_rank.md holds a run's output."""
+[0.5, 60], times a per-caption jitter), drawn on the GPU.  profiles/r11_grouped_rank.md holds a run's output.
+On the two multi-caption shapes a second line each: ops.rank_grouped_vunit (the same sweep with the video-unit direction, a third pass
+over every block) alternating with ops.rank_grouped on the SAME tensors -- both times and their ratio, the (video, group) pairs in reach
+per video and the videos counted by brute force, and the new pass under tags of its own (106 = vunit_count, 107 = vunit_finish: settle,
+brute force and write).  profiles/r13_vunit_rank.md holds a run's output."""
 import argparse
 import json
 import os
@@ -74,6 +78,37 @@ def compare(name, grouped, paired, args, extra):
     return line
 
 
+def compare_vunit(name, a, b, off, args, extra):
+    """ops.rank_grouped_vunit against ops.rank_grouped on the same tensors, alternating."""
+    lib = L.lib()
+    n, m = a.shape[0], b.shape[0]
+    wv = ops.workspace(lib.vtc_l2_rank_grouped_vunit_workspace_bytes(n, m, args.d, 0, 0), a.device)
+    wg = ops.workspace(lib.vtc_l2_rank_grouped_workspace_bytes(n, m, args.d, 0, 0), a.device)
+    fv = lambda: ops.rank_grouped_vunit(a, b, off, ws=wv)                                                          # noqa: E731
+    fg = lambda: ops.rank_grouped(a, b, off, ws=wg)                                                                # noqa: E731
+    for _ in range(args.warmup):
+        fv()
+        fg()
+    tv, tg = [], []
+    for _ in range(args.iters):
+        tv.append(timed(fv))
+        tg.append(timed(fg))
+    ra, rb, rv, bits = fv()
+    ga, gb, _ = fg()
+    st = ops.rank_sweep_stats(wv)
+    line = dict(extra, case=name + "_vunit", d=args.d, iters=args.iters, rank_grouped_vunit_ms=ms(tv), rank_grouped_ms=ms(tg),
+                ratio=round(float(np.median(tv)) / float(np.median(tg)), 3), grouped_spread_max_over_min=round(max(tg) / min(tg), 3),
+                rank_a_b_equal_to_rank_grouped=bool(torch.equal(ra, ga) and torch.equal(rb, gb)),
+                rank_v_le_rank_b=bool((rv <= rb).all()), videos_where_conventions_differ=int((rv != rb).sum()),
+                vunit={"in_reach_per_video_mean": round(st["vunit_in_reach"] / n, 2), "in_reach_per_video_max": st["vunit_in_reach_max"],
+                       "brute_force_videos": st["vunit_brute_force_owners"], "kernel_split_ms": kernel_split(fv)},
+                grouped_kernel_split_ms=kernel_split(fg), nonfinite_bits=int(bits.item()),
+                **{"R@1": [round(float((rb < 1).float().mean()), 4), round(float((rv < 1).float().mean()), 4)],
+                   "median_rank_1based_caption_vs_video": [float(rb.median()) + 1, float(rv.median()) + 1]})
+    print(json.dumps(line), flush=True)
+    return line
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--d", type=int, default=512)
@@ -97,7 +132,9 @@ def main(argv=None):
         lines.append(compare(name, (lambda: ops.rank_grouped(a, b, off, ws=wg), wg, (m, n)),
                              (lambda: ops.rank_bidir(pa, pb, ws=wp), wp, (sq, sq)), args,
                              {"n": n, "m": m, "captions_per_video": [int(counts.min()), int(counts.max())], "paired_n": sq}))
-        del wg, wp, a, b, pa, pb
+        del wg, wp, pa, pb
+        lines.append(compare_vunit(name, a, b, off, args, {"n": n, "m": m, "captions_per_video": [int(counts.min()), int(counts.max())]}))
+        del a, b
         torch.cuda.empty_cache()
     if args.identity:
         n = args.identity

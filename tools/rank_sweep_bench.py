@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 from vtc_amd import _lib as L  # noqa: E402
 from vtc_amd import ops  # noqa: E402
 
-STAGES = {101: "prologue", 102: "row_count", 103: "col_count", 104: "settle", 105: "brute_force"}
+STAGES = {101: "prologue", 102: "row_count", 103: "col_count", 104: "settle", 105: "brute_force", 106: "vunit_count", 107: "vunit_finish"}
 
 
 def unit(x):

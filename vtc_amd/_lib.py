@@ -110,6 +110,8 @@ SIGNATURES = {
     "vtc_l2_rank_bidir": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, vp, C.c_size_t, vp]),
     "vtc_l2_rank_grouped_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtc_l2_rank_grouped": (C.c_int, [fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, vp, C.c_size_t, vp]),
+    "vtc_l2_rank_grouped_vunit_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_rank_grouped_vunit": (C.c_int, [fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, vp, C.c_size_t, vp]),
     "vtc_l2_recall_shard_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "vtc_l2_recall_planes": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int]),
     "vtc_l2_recall_shard_rows": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, ip, vp, C.c_int, vp, C.c_size_t, vp]),

@@ -5,6 +5,7 @@
 //   vtc_l2_rank_bidir  the exact rank of EVERY pair's target in both directions (median / mean rank, MRR, recall at any k): a counting
 //                   sweep over the BF16X3 distance blocks, fp64 for the entries within the error bound of a target (end of this file)
 //   vtc_l2_rank_grouped  the same for videos with several captions each: the sweep made rectangular, the target taken from a table
+//   vtc_l2_rank_grouped_vunit  that sweep with a third direction: video -> text counted in VIDEOS (groups of captions), not captions
 //   vtc_similarity  exp(logit_scale) * V @ T^T (model/model.py:369,478,504,621)
 //   vtc_clip_loss   0.5 (CE(sim, arange) + CE(sim^T, arange)) (model/loss.py:18-22)
 //
@@ -1785,6 +1786,7 @@ int recall_bidir_impl(const float *a, const float *b, int n, int d, const KList 
 // An owner whose pairs did not fit the pool is flagged and counted again by fp64 brute force over the whole other side
 // (rank_brute_kernel), so the ranks do not depend on the pool's capacity.  A pair whose target distance is not finite gets rank n.
 constexpr int RS_STATS = 8;           // 64-bit words at the head of the workspace (include/vtc_hip.h, vtc_l2_rank_bidir)
+constexpr int RS_STATS_V = 8;         // behind them, the video-unit direction's (vtc_l2_rank_grouped_vunit): three figures, five unused words
 constexpr int RS_NB = 8;              // fp64 distances a wave forms at once
 float rank_kappa(int d) { return 3.0f / 65536.0f + 4.0f * d / 16777216.0f + 1e-6f; }      // = exact_finish_lists' kappa
 
@@ -2184,6 +2186,7 @@ __global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir
 //   column direction  owner = video v, target = c* = its own caption with the smallest (D(c, v), c),  -> rank_b [n]
 //                     so d_t[v] is the segmented lexicographic minimum of the row direction's d_t over the video's captions
 // (include/vtc_hip.h has the definition).  The two kernels below are its own; everything else is the sweep above instantiated with RankDirG.
+// Behind them: the video-unit direction (owner = video, other = GROUP of captions), a third pass with kernels of its own.
 
 // g(c) of every caption: the last v with off[v] <= c (an empty group is never the answer: its successor starts at the same caption).
 // Whatever `off` holds, the result lies in [0, n).
@@ -2226,6 +2229,183 @@ __global__ __launch_bounds__(256) void rank_grouped_target_kernel(const int *__r
   hi_c[v] = ok ? __double2float_ru(best + (double)eps_c) : -INFINITY;
 }
 
+// ---- video-unit direction of the grouped sweep (vtc_l2_rank_grouped_vunit) --------------------------------------------------------------
+// owner = video v (a column of D), other = GROUP u (the rows off[u] .. off[u + 1]): E(u, v) = the smallest finite D(c, v) of the group, and
+// rank_v[v] = #{ u != v : (E(u, v), u) < (d_t[v], v) } with d_t the column direction's (E(v, v) = D(c*, v)).  A third pass over the same
+// distance block classifies every (group, column) ONCE, from the group's smallest key and a "saw a NaN" bit:
+//   min key < lo[v]                        closer for certain: the group is counted
+//   else some key <= hi[v], or a NaN       in reach: (v, u) goes to the direction's pool, fp64 over the group's captions decides
+// A lane owns (one group, four adjacent columns) and walks the group's rows itself -- the four row sub-lanes of the column pass take four
+// neighbouring GROUPS here, so a load instruction of the wave is still four 256-byte row pieces and nothing is folded across lanes before a
+// group is classified.  A wave takes a strip of 64 columns and a range of the groups that meet the block.  The one group that is open at the
+// block's end leaves its (min key, NaN bit) per column in a carry [n_ld]; the block that sees its end picks them up.  Two carries, taken
+// in turn by block parity: the group a block closes and the one it leaves open are different lanes of one launch.
+template <int U>
+__global__ __launch_bounds__(256) void rank_vunit_count_kernel(const float *__restrict__ dist, int ld, int n_rows, int n_cols, int row_id0, int m,
+                                                               int n_strips, int S, const int *__restrict__ off, const int *__restrict__ gid,
+                                                               float *__restrict__ carry_key, int *__restrict__ carry_nan, int par,
+                                                               const RankDir P) {
+  constexpr int V = 4;                                    // columns per lane = groups per load instruction of the wave
+  __shared__ int2 stage_all[4][RS_STAGE];
+  int2 *stage = stage_all[threadIdx.x >> 6];              // wave-private
+  int n_st = 0;
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= n_strips * S) return;
+  const int seg = w / n_strips, strip = w - seg * n_strips;
+  // the groups that meet the block (gid lies in [0, n) whatever `off` holds), four per step, the steps dealt to the S waves of a strip
+  const int gA = gid[row_id0], gB = max(gA, gid[row_id0 + n_rows - 1]);
+  const int quads = (gB - gA + V) / V;
+  const int qw = (quads + S - 1) / S;
+  const int q_lo = seg * qw, q_hi = min(quads, q_lo + qw);
+  if (q_lo >= q_hi) return;                               // wave-uniform
+  const int c_strip = strip * 64 + 4 * (lane & 15);
+  const bool live = c_strip < n_cols;                     // (n_cols % 4 == 0: the lane's four columns are in or out together)
+  const int c = live ? c_strip : 0;                       // a lane past the matrix reads column 0, counts nothing and stores nothing
+  const int sub = lane >> 4;
+  const int r_end = row_id0 + n_rows;
+  float lo[V], hi[V];
+  int cnt[V], reach[V];
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    lo[e] = live ? P.lo[c + e] : -INFINITY;
+    hi[e] = live ? P.hi[c + e] : -INFINITY;                // -inf: a padding column, or a video without a finite target
+    cnt[e] = 0; reach[e] = 0;
+  }
+  for (int q = q_lo; q < q_hi; ++q) {
+    const int u = gA + V * q + sub;                       // the lane's group
+    const bool have = u <= gB;                            // (gB <= n - 1: off[u + 1] is an entry of off)
+    const int g0 = have ? min(max(off[u], 0), m) : 0, g1 = have ? min(max(off[u + 1], 0), m) : 0;
+    const int ra = max(g0, row_id0), rb = min(g1, r_end); // its rows in this block: inside [row_id0, r_end) whatever `off` holds
+    float mn[V];
+    unsigned nanm = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) mn[e] = INFINITY;
+    for (int r = ra; r < rb; r += U) {
+      float4 t[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k)                         // past the group's end its last row again: a minimum does not mind
+        t[k] = *reinterpret_cast<const float4 *>(dist + (size_t)(min(r + k, rb - 1) - row_id0) * ld + c);
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const float x[V] = {t[k].x, t[k].y, t[k].z, t[k].w};
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          mn[e] = x[e] < mn[e] ? x[e] : mn[e];            // a NaN never enters
+          nanm |= x[e] != x[e] ? (1u << e) : 0u;
+        }
+      }
+    }
+    unsigned mk = 0;
+    if (ra < rb && live) {
+      if (g0 < row_id0) {                                 // begun in an earlier block
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const float ck = carry_key[(size_t)(par ^ 1) * ld + c + e];
+          mn[e] = ck < mn[e] ? ck : mn[e];
+          nanm |= carry_nan[(size_t)(par ^ 1) * ld + c + e] ? (1u << e) : 0u;
+        }
+      }
+      if (g1 > r_end) {                                   // open at the block's end: the next block classifies it
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          carry_key[(size_t)par * ld + c + e] = mn[e];
+          carry_nan[(size_t)par * ld + c + e] = (int)((nanm >> e) & 1u);
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const bool ok = hi[e] != -INFINITY && u != c + e;      // the own group is skipped
+          const bool lt = mn[e] < lo[e];
+          cnt[e] += (ok && lt) ? 1 : 0;
+          const bool in = ok && !lt && (!(mn[e] > hi[e]) || ((nanm >> e) & 1u));
+          reach[e] += in ? 1 : 0;
+          mk |= in ? (1u << e) : 0u;
+        }
+      }
+    }
+    if (__ballot(mk != 0) != 0ull)                         // wave-uniform, rare
+      rank_stage_append<V>(P, stage, n_st, mk, lane, [&](int e) { return c + e; }, [&](int) { return u; });
+  }
+  rank_stage_flush(P, stage, n_st, lane);
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    cnt[e] += __shfl_xor(cnt[e], 16, 64); cnt[e] += __shfl_xor(cnt[e], 32, 64);
+    reach[e] += __shfl_xor(reach[e], 16, 64); reach[e] += __shfl_xor(reach[e], 32, 64);
+    if (live && sub == 0) {
+      if (cnt[e]) atomicAdd(&P.cnt[c + e], cnt[e]);
+      if (reach[e]) atomicAdd(&P.reach[c + e], reach[e]);
+    }
+  }
+}
+
+// Is group u closer to video v than v's target?  fp64 over the group's captions, eight at a time, by the sweep's one distance function:
+// some finite D(c, v) with (D, u) < (d_t, v).  Wave-uniform arguments and result.
+__device__ __forceinline__ bool rank_vunit_closer(const RankDir &P, const int *__restrict__ off, int v, int u, double t, int d, int lane) {
+  const int m = P.n_other;
+  const int c0 = min(max(off[u], 0), m), c1 = min(max(off[u + 1], 0), m);
+  bool closer = false;
+  for (int j0 = c0; j0 < c1 && !closer; j0 += RS_NB) {
+    int qi[RS_NB], gi[RS_NB];
+#pragma unroll
+    for (int k = 0; k < RS_NB; ++k) { qi[k] = v; gi[k] = min(j0 + k, c1 - 1); }       // past the end the last caption again
+    double dd[RS_NB];
+    wave_dist64_pairs(P.own, P.other, qi, gi, d, lane, dd);
+#pragma unroll
+    for (int k = 0; k < RS_NB; ++k) closer = closer || dd[k] < t || (dd[k] == t && u < v);      // NaN and inf: neither
+  }
+  return closer;
+}
+
+// The pooled (video, group) pairs, one per wave and step.
+__global__ __launch_bounds__(256) void rank_vunit_settle_kernel(const RankDir P, const int *__restrict__ off, int d) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long offered = *P.pool_n;
+  const long long n_e = (long long)(offered < P.cap ? offered : P.cap);
+  for (long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); e < n_e; e += (long long)gridDim.x * 4) {
+    const int2 pr = P.pool[e];
+    const int v = __builtin_amdgcn_readfirstlane(pr.x), u = __builtin_amdgcn_readfirstlane(pr.y);
+    if (rank_vunit_closer(P, off, v, u, P.dt[v], d, lane) && lane == 0) atomicAdd(&P.cnt[v], 1);
+  }
+}
+
+// Flagged videos (their pairs overflowed the pool): the count again, by fp64 brute force over all captions, group by group; one workgroup
+// of eight waves per video.  Also the direction's statistics (stats[1]: the largest in-reach count of a video, stats[2]: videos sent here).
+__global__ __launch_bounds__(512) void rank_vunit_brute_kernel(const RankDir P, const int *__restrict__ off, int d,
+                                                               unsigned long long *__restrict__ stats) {
+  __shared__ int part[8];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int n = P.n_own;
+  int mx = 0;
+  for (int o = blockIdx.x; o < n; o += gridDim.x) {        // uniform for the workgroup
+    mx = max(mx, P.reach[o]);
+    if (!P.ovf[o]) continue;
+    const double t = P.dt[o];
+    int cnt = 0;
+    for (int u = w; u < n; u += 8) {
+      if (u != o && rank_vunit_closer(P, off, o, u, t, d, lane)) ++cnt;
+    }
+    if (lane == 0) part[w] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int total = 0;
+#pragma unroll
+      for (int ww = 0; ww < 8; ++ww) total += part[ww];
+      P.cnt[o] = total;
+      atomicAdd(&stats[2], 1ull);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && mx) atomicMax(&stats[1], (unsigned long long)mx);
+}
+
+// A video without a finite target ranks behind all n groups.
+__global__ __launch_bounds__(256) void rank_vunit_write_kernel(const double *__restrict__ dt_c, const int *__restrict__ cnt_v, int n,
+                                                               int64_t *__restrict__ rank_v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) rank_v[i] = dt_c[i] < (double)INFINITY ? (int64_t)cnt_v[i] : (int64_t)n;
+}
+
 // ---- both forms: the finish, the workspace and the driver -----------------------------------------------------------------------------
 // A caption (row direction, m owners) without a finite target distance ranks behind all n videos, a video (column direction) behind all m captions.
 __global__ __launch_bounds__(256) void rank_write_kernel(const double *__restrict__ dt_r, const double *__restrict__ dt_c, const int *__restrict__ cnt_r,
@@ -2251,16 +2431,22 @@ struct RankWs {
   int *zero;                       // cnt_r, reach_r, ovf_r: [3][m], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_prep_kernel
   int2 *pool_r, *pool_c;
   size_t cap_r, cap_c;
+  // video-unit direction only (vtc_l2_rank_grouped_vunit): O(n) words and its pool
+  int *zero_v;                     // cnt_v, reach_v, ovf_v: [3][n_ld], behind `zero` and zeroed with it
+  float *carry_key;                // [2][n_ld] smallest key of the group that is open at a block's end, by block parity
+  int *carry_nan;                  // [2][n_ld] its NaN bit
+  int2 *pool_v;
+  size_t cap_v;
   size_t total;
 };
 // default pool: 512 pairs per owner and direction (8 bytes each).  Measured (profiles/r10_rank_sweep.md): an owner in the bulk of unrelated
 // unit vectors at d = 512 has 0.216 % of the other side in reach (108 pairs at 50k, at most 203), one whose target leads almost none.
 size_t rank_default_capacity(int n) { return std::max<size_t>(4096, (size_t)512 * n); }
-RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity, bool table) {
+RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity, bool table, bool vunit = false) {
   RankWs s;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return ws ? ws + o : (char *)nullptr; };
-  s.stats = (unsigned long long *)take(RS_STATS * 8);
+  s.stats = (unsigned long long *)take((RS_STATS + RS_STATS_V) * 8);      // (one 256-byte unit with or without the second eight)
   const int n_ld = (n + 3) & ~3;
   s.n_ld = n_ld;
   s.qn = (float *)take((size_t)m * 4);
@@ -2279,19 +2465,25 @@ RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_ca
   s.hi_r = (float *)take((size_t)m * 4);
   s.lo_c = (float *)take((size_t)n_ld * 4);
   s.hi_c = (float *)take((size_t)n_ld * 4);
-  s.zero = (int *)take(((size_t)3 * m + (size_t)3 * n_ld) * 4);
+  s.zero = (int *)take(((size_t)3 * m + (size_t)(vunit ? 6 : 3) * n_ld) * 4);
+  s.zero_v = vunit ? s.zero + 3 * (size_t)m + 3 * (size_t)n_ld : nullptr;
   s.cap_r = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(m);      // per direction: 512 pairs per OWNER
   s.cap_c = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(n);
   s.pool_r = (int2 *)take(s.cap_r * 8);
   s.pool_c = (int2 *)take(s.cap_c * 8);
+  s.cap_v = s.cap_c;
+  s.carry_key = vunit ? (float *)take((size_t)2 * n_ld * 4) : nullptr;
+  s.carry_nan = vunit ? (int *)take((size_t)2 * n_ld * 4) : nullptr;
+  s.pool_v = vunit ? (int2 *)take(s.cap_v * 8) : nullptr;
   s.total = off;
   return s;
 }
 
-// Both entry points: Dir = RankDir (off == nullptr, m == n) or RankDirG.  The policy decides the prologue's target step and nothing after it.
+// All entry points: Dir = RankDir (off == nullptr, m == n) or RankDirG.  The policy decides the prologue's target step and nothing after it.
+// rank_v != nullptr (RankDirG, a plan with the video-unit arrays): the video-unit direction rides along, a third pass over every block.
 template <typename Dir>
 int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *off, int n, int m, int d, int64_t *rank_a, int64_t *rank_b,
-                    int *nonfinite, const RankWs &s, hipStream_t stream) {
+                    int *nonfinite, const RankWs &s, hipStream_t stream, int64_t *rank_v = nullptr) {
   constexpr bool table = rank_has_table<Dir>;
   const int n_ld = s.n_ld;
   int *cnt_r = s.zero, *reach_r = s.zero + (size_t)m, *ovf_r = s.zero + 2 * (size_t)m;
@@ -2304,7 +2496,10 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
   const RankDir r{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r, s.dt_r, m, n};
   const RankDir c{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c, s.dt_c, n, m};
   const Dir R = dir(r, s.gid), Cd = dir(c, s.tgt_c);
-  (void)hipMemsetAsync(s.stats, 0, RS_STATS * 8, stream);
+  // owner = video v, other = GROUP u: the column direction's thresholds and target distance, counters and a pool of its own
+  int *cnt_v = s.zero_v, *reach_v = rank_v ? cnt_v + (size_t)n_ld : nullptr, *ovf_v = rank_v ? cnt_v + 2 * (size_t)n_ld : nullptr;
+  const RankDir vu{a, b, s.lo_c, s.hi_c, cnt_v, reach_v, ovf_v, s.pool_v, s.stats + RS_STATS, (unsigned long long)s.cap_v, s.dt_c, n, m};
+  (void)hipMemsetAsync(s.stats, 0, (RS_STATS + (rank_v ? RS_STATS_V : 0)) * 8, stream);
   (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
   if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)m * d, nonfinite, stream)) return rc;
   if (n_ld != n) {                                         // the padding columns' operands: zero rows, zero norms (their entries are never counted)
@@ -2322,7 +2517,7 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)m * d + 255) / 256)), dim3(256), 0, stream, b, s.qb, m, d, 3, 0);
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)n * d + 255) / 256)), dim3(256), 0, stream, a, s.gb, n, d, 3, 1);
     hipLaunchKernelGGL(rank_max_kernel, dim3(2), dim3(256), 0, stream, s.gn, n, s.qn, m, s.gmax, s.qmax);
-    hipLaunchKernelGGL(rank_prep_kernel<Dir>, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, R, tr, tc, n_ld, d, kappa, s.zero, 3 * m + 3 * n_ld);
+    hipLaunchKernelGGL(rank_prep_kernel<Dir>, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, R, tr, tc, n_ld, d, kappa, s.zero, 3 * m + (rank_v ? 6 : 3) * n_ld);
     if constexpr (table)
       hipLaunchKernelGGL(rank_grouped_target_kernel, dim3(cdiv(n_ld, 256)), dim3(256), 0, stream, off, n, n_ld, m, s.dt_r, s.gn, s.qmax, kappa, s.dt_c,
                          s.tgt_c, s.lo_c, s.hi_c);
@@ -2349,7 +2544,22 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
       prof.tag(103, rows, n);
       hipLaunchKernelGGL(rank_col_count_kernel<Dir>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n_ld, r0, n_strips, S, seg_rows, Cd);
     }
+    if (rank_v) {
+      // (strip, range of groups) waves: ~32 per CU; the groups that meet the block are counted on the device
+      const int S = std::max(1, std::min(cdiv(n, 4), cdiv(32 * vtcgemm::num_cus(), n_strips)));
+      ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
+      prof.tag(106, rows, n);
+      hipLaunchKernelGGL(rank_vunit_count_kernel<4>, dim3(cdiv(n_strips * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n_ld, r0, m, n_strips, S,
+                         off, s.gid, s.carry_key, s.carry_nan, (r0 / s.rows_per_block) & 1, vu);
+    }
     VTC_LAUNCH_CHECK2(fn, "count");
+  }
+  if (rank_v) {
+    ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
+    prof.tag(107, n, d);
+    hipLaunchKernelGGL(rank_vunit_settle_kernel, dim3((int)std::min<size_t>(2048, (s.cap_v + 3) / 4)), dim3(256), 0, stream, vu, off, d);
+    hipLaunchKernelGGL(rank_vunit_brute_kernel, dim3(std::min(n, 1024)), dim3(512), 0, stream, vu, off, d, s.stats + RS_STATS);
+    hipLaunchKernelGGL(rank_vunit_write_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, s.dt_c, cnt_v, n, rank_v);
   }
   {
     // eight pairs per wave and step; the pools' fill lives on the device, so the grid is sized for a full pool and strides
@@ -2612,6 +2822,23 @@ extern "C" int vtc_l2_rank_grouped(const float *a, const float *b, const int *of
   const RankWs s = rank_plan((char *)ws, n, m, d, rows_per_block, reach_capacity, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped: workspace too small (%zu < %zu)", ws_bytes, s.total);
   return rank_sweep_impl<RankDirG>("l2_rank_grouped", a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+}
+
+extern "C" size_t vtc_l2_rank_grouped_vunit_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity) {
+  if (n < 1 || m < 1 || d <= 0 || reach_capacity < 0) return 0;
+  return rank_plan(nullptr, n, m, d, rows_per_block, reach_capacity, true, true).total;
+}
+extern "C" int vtc_l2_rank_grouped_vunit(const float *a, const float *b, const int *off, int n, int m, int d, int rows_per_block,
+                                         int reach_capacity, int64_t *rank_a, int64_t *rank_b, int64_t *rank_v, int *nonfinite, void *ws,
+                                         size_t ws_bytes, void *stream) {
+  VTC_CHECK(a && b && off && rank_a && rank_b && rank_v && nonfinite, "l2_rank_grouped_vunit: null argument");
+  VTC_CHECK(n >= 1, "l2_rank_grouped_vunit: n=%d must be >= 1", n);
+  VTC_CHECK(m >= 1, "l2_rank_grouped_vunit: m=%d must be >= 1", m);
+  VTC_CHECK(d > 0 && d % 64 == 0, "l2_rank_grouped_vunit: d=%d must be a positive multiple of 64", d);
+  VTC_CHECK(reach_capacity >= 0, "l2_rank_grouped_vunit: reach_capacity=%d must be >= 0 (0: the default)", reach_capacity);
+  const RankWs s = rank_plan((char *)ws, n, m, d, rows_per_block, reach_capacity, true, true);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped_vunit: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  return rank_sweep_impl<RankDirG>("l2_rank_grouped_vunit", a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream, rank_v);
 }
 
 extern "C" int vtc_similarity(const float *v, const float *t, int nv, int nt, int d, const float *logit_scale, float *sim,

@@ -207,18 +207,27 @@ class RecallAtK(BaseMetric):
                 raise self._nonfinite_error(bad)
         return rank_a, rank_b
 
-    def grouped_ranks(self, features_a, features_b, offsets):
+    def grouped_ranks(self, features_a, features_b, offsets, video_to_text="caption"):
         """ranks() for videos with several captions each (ops.rank_grouped): features_a [N, D] one row per video, features_b [M, D] the
         captions (those of a video contiguous, in video order), offsets [N + 1] with the captions of video v at offsets[v]:offsets[v + 1].
         Returns (rank_a [M], rank_b [N]) int64 on the GPU: rank_a[c] the 0-based rank of caption c's own video among the N videos;
         rank_b[v] the best rank one of video v's own captions reaches among all M captions (the caption-level convention of the image-text
-        literature, include/vtc_hip.h).  rank_statistics() turns either into R@k / MedR / MeanR / MRR.  A video without a caption is a
-        data error here (ValueError, raised with the other offsets errors before any device is touched)."""
+        literature, include/vtc_hip.h).  ``video_to_text="video"`` returns (rank_a, rank_v) instead: rank_v[v] is the video-unit
+        convention of the video-retrieval literature, the number of OTHER VIDEOS whose best caption is closer to video v than v's own
+        best caption (ops.rank_grouped_vunit; rank_v <= rank_b, equal at rank 0).  rank_statistics() turns any of them into R@k / MedR /
+        MeanR / MRR.  A video without a caption is a data error here (ValueError, raised with the other offsets errors and an unknown
+        ``video_to_text`` before any device is touched)."""
+        if video_to_text not in ("caption", "video"):
+            raise ValueError(f"RecallAtK.grouped_ranks: video_to_text must be 'caption' or 'video', got {video_to_text!r}")
         if len(features_a.shape) != 2 or len(features_b.shape) != 2:
             raise ValueError(f"RecallAtK.grouped_ranks expects [N, D] videos and flat [M, D] captions, got {tuple(features_a.shape)} and "
                              f"{tuple(features_b.shape)}")
         off = ops.check_offsets(offsets, features_a.shape[0], features_b.shape[0], allow_empty=False)
         a, b = self._padded(features_a, features_b)
+        if video_to_text == "video":
+            rank_a, _, rank_v, bits = ops.rank_grouped_vunit(a, b, off, ws=self._workspace(
+                L.lib().vtc_l2_rank_grouped_vunit_workspace_bytes(a.shape[0], b.shape[0], a.shape[1], 0, 0), a.device))
+            return self._finite_ranks(rank_a, rank_v, bits)
         return self._finite_ranks(*ops.rank_grouped(a, b, off, ws=self._workspace(
             L.lib().vtc_l2_rank_grouped_workspace_bytes(a.shape[0], b.shape[0], a.shape[1], 0, 0), a.device)))
 

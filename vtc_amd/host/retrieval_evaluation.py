@@ -138,15 +138,18 @@ def padded_captions_to_offsets(tensor_t):
     return tt[keep], np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
 
 
-def compute_multi_caption_table(tensor_v, tensor_t, split: str = "full-test", dataset_name: str = "MSRVTT", offsets=None):
+def compute_multi_caption_table(tensor_v, tensor_t, split: str = "full-test", dataset_name: str = "MSRVTT", offsets=None,
+                                video_to_text: str = "caption"):
     """compute_rank_table for videos with SEVERAL captions each: rows R@1 / R@5 / R@10 (percent), MedR, MeanR (1-based ranks) and MRR in
     compute_recall's two columns.  ``tensor_t`` is the reference's own padded tensor [N, C, D] (:238-260; all -inf rows are padding and
     are dropped) when ``offsets`` is None, else the flat [M, D] captions with ``offsets`` [N + 1] (the captions of video v are rows
     offsets[v]:offsets[v + 1]).
       "Text to Video": over the M captions, the rank of the caption's own video among the N videos;
       "Video to Text": over the N videos, the best rank one of the video's own captions reaches among all M captions -- the caption-level
-      convention of the image-text literature (not the video-unit one, which counts other VIDEOS with a closer caption).
-    Exact ranks (RecallAtK.grouped_ranks).  With one caption per video the frame equals compute_rank_table's."""
+      convention of the image-text literature.  ``video_to_text="video"``: the video-unit convention of the video-retrieval literature
+      (multi-sentence evaluation) instead -- the number of other VIDEOS whose best caption is closer than the video's own best caption;
+      the frame then carries ``attrs["video_to_text"] = "video"``.  The conventions agree on R@1; index and columns are the same.
+    Exact ranks (RecallAtK.grouped_ranks).  With one caption per video the frame equals compute_rank_table's under either convention."""
     import pandas as pd
     tv, tt = torch.as_tensor(tensor_v), torch.as_tensor(tensor_t)
     if offsets is None:
@@ -158,7 +161,7 @@ def compute_multi_caption_table(tensor_v, tensor_t, split: str = "full-test", da
     if tv.dim() != 2:
         raise ValueError(f"compute_multi_caption_table: videos [N, D] expected, got {tuple(tv.shape)}")
     recall_range = [1, 5, 10]
-    rank_t2v, rank_v2t = RecallAtK("videos", "titles", recall_range).grouped_ranks(tv, tt, offsets)
+    rank_t2v, rank_v2t = RecallAtK("videos", "titles", recall_range).grouped_ranks(tv, tt, offsets, video_to_text=video_to_text)
 
     def column(ranks):
         st = rank_statistics(ranks, recall_range)
@@ -166,6 +169,8 @@ def compute_multi_caption_table(tensor_v, tensor_t, split: str = "full-test", da
     df = pd.DataFrame({f"{dataset_name} {split} split Video to Text": column(rank_v2t),
                        f"{dataset_name} {split} split Text to Video": column(rank_t2v)},
                       index=[f"R@{i}" for i in recall_range] + ["MedR", "MeanR", "MRR"])
+    if video_to_text != "caption":
+        df.attrs["video_to_text"] = video_to_text
     logging.info(df)
     return df
 
@@ -299,17 +304,19 @@ def _resolve_dataset(datasetname, split):
 @torch.no_grad()
 def retrieval_evaluation(model, datasetname, split: str = "full-test", device="cuda", out_csv: Optional[str] = None,
                          frame_stride: int = 16, first_frame_only: bool = False, first_chunk_only: bool = False,
-                         videos_per_batch: int = 64, return_embeddings: bool = False, multi_caption: bool = False):
+                         videos_per_batch: int = 64, return_embeddings: bool = False, multi_caption: bool = False,
+                         video_to_text: str = "caption"):
     """retrieval_evaluation (:108-268) with the reference's positional arguments; returns its DataFrame.
     ``datasetname`` may also be a Dataset or a list of items (frames, captions[, comments], id).
     ``videos_per_batch`` bounds how many videos are decoded before their chunks are encoded (host memory);
     ``return_embeddings``: also the two stacked embedding tensors of :254-260 (GPU).
     ``multi_caption``: an item's captions may be [C_i, 77] with C_i >= 1; the result is compute_multi_caption_table's frame (R@K, MedR,
-    MeanR, MRR) and ``return_embeddings`` adds (video_emb [N, D], caption_emb [M, D], offsets [N + 1] int64 on the host)."""
+    MeanR, MRR) and ``return_embeddings`` adds (video_emb [N, D], caption_emb [M, D], offsets [N + 1] int64 on the host);
+    ``video_to_text`` ("caption" | "video") is compute_multi_caption_table's and is read with ``multi_caption`` only."""
     dataset, name = _resolve_dataset(datasetname, split)
     if multi_caption:
         return _retrieval_evaluation_multi(model, dataset, name, split, device, out_csv, frame_stride, first_frame_only, first_chunk_only,
-                                           videos_per_batch, return_embeddings)
+                                           videos_per_batch, return_embeddings, video_to_text)
     v_parts, c_parts = [], []
     batch = []
     n = len(dataset)
@@ -330,7 +337,7 @@ def retrieval_evaluation(model, datasetname, split: str = "full-test", device="c
 
 
 def _retrieval_evaluation_multi(model, dataset, name, split, device, out_csv, frame_stride, first_frame_only, first_chunk_only,
-                                videos_per_batch, return_embeddings):
+                                videos_per_batch, return_embeddings, video_to_text="caption"):
     v_parts, c_parts, counts = [], [], []
     batch = []
     n = len(dataset)
@@ -345,7 +352,8 @@ def _retrieval_evaluation_multi(model, dataset, name, split, device, out_csv, fr
             batch = []
     video_emb, caption_emb = torch.cat(v_parts), torch.cat(c_parts)
     offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    outdf = compute_multi_caption_table(video_emb, caption_emb, split=split, dataset_name=name, offsets=offsets)
+    outdf = compute_multi_caption_table(video_emb, caption_emb, split=split, dataset_name=name, offsets=offsets,
+                                        video_to_text=video_to_text)
     if getattr(dataset, "synthetic", False):
         outdf.attrs["synthetic"] = True
     if out_csv is not None:

@@ -440,16 +440,48 @@ def _rank_grouped(a, b, off, rows_per_block, reach_capacity, ws):
                       rows_per_block, reach_capacity, ws)
 
 
+def rank_grouped_vunit(a: torch.Tensor, b: torch.Tensor, offsets, rows_per_block: int = 0, reach_capacity: int = 0,
+                       ws: Optional[torch.Tensor] = None):
+    """rank_grouped with video -> text in BOTH conventions from one sweep (vtc_l2_rank_grouped_vunit): returns (rank_a [m], rank_b [n],
+    rank_v [n], nonfinite_bits).  rank_a and rank_b are rank_grouped's, element for element; rank_v[v] is the video-unit convention of the
+    video-retrieval literature: the number of OTHER VIDEOS whose best caption is closer to video v than v's own best caption (an exact tie
+    goes to the lower video index; include/vtc_hip.h has the definition).  rank_v <= rank_b, and the two agree on rank 0.  A video without
+    a finite own caption (an empty group too) has rank_v = n.  Offsets are validated on the host before anything is launched."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[0] < 1 or b.shape[0] < 1:
+        raise ValueError(f"rank_grouped_vunit: a [n, d] and b [m, d] expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    off = check_offsets(offsets, a.shape[0], b.shape[0])
+    return _rank_grouped_vunit(a, b, off, rows_per_block, reach_capacity, ws)
+
+
+@on_device
+def _rank_grouped_vunit(a, b, off, rows_per_block, reach_capacity, ws):
+    a, b = _gpu(a, torch.float32, "a"), _gpu(b, torch.float32, "b")
+    (n, d), m = a.shape, b.shape[0]
+    lib = L.lib()
+    off_dev = torch.from_numpy(off.astype("int32")).to(a.device)
+    ws = _ws_for(ws, lib.vtc_l2_rank_grouped_vunit_workspace_bytes(n, m, d, rows_per_block, reach_capacity), a.device)
+    rank_a = torch.empty(m, dtype=torch.int64, device=a.device)
+    rank_b = torch.empty(n, dtype=torch.int64, device=a.device)
+    rank_v = torch.empty(n, dtype=torch.int64, device=a.device)
+    bits = torch.empty(1, dtype=torch.int32, device=a.device)
+    L.check(lib.vtc_l2_rank_grouped_vunit(a.data_ptr(), b.data_ptr(), off_dev.data_ptr(), n, m, d, rows_per_block, reach_capacity,
+                                          rank_a.data_ptr(), rank_b.data_ptr(), rank_v.data_ptr(), bits.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _stream()), "vtc_l2_rank_grouped_vunit")
+    return rank_a, rank_b, rank_v, bits
+
+
 def rank_kappa(d: int) -> float:
     """kappa of the rank sweep's error bound eps = kappa (|q|^2 + max|g|^2) at feature width d."""
     return float(L.lib().vtc_l2_rank_kappa(int(d)))
 
 
 def rank_sweep_stats(ws: torch.Tensor) -> dict:
-    """What the last rank_bidir call on workspace ``ws`` left in its first words (include/vtc_hip.h): per direction the pairs in reach
-    of their target, the largest number of them for one owner, and the owners counted by fp64 brute force."""
-    w = ws[:64].view(torch.int64).cpu().tolist()
-    return {"in_reach": (w[0], w[1]), "in_reach_max": (w[2], w[3]), "brute_force_owners": (w[4], w[5])}
+    """What the last rank sweep on workspace ``ws`` left in its first words (include/vtc_hip.h): per direction the pairs in reach
+    of their target, the largest number of them for one owner, and the owners counted by fp64 brute force.  The ``vunit_*`` keys are the
+    video-unit direction's (video, group) figures; only rank_grouped_vunit writes them (after another call they hold what the workspace held)."""
+    w = ws[:88].view(torch.int64).cpu().tolist()
+    return {"in_reach": (w[0], w[1]), "in_reach_max": (w[2], w[3]), "brute_force_owners": (w[4], w[5]),
+            "vunit_in_reach": w[8], "vunit_in_reach_max": w[9], "vunit_brute_force_owners": w[10]}
 
 
 def split_recall_counters(hits_host: torch.Tensor):
