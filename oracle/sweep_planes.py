@@ -113,7 +113,7 @@ def midpoint_case(n_gallery=2048, d=512, depth=11):
 
 
 def measured_eps(gallery, query, kappa_fp32):
-    """Round 4's per-row error bound (sweep.hip: sweep_prep_kernel + minsel_kernel): with x~ = bf16(x) and e = x - x~ the rows'
+    """Round 4's per-row error bound (sweep_front.hip: sweep_prep_kernel, sweep_topk.hip: minsel_kernel): with x~ = bf16(x) and e = x - x~ the rows'
     ACTUAL rounding errors, | q~.g~ - q.g | = | q~.e_g + e_q.g~ + e_q.e_g | <= |q~||e_g| + |e_q||g~| + |e_q||e_g| (Cauchy-Schwarz),
     twice that on the distance, the gallery side by its maxima, plus kappa_fp32 (|q|^2 + max|g|^2) for the fp32 terms; the same
     1e-4 slack on the measured norms and 1e-3 on the whole as the kernels carry."""
@@ -125,7 +125,7 @@ def measured_eps(gallery, query, kappa_fp32):
 
 
 def certificate_sets(gallery, query, depth, kappa, bw=64, eps=None):
-    """The block-minima certificate of sweep.hip (minsel_kernel) restated for ONE query: plain-bf16 approximate distances in
+    """The block-minima certificate of sweep_topk.hip (minsel_kernel) restated for ONE query: plain-bf16 approximate distances in
     fp32, per-block three smallest + the fourth as a bound, u = depth-th smallest block minimum, theta = u + 2 eps with
     eps = kappa (|q|^2 + max|g|^2) (rounds 2-3: a worst-case constant) or the `eps` given (round 4: measured_eps).
     Returns (candidate ids with approx <= theta, certified?, approx distances)."""

@@ -22,6 +22,27 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name)
 
 
+def test_every_source_is_built_and_every_project_header_is_tracked():
+    """The Makefile's SRCS is exactly the *.hip files of vtc_amd/csrc/ (a source split off another cannot drop out of the build;
+    sweep.hip is gone for good), and every project header a source or a header includes is a prerequisite of the object rule (an edit
+    of it rebuilds the objects)."""
+    csrc = os.path.join(ROOT, "vtc_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*=\s*(.+)$", mk, re.M).group(1).split()
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert sorted(srcs) == on_disk and len(set(srcs)) == len(srcs), set(srcs) ^ set(on_disk)
+    assert "sweep.hip" not in srcs and "sweep.hip" not in on_disk
+    prereq = re.search(r"^\$\(OBJDIR\)/%\.o:\s*%\.hip\s+(.+)$", mk, re.M).group(1).split()
+    tracked = {os.path.normpath(os.path.join(csrc, h)) for h in prereq}
+    assert all(os.path.isfile(h) for h in tracked), tracked
+    seen = 0
+    for f in on_disk + sorted(os.path.basename(h) for h in tracked if os.path.dirname(h) == csrc):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, f)).read(), re.M):
+            assert os.path.normpath(os.path.join(csrc, inc)) in tracked, (f, inc)
+            seen += 1
+    assert seen >= len(on_disk)            # every source includes at least common.h: the pattern matched
+
+
 def test_ctypes_structs_match_the_c_header(tmp_path):
     """The weight structs travel by pointer: the ctypes mirrors (vtc_amd/_lib.py) must have the C compiler's layout of
     include/vtc_hip.h -- sizes and the offsets of the fields added in ABI 5 (per-model `flags`)."""

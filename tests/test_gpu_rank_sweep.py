@@ -142,7 +142,7 @@ def test_forced_pool_overflow_changes_nothing():
     n, d = 1027, 64
     a, b, want_a, want_b = _case("spread", n, d, 2)
     kappa = ops.rank_kappa(d)
-    assert kappa == pytest.approx(3.0 / 65536 + 4.0 * d / 16777216 + 1e-6, rel=1e-6)         # vtc_amd/csrc/sweep.hip, rank_kappa
+    assert kappa == pytest.approx(3.0 / 65536 + 4.0 * d / 16777216 + 1e-6, rel=1e-6)         # vtc_amd/csrc/sweep_front.hip, split_kappa
     assert RR.in_reach_total(a, b, kappa) > 8                                                # else the test proves nothing
     ta, tb = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     ws = ops.workspace(L.lib().vtc_l2_rank_bidir_workspace_bytes(n, d, 256, 8), ta.device)

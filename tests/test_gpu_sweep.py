@@ -154,6 +154,40 @@ def test_l2_topk_exact_mode_dense_near_ties_take_the_fp64_brute_force():
     assert np.array_equal(ids.cpu().numpy(), E.l2_topk(small, q, 11, np.float64)[0])
 
 
+@pytest.mark.parametrize("d", [64, 320])      # 64: most lanes of the distance loop have no chunk; 320: one full 256-wide chunk and a partial one
+def test_exact_list_paths_form_the_same_doubles(d):
+    """ONE function forms every fp64 distance (vtc_amd/csrc/sweep_common.h), so the EXACT paths agree to the bit: the block-minima path
+    (re-rank + rescan; n = 1 024 is the smallest gallery it accepts) and the distance-matrix path (re-rank + brute-force fallback), on
+    exact duplicates, near-duplicates far below the bf16 resolution and queries that sit on them.  Depth 40 takes the distance-matrix
+    path whatever the blocking; its first 11 columns are the depth-11 answer."""
+    from vtc_amd import _lib as L
+    from vtc_amd import ops
+    rng = np.random.default_rng(1024 + d)
+    a = unit(rng.standard_normal((1024, d))).astype(np.float32)
+    base = a[7].copy()
+    for j in range(60):                                      # 60 near-duplicates of row 7, 1e-7-scale differences
+        a[100 + j] = base
+        a[100 + j, j % d] += np.float32(1e-7 * (j + 1))
+    a[500:530] = a[499]                                      # 30 exact duplicates: ties resolve to the lowest index
+    q = unit(rng.standard_normal((64, d))).astype(np.float32)
+    q[0], q[1] = base, a[499]
+    ga, gq = torch.from_numpy(a).cuda(), torch.from_numpy(q).cuda()
+
+    def both(depth):
+        out = [ops.l2_topk(ga, gq, depth, precision=L.SWEEP_EXACT, rows_per_block=rpb) for rpb in (0, 256)]
+        return [(i.cpu().numpy(), x.cpu().numpy()) for i, x in out]
+
+    (i_min, d_min), (i_mat, d_mat) = both(11)
+    assert np.array_equal(i_min, i_mat)
+    assert np.array_equal(d_min.view(np.uint32), d_mat.view(np.uint32))
+    assert np.array_equal(i_min, E.l2_topk(a, q, 11, np.float64)[0])
+    ids40 = E.l2_topk(a, q, 40, np.float64)[0]
+    for i40, d40 in both(40):
+        assert np.array_equal(i40, ids40)
+        assert np.array_equal(i40[:, :11], i_min)
+        assert np.array_equal(d40[:, :11].view(np.uint32), d_min.view(np.uint32))
+
+
 def _bidir_cases():
     out = []
     for prec in ("exact", "f32", "bf16x3"):

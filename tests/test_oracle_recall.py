@@ -107,7 +107,7 @@ def test_oracle_recall_equals_the_references_own_recallatk():
 
 
 def test_certificate_error_bound_needs_the_full_bf16_roundoff():
-    """The EXACT sweep's certificate (vtc_amd/csrc/sweep.hip minsel_kernel, restated in oracle/sweep_planes.certificate_sets)
+    """The EXACT sweep's certificate (vtc_amd/csrc/sweep_topk.hip minsel_kernel, restated in oracle/sweep_planes.certificate_sets)
     is only as good as its per-entry error bound.  On the midpoint case the constant of rounds 1-2 (bf16 unit roundoff taken
     as 2^-9) certifies a candidate list WITHOUT the true nearest row; the corrected one (2^-8) keeps it.  Pins the reasoning
     behind exact2_kappa on the CPU; the kernel itself is checked against fp64 brute force in tests/test_gpu_sweep.py."""
@@ -129,7 +129,7 @@ def test_certificate_error_bound_needs_the_full_bf16_roundoff():
 
 def test_measured_rounding_error_bound_is_rigorous_and_tighter():
     """Round 4: the certificate's eps is built from the rows' MEASURED bf16 rounding errors (|x - bf16(x)|, exact in fp32) instead
-    of the worst case 2^-8 |x| (oracle/sweep_planes.measured_eps = sweep.hip sweep_prep_kernel + minsel_kernel).  It must (a) still
+    of the worst case 2^-8 |x| (oracle/sweep_planes.measured_eps = sweep_front.hip sweep_prep_kernel + sweep_topk.hip minsel_kernel).  It must (a) still
     bound every entry's error -- also on the adversarial midpoint case, where every coordinate's error IS the worst case, so the
     bound may not shrink there -- and keep the true nearest row in the certified list; (b) be several times smaller on ordinary
     embeddings, which is what shrinks the candidate sets."""

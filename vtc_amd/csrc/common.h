@@ -164,6 +164,18 @@ __device__ __forceinline__ unsigned xor16_of(unsigned x, bool odd_row) {
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Carves a workspace into 256-byte aligned pieces, in the order they are asked for.  A null base sizes it: every piece is null, `off` the total.
+struct Bump {
+  char *base;
+  size_t off = 0;
+  explicit Bump(void *b) : base((char *)b) {}
+  void *take(size_t bytes) {
+    const size_t o = off;
+    off = align_up(off + bytes, 256);
+    return base ? base + o : nullptr;
+  }
+};
+
 // ---- per-device launch state ----------------------------------------------------------------
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE setting: a process that drives several GPUs (one
 // thread per replica, train.py:77-80) must opt every device in.  One bit per device; setting it twice is harmless, so

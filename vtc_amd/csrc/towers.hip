@@ -70,17 +70,6 @@ namespace {
 // every configuration -- in round 5 also with the folded LayerNorm kept, on the time branch alone: 2.09 ms against 1.20 + 0.49 per
 // layer at 1 024 videos, profiles/r05_experiments.txt 1 -- and left the product: tools/probes/qkv_attn.hip.)
 
-struct Bump {
-  char *base;
-  size_t off = 0;
-  explicit Bump(void *b) : base((char *)b) {}
-  void *take(size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return base ? base + o : nullptr;
-  }
-};
-
 #define RUN(call)        \
   do {                   \
     int rc_ = (call);    \
