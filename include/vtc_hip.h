@@ -330,6 +330,28 @@ float vtc_l2_rank_kappa(int d);
 size_t vtc_l2_rank_bidir_workspace_bytes(int n, int d, int rows_per_block, int reach_capacity);
 int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, int rows_per_block, int reach_capacity, int64_t *rank_a,
                       int64_t *rank_b, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* The paired sweep over a WINDOW of rows: one rank's share of a row-sharded evaluation.  The caller holds both gathered sets (a_all, b_all:
+ * [n_total, d]) and owns the rows [row_base, row_base + n_local) of D(i, j) = |b_i - a_j|^2 (notation and arithmetic of vtc_l2_rank_bidir:
+ * fp64 distances of the fp32 inputs from the sweep's one device function, pairs compared lexicographically).
+ *   rank_a_local[i] = rank_a[row_base + i] of vtc_l2_rank_bidir(a_all, b_all)             i in [0, n_local): complete, the rank holds whole rows
+ *   rank_b_part[j]  = #{ i in [row_base, row_base + n_local) : (D(i, j), i) < (D(j, j), j) }      if D(j, j) is finite
+ *                   = n_total if row_base <= j < row_base + n_local, else 0                        otherwise
+ * for EVERY j in [0, n_total), written, not added to.  Summed over any disjoint windows that cover [0, n_total), rank_b_part is rank_b of
+ * vtc_l2_rank_bidir, element for element: counts are sums, and a pair without a finite distance gets its rank n_total from the one window
+ * that owns its row.  A local pair without a finite distance has rank_a_local = n_total.  nonfinite[0] is that of the paired call, over
+ * all of a_all and b_all: the same word on every rank.
+ * The thresholds are the paired call's: a row's eps = kappa (|b_i|^2 + max_j |a_j|^2), a column's eps = kappa (|a_j|^2 + max_i |b_i|^2)
+ * with the maximum over ALL of b_all, so the pairs a window settles in fp64 are exactly the paired call's pairs that lie in it.  The
+ * statistics words keep their meaning, restricted to the window: direction a counts the local owners, direction b all columns against
+ * the local rows.  With row_base = 0, n_local = n_total both outputs and the eight words are those of vtc_l2_rank_bidir, element for element.
+ * n_total >= 1, 0 <= row_base, 0 <= n_local, row_base + n_local <= n_total, d % 64 == 0.  n_local = 0 is valid (fewer rows than ranks):
+ * no distance GEMM runs and rank_b_part is all zero.  Workspace: what grows with the rank's share has n_local entries (the split-bf16
+ * query operands, the distance block -- rows_per_block is capped at n_local --, the row direction's thresholds, counters and default
+ * pool, 512 n_local pairs); the gallery operands and the column direction's arrays are O(n_total). */
+size_t vtc_l2_rank_shard_workspace_bytes(int n_total, int n_local, int d, int rows_per_block, int reach_capacity);
+int vtc_l2_rank_shard(const float *a_all, const float *b_all, int n_total, int row_base, int n_local, int d, int rows_per_block,
+                      int reach_capacity, int64_t *rank_a_local /* [n_local] */, int64_t *rank_b_part /* [n_total] */, int *nonfinite,
+                      void *ws, size_t ws_bytes, void *stream);
 /* The same ranks for videos with SEVERAL captions each (MSR-VTT: 20 per video, MSVD: about 40).  a [n, d]: one row per video; b [m, d]: the
  * captions, those of one video contiguous and in video order; off [n + 1] (device int32): non-decreasing, off[0] = 0, off[n] = m.  Caption c
  * belongs to video g(c), the v with off[v] <= c < off[v + 1].  With D(c, j) the fp64 value sum_k (b_c[k] - a_j[k])^2 of the fp32 inputs

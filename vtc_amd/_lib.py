@@ -108,6 +108,8 @@ SIGNATURES = {
     "vtc_l2_rank_kappa": (C.c_float, [C.c_int]),
     "vtc_l2_rank_bidir_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtc_l2_rank_bidir": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, vp, C.c_size_t, vp]),
+    "vtc_l2_rank_shard_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_rank_shard": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, vp, C.c_size_t, vp]),
     "vtc_l2_rank_grouped_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtc_l2_rank_grouped": (C.c_int, [fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, ip, vp, C.c_size_t, vp]),
     "vtc_l2_rank_grouped_vunit_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

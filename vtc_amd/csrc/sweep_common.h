@@ -61,9 +61,10 @@ __device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, 
 }
 
 // ---- host pieces, defined in sweep_front.hip ----------------------------------------------------------------------------------------
-// |x|^2 of both sets and, for parts = 3 / 1, their split-bf16 operand rows ([hi | lo | hi] queries, [hi | hi | lo] gallery / [hi]); parts = 0: norms only
+// |x|^2 of both sets and, for parts = 3 / 1, their split-bf16 operand rows ([hi | lo | hi] queries, [hi | hi | lo] gallery / [hi]); parts = 0: norms only.
+// q_rows >= 0: operand rows for the queries [q0, q0 + q_rows) only, qb[0] being row q0's (the norms are still all nq).
 void launch_norms_split(const float *queries, int nq, float *qn, bf16_t *qb, const float *gallery, int ng, float *gn, bf16_t *gb, int d, int parts,
-                        hipStream_t stream);
+                        hipStream_t stream, int q0 = 0, int q_rows = -1);
 
 constexpr int MAX_SEG = 16;   // column segments of a row pass, at most
 int default_rows_per_block(int cols);

@@ -134,11 +134,14 @@ static void launch_sweep_prep(const PrepSide &A, const PrepSide &B, int d, float
 namespace vtcsweep {
 
 void launch_norms_split(const float *queries, int nq, float *qn, bf16_t *qb, const float *gallery, int ng, float *gn, bf16_t *gb, int d, int parts,
-                        hipStream_t stream) {
+                        hipStream_t stream, int q0, int q_rows) {
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, stream, queries, qn, nq, d);
   hipLaunchKernelGGL(row_sqnorm_kernel, dim3(cdiv(ng, 4)), dim3(256), 0, stream, gallery, gn, ng, d);
   if (parts == 0) return;
-  hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)nq * d + 255) / 256)), dim3(256), 0, stream, queries, qb, nq, d, parts, 0);
+  if (q_rows < 0) q0 = 0, q_rows = nq;
+  if (q_rows > 0)
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)q_rows * d + 255) / 256)), dim3(256), 0, stream, queries + (size_t)q0 * d, qb, q_rows, d,
+                       parts, 0);
   hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(((size_t)ng * d + 255) / 256)), dim3(256), 0, stream, gallery, gb, ng, d, parts, 1);
 }
 

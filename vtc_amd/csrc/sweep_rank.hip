@@ -1,6 +1,7 @@
 // sweep_rank.hip -- the full-rank sweep: the exact rank of EVERY pair's target (median / mean rank, MRR, recall at any k) by COUNTING over
 // the blocks of one BF16X3 distance matrix, fp64 for the entries within the error bound of a target.
 //   vtc_l2_rank_bidir           both directions of n paired rows
+//   vtc_l2_rank_shard           the same sweep over a window of the rows: one rank's share of a row-sharded evaluation, partial column counts
 //   vtc_l2_rank_grouped         videos with several captions each: the sweep made rectangular, the target taken from a table
 //   vtc_l2_rank_grouped_vunit   that sweep with a third direction: video -> text counted in VIDEOS (groups of captions), not captions
 // Norms, operand split, blocking and the error constant are sweep_front.hip's; the fp64 distance is sweep_common.h's.
@@ -56,6 +57,8 @@ struct RankDir {
   unsigned long long cap;
   const double *dt;              // [n_own] fp64 distance of the owner to its target (paired: one array for both directions)
   int n_own, n_other;
+  int tgt0;                      // paired: owner o's target is tgt0 + o.  The row direction of a row window (vtc_l2_rank_shard) numbers its owners
+                                 // from the window's first row, so tgt0 = that row; 0 everywhere else.  `own` starts at the direction's owner 0.
 };
 // The kernels below take the direction as a compile-time policy that says ONE thing, where an owner's target is: its own index (RankDir,
 // vtc_l2_rank_bidir) or an entry of a table (RankDirG, vtc_l2_rank_grouped).
@@ -66,7 +69,7 @@ template <typename Dir> constexpr bool rank_has_table = std::is_same<Dir, RankDi
 template <typename Dir>
 __device__ __forceinline__ int rank_target(const Dir &P, int owner) {
   if constexpr (rank_has_table<Dir>) return P.tgt[owner];
-  else return owner;
+  else return P.tgt0 + owner;
 }
 
 // What the prologue writes for a direction: the owners' target distances and thresholds, from their norms and the other side's maximum.
@@ -82,35 +85,47 @@ __device__ __forceinline__ void rank_set_thresholds(const RankThresholds &T, int
   T.hi[i] = ok ? __double2float_ru(dt + (double)eps) : -INFINITY;
 }
 
-// One wave per 8 owners of the row direction: the fp64 distance to the owner's target, the direction's thresholds, and the counters' zeroes.
-// Paired: the column direction's owner i has the same target distance, so its thresholds are written here too (TC.dt == TR.dt), and the
-// columns [n, n_ld) that pad the matrix's rows to 16 bytes get lo = hi = -inf: the column pass neither counts nor pools them.  Grouped:
+// One wave per 8 rows of D, ALL n_rows of them (`rows`: their queries, b): the fp64 distance of the row to its target, the counters' zeroes,
+// and the row direction's thresholds for the rows it owns -- TR is indexed by the direction's owner, row - R.tgt0 (every row but in a row
+// window).  Paired: the column direction's owner i has the same target distance, so its thresholds are written here too, for every i
+// whatever the window (TC.dt is the whole array, TR.dt the same array from the window's first row), and the columns [n, n_ld) that pad
+// the matrix's rows to 16 bytes get lo = hi = -inf: the column pass neither counts nor pools them.  Grouped:
 // rank_grouped_target_kernel writes the column direction (TC is not read).
 template <typename Dir>
-__global__ __launch_bounds__(256) void rank_prep_kernel(const Dir R, const RankThresholds TR, const RankThresholds TC, int n_ld, int d, float kappa,
-                                                        int *__restrict__ zero, int n_zero) {
+__global__ __launch_bounds__(256) void rank_prep_kernel(const Dir R, const float *__restrict__ rows, int n_rows, const RankThresholds TR,
+                                                        const RankThresholds TC, int n_ld, int d, float kappa, int *__restrict__ zero, int n_zero) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   for (int i = t; i < n_zero; i += gridDim.x * 256) zero[i] = 0;
-  const int n = R.n_own;
   if constexpr (!rank_has_table<Dir>) {
+    const int n = R.n_other;
     if (t < n_ld - n) TC.lo[n + t] = TC.hi[n + t] = -INFINITY;
   }
   const int lane = threadIdx.x & 63;
   const int i0 = (t >> 6) * RS_NB;
-  if (i0 >= n) return;                                  // wave-uniform
+  if (i0 >= n_rows) return;                             // wave-uniform
   int qi[RS_NB], gi[RS_NB];
 #pragma unroll
-  for (int u = 0; u < RS_NB; ++u) { qi[u] = min(i0 + u, n - 1); gi[u] = rank_target(R, qi[u]); }
+  for (int u = 0; u < RS_NB; ++u) {
+    qi[u] = min(i0 + u, n_rows - 1);
+    if constexpr (rank_has_table<Dir>) gi[u] = R.tgt[qi[u]];
+    else gi[u] = qi[u];
+  }
   double dd[RS_NB];
-  wave_dist64_pairs(R.own, R.other, qi, gi, d, lane, dd);
+  wave_dist64_pairs(rows, R.other, qi, gi, d, lane, dd);
   double mine = 0.0;
 #pragma unroll
   for (int u = 0; u < RS_NB; ++u) mine = lane == u ? dd[u] : mine;
   const int i = i0 + lane;
-  if (lane < RS_NB && i < n) {
-    TR.dt[i] = mine;
-    rank_set_thresholds(TR, i, mine, kappa);            // rows of D: query b_i against the a's
-    if constexpr (!rank_has_table<Dir>) rank_set_thresholds(TC, i, mine, kappa);      // columns: query a_i against the b's
+  if (lane < RS_NB && i < n_rows) {
+    const int o = i - R.tgt0;
+    if (o >= 0 && o < R.n_own) {
+      TR.dt[o] = mine;
+      rank_set_thresholds(TR, o, mine, kappa);          // rows of D: query b_i against the a's
+    }
+    if constexpr (!rank_has_table<Dir>) {
+      TC.dt[i] = mine;
+      rank_set_thresholds(TC, i, mine, kappa);          // columns: query a_i against the b's
+    }
   }
 }
 
@@ -295,8 +310,14 @@ __global__ __launch_bounds__(256) void rank_col_count_kernel(const float *__rest
   float lo[V], hi[V];
   int cnt[V], reach[V], tg[V];                            // tg: the row (global id) of the column's target
   rank_col_thresholds(P, c, live, lo, hi, cnt, reach);
+  // Table form: tgt has n_cols >= 4 entries, the padding ones written too; a lane past it reads tgt[0 .. 3].  Paired: a column's target is
+  // the row of its own number in every row window -- written out, not rank_target(): the column direction's tgt0 is always 0, and reading
+  // it costs this instantiation four VGPRs and the fifth wave per SIMD (profiles/rank_shard.md).
 #pragma unroll
-  for (int e = 0; e < V; ++e) tg[e] = rank_target(P, c + e);      // (table form: tgt has n_cols >= 4 entries, the padding ones written too; a lane past it reads tgt[0 .. 3])
+  for (int e = 0; e < V; ++e) {
+    if constexpr (rank_has_table<Dir>) tg[e] = P.tgt[c + e];
+    else tg[e] = c + e;
+  }
   for (int rb = r_lo; rb < r_hi; rb += V * U) {
     float v[U][V];
 #pragma unroll
@@ -368,7 +389,8 @@ __global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir
   int mx = 0;
   // PB is PA transposed (its owners are PA's others): both sizes come from PA, beside nblocks_a in the argument block.  Read through P, the
   // loop bound waits for one more scalar load, behind the one that selects P (+0.002 ms at 10k: a CU runs its workgroups one after another).
-  const int n_own = second ? PA.n_other : PA.n_own, n_oth = second ? PA.n_own : PA.n_other;
+  // In a row window PA's owners are the window's rows, so PB counts over exactly those: the rows PA.tgt0 + [0, PA.n_own) of its other side.
+  const int n_own = second ? PA.n_other : PA.n_own, n_oth = second ? PA.n_own : PA.n_other, oth0 = second ? PA.tgt0 : 0;
   for (int o = bid; o < n_own; o += nbl) {                   // uniform for the workgroup
     mx = max(mx, P.reach[o]);
     if (!P.ovf[o]) continue;
@@ -378,13 +400,13 @@ __global__ __launch_bounds__(512) void rank_brute_kernel(const Dir PA, const Dir
     for (int j0 = RS_NB * w; j0 < n_oth; j0 += RS_NB * 8) {
       int qi[RS_NB], gi[RS_NB];
 #pragma unroll
-      for (int u = 0; u < RS_NB; ++u) { qi[u] = o; gi[u] = min(j0 + u, n_oth - 1); }
+      for (int u = 0; u < RS_NB; ++u) { qi[u] = o; gi[u] = oth0 + min(j0 + u, n_oth - 1); }
       double dd[RS_NB];
       wave_dist64_pairs(P.own, P.other, qi, gi, d, lane, dd);
 #pragma unroll
       for (int u = 0; u < RS_NB; ++u) {
-        const int j = j0 + u;
-        if (j < n_oth && j != tg && (dd[u] < t || (dd[u] == t && j < tg))) ++cnt;
+        const int j = oth0 + j0 + u;
+        if (j0 + u < n_oth && j != tg && (dd[u] < t || (dd[u] == t && j < tg))) ++cnt;
       }
     }
     if (lane == 0) part[w] = cnt;
@@ -616,28 +638,34 @@ __global__ __launch_bounds__(256) void rank_vunit_write_kernel(const double *__r
 }
 
 // ---- both forms: the finish, the workspace and the driver -----------------------------------------------------------------------------
-// A caption (row direction, m owners) without a finite target distance ranks behind all n videos, a video (column direction) behind all m captions.
+// A caption (row direction, n_r owners) without a finite target distance ranks behind all n videos, a video (column direction) behind all m
+// captions.  In a row window the column counts are PARTIAL -- summed over the windows that tile the rows they are rank_b -- so that rank m
+// is written by one window only, the one that holds the video's own row [own0, own1); the others write 0.  (Everywhere else the
+// range is all n columns.)
 __global__ __launch_bounds__(256) void rank_write_kernel(const double *__restrict__ dt_r, const double *__restrict__ dt_c, const int *__restrict__ cnt_r,
-                                                         const int *__restrict__ cnt_c, int n, int m, int64_t *__restrict__ rank_a,
-                                                         int64_t *__restrict__ rank_b) {
+                                                         const int *__restrict__ cnt_c, int n, int m, int n_r, int own0, int own1,
+                                                         int64_t *__restrict__ rank_a, int64_t *__restrict__ rank_b) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m) rank_a[i] = dt_r[i] < (double)INFINITY ? (int64_t)cnt_r[i] : (int64_t)n;
-  if (i < n) rank_b[i] = dt_c[i] < (double)INFINITY ? (int64_t)cnt_c[i] : (int64_t)m;
+  if (i < n_r) rank_a[i] = dt_r[i] < (double)INFINITY ? (int64_t)cnt_r[i] : (int64_t)n;
+  if (i < n) rank_b[i] = dt_c[i] < (double)INFINITY ? (int64_t)cnt_c[i] : (i >= own0 && i < own1) ? (int64_t)m : (int64_t)0;
 }
 
 // The workspace of both forms: a [n, d] (the columns of D), b [m, d] (its rows; paired: m = n).  A row of D has n_ld = n rounded up to 4
 // columns, so the GEMM writes and both passes read 16-byte aligned rows at every n (measured with ld = n at 2 990 x 20: 1.70 against
 // 1.44 ms, profiles/r11_grouped_rank.md); the column-side arrays have n_ld entries, the padding columns zero operands and hi = -inf.
+// A row window (vtc_l2_rank_shard: the call owns the rows [w0, w0 + wn) of D; everywhere else wn = m): what belongs to the row direction
+// and the rows' operands have wn entries, indexed from the window's first row.  The norms and the pairs' distances are kept for all m rows
+// (max |b|^2 and the column direction's thresholds are those of the whole matrix).
 struct RankWs {
   unsigned long long *stats;       // [RS_STATS]
   float *qn, *gn, *qmax, *gmax;    // queries = b (m rows of D), gallery = a (n columns)
-  bf16_t *qb, *gb;
+  bf16_t *qb, *gb;                 // [wn], [n_ld] operand rows
   float *dist;
   int rows_per_block, n_ld;
   int *gid, *tgt_c;                // table form only: [m] g(c); [n_ld] c*
   double *dt_r, *dt_c;             // [m]; table form: [n_ld]; paired: dt_c = dt_r, the pair's distance -- n entries, none for the padding columns
-  float *lo_r, *hi_r, *lo_c, *hi_c;
-  int *zero;                       // cnt_r, reach_r, ovf_r: [3][m], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_prep_kernel
+  float *lo_r, *hi_r, *lo_c, *hi_c;      // [wn], [n_ld]
+  int *zero;                       // cnt_r, reach_r, ovf_r: [3][wn], then cnt_c, reach_c, ovf_c: [3][n_ld], zeroed by rank_prep_kernel
   int2 *pool_r, *pool_c;
   size_t cap_r, cap_c;
   // video-unit direction only (vtc_l2_rank_grouped_vunit): O(n) words and its pool
@@ -651,8 +679,9 @@ struct RankWs {
 // default pool: 512 pairs per owner and direction (8 bytes each).  Measured (profiles/r10_rank_sweep.md): an owner in the bulk of unrelated
 // unit vectors at d = 512 has 0.216 % of the other side in reach (108 pairs at 50k, at most 203), one whose target leads almost none.
 size_t rank_default_capacity(int n) { return std::max<size_t>(4096, (size_t)512 * n); }
-RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity, bool table, bool vunit = false) {
+RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_capacity, bool table, bool vunit = false, int wn = -1) {
   RankWs s;
+  if (wn < 0) wn = m;                                      // no window: every row
   Bump b(ws);
   auto take = [&](size_t bytes) { return b.take(bytes); };
   s.stats = (unsigned long long *)take((RS_STATS + RS_STATS_V) * 8);      // (one 256-byte unit with or without the second eight)
@@ -662,21 +691,21 @@ RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_ca
   s.gn = (float *)take((size_t)n_ld * 4);
   s.qmax = (float *)take(4);
   s.gmax = (float *)take(4);
-  s.qb = (bf16_t *)take((size_t)m * d * 3 * 2);
+  s.qb = (bf16_t *)take((size_t)wn * d * 3 * 2);
   s.gb = (bf16_t *)take((size_t)n_ld * d * 3 * 2);
-  s.rows_per_block = std::min(m, rows_per_block > 0 ? rows_per_block : default_rows_per_block(n_ld));
+  s.rows_per_block = std::min(wn, rows_per_block > 0 ? rows_per_block : default_rows_per_block(n_ld));
   s.dist = (float *)take((size_t)s.rows_per_block * n_ld * 4);
   s.gid = table ? (int *)take((size_t)m * 4) : nullptr;
   s.tgt_c = table ? (int *)take((size_t)n_ld * 4) : nullptr;
   s.dt_r = (double *)take((size_t)m * 8);
   s.dt_c = table ? (double *)take((size_t)n_ld * 8) : s.dt_r;
-  s.lo_r = (float *)take((size_t)m * 4);
-  s.hi_r = (float *)take((size_t)m * 4);
+  s.lo_r = (float *)take((size_t)wn * 4);
+  s.hi_r = (float *)take((size_t)wn * 4);
   s.lo_c = (float *)take((size_t)n_ld * 4);
   s.hi_c = (float *)take((size_t)n_ld * 4);
-  s.zero = (int *)take(((size_t)3 * m + (size_t)(vunit ? 6 : 3) * n_ld) * 4);
-  s.zero_v = vunit ? s.zero + 3 * (size_t)m + 3 * (size_t)n_ld : nullptr;
-  s.cap_r = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(m);      // per direction: 512 pairs per OWNER
+  s.zero = (int *)take(((size_t)3 * wn + (size_t)(vunit ? 6 : 3) * n_ld) * 4);
+  s.zero_v = vunit ? s.zero + 3 * (size_t)wn + 3 * (size_t)n_ld : nullptr;
+  s.cap_r = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(wn);     // per direction: 512 pairs per OWNER
   s.cap_c = reach_capacity > 0 ? (size_t)reach_capacity : rank_default_capacity(n);
   s.pool_r = (int2 *)take(s.cap_r * 8);
   s.pool_c = (int2 *)take(s.cap_c * 8);
@@ -690,24 +719,29 @@ RankWs rank_plan(char *ws, int n, int m, int d, int rows_per_block, int reach_ca
 
 // All entry points: Dir = RankDir (off == nullptr, m == n) or RankDirG.  The policy decides the prologue's target step and nothing after it.
 // rank_v != nullptr (RankDirG, a plan with the video-unit arrays): the video-unit direction rides along, a third pass over every block.
+// [w0, w0 + wn): the rows of D this call sweeps (RankDir only, a plan made for wn; everything but vtc_l2_rank_shard passes 0, m).  The row
+// direction then has wn owners, numbered from w0 (its arrays and rank_a have wn entries), and the column direction counts every column
+// over those rows alone: rank_b holds partial counts that add up over windows that tile the rows (rank_write_kernel).  The blocks carry
+// global row ids, the thresholds are those of the whole matrix, so a window settles exactly the whole sweep's pairs that lie in it.
 template <typename Dir>
-int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *off, int n, int m, int d, int64_t *rank_a, int64_t *rank_b,
-                    int *nonfinite, const RankWs &s, hipStream_t stream, int64_t *rank_v = nullptr) {
+int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *off, int n, int m, int w0, int wn, int d, int64_t *rank_a,
+                    int64_t *rank_b, int *nonfinite, const RankWs &s, hipStream_t stream, int64_t *rank_v = nullptr) {
   constexpr bool table = rank_has_table<Dir>;
   const int n_ld = s.n_ld;
-  int *cnt_r = s.zero, *reach_r = s.zero + (size_t)m, *ovf_r = s.zero + 2 * (size_t)m;
-  int *cnt_c = s.zero + 3 * (size_t)m, *reach_c = cnt_c + (size_t)n_ld, *ovf_c = cnt_c + 2 * (size_t)n_ld;
+  int *cnt_r = s.zero, *reach_r = s.zero + (size_t)wn, *ovf_r = s.zero + 2 * (size_t)wn;
+  int *cnt_c = s.zero + 3 * (size_t)wn, *reach_c = cnt_c + (size_t)n_ld, *ovf_c = cnt_c + 2 * (size_t)n_ld;
   auto dir = [](const RankDir &p, const int *tgt) {
     if constexpr (table) return RankDirG{p, tgt};
     else return p;
   };
-  // gallery a, query b_c: the rows of D (m owners, n others);  gallery b, query a_v: its columns (n owners, m others)
-  const RankDir r{b, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r, s.dt_r, m, n};
-  const RankDir c{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c, s.dt_c, n, m};
+  // gallery a, query b_c: the rows of D (wn owners from row w0, n others);  gallery b, query a_v: its columns (n owners, the wn rows as others,
+  // under their global ids)
+  const RankDir r{b + (size_t)w0 * d, a, s.lo_r, s.hi_r, cnt_r, reach_r, ovf_r, s.pool_r, s.stats + 0, (unsigned long long)s.cap_r, s.dt_r + w0, wn, n, w0};
+  const RankDir c{a, b, s.lo_c, s.hi_c, cnt_c, reach_c, ovf_c, s.pool_c, s.stats + 1, (unsigned long long)s.cap_c, s.dt_c, n, wn, 0};
   const Dir R = dir(r, s.gid), Cd = dir(c, s.tgt_c);
   // owner = video v, other = GROUP u: the column direction's thresholds and target distance, counters and a pool of its own
   int *cnt_v = s.zero_v, *reach_v = rank_v ? cnt_v + (size_t)n_ld : nullptr, *ovf_v = rank_v ? cnt_v + 2 * (size_t)n_ld : nullptr;
-  const RankDir vu{a, b, s.lo_c, s.hi_c, cnt_v, reach_v, ovf_v, s.pool_v, s.stats + RS_STATS, (unsigned long long)s.cap_v, s.dt_c, n, m};
+  const RankDir vu{a, b, s.lo_c, s.hi_c, cnt_v, reach_v, ovf_v, s.pool_v, s.stats + RS_STATS, (unsigned long long)s.cap_v, s.dt_c, n, m, 0};
   (void)hipMemsetAsync(s.stats, 0, (RS_STATS + (rank_v ? RS_STATS_V : 0)) * 8, stream);
   (void)hipMemsetAsync(nonfinite, 0, sizeof(int), stream);
   if (int rc = vtc_nonfinite_flag2(a, (size_t)n * d, b, (size_t)m * d, nonfinite, stream)) return rc;
@@ -719,11 +753,12 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
     ProfScope prof(VTC_PROF_TOPK, (double)(n + m) * d * (4 + 6 + 4), stream);
     prof.tag(101, m, d);
     const float kappa = split_kappa(d);
-    const RankThresholds tr{s.qn, s.gmax, s.dt_r, s.lo_r, s.hi_r}, tc{s.gn, s.qmax, s.dt_c, s.lo_c, s.hi_c};
+    const RankThresholds tr{s.qn + w0, s.gmax, s.dt_r + w0, s.lo_r, s.hi_r}, tc{s.gn, s.qmax, s.dt_c, s.lo_c, s.hi_c};
     if constexpr (table) hipLaunchKernelGGL(rank_group_id_kernel, dim3(cdiv(m, 256)), dim3(256), 0, stream, off, n, m, s.gid);
-    launch_norms_split(b, m, s.qn, s.qb, a, n, s.gn, s.gb, d, 3, stream);
+    launch_norms_split(b, m, s.qn, s.qb, a, n, s.gn, s.gb, d, 3, stream, w0, wn);      // every norm (max |b|^2 is the whole matrix's), the window's operand rows
     hipLaunchKernelGGL(rank_max_kernel, dim3(2), dim3(256), 0, stream, s.gn, n, s.qn, m, s.gmax, s.qmax);
-    hipLaunchKernelGGL(rank_prep_kernel<Dir>, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, R, tr, tc, n_ld, d, kappa, s.zero, 3 * m + (rank_v ? 6 : 3) * n_ld);
+    hipLaunchKernelGGL(rank_prep_kernel<Dir>, dim3(cdiv(cdiv(m, RS_NB), 4)), dim3(256), 0, stream, R, b, m, tr, tc, n_ld, d, kappa, s.zero,
+                       3 * wn + (rank_v ? 6 : 3) * n_ld);
     if constexpr (table)
       hipLaunchKernelGGL(rank_grouped_target_kernel, dim3(cdiv(n_ld, 256)), dim3(256), 0, stream, off, n, n_ld, m, s.dt_r, s.gn, s.qmax, kappa, s.dt_c,
                          s.tgt_c, s.lo_c, s.hi_c);
@@ -731,16 +766,16 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
   VTC_LAUNCH_CHECK2(fn, "prologue");
   // D is [rows, n_ld].  The row pass scans the n real columns; the column pass takes all n_ld.
   const int n_strips = cdiv(n_ld, 64);
-  for (int r0 = 0; r0 < m; r0 += s.rows_per_block) {
-    const int rows = min(s.rows_per_block, m - r0);
+  for (int r0 = w0; r0 < w0 + wn; r0 += s.rows_per_block) {      // r0: the block's first row of D; r0 - w0: the row direction's owner, the operand row
+    const int rows = min(s.rows_per_block, w0 + wn - r0);
     GemmEpi e;
     e.mode = EPI_L2DIST; e.out_dtype = VTC_F32; e.rown = s.qn + r0; e.coln = s.gn;
-    if (int rc = launch_gemm(s.qb + (size_t)r0 * d * 3, s.gb, nullptr, s.dist, rows, n_ld, d * 3, VTC_BF16, e, stream)) return rc;
+    if (int rc = launch_gemm(s.qb + (size_t)(r0 - w0) * d * 3, s.gb, nullptr, s.dist, rows, n_ld, d * 3, VTC_BF16, e, stream)) return rc;
     {
       const auto [S, seg_cols] = row_segments(rows, n);
       ProfScope prof(VTC_PROF_TOPK, (double)rows * n * 4, stream);
       prof.tag(102, rows, n);
-      hipLaunchKernelGGL(rank_row_count_kernel<Dir>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n, r0, S, seg_cols, R);
+      hipLaunchKernelGGL(rank_row_count_kernel<Dir>, dim3(cdiv(rows * S, 4)), dim3(256), 0, stream, s.dist, n_ld, rows, n, r0 - w0, S, seg_cols, R);
     }
     {
       // (strip, segment) waves: ~32 per CU; a segment is a whole number of the wave's steps of 8 loads x 4 rows
@@ -776,12 +811,13 @@ int rank_sweep_impl(const char *fn, const float *a, const float *b, const int *o
     hipLaunchKernelGGL(rank_settle_kernel<Dir>, dim3(ga + gb), dim3(256), 0, stream, R, Cd, ga, d);
   }
   {
-    const int ga = std::min(m, 1024), gb = std::min(n, 1024);
+    const int ga = std::min(wn, 1024), gb = std::min(n, 1024);
     ProfScope prof(VTC_PROF_TOPK, 0.0, stream);
     prof.tag(105, m, d);
     hipLaunchKernelGGL(rank_brute_kernel<Dir>, dim3(ga + gb), dim3(512), 0, stream, R, Cd, ga, d, s.stats);
   }
-  hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(std::max(n, m), 256)), dim3(256), 0, stream, s.dt_r, s.dt_c, cnt_r, cnt_c, n, m, rank_a, rank_b);
+  hipLaunchKernelGGL(rank_write_kernel, dim3(cdiv(std::max(n, wn), 256)), dim3(256), 0, stream, s.dt_r + w0, s.dt_c, cnt_r, cnt_c, n, m, wn, table ? 0 : w0,
+                     table ? n : w0 + wn, rank_a, rank_b);
   VTC_LAUNCH_CHECK2(fn, "finish");
   return 0;
 }
@@ -808,7 +844,24 @@ extern "C" int vtc_l2_rank_bidir(const float *a, const float *b, int n, int d, i
   if (int rc = rank_check_args("l2_rank_bidir", a && b && rank_a && rank_b && nonfinite, n, -1, d, reach_capacity)) return rc;
   const RankWs s = rank_plan((char *)ws, n, n, d, rows_per_block, reach_capacity, false);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_bidir: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return rank_sweep_impl<RankDir>("l2_rank_bidir", a, b, nullptr, n, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+  return rank_sweep_impl<RankDir>("l2_rank_bidir", a, b, nullptr, n, n, 0, n, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+}
+
+// ---- the paired sweep over a window of rows (one rank of a row-sharded evaluation): include/vtc_hip.h -------------------------------
+extern "C" size_t vtc_l2_rank_shard_workspace_bytes(int n_total, int n_local, int d, int rows_per_block, int reach_capacity) {
+  if (n_total < 1 || d < 1 || n_local < 0 || n_local > n_total) return 0;
+  return rank_plan(nullptr, n_total, n_total, d, rows_per_block, reach_capacity, false, false, n_local).total;
+}
+extern "C" int vtc_l2_rank_shard(const float *a_all, const float *b_all, int n_total, int row_base, int n_local, int d, int rows_per_block,
+                                 int reach_capacity, int64_t *rank_a_local, int64_t *rank_b_part, int *nonfinite, void *ws, size_t ws_bytes,
+                                 void *stream) {
+  if (int rc = rank_check_args("l2_rank_shard", a_all && b_all && rank_a_local && rank_b_part && nonfinite, n_total, -1, d, reach_capacity)) return rc;
+  VTC_CHECK(row_base >= 0 && n_local >= 0 && (long long)row_base + n_local <= n_total,
+            "l2_rank_shard: window row_base=%d, n_local=%d must lie in [0, n_total=%d]", row_base, n_local, n_total);
+  const RankWs s = rank_plan((char *)ws, n_total, n_total, d, rows_per_block, reach_capacity, false, false, n_local);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_shard: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  return rank_sweep_impl<RankDir>("l2_rank_shard", a_all, b_all, nullptr, n_total, n_total, row_base, n_local, d, rank_a_local, rank_b_part, nonfinite,
+                                  s, (hipStream_t)stream);
 }
 
 extern "C" size_t vtc_l2_rank_grouped_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity) {
@@ -820,7 +873,7 @@ extern "C" int vtc_l2_rank_grouped(const float *a, const float *b, const int *of
   if (int rc = rank_check_args("l2_rank_grouped", a && b && off && rank_a && rank_b && nonfinite, n, m, d, reach_capacity)) return rc;
   const RankWs s = rank_plan((char *)ws, n, m, d, rows_per_block, reach_capacity, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return rank_sweep_impl<RankDirG>("l2_rank_grouped", a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
+  return rank_sweep_impl<RankDirG>("l2_rank_grouped", a, b, off, n, m, 0, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream);
 }
 
 extern "C" size_t vtc_l2_rank_grouped_vunit_workspace_bytes(int n, int m, int d, int rows_per_block, int reach_capacity) {
@@ -833,5 +886,5 @@ extern "C" int vtc_l2_rank_grouped_vunit(const float *a, const float *b, const i
   if (int rc = rank_check_args("l2_rank_grouped_vunit", a && b && off && rank_a && rank_b && rank_v && nonfinite, n, m, d, reach_capacity)) return rc;
   const RankWs s = rank_plan((char *)ws, n, m, d, rows_per_block, reach_capacity, true, true);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_rank_grouped_vunit: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  return rank_sweep_impl<RankDirG>("l2_rank_grouped_vunit", a, b, off, n, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream, rank_v);
+  return rank_sweep_impl<RankDirG>("l2_rank_grouped_vunit", a, b, off, n, m, 0, m, d, rank_a, rank_b, nonfinite, s, (hipStream_t)stream, rank_v);
 }

@@ -412,3 +412,58 @@ def sharded_recall(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_t
     h = [v & ((1 << 40) - 1) for v in vals[:nh]] if marked else vals[:nh]
     nk = len(ks)
     return ({k: h[j] / n_total for j, k in enumerate(k_vals)}, {k: h[nk + j] / n_total for j, k in enumerate(k_vals)})
+
+
+def sharded_ranks(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_total: int, rank: int, world: int,
+                  ws: Optional[torch.Tensor] = None,
+                  shard_op: Optional[Callable[[torch.Tensor, torch.Tensor, int, int], tuple]] = None,
+                  phases: Optional[dict] = None):
+    """The exact full ranks of both directions (what RecallAtK.ranks returns on one GPU) for row-sharded embeddings: (rank_a [n_total],
+    rank_b [n_total]) int64, identical on every rank, on the inputs' device.
+
+    all_gather of both sets, then every rank runs the counting sweep over its own rows of the distance matrix (ops.rank_shard: ONE
+    [N/G, N] distance GEMM; rank_a of its rows is complete, rank_b comes as partial counts of every column), then ONE all_reduce(SUM) of
+    one int64 buffer [2 n_total + 1]: zeros with rank_a_local at [lo, hi), the partial rank_b, the non-finite word -- counts are sums, so
+    nothing else is exchanged (8 (2 n_total + 1) bytes per rank).  ``world == 1`` is ops.rank_bidir.
+    ``shard_op(a_all, b_all, row_base, n_local) -> (rank_a_local, rank_b_part, nonfinite_bits)``: a stand-in for ops.rank_shard (tests:
+    the exchange under gloo on CPU tensors).  ``phases`` receives this rank's GPU time per phase in ms (allgather / shard_sweep /
+    allreduce) and the path's label.  Non-finite embeddings on ANY rank raise ValueError on EVERY rank."""
+    lo, hi = shard_bounds(n_total, rank, world)
+    clock = _PhaseClock(phases, feats_a_local.is_cuda)
+    clock.mark("start")
+    assert feats_a_local.shape[0] == hi - lo and feats_b_local.shape[0] == hi - lo
+    a_all, b_all = gather_both(feats_a_local, feats_b_local, n_total, rank, world)
+    clock.mark("allgather")
+    if shard_op is not None:
+        label = "injected shard op"
+    elif world == 1:
+        label = "one distance matrix, exact ranks of every pair (counting sweep)"
+        shard_op = lambda a_, b_, base, nl: ops.rank_bidir(a_, b_, ws=ws)                                              # noqa: E731
+    else:
+        label = "one [N/G, N] distance GEMM per rank, exact ranks of every pair (counting sweep), partial column counts all-reduced"
+        shard_op = lambda a_, b_, base, nl: ops.rank_shard(a_, b_, base, nl, ws=ws)                                    # noqa: E731
+    rank_a_local, rank_b_part, bits = shard_op(a_all, b_all, lo, hi - lo)
+    acc = torch.zeros(2 * n_total + 1, dtype=torch.int64, device=feats_a_local.device)      # rank_a | rank_b | the non-finite word
+    acc[lo:hi] = rank_a_local
+    acc[n_total: 2 * n_total] = rank_b_part
+    acc[2 * n_total:] = torch.as_tensor(bits, device=acc.device).reshape(-1)[:1]
+    clock.mark("shard_sweep")
+    if world > 1:
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        clock.mark("allreduce")
+    flagged = int(acc[2 * n_total].item())      # (the D2H that ends the phases' events)
+    clock.close(label)
+    if flagged != 0:
+        raise ValueError("sharded_ranks: non-finite values in the embeddings of at least one rank -- the ranks of such rows are undefined "
+                         "(vtc_amd.host.model.nonfinite_cause lists what this build knows can produce them)")
+    return acc[:n_total], acc[n_total: 2 * n_total]
+
+
+def sharded_rank_stats(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor, n_total: int, rank: int, world: int,
+                       k_vals: Sequence[int] = (1, 5, 10), **kw):
+    """host.metric.rank_statistics (recall at every k of ``k_vals``, median / mean rank, MRR) of the two rank arrays of sharded_ranks, in
+    its order: (the direction of RecallAtK.compute(a, b), the direction of compute(b, a)).  The same pair of dicts on every rank.
+    Keyword arguments go to sharded_ranks."""
+    from .host.metric import rank_statistics
+    rank_a, rank_b = sharded_ranks(feats_a_local, feats_b_local, n_total, rank, world, **kw)
+    return rank_statistics(rank_a, k_vals), rank_statistics(rank_b, k_vals)

@@ -373,12 +373,12 @@ def _rank_call(name, head, size_args, n_a, n_b, device, rows_per_block, reach_ca
     word, call, return the three."""
     lib = L.lib()
     ws = _ws_for(ws, getattr(lib, name + "_workspace_bytes")(*size_args, rows_per_block, reach_capacity), device)
-    rank_a = torch.empty(n_a, dtype=torch.int64, device=device)
+    rank_a = torch.empty(max(n_a, 1), dtype=torch.int64, device=device)      # (rank_shard's empty window: no null pointer for a tensor without elements)
     rank_b = torch.empty(n_b, dtype=torch.int64, device=device)
     bits = torch.empty(1, dtype=torch.int32, device=device)
     L.check(getattr(lib, name)(*head, rows_per_block, reach_capacity, rank_a.data_ptr(), rank_b.data_ptr(), bits.data_ptr(), ws.data_ptr(),
                                ws.numel(), _stream()), name)
-    return rank_a, rank_b, bits
+    return rank_a[:n_a], rank_b, bits
 
 
 @on_device
@@ -392,6 +392,30 @@ def rank_bidir(a: torch.Tensor, b: torch.Tensor, rows_per_block: int = 0, reach_
     if b.shape != (n, d):
         raise ValueError(f"rank_bidir: paired rows expected, got {tuple(a.shape)} and {tuple(b.shape)}")
     return _rank_call("vtc_l2_rank_bidir", (a.data_ptr(), b.data_ptr(), n, d), (n, d), n, n, a.device, rows_per_block, reach_capacity, ws)
+
+
+def rank_shard(a_all: torch.Tensor, b_all: torch.Tensor, row_base: int, n_local: int, rows_per_block: int = 0, reach_capacity: int = 0,
+               ws: Optional[torch.Tensor] = None):
+    """One rank's share of rank_bidir on row-sharded embeddings (vtc_l2_rank_shard): the rank holds both gathered sets and owns the rows
+    [row_base, row_base + n_local).  Returns (rank_a_local [n_local] int64 = rank_bidir's rank_a[row_base:row_base + n_local], complete;
+    rank_b_part [n_total] int64 = this window's partial counts of rank_b -- their sum over windows that tile [0, n_total) is rank_bidir's
+    rank_b, element for element; nonfinite_bits over both whole sets, as rank_bidir).  An empty window is valid: all-zero partials.  The
+    window is validated on the host (ValueError) before anything is launched."""
+    if a_all.dim() != 2 or a_all.shape[0] < 1 or b_all.shape != a_all.shape:
+        raise ValueError(f"rank_shard: paired rows expected, got {tuple(a_all.shape)} and {tuple(b_all.shape)}")
+    n = a_all.shape[0]
+    row_base, n_local = int(row_base), int(n_local)
+    if row_base < 0 or n_local < 0 or row_base + n_local > n:
+        raise ValueError(f"rank_shard: window row_base={row_base}, n_local={n_local} must lie in [0, n_total={n}]")
+    return _rank_shard(a_all, b_all, row_base, n_local, rows_per_block, reach_capacity, ws)
+
+
+@on_device
+def _rank_shard(a_all, b_all, row_base, n_local, rows_per_block, reach_capacity, ws):
+    a_all, b_all = _gpu(a_all, torch.float32, "a_all"), _gpu(b_all, torch.float32, "b_all")
+    n, d = a_all.shape
+    return _rank_call("vtc_l2_rank_shard", (a_all.data_ptr(), b_all.data_ptr(), n, row_base, n_local, d), (n, n_local, d), n_local, n,
+                      a_all.device, rows_per_block, reach_capacity, ws)
 
 
 def check_offsets(offsets, n: int, m: int, allow_empty: bool = True):
