@@ -205,6 +205,44 @@ size_t vtc_feature_mlp_workspace_bytes(int n, int d);
 int vtc_feature_mlp(const float *x, int n, int d, const float *w1, const float *b1, const float *w2, const float *b2, float *y,
                     void *ws, size_t ws_bytes, void *stream);
 
+/* ---- frame preprocessing: the Resize(size, BICUBIC) + CenterCrop(size) half of CLIP_TRANSFORM
+ * (dataset_loaders/dataset_loaders.py:40-49, video_retrieval_videodatasets.py:21-29); ToTensor + Normalize are the VTC_U8
+ * pixel path of vtc_vision_forward ------------------------------------------------------------------------------------- */
+
+/* Decoded RGB uint8 frames of in_h x in_w -> [n, 3, size, size] uint8, BIT FOR BIT what torchvision's Resize(size) +
+ * CenterCrop(size) give on a PIL image (Pillow's 8-bit resampler, integer arithmetic):
+ *   1. resize target: the shorter edge becomes `size`, the longer trunc((size * long) / short) (the double quotient of the exact
+ *      product); in_w <= in_h: the width is the shorter edge;
+ *   2. two separable passes, horizontal first, the intermediate image rounded to uint8.  Per output index xx of an axis of n_in
+ *      input and n_out output samples: scale = n_in / n_out, fs = max(scale, 1), support = 2 fs, center = (xx + 0.5) scale,
+ *      xmin = max(trunc(center - support + 0.5), 0), count = min(trunc(center + support + 0.5), n_in) - xmin, weights
+ *      bicubic((x + xmin - center + 0.5) * (1 / fs)) with a = -0.5 in double, divided by their sum, each then
+ *      trunc(w 2^22 +- 0.5) (the sign of w); pixel = clamp((2^21 + sum p_x k_x) >> 22, 0, 255), arithmetic shift.  A pass with
+ *      n_in == n_out is the identity;
+ *   3. crop: top = round((out_h - size) / 2), left likewise, ties to even (Python's round);
+ *   only output pixels inside the crop are computed and only the source rows and columns in their support are read.
+ * LIMITS (refused with a status + vtc_last_error, nothing is launched): size a positive multiple of 16 (a plane stays a multiple of
+ * 16 pixels for the VTC_U8 path), at most 1024; 1 <= in_h, in_w <= 8192 (2160 x 3840 and 4320 x 7680 are inside).
+ *
+ * vtc_resize_plan (pure HOST code; plan_host is the one HOST pointer of this group) fills a relocatable table of int32 words:
+ *   [0..15]  header: magic "VRP1", in_h, in_w, size, out_w, out_h, left, top, column taps kx, row taps ky, 0 ...
+ *   then per cropped output COLUMN (size records of 2 + kx words): first source column, count, coefficients[kx] (zero padded),
+ *   then per cropped output ROW    (size records of 2 + ky words): first source row,    count, coefficients[ky].
+ * An identity pass has one tap of 2^22.  vtc_resize_plan_bytes = its size (0 for arguments the plan call refuses).  The caller
+ * uploads the plan once per distinct (in_h, in_w, size).
+ *
+ * vtc_resize_crop_u8: layout 0 = frames [n, in_h, in_w, 3] (what decoders deliver), 1 = [n, 3, in_h, in_w]; frames need no
+ * alignment (rows of in_w * 3 bytes, odd widths included); out [n, 3, size, size] must be 16-byte aligned (rows are written with
+ * 16-byte stores).  One launch: a workgroup takes one frame and a band of 16 (8, 4, 2, 1 when the vertical support is long) output
+ * rows, resamples the source rows in the band's support along x into LDS, then along y out of it; the intermediate image never
+ * reaches memory.  The plan lives in device memory and the call only enqueues, so it cannot read it: the KERNEL compares the plan's
+ * header with the header these arguments imply and, when they disagree, reads no frame and writes nothing (`out` keeps its bytes);
+ * every index taken from the table is clamped, so a damaged plan cannot address outside `frames`, `out` or the LDS. */
+size_t vtc_resize_plan_bytes(int in_h, int in_w, int size);
+int vtc_resize_plan(int in_h, int in_w, int size, void *plan_host, size_t bytes);
+int vtc_resize_crop_u8(const unsigned char *frames, int n, int in_h, int in_w, int layout, const void *plan_dev, int size,
+                       unsigned char *out, void *stream);
+
 /* ---- small fp32 ops of the wrappers (model/model.py:26-27, 338, 357-362, 369) -------- */
 int vtc_normalize_rows(const float *x, float *out, int n, int d, void *stream);
 /* Both embedding sets of a forward in one launch: outx = rows of x [nx, d] / their norms, outy likewise for y [ny, d] (the two

@@ -78,6 +78,10 @@ SIGNATURES = {
                                       vp]),
     "vtc_feature_mlp_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "vtc_feature_mlp": (C.c_int, [fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, vp, C.c_size_t, vp]),
+    # frame preprocessing (preproc.hip); vtc_resize_plan's buffer is a HOST pointer
+    "vtc_resize_plan_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vtc_resize_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_size_t]),
+    "vtc_resize_crop_u8": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "vtc_normalize_rows": (C.c_int, [fp, fp, C.c_int, C.c_int, vp]),
     "vtc_normalize_rows2": (C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, C.c_int, vp, vp]),
     "vtc_mean_groups": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, vp]),

@@ -14,13 +14,17 @@ import torch
 
 @torch.no_grad()
 def cache_clip_vit_embeddings(model, batches: Iterable[torch.Tensor], ids: Sequence[int], out_path: str, device="cuda",
-                              verbose: bool = False) -> dict:
+                              verbose: bool = False, preprocess=None) -> dict:
     """``batches`` yields image tensors [b,3,224,224] (fp32 / bf16 pre-normalised, or raw uint8 -- then the
-    CLIP ToTensor+Normalize is fused into the patch gather).  Returns the saved dict."""
+    CLIP ToTensor+Normalize is fused into the patch gather).  With ``preprocess`` (``model.preprocess`` or a
+    ``ClipPreprocessGPU``) a batch may be decoded frames of any size instead, [b,H,W,3] uint8 or a list of [H,W,3] uint8
+    tensors: Resize + CenterCrop run on the GPU first (host/transforms.py).  Returns the saved dict."""
     model.eval()
     out = []
     for bi, imgs in enumerate(batches):
         tic = time.time()
+        if preprocess is not None:
+            imgs = preprocess(imgs)
         y = model.encode_image(imgs.to(device))              # get_clip_vit_embeddings.py:61
         out.append(y.float().cpu())
         if verbose:

@@ -260,6 +260,14 @@ class PretrainedCLIPBase(nn.Module):
                 raise RuntimeError("vtc_amd: inputs must be on the GPU (no CPU fallback)")
 
     # ---- towers ----------------------------------------------------------------------------
+    def preprocess(self, frames, layout="hwc"):
+        """Decoded RGB uint8 frames -- one tensor [..., H, W, 3] or a list of tensors of different frame sizes, on the CPU or the GPU --
+        -> uint8 [..., 3, res, res] at the visual tower's own input resolution: Resize(res, BICUBIC) + CenterCrop(res) of the reference's
+        CLIP_TRANSFORM (dataset_loaders/dataset_loaders.py:40-49), bit for bit (host/transforms.py).  The result is what forward() /
+        encode_image() take as raw pixels (ToTensor + Normalize are fused into the patch gather)."""
+        from .transforms import ClipPreprocessGPU
+        return ClipPreprocessGPU(self.model.visual.input_resolution, next(self.parameters()).device, layout)(frames)
+
     def encode_image(self, image):
         return self._pack()["visual"].forward(image)
 

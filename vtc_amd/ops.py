@@ -164,6 +164,66 @@ def single_query_attention(qkv: torch.Tensor, q: torch.Tensor, n_out: int, L_: i
     return out
 
 
+# ---- frame preprocessing --------------------------------------------------------------------
+_RESIZE_PLANS: dict = {}     # (device, in_h, in_w, size) -> the plan in device memory (int32)
+
+
+def _resize_plan(in_h: int, in_w: int, size: int, device) -> torch.Tensor:
+    key = (device, in_h, in_w, size)
+    plan = _RESIZE_PLANS.get(key)
+    if plan is None:
+        lib = L.lib()
+        nbytes = lib.vtc_resize_plan_bytes(in_h, in_w, size)
+        host = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32)
+        L.check(lib.vtc_resize_plan(in_h, in_w, size, host.data_ptr(), nbytes), "vtc_resize_plan")
+        if len(_RESIZE_PLANS) >= 256:        # a dataset has a handful of frame sizes; do not grow without bound on adversarial input
+            _RESIZE_PLANS.clear()
+        plan = _RESIZE_PLANS[key] = host.to(device)
+    return plan
+
+
+def clip_resize_crop(frames: torch.Tensor, size: int = 224, layout: str = "hwc", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Resize(size, BICUBIC) + CenterCrop(size) of CLIP_TRANSFORM (dataset_loaders/dataset_loaders.py:40-49) on decoded RGB uint8 frames,
+    bit for bit what torchvision gives on PIL images (vtc_resize_crop_u8).  frames: [..., H, W, 3] (layout "hwc", what decoders deliver) or
+    [..., 3, H, W] ("chw") with zero, one or two leading dimensions (n, or batch x frames), uint8 on the GPU; returns [..., 3, size, size]
+    uint8, what the towers' uint8 pixel path takes.  ``out``: a contiguous uint8 tensor of that shape, 16-byte aligned.  Bad arguments
+    raise ValueError before anything is launched; plans are cached per (H, W, size) and device."""
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"clip_resize_crop: layout {layout!r} (\"hwc\" or \"chw\")")
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise ValueError(f"clip_resize_crop: uint8 frames expected, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() not in (3, 4, 5):
+        raise ValueError(f"clip_resize_crop: frames of rank 3, 4 or 5 expected ([..., H, W, 3] or [..., 3, H, W]), got {tuple(frames.shape)}")
+    lead = tuple(frames.shape[:-3])
+    ch, (in_h, in_w) = (frames.shape[-1], frames.shape[-3:-1]) if layout == "hwc" else (frames.shape[-3], frames.shape[-2:])
+    if ch != 3:
+        raise ValueError(f"clip_resize_crop: 3 channels expected in layout {layout!r}, got shape {tuple(frames.shape)}")
+    size = int(size)
+    if size <= 0 or size % 16 or L.lib().vtc_resize_plan_bytes(int(in_h), int(in_w), size) == 0:
+        raise ValueError(f"clip_resize_crop: size={size} must be a positive multiple of 16 (at most 1024) and the frame edges "
+                         f"({in_h} x {in_w}) within [1, 8192]")
+    n = 1
+    for d in lead:
+        n *= int(d)
+    if n < 1:
+        raise ValueError(f"clip_resize_crop: no frames in shape {tuple(frames.shape)}")
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != lead + (3, size, size) or not out.is_contiguous()
+                            or out.device != frames.device or out.data_ptr() % 16):
+        raise ValueError(f"clip_resize_crop: out must be a contiguous, 16-byte aligned uint8 tensor of shape {lead + (3, size, size)} on {frames.device}")
+    return _clip_resize_crop(frames, n, int(in_h), int(in_w), size, 0 if layout == "hwc" else 1, lead, out)
+
+
+@on_device
+def _clip_resize_crop(frames, n, in_h, in_w, size, layout, lead, out):
+    frames = _gpu(frames, torch.uint8, "frames")
+    plan = _resize_plan(in_h, in_w, size, frames.device)
+    if out is None:
+        out = torch.empty(lead + (3, size, size), dtype=torch.uint8, device=frames.device)
+    L.check(L.lib().vtc_resize_crop_u8(frames.data_ptr(), n, in_h, in_w, layout, plan.data_ptr(), size, out.data_ptr(), _stream()),
+            "vtc_resize_crop_u8")
+    return out
+
+
 # ---- wrapper-level fp32 ops ---------------------------------------------------------------
 @on_device
 def normalize_rows(x: torch.Tensor) -> torch.Tensor:
