@@ -328,6 +328,31 @@ int vtc_l2_sweep_shard_rows(const float *a_all, const float *b_local, int n_tota
 int vtc_l2_sweep_shard_cols(const float *b_all, const float *a_local, int n_total, int n_local, int d, int depth,
                             const unsigned *planes, int n_src, int nblk_pad, const int *src_base, int64_t *ids, float *dists,
                             void *ws, size_t ws_bytes, void *stream);
+/* Query-time search: the exact nearest rows of a stored gallery for a FEW queries (no reference counterpart: the reference only evaluates).
+ * With D(q, j) the fp64 value sum_k (queries[q][k] - gallery[j][k])^2 of the fp32 inputs (the one device function of the sweeps, so a
+ * distance has the bits every other entry point gives it and exact ties are bit-equal):
+ *   ids[q, 0 .. depth)  (int64)  = id_base + j for the `depth` gallery rows with the smallest (D(q, j), j), compared lexicographically, ascending
+ *   dists[q, p]  (fp32, may be NULL) = (float) D
+ * A gallery row whose distance is not finite is never returned; when fewer than `depth` rows have a finite distance the tail of the row is
+ * ids = -1, dists = +inf, and so is the whole row of a query with a NaN / inf coordinate.  nonfinite[0] (int32, device, may be NULL; the
+ * word of the rank family, here ORed into: the caller zeroes it) |= 1 if the gallery holds a NaN / inf, |= 2 if the queries do.
+ * The gallery is streamed and never rewritten: no operand planes, no distance matrix, no candidate lists -- one pass over the gallery per
+ * TILE of queries (1 query: 1 pass; 2: 1; 3-4: 1; more: ceil(n_queries / 8) passes), every workgroup of the scan leaving one sorted list per
+ * query in the workspace, and a second small launch merging them.  Two launches, no allocation, no host sync.
+ * The fp64 distances of the result stay in the workspace: after the call its first n_queries * depth doubles are D of ids[q, p] (+inf where
+ * ids is -1) -- what vtc_l2_search_merge takes, since the fp32 dists alone would break ties that the fp64 values decide.
+ * LIMITS (refused with a status + vtc_last_error, nothing is launched): 1 <= n_queries <= 64 (more: vtc_l2_topk), 1 <= depth <=
+ * min(64, n_gallery), d % 64 == 0 and 64 <= d <= 2048, n_gallery >= 1, id_base >= 0, non-null gallery / queries / ids, ws_bytes >=
+ * vtc_l2_search_workspace_bytes(...), which is 0 for arguments the call refuses. */
+size_t vtc_l2_search_workspace_bytes(int n_gallery, int n_queries, int d, int depth);
+int vtc_l2_search(const float *gallery, const float *queries, int n_gallery, int n_queries, int d, int depth, int64_t id_base,
+                  int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* The lists of n_parts searches over DISJOINT gallery windows (each with its window's id_base) -> the list of the union: ids_parts
+ * [n_parts, n_queries, depth] (int64) and dists_parts of the same shape (DOUBLE: the head of each search's workspace), entries with a
+ * negative id ignored; ids / dists (fp32, may be NULL) [n_queries, depth] = the first `depth` of the union by (dist, id), padded with
+ * -1 / +inf.  1 <= n_parts <= 64, 1 <= n_queries <= 64, 1 <= depth <= 64; one launch. */
+int vtc_l2_search_merge(const int64_t *ids_parts, const double *dists_parts, int n_parts, int n_queries, int depth, int64_t *ids,
+                        float *dists, void *stream);
 /* hits[j] += #{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);

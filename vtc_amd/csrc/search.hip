@@ -1,0 +1,333 @@
+// search.hip -- query-time search: the exact top-`depth` of a FEW queries (1 .. 64) over a stored gallery, vtc_l2_search, and the merge of
+// such lists over disjoint gallery windows, vtc_l2_search_merge.  The N x N sweeps (sweep_topk.hip) split the gallery into bf16 operand
+// planes, run a distance GEMM, select, and settle the result in fp64; at a handful of queries all of that is overhead.  Here the gallery
+// is streamed ONCE per tile of queries and the fp64 distances of sweep_common.h are formed directly: exact by construction, so there are
+// no candidate lists, error bounds or certification, and nothing of the gallery is written.
+//
+//   search_scan_kernel<NQ, NR>   a grid of persistent workgroups; the tile of NQ queries lives in the LDS for the whole scan; each wave
+//                                takes groups of NR gallery rows round-robin (NQ x NR distances per step, all their loads in flight together)
+//                                and keeps one sorted (fp64 distance, row) list per query, an entry per lane.  The list's last key is held in
+//                                scalar registers: a row that is not closer than the current depth-th costs one compare.  The four waves'
+//                                lists are merged in the LDS; a workgroup writes ONE list per query to the workspace.
+//   merge_kernel<Src>            one workgroup per query merges the workgroups' lists (Src = ScanLists) or the caller's partial lists
+//                                (Src = PartLists): the lists are sorted, so a lane follows one list and leaves at its first entry that
+//                                does not beat the current depth-th.
+#include "sweep_common.h"
+
+#include <algorithm>
+
+namespace {
+using namespace vtcsweep;
+
+constexpr int SEARCH_MAX_Q = 64, SEARCH_MAX_DEPTH = 64, SEARCH_MAX_D = 2048, SEARCH_MAX_PARTS = 64;
+constexpr int SEARCH_MAX_BLOCKS = 1024;       // workgroups of a scan (4 per CU on a 256-CU part): the number of lists per query in the workspace
+constexpr int EMPTY_ROW = 0x7fffffff;         // index of an empty list slot (distance +inf)
+constexpr long long EMPTY_ID = 0x7fffffffffffffffll;
+
+__device__ __forceinline__ double uniform_f64(double v) {      // a wave-uniform value -> scalar registers
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+__device__ __forceinline__ int uniform_of(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ long long uniform_of(long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// A sorted list of (fp64 distance, index) keys, one entry per lane, ascending; the first `depth` lanes are the list, (tau, tau_i) its last
+// key, wave-uniform.  Empty slots hold (+inf, EMPTY).  The insertion is exact_fallback_kernel's `offer` (sweep_topk.hip).
+template <typename I>
+struct WaveList {
+  double bd, tau;
+  I bi, tau_i;
+  __device__ __forceinline__ void init(I empty) {
+    bd = tau = INFINITY;
+    bi = tau_i = empty;
+  }
+  // wave-uniform candidate: is it finite and before the depth-th entry?
+  __device__ __forceinline__ bool beats(double cv, I ci) const { return cv < INFINITY && (cv < tau || (cv == tau && ci < tau_i)); }
+  __device__ __forceinline__ void insert(double cv, I ci, int lane, int depth) {
+    const bool less = bd < cv || (bd == cv && bi < ci);
+    const int pos = __popcll(__ballot(less));
+    const double ud = __shfl_up(bd, 1, 64);
+    const I ui = __shfl_up(bi, 1, 64);
+    if (lane > pos) { bd = ud; bi = ui; }
+    if (lane == pos) { bd = cv; bi = ci; }
+    tau = uniform_f64(__shfl(bd, depth - 1, 64));
+    tau_i = uniform_of(__shfl(bi, depth - 1, 64));
+  }
+  __device__ __forceinline__ void offer(double cv, I ci, int lane, int depth) {
+    if (beats(cv, ci)) insert(cv, ci, lane, depth);
+  }
+};
+
+// Merges the sorted lists list0, list0 + stride, ... < nlists into wl, 64 lists at a time: lane l follows list l0 + l entry by entry
+// (src(list, e, cv, ci): the entry, cv = +inf for an empty one) and drops out at the first entry that does not beat the current
+// depth-th -- the rest of a sorted list cannot either.  The entries that do are offered one by one.
+template <typename Src>
+__device__ __forceinline__ void merge_lists(WaveList<long long> &wl, Src src, int nlists, int list0, int stride, int depth, int lane) {
+  for (int l0 = list0; l0 < nlists; l0 += stride) {       // wave-uniform
+    const int l = l0 + lane;
+    bool alive = l < nlists;
+    for (int e = 0; e < depth; ++e) {
+      double cv = INFINITY;
+      long long ci = EMPTY_ID;
+      if (alive) src(l, e, cv, ci);
+      alive = alive && wl.beats(cv, ci);
+      unsigned long long m = __ballot(alive);
+      if (!m) break;
+      while (m) {
+        const int from = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), lane, depth);
+      }
+    }
+  }
+}
+
+// the lists the scan's workgroups wrote: [query][entry][list], so that the 64 lanes of a merge step read neighbours
+struct ScanLists {
+  const double *d;
+  const int *i;
+  int nlists, depth, q;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci) const {
+    const size_t o = ((size_t)q * depth + e) * nlists + l;
+    cv = d[o];
+    ci = i[o];
+  }
+};
+// the caller's partial lists [part][query][depth]; an entry with a negative id is empty
+struct PartLists {
+  const double *d;
+  const int64_t *i;
+  int nq, depth, q;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci) const {
+    const size_t o = ((size_t)l * nq + q) * depth + e;
+    ci = i[o];
+    cv = ci < 0 ? INFINITY : d[o];
+  }
+};
+// the four waves' lists of a workgroup in the LDS: sd / si [4][64]
+struct LdsLists {
+  const double *sd;
+  const long long *si;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci) const {
+    cv = sd[l * 64 + e];
+    ci = si[l * 64 + e];
+  }
+};
+
+// LDS of the scan: the query tile, then (re-used) the waves' lists of the tile's queries
+constexpr size_t scan_lds_bytes(int nq_tile, int d) {
+  const size_t tile = (size_t)nq_tile * d * sizeof(float), lists = (size_t)nq_tile * 4 * 64 * (sizeof(double) + sizeof(long long));
+  return tile > lists ? tile : lists;
+}
+
+template <int NQ, int NR>
+__global__ __launch_bounds__(256) void search_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries, int ng, int nq, int d,
+                                                          int depth, double *__restrict__ part_d, int *__restrict__ part_i,
+                                                          int *__restrict__ nonfinite) {
+  extern __shared__ float4 smem4[];
+  float *qt = reinterpret_cast<float *>(smem4);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q0 = blockIdx.y * NQ;
+  // ---- the query tile -> LDS; a query with a NaN / inf (and a slot past the last query) becomes a row of zeros that is never offered
+  // to: every distance formed below then has finite query terms, so it is non-finite exactly when the GALLERY row holds a NaN / inf.
+  const int d4 = d >> 2;
+  unsigned bad_bits = 0;
+  for (int x = tid; x < NQ * d4; x += 256) {
+    const int u = x / d4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q0 + u < nq) v = reinterpret_cast<const float4 *>(queries + (size_t)(q0 + u) * d)[x - u * d4];
+    if (!(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w))) bad_bits |= 1u << u;
+    smem4[x] = v;
+  }
+  unsigned dead = 0;                                       // bit u: query q0 + u takes no candidates (uniform for the workgroup)
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    const int bad = __syncthreads_or((bad_bits >> u) & 1);
+    if (bad || q0 + u >= nq) dead |= 1u << u;
+    if (bad) {
+      for (int x = tid; x < d4; x += 256) smem4[u * d4 + x] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (nonfinite && blockIdx.x == 0 && tid == 0) atomicOr(nonfinite, 2);
+    }
+  }
+  __syncthreads();
+
+  // ---- the scan: wave gw of GW takes the row groups gw, gw + GW, ...: ascending rows, so exact ties keep (distance, row) order
+  WaveList<int> wl[NQ];
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) wl[u].init(EMPTY_ROW);
+  bool gallery_bad = false;
+  const long long n_groups = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
+  for (long long s = (long long)blockIdx.x * 4 + wave; s < n_groups; s += GW) {
+    int jj[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) jj[r] = (int)min(s * NR + r, (long long)ng - 1);    // a slot past the gallery: clamped, its results dropped
+    double dist[NQ * NR];
+    wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      if (s * NR + r < ng) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          const double cv = dist[u * NR + r];
+          if (!(cv < INFINITY)) gallery_bad = true;
+          else if (!((dead >> u) & 1) && wl[u].beats(cv, jj[r])) wl[u].insert(cv, jj[r], lane, depth);
+        }
+      }
+    }
+  }
+  if (nonfinite && gallery_bad && lane == 0) atomicOr(nonfinite, 1);
+
+  // ---- the workgroup's four lists of a query -> one: wave w merges the queries w, w + 4, ...
+  __syncthreads();                                         // every wave is done with the query tile
+  double *sd = reinterpret_cast<double *>(smem4);          // [NQ][4][64]
+  long long *si = reinterpret_cast<long long *>(sd + NQ * 4 * 64);      // 64-bit indices: what merge_lists reads
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    sd[(u * 4 + wave) * 64 + lane] = wl[u].bd;
+    si[(u * 4 + wave) * 64 + lane] = wl[u].bi == EMPTY_ROW ? EMPTY_ID : (long long)wl[u].bi;
+  }
+  __syncthreads();
+  const int nlists = gridDim.x;
+  for (int u = wave; u < NQ; u += 4) {
+    if (q0 + u >= nq) break;
+    WaveList<long long> m;
+    m.init(EMPTY_ID);
+    merge_lists(m, LdsLists{sd + u * 4 * 64, si + u * 4 * 64}, 4, 0, 64, depth, lane);
+    if (lane < depth) {
+      const size_t o = ((size_t)(q0 + u) * depth + lane) * nlists + blockIdx.x;
+      part_d[o] = m.bd;
+      part_i[o] = m.bi == EMPTY_ID ? EMPTY_ROW : (int)m.bi;
+    }
+  }
+}
+
+// One workgroup per query: the first `depth` of the union of the lists by (distance, index).
+template <typename Src>
+__global__ __launch_bounds__(256) void merge_kernel(Src src, int nlists, int depth, int64_t id_base, int64_t *__restrict__ ids,
+                                                    float *__restrict__ dists, double *__restrict__ dists64) {
+  __shared__ double sd[4][64];
+  __shared__ long long si[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x;
+  src.q = q;
+  WaveList<long long> wl;
+  wl.init(EMPTY_ID);
+  merge_lists(wl, src, nlists, wave * 64, 256, depth, lane);
+  sd[wave][lane] = wl.bd;
+  si[wave][lane] = wl.bi;
+  __syncthreads();
+  if (wave != 0) return;
+  merge_lists(wl, LdsLists{&sd[1][0], &si[1][0]}, 3, 0, 64, depth, lane);
+  if (lane < depth) {
+    const size_t o = (size_t)q * depth + lane;
+    const bool empty = wl.bi == EMPTY_ID;
+    ids[o] = empty ? -1 : id_base + wl.bi;
+    if (dists) dists[o] = empty ? INFINITY : (float)wl.bd;
+    if (dists64) dists64[o] = empty ? (double)INFINITY : wl.bd;
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+struct SearchPlan {
+  int tile_q, tile_r;       // queries of a tile (a gallery pass each), gallery rows of a step
+  int tiles;
+};
+SearchPlan search_plan(int nq) {
+  SearchPlan p;
+  if (nq == 1) p.tile_q = 1, p.tile_r = 4;
+  else if (nq == 2) p.tile_q = 2, p.tile_r = 4;
+  else if (nq <= 4) p.tile_q = 4, p.tile_r = 2;
+  else p.tile_q = 8, p.tile_r = 1;
+  p.tiles = cdiv(nq, p.tile_q);
+  return p;
+}
+bool search_args_ok(int ng, int nq, int d, int depth) {
+  return ng >= 1 && nq >= 1 && nq <= SEARCH_MAX_Q && depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng && d >= 64 && d <= SEARCH_MAX_D &&
+         d % 64 == 0;
+}
+// lists per query the workspace has room for: no scan has more workgroups than groups of four rows
+int search_max_lists(int ng) { return (int)std::min<long long>(SEARCH_MAX_BLOCKS, ((long long)ng + 3) / 4); }
+struct SearchWs {
+  double *dists64, *part_d;
+  int *part_i;
+  size_t total;
+};
+SearchWs search_ws(void *ws, int ng, int nq, int depth) {
+  Bump b(ws);
+  SearchWs s;
+  const size_t entries = (size_t)nq * depth;
+  s.dists64 = (double *)b.take(entries * sizeof(double));            // FIRST: the documented region of the header
+  s.part_d = (double *)b.take(entries * search_max_lists(ng) * sizeof(double));
+  s.part_i = (int *)b.take(entries * search_max_lists(ng) * sizeof(int));
+  s.total = b.off;
+  return s;
+}
+
+// The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
+// most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
+template <int NQ, int NR>
+int launch_scan(const float *gallery, const float *queries, int ng, int nq, int d, int depth, const SearchWs &s, int tiles, int *nonfinite,
+                hipStream_t stream) {
+  // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
+  static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  std::atomic<int> &slot = resident[dev][d / 64 - 1];
+  int per_cu = slot.load(std::memory_order_relaxed);
+  if (per_cu == 0) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_scan_kernel<NQ, NR>, 256, scan_lds_bytes(NQ, d)) != hipSuccess || per_cu < 1)
+      per_cu = 1;
+    slot.store(per_cu, std::memory_order_relaxed);
+  }
+  const long long n_groups = ((long long)ng + NR - 1) / NR;
+  const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
+  hipLaunchKernelGGL((search_scan_kernel<NQ, NR>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, ng, nq, d, depth,
+                     s.part_d, s.part_i, nonfinite);
+  return blocks;
+}
+}  // namespace
+
+extern "C" size_t vtc_l2_search_workspace_bytes(int n_gallery, int n_queries, int d, int depth) {
+  if (!search_args_ok(n_gallery, n_queries, d, depth)) return 0;
+  return search_ws(nullptr, n_gallery, n_queries, depth).total;
+}
+
+extern "C" int vtc_l2_search(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int64_t id_base, int64_t *ids,
+                             float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && ids, "l2_search: null argument");
+  VTC_CHECK(ng >= 1, "l2_search: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search: n_queries=%d must be in [1, %d] (more queries: vtc_l2_topk)", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search: depth=%d must be in [1, min(%d, n_gallery)]", depth, SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "l2_search: id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const SearchPlan p = search_plan(nq);
+  int blocks;
+  if (p.tile_q == 1) blocks = launch_scan<1, 4>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  else if (p.tile_q == 2) blocks = launch_scan<2, 4>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  else if (p.tile_q == 4) blocks = launch_scan<4, 2>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  else blocks = launch_scan<8, 1>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  VTC_LAUNCH_CHECK2("l2_search", "scan");
+  hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth, id_base,
+                     ids, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search", "merge");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_merge(const int64_t *ids_parts, const double *dists_parts, int n_parts, int nq, int depth, int64_t *ids,
+                                   float *dists, void *stream) {
+  VTC_CHECK(ids_parts && dists_parts && ids, "l2_search_merge: null argument");
+  VTC_CHECK(n_parts >= 1 && n_parts <= SEARCH_MAX_PARTS, "l2_search_merge: n_parts=%d must be in [1, %d]", n_parts, SEARCH_MAX_PARTS);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_merge: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH, "l2_search_merge: depth=%d must be in [1, %d]", depth, SEARCH_MAX_DEPTH);
+  hipLaunchKernelGGL(merge_kernel<PartLists>, dim3(nq), dim3(256), 0, (hipStream_t)stream, PartLists{dists_parts, ids_parts, nq, depth, 0}, n_parts,
+                     depth, (int64_t)0, ids, dists, (double *)nullptr);
+  VTC_LAUNCH_CHECK("l2_search_merge");
+  return 0;
+}

@@ -59,6 +59,13 @@ __device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, 
                                                   int d, int lane, double (&out)[NB]) {
   wave_dist64_core<NB>([&](int u) { return qs + (size_t)qi[u] * d; }, [&](int u) { return gs + (size_t)gi[u] * d; }, d, lane, out);
 }
+// the NB consecutive query rows qs[0 .. NB) (row stride d; global memory or LDS) against the NR gallery rows jj[] (valid indices, as above):
+// out[u * NR + r] = query u, gallery row jj[r].  The query-time search (search.hip): its tile of queries stays put while the gallery streams by.
+template <int NB, int NR = 1>
+__device__ __forceinline__ void wave_dist64_queries(const float *qs, const float *__restrict__ gallery, const int (&jj)[NR], int d, int lane,
+                                                    double (&out)[NB * NR]) {
+  wave_dist64_core<NB * NR>([&](int p) { return qs + (size_t)(p / NR) * d; }, [&](int p) { return gallery + (size_t)jj[p % NR] * d; }, d, lane, out);
+}
 
 // ---- host pieces, defined in sweep_front.hip ----------------------------------------------------------------------------------------
 // |x|^2 of both sets and, for parts = 3 / 1, their split-bf16 operand rows ([hi | lo | hi] queries, [hi | hi | lo] gallery / [hi]); parts = 0: norms only.

@@ -467,3 +467,30 @@ def sharded_rank_stats(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor,
     from .host.metric import rank_statistics
     rank_a, rank_b = sharded_ranks(feats_a_local, feats_b_local, n_total, rank, world, **kw)
     return rank_statistics(rank_a, k_vals), rank_statistics(rank_b, k_vals)
+
+
+def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int, world: int):
+    """Query-time search over a gallery that is row-sharded across ranks: this rank stores the rows [row_base, row_base + n_local) of the
+    index (fp32 [n_local, d], d % 64 == 0) and every rank holds the same queries [Q <= 64, d].  Returns (ids [Q, k] int64 -- global row
+    ids --, dists [Q, k] fp32), identical on every rank and equal to ops.l2_search over the whole gallery.
+
+    A local ops.l2_search_part(id_base = row_base), ONE all_gather of the partial lists -- ids and fp64 distances in one int64 buffer
+    [2, Q, k] per rank: the fp32 distances alone would break ties that the fp64 values decide --, then ops.l2_search_merge.  A rank with
+    fewer than k rows (none, too) sends a list padded with -1 / +inf; world <= 64 (the merge's limit on parts).  No multi-GPU box has
+    run this: what is tested is the code path at world = 1 and the windowed merge on one card (tests/test_gpu_search.py)."""
+    if not 1 <= world <= 64:
+        raise ValueError(f"sharded_search: world={world} must be in [1, 64]")
+    nq, n_local = queries.shape[0], index_rows_local.shape[0]
+    if n_local:
+        ids, d64, _ = ops.l2_search_part(index_rows_local, queries, min(int(k), n_local), id_base=int(row_base))
+        ids, d64 = ops.pad_search_part(ids, d64, int(k))
+    else:
+        ids = torch.full((nq, int(k)), -1, dtype=torch.int64, device=queries.device)
+        d64 = torch.full((nq, int(k)), float("inf"), dtype=torch.float64, device=queries.device)
+    mine = torch.stack([ids, d64.contiguous().view(torch.int64)])                 # [2, Q, k]: one buffer, one collective
+    if world > 1:
+        parts = torch.empty((world,) + tuple(mine.shape), dtype=torch.int64, device=mine.device)
+        dist.all_gather_into_tensor(parts, mine.contiguous())
+    else:
+        parts = mine[None]
+    return ops.l2_search_merge(parts[:, 0].contiguous(), parts[:, 1].contiguous().view(torch.float64))

@@ -359,6 +359,81 @@ def l2_topk_bidir(a: torch.Tensor, b: torch.Tensor, depth: int, precision: int =
     return ids1, d1, ids2, d2
 
 
+SEARCH_MAX_QUERIES = 64       # vtc_l2_search's limit; more queries go through l2_topk
+
+
+@on_device
+def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
+              ws: Optional[torch.Tensor] = None):
+    """Query-time search (vtc_l2_search): the exact ``depth`` nearest gallery rows of at most 64 queries, by the fp64 squared distances of
+    the fp32 rows, ties to the lower row.  Returns (ids [Q, depth] int64 = id_base + row, -1 where fewer rows have a finite distance;
+    dists [Q, depth] fp32 or None; nonfinite_bits, a device int32 [1]: 1 = the gallery holds a NaN / inf, 2 = the queries do).  With a
+    caller's ``ws`` of at least ``l2_search_workspace_bytes`` the fp64 distances of the result are ``search_dists64(ws, Q, depth)``."""
+    gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise ValueError(f"l2_search: gallery rows have {d} columns, queries {queries.shape[1]}")
+    need = L.lib().vtc_l2_search_workspace_bytes(ng, nq, d, depth)
+    if ws is None:
+        ws = workspace(need, gallery.device)
+    elif need and (ws.numel() < need or ws.device != gallery.device):
+        # never a silent fresh workspace here: the caller reads the fp64 list out of the tensor it passed
+        raise ValueError(f"l2_search: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on {gallery.device}")
+    ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
+    bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
+    L.check(L.lib().vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, int(id_base), ids.data_ptr(),
+                                  dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            "vtc_l2_search")
+    return ids, dists, bits
+
+
+def l2_search_workspace_bytes(n_gallery: int, n_queries: int, d: int, depth: int) -> int:
+    """0 for a shape vtc_l2_search refuses."""
+    return int(L.lib().vtc_l2_search_workspace_bytes(int(n_gallery), int(n_queries), int(d), int(depth)))
+
+
+def search_dists64(ws: torch.Tensor, n_queries: int, depth: int) -> torch.Tensor:
+    """The fp64 distances [Q, depth] of the last l2_search that ran in ``ws`` (a view of the workspace's head: the next call overwrites it)."""
+    return ws[:n_queries * depth * 8].view(torch.float64).view(n_queries, depth)
+
+
+@on_device
+def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0):
+    """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
+    l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list)."""
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
+    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws)
+    return ids, search_dists64(ws, nq, depth), bits
+
+
+@on_device
+def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return_dists: bool = True):
+    """The lists of searches over disjoint gallery windows -> the list of their union (vtc_l2_search_merge).  ids_parts [P, Q, depth] int64
+    and dists64_parts [P, Q, depth] fp64 (l2_search_part's outputs, stacked; entries with id -1 are ignored); returns (ids [Q, depth],
+    dists fp32 or None): the first ``depth`` by (distance, id)."""
+    ids_parts, dists64_parts = _gpu(ids_parts, torch.int64, "ids_parts"), _gpu(dists64_parts, torch.float64, "dists64_parts")
+    if ids_parts.dim() != 3 or dists64_parts.shape != ids_parts.shape:
+        raise ValueError(f"l2_search_merge: [parts, queries, depth] lists expected, got {tuple(ids_parts.shape)} and {tuple(dists64_parts.shape)}")
+    n_parts, nq, depth = ids_parts.shape
+    ids = torch.empty(nq, depth, dtype=torch.int64, device=ids_parts.device)
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=ids_parts.device) if return_dists else None
+    L.check(L.lib().vtc_l2_search_merge(ids_parts.data_ptr(), dists64_parts.data_ptr(), n_parts, nq, depth, ids.data_ptr(),
+                                        dists.data_ptr() if dists is not None else None, _stream()), "vtc_l2_search_merge")
+    return ids, dists
+
+
+def pad_search_part(ids: torch.Tensor, dists64: torch.Tensor, depth: int):
+    """A window's lists widened to ``depth`` columns with empty entries (-1 / +inf): windows with fewer rows than the merged list's depth."""
+    short = depth - ids.shape[1]
+    if short <= 0:
+        return ids, dists64
+    return (torch.nn.functional.pad(ids, (0, short), value=-1), torch.nn.functional.pad(dists64, (0, short), value=float("inf")))
+
+
 def sweep_shard_supported(n_total: int, n_local: int, depth: int) -> bool:
     return bool(L.lib().vtc_l2_sweep_shard_supported(int(n_total), int(n_local), int(depth)))
 
