@@ -347,6 +347,25 @@ int vtc_l2_sweep_shard_cols(const float *b_all, const float *a_local, int n_tota
 size_t vtc_l2_search_workspace_bytes(int n_gallery, int n_queries, int d, int depth);
 int vtc_l2_search(const float *gallery, const float *queries, int n_gallery, int n_queries, int d, int depth, int64_t id_base,
                   int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* vtc_l2_search over the LIVE rows of the gallery only: a deleted row, or a query that searches a subset (one subreddit, one split).
+ * live (uint32, device, ceil(n_gallery / 32) words; only read): row j takes part iff bit (j & 31) of live[j >> 5] is set; the bits at
+ * and above n_gallery in the last word are ignored, whatever they hold.  live == NULL: every row takes part -- the call IS vtc_l2_search
+ * (same launches, same bits).
+ * The result is that of vtc_l2_search over the gallery COMPACTED to its live rows in order, every returned position mapped back to the
+ * row's original index: ids = id_base + j of the live rows with the smallest (D(q, j), j); ties go to the lower original row (compaction
+ * keeps order); a live row with a non-finite distance is never returned; fewer than `depth` live finite rows leave a tail of -1 / +inf
+ * (the ordinary outcome of a small subset).  A dead row influences nothing -- not ids, not dists, not nonfinite (a NaN in a removed row
+ * does not set bit 0) -- and its memory is not read: a step of the scan none of whose rows is live issues no gallery load, so a filter
+ * costs about its live fraction of the scan.  The fp64 distances stay at the head of the workspace as above, so vtc_l2_search_merge takes
+ * masked partial lists unchanged.  No compaction: rows keep their index.
+ * LIMITS: those of vtc_l2_search, including depth <= n_gallery, which counts the PHYSICAL rows (the number of live ones is not known on
+ * the host); the workspace is vtc_l2_search_workspace_bytes(...).  vtc_l2_topk has no mask. */
+int vtc_l2_search_masked(const float *gallery, const float *queries, const uint32_t *live, int n_gallery, int n_queries, int d, int depth,
+                         int64_t id_base, int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* Packs row flags into the words vtc_l2_search_masked reads: words[w] (ceil(n_rows / 32) of them) bit b = (flags[32 w + b] != 0), ANDed
+ * with and_mask[w] when and_mask is non-null (a subset intersected with the rows that are still live); the bits past n_rows are written
+ * as 0.  flags: uint8 [n_rows], device.  One launch, no atomics.  n_rows >= 1; null flags / words are refused (status + vtc_last_error). */
+int vtc_row_mask_pack(const uint8_t *flags, int n_rows, const uint32_t *and_mask, uint32_t *words, void *stream);
 /* The lists of n_parts searches over DISJOINT gallery windows (each with its window's id_base) -> the list of the union: ids_parts
  * [n_parts, n_queries, depth] (int64) and dists_parts of the same shape (DOUBLE: the head of each search's workspace), entries with a
  * negative id ignored; ids / dists (fp32, may be NULL) [n_queries, depth] = the first `depth` of the union by (dist, id), padded with

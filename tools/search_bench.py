@@ -11,7 +11,21 @@ Per (n_gallery, n_queries) one JSON line:
                         ceil(Q / 8) above four queries) -- against the 6.0 - 6.3 TB/s streaming read of an MI355X
   same_ids              the two entries returned the same ids (asserted)
 Unit rows from a seeded generator on the device, queries = gallery rows plus noise (a retrieval query has near neighbours).  One process
-on an otherwise idle card.  profiles/search.md holds a run's table; VideoIndex.ROUTE_TOPK_MIN_QUERIES cites it."""
+on an otherwise idle card.  profiles/search.md holds a run's table; VideoIndex.ROUTE_TOPK_MIN_QUERIES cites it.
+
+With --live the tool measures the MASKED scan (ops.l2_search(live=...) = vtc_l2_search_masked) instead:
+
+    python tools/search_bench.py --live 1.0,0.5,0.1,0.01 [--live-pattern random|blocked] [--topk-gathered] [--queries 1,8] ...
+
+Per (n_gallery, n_queries, live fraction, pattern) one JSON line:
+  masked_us / unmasked_us   the masked scan and the UNMASKED ops.l2_search over the same gallery (every row), in alternation as above
+  masked_over_unmasked      ratio of the medians; at fraction 1.0 the mask is pure overhead and the ratio should stay within 1.05
+  same_ids_as_compacted     the masked ids equal those of the unmasked search over the gallery compacted to its live rows, mapped back
+                            (asserted; the compaction is outside the timing)
+  topk_gathered_us          with --topk-gathered: gallery[live rows] gathered into a fresh tensor and ops.l2_topk(EXACT) over it, the gather
+                            INSIDE the timing -- what routing many masked queries to vtc_l2_topk would cost
+`random` draws every row's bit independently; `blocked` makes one contiguous run of rows live (a subreddit whose rows were added
+together), starting at an odd row a third of the way in.  profiles/search_masked.md holds a run's table."""
 import argparse
 import json
 import os
@@ -43,6 +57,72 @@ def passes(nq):
     return 1 if nq <= 4 else -(-nq // 8)
 
 
+def live_mask(ng, fraction, pattern, gen):
+    if fraction >= 1.0:
+        return torch.ones(ng, dtype=torch.bool, device="cuda")
+    if pattern == "random":
+        return torch.rand(ng, device="cuda", generator=gen) < fraction
+    m = torch.zeros(ng, dtype=torch.bool, device="cuda")
+    lo = (ng // 3) | 1
+    m[lo:lo + max(1, int(round(fraction * ng)))] = True
+    return m
+
+
+def masked_main(args):
+    lib = L.lib()
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        gallery = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(gallery[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            ws_m = ops.workspace(lib.vtc_l2_search_workspace_bytes(ng, nq, args.d, args.depth), gallery.device)
+            ws_u = ops.workspace(lib.vtc_l2_search_workspace_bytes(ng, nq, args.d, args.depth), gallery.device)
+            for fraction in [float(x) for x in args.live.split(",")]:
+                flags = live_mask(ng, fraction, args.live_pattern, gen)
+                words = ops.row_mask_pack(flags)
+                idx = torch.nonzero(flags).reshape(-1)
+                n_live = int(idx.numel())
+                assert n_live >= args.depth, "fewer live rows than the depth: nothing to compare"
+                masked = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws_m, live=words)                 # noqa: E731
+                unmasked = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws_u)                           # noqa: E731
+
+                def topk():
+                    rows = gallery[idx]
+                    ws_t = ops.workspace(lib.vtc_l2_topk_workspace_bytes(n_live, nq, args.d, L.SWEEP_EXACT, 0), gallery.device)
+                    return ops.l2_topk(rows, queries, args.depth, precision=L.SWEEP_EXACT, ws=ws_t)
+                entries = [masked, unmasked] + ([topk] if args.topk_gathered else [])
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times = [[] for _ in entries]
+                for _ in range(args.calls):
+                    for t, fn in zip(times, entries):
+                        us, out = timed(fn)
+                        t.append(us)
+                        if fn is masked:
+                            ids_m = out[0]
+                compact = gallery[idx].contiguous()
+                ids_c = ops.l2_search(compact, queries, args.depth)[0]
+                same = bool(torch.equal(ids_m, idx[ids_c]))
+                del compact
+                m, u = stat(times[0]), stat(times[1])
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "live": fraction,
+                        "pattern": args.live_pattern if fraction < 1.0 else "all", "n_live": n_live, "masked_us": m, "unmasked_us": u,
+                        "masked_over_unmasked": round(m["median"] / u["median"], 3), "passes": passes(nq), "same_ids_as_compacted": same}
+                if args.topk_gathered:
+                    line["topk_gathered_us"] = stat(times[2])
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                assert same, "the masked scan and the unmasked search over the compacted gallery returned different ids"
+            del ws_m, ws_u
+        del gallery
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -52,9 +132,15 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--live", type=str, default=None, help="live fractions, e.g. 1.0,0.5,0.1,0.01: measure the masked scan (see above)")
+    ap.add_argument("--live-pattern", type=str, default="random", choices=("random", "blocked"))
+    ap.add_argument("--topk-gathered", action="store_true", help="with --live: also time gather + l2_topk(EXACT) over the live rows")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.live:
+        write_out(args.out, masked_main(args))
+        return
     lib = L.lib()
     gen = torch.Generator(device="cuda").manual_seed(5)
     lines = []
@@ -91,9 +177,13 @@ def main(argv=None):
             del ws_s, ws_t
         del gallery
         torch.cuda.empty_cache()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    write_out(args.out, lines)
+
+
+def write_out(out, lines):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.writelines(json.dumps(ln) + "\n" for ln in lines)
 
 

@@ -106,6 +106,8 @@ SIGNATURES = {
                                           C.c_size_t, vp]),
     "vtc_l2_search_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtc_l2_search": (C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, fp, ip, vp, C.c_size_t, vp]),
+    "vtc_l2_search_masked": (C.c_int, [fp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, fp, ip, vp, C.c_size_t, vp]),
+    "vtc_row_mask_pack": (C.c_int, [vp, C.c_int, ip, ip, vp]),
     "vtc_l2_search_merge": (C.c_int, [ip, fp, C.c_int, C.c_int, C.c_int, ip, fp, vp]),
     "vtc_recall_hits": (C.c_int, [ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp]),
     "vtc_recall_hits_pair": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp, vp]),

@@ -1,10 +1,12 @@
 // search.hip -- query-time search: the exact top-`depth` of a FEW queries (1 .. 64) over a stored gallery, vtc_l2_search, and the merge of
-// such lists over disjoint gallery windows, vtc_l2_search_merge.  The N x N sweeps (sweep_topk.hip) split the gallery into bf16 operand
+// such lists over disjoint gallery windows, vtc_l2_search_merge; vtc_l2_search_masked is the same scan over the rows whose bit of a row
+// mask is set (a deleted row, a query that searches a subset), vtc_row_mask_pack packs such a mask.  The N x N sweeps (sweep_topk.hip) split the gallery into bf16 operand
 // planes, run a distance GEMM, select, and settle the result in fp64; at a handful of queries all of that is overhead.  Here the gallery
 // is streamed ONCE per tile of queries and the fp64 distances of sweep_common.h are formed directly: exact by construction, so there are
 // no candidate lists, error bounds or certification, and nothing of the gallery is written.
 //
-//   search_scan_kernel<NQ, NR>   a grid of persistent workgroups; the tile of NQ queries lives in the LDS for the whole scan; each wave
+//   search_scan_kernel<NQ, NR, MASKED>
+//                                a grid of persistent workgroups; the tile of NQ queries lives in the LDS for the whole scan; each wave
 //                                takes groups of NR gallery rows round-robin (NQ x NR distances per step, all their loads in flight together)
 //                                and keeps one sorted (fp64 distance, row) list per query, an entry per lane.  The list's last key is held in
 //                                scalar registers: a row that is not closer than the current depth-th costs one compare.  The four waves'
@@ -123,10 +125,15 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
   return tile > lists ? tile : lists;
 }
 
-template <int NQ, int NR>
-__global__ __launch_bounds__(256) void search_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries, int ng, int nq, int d,
-                                                          int depth, double *__restrict__ part_d, int *__restrict__ part_i,
-                                                          int *__restrict__ nonfinite) {
+// MASKED: only the rows whose bit of `live` is set take part (vtc_l2_search_masked).  A step's NR rows start at a multiple of NR, which
+// divides 32: their bits lie in ONE word, and the step -- so the word -- is wave-uniform.  The wave reads the word of its NEXT step while
+// it works on this one; a step with no live row issues no gallery load, and in a partly live one a dead slot is pointed at a live row of
+// the same step and its results are dropped, exactly as a slot past the gallery is: a dead row's memory is never read.  The mask is only
+// read.  Without MASKED `live` is not looked at and the kernel is the scan of vtc_l2_search.
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void search_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
+                                                          const unsigned *__restrict__ live, int ng, int nq, int d, int depth,
+                                                          double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
   extern __shared__ float4 smem4[];
   float *qt = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -160,15 +167,38 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
   for (int u = 0; u < NQ; ++u) wl[u].init(EMPTY_ROW);
   bool gallery_bad = false;
   const long long n_groups = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
-  for (long long s = (long long)blockIdx.x * 4 + wave; s < n_groups; s += GW) {
+  // The mask word of step s's rows, as loaded: every lane reads the same address with an ordinary (vector) load, which returns in order
+  // -- requested a step ahead, before that step's gallery rows, it has arrived by the time they have and is never waited for on its own.
+  auto live_word = [&](long long s) -> unsigned { return live[(s * NR) >> 5]; };
+  // bit r: row s * NR + r is live and inside the gallery (wave-uniform, moved to a scalar register only here, where it is used)
+  auto live_bits = [&](long long s, unsigned word) -> unsigned {
+    const int j0 = (int)(s * NR), left = ng - j0;          // s < n_groups: j0 < ng, left >= 1
+    const unsigned inside = NR == 1 || left >= NR ? (1u << NR) - 1 : (1u << left) - 1;
+    return (unsigned)uniform_of((int)((word >> (j0 & 31)) & inside));
+  };
+  long long s = (long long)blockIdx.x * 4 + wave;
+  unsigned next_word = 0;
+  if constexpr (MASKED) {
+    if (s < n_groups) next_word = live_word(s);
+  }
+  for (; s < n_groups; s += GW) {
+    unsigned bits = 0;
+    if constexpr (MASKED) {
+      bits = live_bits(s, next_word);
+      if (s + GW < n_groups) next_word = live_word(s + GW);
+      if (!bits) continue;                                 // nothing live in this step: no gallery load
+    }
     int jj[NR];
 #pragma unroll
-    for (int r = 0; r < NR; ++r) jj[r] = (int)min(s * NR + r, (long long)ng - 1);    // a slot past the gallery: clamped, its results dropped
+    for (int r = 0; r < NR; ++r) {
+      if constexpr (MASKED) jj[r] = (int)(s * NR) + (NR == 1 || ((bits >> r) & 1) ? r : __ffs((int)bits) - 1);      // a dead slot: a live row of the step
+      else jj[r] = (int)min(s * NR + r, (long long)ng - 1);                                           // a slot past the gallery: clamped
+    }                                                                                                 // (the results of both are dropped)
     double dist[NQ * NR];
     wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-      if (s * NR + r < ng) {
+      if (MASKED ? (bits >> r) & 1 : s * NR + r < ng) {
 #pragma unroll
         for (int u = 0; u < NQ; ++u) {
           const double cv = dist[u * NR + r];
@@ -268,9 +298,9 @@ SearchWs search_ws(void *ws, int ng, int nq, int depth) {
 
 // The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
 // most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
-template <int NQ, int NR>
-int launch_scan(const float *gallery, const float *queries, int ng, int nq, int d, int depth, const SearchWs &s, int tiles, int *nonfinite,
-                hipStream_t stream) {
+template <int NQ, int NR, bool MASKED>
+int launch_scan(const float *gallery, const float *queries, const unsigned *live, int ng, int nq, int d, int depth, const SearchWs &s, int tiles,
+                int *nonfinite, hipStream_t stream) {
   // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
   static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
   int dev = 0;
@@ -278,15 +308,47 @@ int launch_scan(const float *gallery, const float *queries, int ng, int nq, int 
   std::atomic<int> &slot = resident[dev][d / 64 - 1];
   int per_cu = slot.load(std::memory_order_relaxed);
   if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_scan_kernel<NQ, NR>, 256, scan_lds_bytes(NQ, d)) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_scan_kernel<NQ, NR, false>, 256, scan_lds_bytes(NQ, d)) != hipSuccess || per_cu < 1)
       per_cu = 1;
+    // The masked scan runs the unmasked scan's grid (never more than is resident of its own), so both leave the same number of lists.
+    // The 8 x 1 tile takes fewer registers with the mask and would fit a fourth workgroup per CU; every wave fills lists of its own
+    // before it starts rejecting rows, and with all rows live at 10^5 rows the fourth workgroup put the masked scan 4.5 - 5.8 % behind
+    // the unmasked one instead of 3.4 - 3.6 %.  It was 2.5 % faster at 10^6 rows and 4 - 12 % on partly live masks there: the trade is
+    // written down in profiles/search_masked.md.
+    int own = per_cu;
+    if (MASKED && hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_scan_kernel<NQ, NR, true>, 256, scan_lds_bytes(NQ, d)) == hipSuccess && own >= 1)
+      per_cu = std::min(per_cu, own);
     slot.store(per_cu, std::memory_order_relaxed);
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  hipLaunchKernelGGL((search_scan_kernel<NQ, NR>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, ng, nq, d, depth,
-                     s.part_d, s.part_i, nonfinite);
+  hipLaunchKernelGGL((search_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live, ng,
+                     nq, d, depth, s.part_d, s.part_i, nonfinite);
   return blocks;
+}
+// the instantiation of the plan's tile shape
+template <bool MASKED>
+int launch_scan_tile(const SearchPlan &p, const float *gallery, const float *queries, const unsigned *live, int ng, int nq, int d, int depth,
+                     const SearchWs &s, int *nonfinite, hipStream_t stream) {
+  if (p.tile_q == 1) return launch_scan<1, 4, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  if (p.tile_q == 2) return launch_scan<2, 4, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  if (p.tile_q == 4) return launch_scan<4, 2, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  return launch_scan<8, 1, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+}
+
+// words[w] bit b = (flags[32 w + b] != 0) & and_mask[w] bit b: a thread per row, a ballot per wave -- 64 rows, two words, written by
+// two lanes.  A row past n_rows votes 0, so the tail bits are 0.
+__global__ __launch_bounds__(256) void row_mask_pack_kernel(const uint8_t *__restrict__ flags, int n_rows, const unsigned *__restrict__ and_mask,
+                                                            unsigned *__restrict__ words) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m = __ballot(row < n_rows && flags[row] != 0);
+  const long long w = (row >> 6) * 2 + lane;               // lanes 0 and 1: the wave's two words
+  if (lane < 2 && w < ((long long)n_rows + 31) / 32) {
+    unsigned v = (unsigned)(m >> (32 * lane));
+    if (and_mask) v &= and_mask[w];
+    words[w] = v;
+  }
 }
 }  // namespace
 
@@ -295,8 +357,8 @@ extern "C" size_t vtc_l2_search_workspace_bytes(int n_gallery, int n_queries, in
   return search_ws(nullptr, n_gallery, n_queries, depth).total;
 }
 
-extern "C" int vtc_l2_search(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int64_t id_base, int64_t *ids,
-                             float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
+extern "C" int vtc_l2_search_masked(const float *gallery, const float *queries, const uint32_t *live, int ng, int nq, int d, int depth,
+                                    int64_t id_base, int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   VTC_CHECK(gallery && queries && ids, "l2_search: null argument");
   VTC_CHECK(ng >= 1, "l2_search: n_gallery=%d must be at least 1", ng);
@@ -308,15 +370,25 @@ extern "C" int vtc_l2_search(const float *gallery, const float *queries, int ng,
   const SearchWs s = search_ws(ws, ng, nq, depth);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_search: workspace too small (%zu < %zu)", ws_bytes, s.total);
   const SearchPlan p = search_plan(nq);
-  int blocks;
-  if (p.tile_q == 1) blocks = launch_scan<1, 4>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  else if (p.tile_q == 2) blocks = launch_scan<2, 4>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  else if (p.tile_q == 4) blocks = launch_scan<4, 2>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  else blocks = launch_scan<8, 1>(gallery, queries, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  const int blocks = live ? launch_scan_tile<true>(p, gallery, queries, live, ng, nq, d, depth, s, nonfinite, stream)
+                          : launch_scan_tile<false>(p, gallery, queries, nullptr, ng, nq, d, depth, s, nonfinite, stream);
   VTC_LAUNCH_CHECK2("l2_search", "scan");
   hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth, id_base,
                      ids, dists, s.dists64);
   VTC_LAUNCH_CHECK2("l2_search", "merge");
+  return 0;
+}
+
+extern "C" int vtc_l2_search(const float *gallery, const float *queries, int ng, int nq, int d, int depth, int64_t id_base, int64_t *ids,
+                             float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream) {
+  return vtc_l2_search_masked(gallery, queries, nullptr, ng, nq, d, depth, id_base, ids, dists, nonfinite, ws, ws_bytes, stream);
+}
+
+extern "C" int vtc_row_mask_pack(const uint8_t *flags, int n_rows, const uint32_t *and_mask, uint32_t *words, void *stream) {
+  VTC_CHECK(flags && words, "row_mask_pack (the search's row mask): null argument");
+  VTC_CHECK(n_rows >= 1, "row_mask_pack (the search's row mask): n_rows=%d must be at least 1", n_rows);
+  hipLaunchKernelGGL(row_mask_pack_kernel, dim3(cdiv(n_rows, 256)), dim3(256), 0, (hipStream_t)stream, flags, n_rows, and_mask, words);
+  VTC_LAUNCH_CHECK("row_mask_pack");
   return 0;
 }
 

@@ -9,6 +9,12 @@ is what a retrieval model is for:
 
 The search is exact: fp64 squared distances of the stored fp32 rows, ties to the earlier row (libvtc_hip.so, vtc_l2_search for up to
 ``ROUTE_TOPK_MIN_QUERIES - 1`` queries, vtc_l2_topk(EXACT) above; both return the same ids by construction).  No CPU path.
+
+Rows can go away and a query can search part of the gallery; both are one bit per row that the scan reads (vtc_l2_search_masked):
+
+    index.remove([17, 42])                            # ids are never reused, nothing is renumbered or compacted
+    cats = index.subset(subreddit_of_row == 3)        # bool [ntotal] or ids; reusable across queries
+    ids, scores = index.search_text(model, title_tokens, k=10, subset=cats)
 """
 from __future__ import annotations
 
@@ -17,10 +23,52 @@ import torch
 from .. import _lib as L
 from .. import ops
 
-__all__ = ["VideoIndex"]
+__all__ = ["VideoIndex", "RowSubset"]
+
+
+def _id_tensor(ids, ntotal, device, what):
+    """An int64 id sequence or tensor -> int64 [m] on ``device``; an id outside [0, ntotal) raises ValueError (a device-to-host read)."""
+    ids = torch.as_tensor(ids)
+    if ids.numel() == 0:
+        return torch.empty(0, dtype=torch.int64, device=device)
+    if ids.dtype == torch.bool or ids.is_floating_point() or ids.is_complex():
+        raise ValueError(f"VideoIndex.{what}: ids must be integers, got {ids.dtype}")
+    ids = ids.to(device=device, dtype=torch.int64).reshape(-1)
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= ntotal):
+        raise ValueError(f"VideoIndex.{what}: ids must be in [0, ntotal = {ntotal}), got {int(ids.min())} .. {int(ids.max())}")
+    return ids
+
+
+class RowSubset:
+    """The rows of one VideoIndex a query may return (``VideoIndex.subset``): built once, passed to any number of searches.  Rows added
+    to the index afterwards are not members.  It keeps its packed words ANDed with the index's live rows and packs them again (one
+    launch, vtc_row_mask_pack) only when the index has changed since -- a query with an unchanged subset adds no launch and no host sync
+    over an unmasked one."""
+
+    def __init__(self, index, flags):
+        self.index = index
+        self._flags = flags                 # uint8 [ntotal when built or last refreshed]
+        self._words = None
+        self._generation = -1
+
+    def words(self):
+        index = self.index
+        if self._generation != index._generation:
+            n = index.ntotal
+            if self._flags.shape[0] > n:
+                raise ValueError(f"RowSubset: built for {self._flags.shape[0]} rows, the index now holds {n} (its state was reloaded)")
+            if self._flags.shape[0] < n:
+                self._flags = torch.nn.functional.pad(self._flags, (0, n - self._flags.shape[0]))
+            self._words = ops.row_mask_pack(self._flags, and_mask=index._live_words())
+            self._generation = index._generation
+        return self._words
 
 
 class VideoIndex:
+    """A gallery of fp32 rows on the GPU with exact nearest-row search.  Ids are positions in insertion order and are never reused:
+    ``ntotal`` counts the rows ever added, ``len(index)`` the live ones, ``remove`` only clears a row's bit (no compaction, no
+    renumbering; the memory stays).  With nothing removed and no ``subset`` a search is routed as the constants below say; otherwise it
+    is the masked scan (vtc_l2_search_masked) for any number of queries, in slices of 64 -- vtc_l2_topk has no mask."""
     #: queries per call from which search() goes through ops.l2_topk(precision=SWEEP_EXACT) instead of ops.l2_search (which takes up to
     #: 64).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
     #: vtc_l2_topk): the scan's time grows with the number of queries (one gallery pass per started tile of 8), vtc_l2_topk's does not.
@@ -49,9 +97,24 @@ class VideoIndex:
         self._rows = torch.empty(0, self.width, dtype=torch.float32, device=device)       # capacity rows; the first _n are the index
         self._n = 0
         self._ws = None
+        self._live = None                   # bool [ntotal] on the device once a row was removed; None: every row is live
+        self._n_live = 0
+        self._generation = 0                # bumped by add / remove / load_state_dict: what a RowSubset's cached words are valid for
+        self._words = None                  # (generation, packed words of _live)
 
     def __len__(self):
+        """The number of live rows."""
+        return self._n_live
+
+    @property
+    def ntotal(self):
+        """The number of rows ever added: one more than the largest id."""
         return self._n
+
+    @property
+    def live_mask(self):
+        """bool [ntotal] on the device (a copy): False for a removed row."""
+        return torch.ones(self._n, dtype=torch.bool, device=self.device) if self._live is None else self._live.clone()
 
     # ---- rows ----------------------------------------------------------------------------------
     def _prepared(self, x, what, check=True):
@@ -74,7 +137,8 @@ class VideoIndex:
         return x
 
     def add(self, embeddings):
-        """Appends [n, dim] fp32 rows; their ids are their positions in insertion order.  Returns the id of the first one."""
+        """Appends [n, dim] fp32 rows; their ids are their positions in insertion order (removed ids are not reused).  Returns the id of
+        the first one, which is ``ntotal`` before the call."""
         x = self._prepared(embeddings, "embeddings")
         first, n = self._n, x.shape[0]
         if first + n > self._rows.shape[0]:                 # amortised doubling
@@ -83,15 +147,62 @@ class VideoIndex:
             self._rows = grown
         self._rows[first:first + n] = x
         self._n = first + n
+        if n:
+            self._n_live += n
+            if self._live is not None:
+                self._live = torch.cat([self._live, torch.ones(n, dtype=torch.bool, device=self.device)])
+            self._generation += 1
         return first
+
+    def remove(self, ids):
+        """Removes the rows with these ids (an int64 sequence or tensor) from every later search; returns how many were live until now.
+        Duplicates and ids already removed are ignored; an id outside [0, ntotal) raises ValueError and changes nothing.  Reads the count
+        back from the device (a host sync): removal is not the query path."""
+        ids = _id_tensor(ids, self._n, self.device, "remove")
+        if ids.numel() == 0:
+            return 0
+        live = torch.ones(self._n, dtype=torch.bool, device=self.device) if self._live is None else self._live
+        ids = torch.unique(ids)
+        newly = int(live[ids].sum())
+        if newly:
+            live[ids] = False
+            self._live = live
+            self._n_live -= newly
+            self._generation += 1
+        return newly
+
+    def subset(self, members):
+        """The rows a search may return, as a reusable ``RowSubset``: ``members`` is a bool [ntotal] tensor or int64 ids (a sequence or a
+        tensor; an id outside [0, ntotal) raises ValueError).  Removed rows stay out whatever ``members`` says."""
+        m = torch.as_tensor(members)
+        if m.dtype == torch.bool:
+            if tuple(m.shape) != (self._n,):
+                raise ValueError(f"VideoIndex.subset: a bool mask must be [ntotal = {self._n}], got {tuple(m.shape)}")
+            flags = m.to(self.device).contiguous().view(torch.uint8).clone()
+        else:
+            ids = _id_tensor(m, self._n, self.device, "subset")
+            flags = torch.zeros(self._n, dtype=torch.uint8, device=self.device)
+            flags[ids] = 1
+        return RowSubset(self, flags)
+
+    def _live_words(self):
+        """The packed words of the live rows (None while nothing was removed), packed once per generation."""
+        if self._live is None:
+            return None
+        if self._words is None or self._words[0] != self._generation:
+            self._words = (self._generation, ops.row_mask_pack(self._live))
+        return self._words[1]
 
     @property
     def rows(self):
-        """The stored rows [len, width] (a view)."""
+        """The stored rows [ntotal, width] (a view), removed ones included."""
         return self._rows[:self._n]
 
     def state_dict(self):
-        return {"rows": self.rows[:, :self.dim].clone(), "count": self._n, "dim": self.dim, "normalized": self.normalized}
+        state = {"rows": self.rows[:, :self.dim].clone(), "count": self._n, "dim": self.dim, "normalized": self.normalized}
+        if self._live is not None:
+            state["live"] = self._live.clone()
+        return state
 
     def load_state_dict(self, state):
         rows = torch.as_tensor(state["rows"])
@@ -101,7 +212,16 @@ class VideoIndex:
         if rows.shape[0] and ops.nonfinite_bits(rows.contiguous(), rows.contiguous()):
             raise ValueError("VideoIndex.load_state_dict: non-finite values in the stored rows")
         self._rows = torch.nn.functional.pad(rows, (0, self.width - self.dim)).contiguous()     # stored rows are final: not normalised again
+        live = state.get("live")
+        if live is not None:
+            live = torch.as_tensor(live)
+            if live.dtype != torch.bool or tuple(live.shape) != (rows.shape[0],):
+                raise ValueError(f"VideoIndex.load_state_dict: live must be bool [{rows.shape[0]}], got {live.dtype} {tuple(live.shape)}")
+            live = live.to(self.device).clone()
         self._n = rows.shape[0]
+        self._live = live
+        self._n_live = self._n if live is None else int(live.sum())
+        self._generation += 1
 
     # ---- search --------------------------------------------------------------------------------
     def _workspace(self, nbytes):
@@ -110,16 +230,21 @@ class VideoIndex:
             self._ws = ops.workspace(nbytes, self.device)
         return self._ws
 
-    def search(self, queries, k):
+    def search(self, queries, k, subset=None):
         """(ids [Q, k] int64, scores [Q, k] fp32), both on the device: the k nearest stored rows of every query, nearest first, and
-        score = 1 - |q - g|^2 / 2, the cosine for unit rows.  1 <= k <= min(64, len(index)).
+        score = 1 - |q - g|^2 / 2, the cosine for unit rows.  1 <= k <= min(64, len(index)), len being the live rows.
         Fewer than ROUTE_TOPK_MIN_QUERIES queries -- batch 1 is the design point -- are only enqueued: no device-to-host read, no host
         sync.  A query with a NaN / inf (or an all-zero row, which has no direction) is not rejected there; the scan gives it a row of
         ids -1 and scores -inf.  From ROUTE_TOPK_MIN_QUERIES queries on the queries are checked first, as add() checks its rows, and a
-        non-finite one raises ValueError: vtc_l2_topk has no defined answer for such a row."""
+        non-finite one raises ValueError: vtc_l2_topk has no defined answer for such a row.
+        After a ``remove``, or with a ``subset`` (a RowSubset of this index), only the live members are searched: the masked scan for any
+        number of queries, 64 per call, with the few-query rule for a non-finite query (a row of -1 / -inf, no raise, no read) and no host
+        sync.  A subset with fewer than k live members gives rows that end in -1 / -inf."""
         k = int(k)
-        if not 1 <= k <= min(self.MAX_K, self._n):
-            raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n})]")
+        if not 1 <= k <= min(self.MAX_K, self._n_live):
+            raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+        if subset is not None or self._live is not None:
+            return self._search_masked(queries, k, subset)
         scan = 0 < len(queries) < min(self.ROUTE_TOPK_MIN_QUERIES, ops.SEARCH_MAX_QUERIES + 1)
         q = self._prepared(queries, "queries", check=not scan)
         if q.shape[0] == 0:
@@ -133,7 +258,20 @@ class VideoIndex:
             ids, dists = ops.l2_topk(g, q, k, precision=L.SWEEP_EXACT, ws=ws)
         return ids, 1.0 - dists / 2.0
 
-    def search_text(self, model, title_tokens, k, comments=None):
+    def _search_masked(self, queries, k, subset):
+        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
+            raise ValueError("VideoIndex.search: the subset belongs to another index (build it with this index's subset())")
+        q = self._prepared(queries, "queries", check=False)
+        if q.shape[0] == 0:
+            raise ValueError("VideoIndex.search: no queries")
+        words = self._live_words() if subset is None else subset.words()
+        g, step = self.rows, ops.SEARCH_MAX_QUERIES
+        ws = self._workspace(ops.l2_search_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
+        out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
+        ids, dists = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
+        return ids, 1.0 - dists / 2.0
+
+    def search_text(self, model, title_tokens, k, comments=None, subset=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a
         ``*_finaltf`` model that adapts the text branch (branch_to_adapt_val == "text"), ``comments`` [Q, n_comments, ctx] adapts the
         query through the Context Adapter Module as the wrapper's eval forward does."""
@@ -146,4 +284,4 @@ class VideoIndex:
             b, ncomms, ntoks = comments.shape
             feats_comm = model.encode_text(comments.reshape(b * ncomms, ntoks))
             feats = model._pack()["cam"].forward(feats, feats_comm, comments)
-        return self.search(ops.normalize_rows(feats.float().contiguous()), k)
+        return self.search(ops.normalize_rows(feats.float().contiguous()), k, subset=subset)

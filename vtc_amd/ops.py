@@ -364,16 +364,24 @@ SEARCH_MAX_QUERIES = 64       # vtc_l2_search's limit; more queries go through l
 
 @on_device
 def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
-              ws: Optional[torch.Tensor] = None):
+              ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
     """Query-time search (vtc_l2_search): the exact ``depth`` nearest gallery rows of at most 64 queries, by the fp64 squared distances of
     the fp32 rows, ties to the lower row.  Returns (ids [Q, depth] int64 = id_base + row, -1 where fewer rows have a finite distance;
     dists [Q, depth] fp32 or None; nonfinite_bits, a device int32 [1]: 1 = the gallery holds a NaN / inf, 2 = the queries do).  With a
-    caller's ``ws`` of at least ``l2_search_workspace_bytes`` the fp64 distances of the result are ``search_dists64(ws, Q, depth)``."""
+    caller's ``ws`` of at least ``l2_search_workspace_bytes`` the fp64 distances of the result are ``search_dists64(ws, Q, depth)``.
+    ``live`` (vtc_l2_search_masked): packed int32 words [ceil(n / 32)] on the gallery's device (``row_mask_pack``), row j takes part iff bit
+    j & 31 of word j >> 5 is set.  The result is that of the search over the live rows alone, with their original row numbers; a dead
+    row is neither read nor counted in nonfinite_bits.  ``depth`` is still bounded by the physical row count."""
     gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
     ng, d = gallery.shape
     nq = queries.shape[0]
     if queries.shape[1] != d:
         raise ValueError(f"l2_search: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if live is not None:
+        live = _gpu(live, torch.int32, "live")
+        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
+            raise ValueError(f"l2_search: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
+                             f"{tuple(live.shape)} on {live.device}")
     need = L.lib().vtc_l2_search_workspace_bytes(ng, nq, d, depth)
     if ws is None:
         ws = workspace(need, gallery.device)
@@ -383,10 +391,35 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
-    L.check(L.lib().vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, int(id_base), ids.data_ptr(),
-                                  dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-            "vtc_l2_search")
+    tail = (int(id_base), ids.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if live is None:
+        L.check(L.lib().vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, *tail), "vtc_l2_search")
+    else:
+        L.check(L.lib().vtc_l2_search_masked(gallery.data_ptr(), queries.data_ptr(), live.data_ptr(), ng, nq, d, depth, *tail),
+                "vtc_l2_search_masked")
     return ids, dists, bits
+
+
+@on_device
+def row_mask_pack(flags: torch.Tensor, and_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Row flags (uint8 or bool [n], non-zero = the row takes part) -> the int32 words [ceil(n / 32)] l2_search's ``live`` takes
+    (vtc_row_mask_pack): bit b of word w is flags[32 w + b], ANDed with ``and_mask`` (words of the same layout) when given; the bits past
+    n are 0.  One launch."""
+    if flags.dtype == torch.bool:
+        flags = flags.view(torch.uint8) if flags.is_contiguous() else flags.contiguous().view(torch.uint8)
+    flags = _gpu(flags, torch.uint8, "flags")
+    if flags.dim() != 1 or flags.shape[0] < 1:
+        raise ValueError(f"row_mask_pack: flags must be [n] with n >= 1, got {tuple(flags.shape)}")
+    n = flags.shape[0]
+    if and_mask is not None:
+        and_mask = _gpu(and_mask, torch.int32, "and_mask")
+        if and_mask.device != flags.device or tuple(and_mask.shape) != ((n + 31) // 32,):
+            raise ValueError(f"row_mask_pack: and_mask must be int32 [{(n + 31) // 32}] on {flags.device}, got {tuple(and_mask.shape)} on "
+                             f"{and_mask.device}")
+    words = torch.empty((n + 31) // 32, dtype=torch.int32, device=flags.device)
+    L.check(L.lib().vtc_row_mask_pack(flags.data_ptr(), n, and_mask.data_ptr() if and_mask is not None else None, words.data_ptr(), _stream()),
+            "vtc_row_mask_pack")
+    return words
 
 
 def l2_search_workspace_bytes(n_gallery: int, n_queries: int, d: int, depth: int) -> int:
@@ -400,13 +433,14 @@ def search_dists64(ws: torch.Tensor, n_queries: int, depth: int) -> torch.Tensor
 
 
 @on_device
-def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0):
+def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None):
     """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
-    l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list)."""
+    l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list).
+    ``live``: the window's own packed row mask (bit 0 of word 0 is the window's first row), as l2_search takes it."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
-    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws)
+    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live)
     return ids, search_dists64(ws, nq, depth), bits
 
 
