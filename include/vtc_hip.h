@@ -372,6 +372,35 @@ int vtc_row_mask_pack(const uint8_t *flags, int n_rows, const uint32_t *and_mask
  * -1 / +inf.  1 <= n_parts <= 64, 1 <= n_queries <= 64, 1 <= depth <= 64; one launch. */
 int vtc_l2_search_merge(const int64_t *ids_parts, const double *dists_parts, int n_parts, int n_queries, int depth, int64_t *ids,
                         float *dists, void *stream);
+/* The GROUPED search: several rows per video (a title and its comments, 20 - 40 captions, the 8-frame chunks of a long video), and the
+ * `depth` nearest distinct VIDEOS come back, each by its nearest row.  It is the group minimum E(u, v) of the video-unit ranks
+ * (vtc_l2_rank_grouped_vunit above) used at query time.
+ * Inputs: gallery rows j in [0, n_gallery); a group id groups[j] per row (int32, device, only read) with ANY value -- negative, sparse
+ * or unsorted are all legal, and the rows of one group need not be adjacent; an optional live mask as vtc_l2_search_masked takes it
+ * (NULL: every row).  D(q, j) is the fp64 squared distance of the fp32 rows that every sweep uses.
+ * Take the complete list of live rows with a finite D(q, j), sorted by (D(q, j), j).  DELETE EVERY ROW THAT IS NOT THE FIRST OF ITS
+ * GROUP IN THAT ORDER.  The first `depth` entries of what remains are the result.  Per entry:
+ *   ids[q, p]        (int64) = id_base + j, the row: the video's best-matching caption, comment or chunk
+ *   out_groups[q, p] (int32) = groups[j]
+ *   dists[q, p]      (fp32, may be NULL) = (float) D(q, j); the fp64 value in the first n_queries * depth doubles of the workspace
+ * Consequences: ties between groups go to the lower row, ties inside a group go to the lower row.  A row with a non-finite distance
+ * never represents its group (its next row does; a group of such rows only never appears) and sets bit 1 of nonfinite as above.  A dead
+ * row is never read and influences nothing.  Fewer than `depth` distinct live groups with a finite distance give a list that ends in
+ * ids = -1, out_groups = -1, dists = +inf -- ids alone says "empty", -1 is also a legal group id.  A non-finite query gets a row of -1
+ * and bit 2.  With every row in a group of its own the result is vtc_l2_search_masked's, bit for bit.
+ * The same two launches on the same grid as vtc_l2_search; the scan reads 4 more bytes per row.
+ * LIMITS and refusals: those of vtc_l2_search_masked (depth <= n_gallery counts PHYSICAL rows), and groups / out_groups must be
+ * non-null; the workspace is vtc_l2_search_grouped_workspace_bytes(...), 0 for a refused shape. */
+size_t vtc_l2_search_grouped_workspace_bytes(int n_gallery, int n_queries, int d, int depth);
+int vtc_l2_search_grouped(const float *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_gallery, int n_queries,
+                          int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
+                          size_t ws_bytes, void *stream);
+/* vtc_l2_search_merge for grouped lists: groups_parts [n_parts, n_queries, depth] (int32) beside ids_parts / dists_parts.  The windows'
+ * rows are disjoint, their groups need not be: of a group that several parts list, the entry first by (dist, id) stays.  Exact: a group
+ * of the union's first `depth` has its overall nearest row in some part, where fewer than `depth` groups are nearer, so that part lists
+ * it.  Limits of vtc_l2_search_merge; a null groups_parts / out_groups is refused. */
+int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_parts, const int32_t *groups_parts, int n_parts, int n_queries,
+                                int depth, int64_t *ids, int32_t *out_groups, float *dists, void *stream);
 /* hits[j] += #{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);

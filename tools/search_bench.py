@@ -25,7 +25,19 @@ Per (n_gallery, n_queries, live fraction, pattern) one JSON line:
   topk_gathered_us          with --topk-gathered: gallery[live rows] gathered into a fresh tensor and ops.l2_topk(EXACT) over it, the gather
                             INSIDE the timing -- what routing many masked queries to vtc_l2_topk would cost
 `random` draws every row's bit independently; `blocked` makes one contiguous run of rows live (a subreddit whose rows were added
-together), starting at an odd row a third of the way in.  profiles/search_masked.md holds a run's table."""
+together), starting at an odd row a third of the way in.  profiles/search_masked.md holds a run's table.
+
+With --rows-per-video the tool measures the GROUPED scan (ops.l2_search_grouped = vtc_l2_search_grouped) instead:
+
+    python tools/search_bench.py --rows-per-video 1,5,20 [--video-layout contiguous|scattered] [--queries 1,8] ...
+
+Per (n_gallery, n_queries, rows per video, layout) one JSON line:
+  grouped_us / ungrouped_us   the grouped scan and the ungrouped ops.l2_search over the same gallery, in alternation as above
+  grouped_over_ungrouped      ratio of the medians; at one row per video the grouping is pure overhead and the ratio should stay within 1.05
+  same_ids_as_collapsed       on the first 10^4 rows: the grouped ids equal the COMPLETE (fp64 distance, row) order of the slice, formed
+                              outside the library, collapsed to the first row of every video on the host (asserted; outside the timing)
+`contiguous` gives rows r * v .. r * v + r - 1 to video v (the captions of a video added together); `scattered` permutes that
+assignment over the gallery.  profiles/search_grouped.md holds a run's table."""
 import argparse
 import json
 import os
@@ -123,6 +135,64 @@ def masked_main(args):
     return lines
 
 
+def collapsed_ids(gallery, queries, groups, depth):
+    """The definition, outside the library: per query the full fp64 (distance, row) order, the first row of every group, cut."""
+    g64, grp = gallery.double(), groups.cpu().numpy()
+    out = np.full((queries.shape[0], depth), -1, np.int64)
+    for i in range(queries.shape[0]):
+        dist = ((g64 - queries[i].double()) ** 2).sum(1)
+        order = torch.sort(dist, stable=True)[1].cpu().numpy()
+        _, first = np.unique(grp[order], return_index=True)
+        keep = order[np.sort(first)[:depth]]
+        out[i, :keep.size] = keep
+    return out
+
+
+def grouped_main(args):
+    lib = L.lib()
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        gallery = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(gallery[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            ws_g = ops.workspace(lib.vtc_l2_search_grouped_workspace_bytes(ng, nq, args.d, args.depth), gallery.device)
+            ws_u = ops.workspace(lib.vtc_l2_search_workspace_bytes(ng, nq, args.d, args.depth), gallery.device)
+            for rpv in [int(x) for x in args.rows_per_video.split(",")]:
+                groups = (torch.arange(ng, device="cuda") // rpv).to(torch.int32)
+                if args.video_layout == "scattered":
+                    groups = groups[torch.randperm(ng, device="cuda", generator=gen)].contiguous()
+                assert ng // rpv >= args.depth, "fewer videos than the depth: nothing to compare"
+                grouped = lambda: ops.l2_search_grouped(gallery, queries, groups, args.depth, ws=ws_g)           # noqa: E731
+                ungrouped = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws_u)                         # noqa: E731
+                entries = [grouped, ungrouped]
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times = [[] for _ in entries]
+                for _ in range(args.calls):
+                    for t, fn in zip(times, entries):
+                        us, out = timed(fn)
+                        t.append(us)
+                n_check = min(ng, 10 ** 4)
+                got = ops.l2_search_grouped(gallery[:n_check], queries, groups[:n_check].contiguous(), args.depth)[0].cpu().numpy()
+                same = bool(np.array_equal(got, collapsed_ids(gallery[:n_check], queries, groups[:n_check], args.depth)))
+                g, u = stat(times[0]), stat(times[1])
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "rows_per_video": rpv,
+                        "layout": args.video_layout if rpv > 1 else "one row per video", "grouped_us": g, "ungrouped_us": u,
+                        "grouped_over_ungrouped": round(g["median"] / u["median"], 3), "passes": passes(nq),
+                        "gallery_tb_per_s": round(ng * args.d * 4 / (1e6 * g["median"]), 3), "same_ids_as_collapsed": same}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                assert same, "the grouped scan and the host-collapsed full order returned different ids"
+            del ws_g, ws_u
+        del gallery
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -135,11 +205,16 @@ def main(argv=None):
     ap.add_argument("--live", type=str, default=None, help="live fractions, e.g. 1.0,0.5,0.1,0.01: measure the masked scan (see above)")
     ap.add_argument("--live-pattern", type=str, default="random", choices=("random", "blocked"))
     ap.add_argument("--topk-gathered", action="store_true", help="with --live: also time gather + l2_topk(EXACT) over the live rows")
+    ap.add_argument("--rows-per-video", type=str, default=None, help="rows per video, e.g. 1,5,20: measure the grouped scan (see above)")
+    ap.add_argument("--video-layout", type=str, default="contiguous", choices=("contiguous", "scattered"))
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
     if args.live:
         write_out(args.out, masked_main(args))
+        return
+    if args.rows_per_video:
+        write_out(args.out, grouped_main(args))
         return
     lib = L.lib()
     gen = torch.Generator(device="cuda").manual_seed(5)

@@ -14,9 +14,31 @@
 //   merge_kernel<Src>            one workgroup per query merges the workgroups' lists (Src = ScanLists) or the caller's partial lists
 //                                (Src = PartLists): the lists are sorted, so a lane follows one list and leaves at its first entry that
 //                                does not beat the current depth-th.
+//
+// vtc_l2_search_grouped / vtc_l2_search_merge_grouped: several rows per video, and the `depth` nearest distinct VIDEOS come back.  Every
+// row has a group id (int32, any value, rows of a group anywhere).  Take the complete list of live rows with a finite distance, sorted by
+// (distance, row); delete every row that is not the first of its group in that order; the first `depth` of what remains are the result
+// (include/vtc_hip.h) -- the group minimum E(u, v) of the video-unit ranks, at query time.  The de-duplication happens INSIDE the lists:
+//
+//   search_grouped_scan_kernel<NQ, NR, MASKED>
+//                                the same scan (one body, scan_body<NQ, NR, MASKED, GROUPED>; GROUPED = false is search_scan_kernel, whose
+//                                name and parameters stay what they were) with GroupLists: one more int per entry, and an insertion that
+//                                drops a candidate whose group holds a better entry and otherwise lets the group's old entry be the one
+//                                that leaves.  A row that does not beat the depth-th still costs the one compare.  A third part array
+//                                (part_g) carries the groups to the merge; the grid is the ungrouped scan's.
+//   merge_grouped_kernel<Src>    merge_kernel with GroupLists, for the workgroups' lists (ScanGroupLists) and the caller's (PartGroupLists).
+//
+// Why merging de-duplicated lists is exact, for the waves' lists in the LDS, the workgroups' lists and the caller's windows alike: a
+// group of the union's first `depth` has its overall nearest row in some part.  In that part fewer than `depth` groups have a smaller
+// local minimum (a local minimum is not below the overall one of its group, and fewer than `depth` groups are nearer overall), so that
+// part's list holds the entry.  The stale, worse entries of the same group from other parts are absorbed by the insertion: whichever
+// comes first, the better one stays.  The early exit of merge_lists stays valid -- the depth-th key only falls, so a lane may leave its
+// sorted list at the first entry that does not beat it; an entry that beats it but whose group a better entry holds is dropped and the
+// lane goes on.
 #include "sweep_common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 using namespace vtcsweep;
@@ -40,6 +62,7 @@ __device__ __forceinline__ long long uniform_of(long long v) {
 // key, wave-uniform.  Empty slots hold (+inf, EMPTY).  The insertion is exact_fallback_kernel's `offer` (sweep_topk.hip).
 template <typename I>
 struct WaveList {
+  static constexpr bool grouped = false;
   double bd, tau;
   I bi, tau_i;
   __device__ __forceinline__ void init(I empty) {
@@ -63,25 +86,75 @@ struct WaveList {
   }
 };
 
+// The list of the GROUPED search: every entry carries the group id of its row (bg), and over all 64 lanes -- not only the first `depth`
+// -- no two non-empty entries share a group.  An empty slot is known by its index (EMPTY), never by bg: every int is a legal group id.
+// A candidate that has passed `beats` meets the lane p_old that holds its group, if any (one more ballot):
+//   that entry is before the candidate         -> the candidate is dropped;
+//   otherwise, with pos the candidate's place  -> the lanes (pos, p_old] take their left neighbour's entry, lane pos the candidate, the
+//                                                 lanes above p_old keep theirs: the group's old entry is the one that leaves;
+//   no lane holds the group                    -> p_old = 63, WaveList's shift of everything above pos.
+// Entries only ever move towards higher lanes, so what lies past the depth-th never comes back: a row that does not beat the depth-th
+// changes nothing of the first `depth`, whether its group is held (by an entry that is then not worse than the depth-th, or by one
+// past it) or not -- `beats` is WaveList's one compare.  A group no lane holds has no row so far that was before the depth-th key of
+// its time (it would still be held, or has left over lane 63 behind 64 closer groups), and that key only falls: inserting is right.
+template <typename I, I EMPTY>
+struct GroupList {
+  static constexpr bool grouped = true;
+  double bd, tau;
+  I bi, tau_i;
+  int bg;
+  __device__ __forceinline__ void init(I) {
+    bd = tau = INFINITY;
+    bi = tau_i = EMPTY;
+    bg = 0;
+  }
+  __device__ __forceinline__ bool beats(double cv, I ci) const { return cv < INFINITY && (cv < tau || (cv == tau && ci < tau_i)); }
+  __device__ __forceinline__ void insert(double cv, I ci, int cg, int lane, int depth) {
+    const bool less = bd < cv || (bd == cv && bi < ci);
+    const int pos = __popcll(__ballot(less));              // <= depth - 1: the candidate is before the depth-th
+    const unsigned long long held = __ballot(bi != EMPTY && bg == cg);
+    const int p_old = held ? __ffsll((long long)held) - 1 : 63;
+    if (p_old < pos) return;                               // the lanes below pos are the entries before the candidate (wave-uniform)
+    const double ud = __shfl_up(bd, 1, 64);
+    const I ui = __shfl_up(bi, 1, 64);
+    const int ug = __shfl_up(bg, 1, 64);
+    if (lane > pos && lane <= p_old) { bd = ud; bi = ui; bg = ug; }
+    if (lane == pos) { bd = cv; bi = ci; bg = cg; }
+    tau = uniform_f64(__shfl(bd, depth - 1, 64));
+    tau_i = uniform_of(__shfl(bi, depth - 1, 64));
+  }
+  __device__ __forceinline__ void offer(double cv, I ci, int cg, int lane, int depth) {
+    if (beats(cv, ci)) insert(cv, ci, cg, lane, depth);
+  }
+};
+
 // Merges the sorted lists list0, list0 + stride, ... < nlists into wl, 64 lists at a time: lane l follows list l0 + l entry by entry
 // (src(list, e, cv, ci): the entry, cv = +inf for an empty one) and drops out at the first entry that does not beat the current
-// depth-th -- the rest of a sorted list cannot either.  The entries that do are offered one by one.
-template <typename Src>
-__device__ __forceinline__ void merge_lists(WaveList<long long> &wl, Src src, int nlists, int list0, int stride, int depth, int lane) {
+// depth-th -- the rest of a sorted list cannot either.  The entries that do are offered one by one.  For a GroupList the source gives
+// the entry's group too (src(list, e, cv, ci, cg)); an entry that beats the depth-th but whose group a better entry holds is dropped
+// by the insertion and the lane goes on.
+template <typename List, typename Src>
+__device__ __forceinline__ void merge_lists(List &wl, Src src, int nlists, int list0, int stride, int depth, int lane) {
   for (int l0 = list0; l0 < nlists; l0 += stride) {       // wave-uniform
     const int l = l0 + lane;
     bool alive = l < nlists;
     for (int e = 0; e < depth; ++e) {
       double cv = INFINITY;
       long long ci = EMPTY_ID;
-      if (alive) src(l, e, cv, ci);
+      [[maybe_unused]] int cg = 0;
+      if constexpr (List::grouped) {
+        if (alive) src(l, e, cv, ci, cg);
+      } else {
+        if (alive) src(l, e, cv, ci);
+      }
       alive = alive && wl.beats(cv, ci);
       unsigned long long m = __ballot(alive);
       if (!m) break;
       while (m) {
         const int from = __ffsll((long long)m) - 1;
         m &= m - 1;
-        wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), lane, depth);
+        if constexpr (List::grouped) wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), __shfl(cg, from, 64), lane, depth);
+        else wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), lane, depth);
       }
     }
   }
@@ -119,6 +192,43 @@ struct LdsLists {
   }
 };
 
+// the grouped forms of the three: the same places plus the entry's group.  The scan's LDS lists keep the ROW as an int there, so an
+// entry takes the 16 bytes it takes without groups and the LDS of a workgroup -- with it the resident workgroups per CU -- is unchanged.
+struct ScanGroupLists {
+  const double *d;
+  const int *i, *g;
+  int nlists, depth, q;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci, int &cg) const {
+    const size_t o = ((size_t)q * depth + e) * nlists + l;
+    cv = d[o];
+    ci = i[o];
+    cg = g[o];
+  }
+};
+struct PartGroupLists {
+  const double *d;
+  const int64_t *i;
+  const int32_t *g;
+  int nq, depth, q;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci, int &cg) const {
+    const size_t o = ((size_t)l * nq + q) * depth + e;
+    ci = i[o];
+    cv = ci < 0 ? INFINITY : d[o];
+    cg = g[o];
+  }
+};
+template <typename I>
+struct LdsGroupLists {
+  const double *sd;
+  const I *si;
+  const int *sg;
+  __device__ __forceinline__ void operator()(int l, int e, double &cv, long long &ci, int &cg) const {
+    cv = sd[l * 64 + e];
+    ci = si[l * 64 + e];                                   // an empty entry's distance is +inf: it is never offered
+    cg = sg[l * 64 + e];
+  }
+};
+
 // LDS of the scan: the query tile, then (re-used) the waves' lists of the tile's queries
 constexpr size_t scan_lds_bytes(int nq_tile, int d) {
   const size_t tile = (size_t)nq_tile * d * sizeof(float), lists = (size_t)nq_tile * 4 * 64 * (sizeof(double) + sizeof(long long));
@@ -130,10 +240,17 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
 // it works on this one; a step with no live row issues no gallery load, and in a partly live one a dead slot is pointed at a live row of
 // the same step and its results are dropped, exactly as a slot past the gallery is: a dead row's memory is never read.  The mask is only
 // read.  Without MASKED `live` is not looked at and the kernel is the scan of vtc_l2_search.
-template <int NQ, int NR, bool MASKED>
-__global__ __launch_bounds__(256) void search_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
-                                                          const unsigned *__restrict__ live, int ng, int nq, int d, int depth,
-                                                          double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
+//
+// GROUPED: the lists are GroupLists and the workgroup's list of a query goes out with its groups (part_g).  The fast path is the
+// ungrouped one: a row's group is needed only once some query's `beats` is true.  It is loaded EAGERLY all the same, every lane reading
+// the one address groups[row] with an ordinary load issued BEFORE the step's gallery loads, and moved to a scalar register only inside
+// the insertion.  Loads return in order, so when the row's distances are there -- which every step waits for anyway -- the group has
+// arrived: the rejecting path never waits on it, and the insertion never pays a memory round trip of its own, which a lazy load would
+// cost exactly while a wave fills its lists and every row is inserted.  The price is NR load instructions and NR registers a step.
+template <int NQ, int NR, bool MASKED, bool GROUPED>
+__device__ __forceinline__ void scan_body(const float *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
+                                          const int *__restrict__ groups, int ng, int nq, int d, int depth, double *__restrict__ part_d,
+                                          int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite) {
   extern __shared__ float4 smem4[];
   float *qt = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -162,7 +279,7 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
   __syncthreads();
 
   // ---- the scan: wave gw of GW takes the row groups gw, gw + GW, ...: ascending rows, so exact ties keep (distance, row) order
-  WaveList<int> wl[NQ];
+  std::conditional_t<GROUPED, GroupList<int, EMPTY_ROW>, WaveList<int>> wl[NQ];
 #pragma unroll
   for (int u = 0; u < NQ; ++u) wl[u].init(EMPTY_ROW);
   bool gallery_bad = false;
@@ -194,6 +311,11 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
       if constexpr (MASKED) jj[r] = (int)(s * NR) + (NR == 1 || ((bits >> r) & 1) ? r : __ffs((int)bits) - 1);      // a dead slot: a live row of the step
       else jj[r] = (int)min(s * NR + r, (long long)ng - 1);                                           // a slot past the gallery: clamped
     }                                                                                                 // (the results of both are dropped)
+    [[maybe_unused]] int gv[NR];                           // the rows' groups, as loaded (see above): jj[r] is a row of the gallery
+    if constexpr (GROUPED) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) gv[r] = groups[jj[r]];
+    }
     double dist[NQ * NR];
     wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
 #pragma unroll
@@ -203,7 +325,10 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
         for (int u = 0; u < NQ; ++u) {
           const double cv = dist[u * NR + r];
           if (!(cv < INFINITY)) gallery_bad = true;
-          else if (!((dead >> u) & 1) && wl[u].beats(cv, jj[r])) wl[u].insert(cv, jj[r], lane, depth);
+          else if (!((dead >> u) & 1) && wl[u].beats(cv, jj[r])) {
+            if constexpr (GROUPED) wl[u].insert(cv, jj[r], uniform_of(gv[r]), lane, depth);
+            else wl[u].insert(cv, jj[r], lane, depth);
+          }
         }
       }
     }
@@ -213,25 +338,69 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
   // ---- the workgroup's four lists of a query -> one: wave w merges the queries w, w + 4, ...
   __syncthreads();                                         // every wave is done with the query tile
   double *sd = reinterpret_cast<double *>(smem4);          // [NQ][4][64]
-  long long *si = reinterpret_cast<long long *>(sd + NQ * 4 * 64);      // 64-bit indices: what merge_lists reads
+  if constexpr (GROUPED) {
+    int *si = reinterpret_cast<int *>(sd + NQ * 4 * 64), *sg = si + NQ * 4 * 64;      // rows as ints + groups: 16 bytes an entry, as below
 #pragma unroll
-  for (int u = 0; u < NQ; ++u) {
-    sd[(u * 4 + wave) * 64 + lane] = wl[u].bd;
-    si[(u * 4 + wave) * 64 + lane] = wl[u].bi == EMPTY_ROW ? EMPTY_ID : (long long)wl[u].bi;
-  }
-  __syncthreads();
-  const int nlists = gridDim.x;
-  for (int u = wave; u < NQ; u += 4) {
-    if (q0 + u >= nq) break;
-    WaveList<long long> m;
-    m.init(EMPTY_ID);
-    merge_lists(m, LdsLists{sd + u * 4 * 64, si + u * 4 * 64}, 4, 0, 64, depth, lane);
-    if (lane < depth) {
-      const size_t o = ((size_t)(q0 + u) * depth + lane) * nlists + blockIdx.x;
-      part_d[o] = m.bd;
-      part_i[o] = m.bi == EMPTY_ID ? EMPTY_ROW : (int)m.bi;
+    for (int u = 0; u < NQ; ++u) {
+      sd[(u * 4 + wave) * 64 + lane] = wl[u].bd;
+      si[(u * 4 + wave) * 64 + lane] = wl[u].bi;
+      sg[(u * 4 + wave) * 64 + lane] = wl[u].bg;
+    }
+    __syncthreads();
+    const int nlists = gridDim.x;
+    for (int u = wave; u < NQ; u += 4) {
+      if (q0 + u >= nq) break;
+      GroupList<long long, EMPTY_ID> m;
+      m.init(EMPTY_ID);
+      merge_lists(m, LdsGroupLists<int>{sd + u * 4 * 64, si + u * 4 * 64, sg + u * 4 * 64}, 4, 0, 64, depth, lane);
+      if (lane < depth) {
+        const size_t o = ((size_t)(q0 + u) * depth + lane) * nlists + blockIdx.x;
+        part_d[o] = m.bd;
+        part_i[o] = m.bi == EMPTY_ID ? EMPTY_ROW : (int)m.bi;
+        part_g[o] = m.bg;
+      }
+    }
+  } else {
+    long long *si = reinterpret_cast<long long *>(sd + NQ * 4 * 64);      // 64-bit indices: what merge_lists reads
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      sd[(u * 4 + wave) * 64 + lane] = wl[u].bd;
+      si[(u * 4 + wave) * 64 + lane] = wl[u].bi == EMPTY_ROW ? EMPTY_ID : (long long)wl[u].bi;
+    }
+    __syncthreads();
+    const int nlists = gridDim.x;
+    for (int u = wave; u < NQ; u += 4) {
+      if (q0 + u >= nq) break;
+      WaveList<long long> m;
+      m.init(EMPTY_ID);
+      merge_lists(m, LdsLists{sd + u * 4 * 64, si + u * 4 * 64}, 4, 0, 64, depth, lane);
+      if (lane < depth) {
+        const size_t o = ((size_t)(q0 + u) * depth + lane) * nlists + blockIdx.x;
+        part_d[o] = m.bd;
+        part_i[o] = m.bi == EMPTY_ID ? EMPTY_ROW : (int)m.bi;
+      }
     }
   }
+}
+
+// The two kernels of the body.  search_scan_kernel<NQ, NR, MASKED> keeps its name, its parameters and its statements (GROUPED = false
+// compiles every line of the grouping away), so the eight ungrouped instantiations compute what they did, bit for bit, in the same
+// registers (within 2) and without scratch; the compiler's output for the inlined body is not byte-identical to the one it gave the
+// body written in the kernel, and profiles/search_grouped.md has their time before and after (within 1 - 3 %).  The grouped scan
+// is a kernel of its own name with the two extra pointers.
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void search_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
+                                                          const unsigned *__restrict__ live, int ng, int nq, int d, int depth,
+                                                          double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, false>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite);
+}
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void search_grouped_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
+                                                                  const unsigned *__restrict__ live, const int *__restrict__ groups, int ng,
+                                                                  int nq, int d, int depth, double *__restrict__ part_d,
+                                                                  int *__restrict__ part_i, int *__restrict__ part_g,
+                                                                  int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, true>(gallery, queries, live, groups, ng, nq, d, depth, part_d, part_i, part_g, nonfinite);
 }
 
 // One workgroup per query: the first `depth` of the union of the lists by (distance, index).
@@ -260,6 +429,36 @@ __global__ __launch_bounds__(256) void merge_kernel(Src src, int nlists, int dep
   }
 }
 
+// The grouped merge: the same walk with GroupLists, so a group's stale, worse entries from other lists are absorbed by the insertion.
+template <typename Src>
+__global__ __launch_bounds__(256) void merge_grouped_kernel(Src src, int nlists, int depth, int64_t id_base, int64_t *__restrict__ ids,
+                                                            int32_t *__restrict__ out_groups, float *__restrict__ dists,
+                                                            double *__restrict__ dists64) {
+  __shared__ double sd[4][64];
+  __shared__ long long si[4][64];
+  __shared__ int sg[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x;
+  src.q = q;
+  GroupList<long long, EMPTY_ID> wl;
+  wl.init(EMPTY_ID);
+  merge_lists(wl, src, nlists, wave * 64, 256, depth, lane);
+  sd[wave][lane] = wl.bd;
+  si[wave][lane] = wl.bi;
+  sg[wave][lane] = wl.bg;
+  __syncthreads();
+  if (wave != 0) return;
+  merge_lists(wl, LdsGroupLists<long long>{&sd[1][0], &si[1][0], &sg[1][0]}, 3, 0, 64, depth, lane);
+  if (lane < depth) {
+    const size_t o = (size_t)q * depth + lane;
+    const bool empty = wl.bi == EMPTY_ID;
+    ids[o] = empty ? -1 : id_base + wl.bi;
+    out_groups[o] = empty ? -1 : wl.bg;
+    if (dists) dists[o] = empty ? INFINITY : (float)wl.bd;
+    if (dists64) dists64[o] = empty ? (double)INFINITY : wl.bd;
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 struct SearchPlan {
   int tile_q, tile_r;       // queries of a tile (a gallery pass each), gallery rows of a step
@@ -282,25 +481,26 @@ bool search_args_ok(int ng, int nq, int d, int depth) {
 int search_max_lists(int ng) { return (int)std::min<long long>(SEARCH_MAX_BLOCKS, ((long long)ng + 3) / 4); }
 struct SearchWs {
   double *dists64, *part_d;
-  int *part_i;
+  int *part_i, *part_g;     // part_g: the grouped search's third part array, after the two every search has
   size_t total;
 };
-SearchWs search_ws(void *ws, int ng, int nq, int depth) {
+SearchWs search_ws(void *ws, int ng, int nq, int depth, bool grouped = false) {
   Bump b(ws);
   SearchWs s;
   const size_t entries = (size_t)nq * depth;
   s.dists64 = (double *)b.take(entries * sizeof(double));            // FIRST: the documented region of the header
   s.part_d = (double *)b.take(entries * search_max_lists(ng) * sizeof(double));
   s.part_i = (int *)b.take(entries * search_max_lists(ng) * sizeof(int));
+  s.part_g = grouped ? (int *)b.take(entries * search_max_lists(ng) * sizeof(int)) : nullptr;
   s.total = b.off;
   return s;
 }
 
 // The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
 // most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
-template <int NQ, int NR, bool MASKED>
-int launch_scan(const float *gallery, const float *queries, const unsigned *live, int ng, int nq, int d, int depth, const SearchWs &s, int tiles,
-                int *nonfinite, hipStream_t stream) {
+template <int NQ, int NR, bool MASKED, bool GROUPED>
+int launch_scan(const float *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
+                const SearchWs &s, int tiles, int *nonfinite, hipStream_t stream) {
   // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
   static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
   int dev = 0;
@@ -315,25 +515,35 @@ int launch_scan(const float *gallery, const float *queries, const unsigned *live
     // before it starts rejecting rows, and with all rows live at 10^5 rows the fourth workgroup put the masked scan 4.5 - 5.8 % behind
     // the unmasked one instead of 3.4 - 3.6 %.  It was 2.5 % faster at 10^6 rows and 4 - 12 % on partly live masks there: the trade is
     // written down in profiles/search_masked.md.
+    // The grouped scan follows the same rule: the unmasked, ungrouped scan's grid, never more than is resident of its own.
     int own = per_cu;
-    if (MASKED && hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_scan_kernel<NQ, NR, true>, 256, scan_lds_bytes(NQ, d)) == hipSuccess && own >= 1)
+    if (GROUPED) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_grouped_scan_kernel<NQ, NR, MASKED>, 256, scan_lds_bytes(NQ, d)) == hipSuccess &&
+          own >= 1)
+        per_cu = std::min(per_cu, own);
+    } else if (MASKED && hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_scan_kernel<NQ, NR, true>, 256, scan_lds_bytes(NQ, d)) == hipSuccess &&
+               own >= 1)
       per_cu = std::min(per_cu, own);
     slot.store(per_cu, std::memory_order_relaxed);
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  hipLaunchKernelGGL((search_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live, ng,
-                     nq, d, depth, s.part_d, s.part_i, nonfinite);
+  if constexpr (GROUPED)
+    hipLaunchKernelGGL((search_grouped_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
+                       live, groups, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
+  else
+    hipLaunchKernelGGL((search_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live, ng,
+                       nq, d, depth, s.part_d, s.part_i, nonfinite);
   return blocks;
 }
 // the instantiation of the plan's tile shape
-template <bool MASKED>
-int launch_scan_tile(const SearchPlan &p, const float *gallery, const float *queries, const unsigned *live, int ng, int nq, int d, int depth,
-                     const SearchWs &s, int *nonfinite, hipStream_t stream) {
-  if (p.tile_q == 1) return launch_scan<1, 4, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 2) return launch_scan<2, 4, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 4) return launch_scan<4, 2, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  return launch_scan<8, 1, MASKED>(gallery, queries, live, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+template <bool MASKED, bool GROUPED = false>
+int launch_scan_tile(const SearchPlan &p, const float *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d,
+                     int depth, const SearchWs &s, int *nonfinite, hipStream_t stream) {
+  if (p.tile_q == 1) return launch_scan<1, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  if (p.tile_q == 2) return launch_scan<2, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  if (p.tile_q == 4) return launch_scan<4, 2, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+  return launch_scan<8, 1, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
 }
 
 // words[w] bit b = (flags[32 w + b] != 0) & and_mask[w] bit b: a thread per row, a ballot per wave -- 64 rows, two words, written by
@@ -370,8 +580,8 @@ extern "C" int vtc_l2_search_masked(const float *gallery, const float *queries, 
   const SearchWs s = search_ws(ws, ng, nq, depth);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_search: workspace too small (%zu < %zu)", ws_bytes, s.total);
   const SearchPlan p = search_plan(nq);
-  const int blocks = live ? launch_scan_tile<true>(p, gallery, queries, live, ng, nq, d, depth, s, nonfinite, stream)
-                          : launch_scan_tile<false>(p, gallery, queries, nullptr, ng, nq, d, depth, s, nonfinite, stream);
+  const int blocks = live ? launch_scan_tile<true>(p, gallery, queries, live, nullptr, ng, nq, d, depth, s, nonfinite, stream)
+                          : launch_scan_tile<false>(p, gallery, queries, nullptr, nullptr, ng, nq, d, depth, s, nonfinite, stream);
   VTC_LAUNCH_CHECK2("l2_search", "scan");
   hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth, id_base,
                      ids, dists, s.dists64);
@@ -401,5 +611,47 @@ extern "C" int vtc_l2_search_merge(const int64_t *ids_parts, const double *dists
   hipLaunchKernelGGL(merge_kernel<PartLists>, dim3(nq), dim3(256), 0, (hipStream_t)stream, PartLists{dists_parts, ids_parts, nq, depth, 0}, n_parts,
                      depth, (int64_t)0, ids, dists, (double *)nullptr);
   VTC_LAUNCH_CHECK("l2_search_merge");
+  return 0;
+}
+
+extern "C" size_t vtc_l2_search_grouped_workspace_bytes(int n_gallery, int n_queries, int d, int depth) {
+  if (!search_args_ok(n_gallery, n_queries, d, depth)) return 0;
+  return search_ws(nullptr, n_gallery, n_queries, depth, true).total;
+}
+
+extern "C" int vtc_l2_search_grouped(const float *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int ng, int nq, int d,
+                                     int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
+                                     size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && groups && ids && out_groups, "l2_search_grouped: null argument");
+  VTC_CHECK(ng >= 1, "l2_search_grouped: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_grouped: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search_grouped: depth=%d must be in [1, min(%d, n_gallery)]", depth,
+            SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search_grouped: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "l2_search_grouped: id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth, true);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search_grouped: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const SearchPlan p = search_plan(nq);
+  const int blocks = live ? launch_scan_tile<true, true>(p, gallery, queries, live, groups, ng, nq, d, depth, s, nonfinite, stream)
+                          : launch_scan_tile<false, true>(p, gallery, queries, nullptr, groups, ng, nq, d, depth, s, nonfinite, stream);
+  VTC_LAUNCH_CHECK2("l2_search_grouped", "scan");
+  hipLaunchKernelGGL(merge_grouped_kernel<ScanGroupLists>, dim3(nq), dim3(256), 0, stream, ScanGroupLists{s.part_d, s.part_i, s.part_g, blocks, depth, 0},
+                     blocks, depth, id_base, ids, out_groups, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search_grouped", "merge");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_parts, const int32_t *groups_parts, int n_parts, int nq,
+                                           int depth, int64_t *ids, int32_t *out_groups, float *dists, void *stream) {
+  VTC_CHECK(ids_parts && dists_parts && groups_parts && ids && out_groups, "l2_search_merge_grouped: null argument");
+  VTC_CHECK(n_parts >= 1 && n_parts <= SEARCH_MAX_PARTS, "l2_search_merge_grouped: n_parts=%d must be in [1, %d]", n_parts, SEARCH_MAX_PARTS);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_merge_grouped: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH, "l2_search_merge_grouped: depth=%d must be in [1, %d]", depth, SEARCH_MAX_DEPTH);
+  hipLaunchKernelGGL(merge_grouped_kernel<PartGroupLists>, dim3(nq), dim3(256), 0, (hipStream_t)stream,
+                     PartGroupLists{dists_parts, ids_parts, groups_parts, nq, depth, 0}, n_parts, depth, (int64_t)0, ids, out_groups, dists,
+                     (double *)nullptr);
+  VTC_LAUNCH_CHECK("l2_search_merge_grouped");
   return 0;
 }

@@ -494,3 +494,38 @@ def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch
     else:
         parts = mine[None]
     return ops.l2_search_merge(parts[:, 0].contiguous(), parts[:, 1].contiguous().view(torch.float64))
+
+
+def sharded_search_videos(index_rows_local: torch.Tensor, video_ids_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int,
+                          world: int):
+    """``sharded_search`` for a gallery with several rows per video: this rank stores the rows [row_base, row_base + n_local) and their
+    video ids (int32 [n_local]); a video's rows may lie on different ranks.  Returns (video_ids [Q, k] int64, row_ids [Q, k] int64 --
+    global row ids --, dists [Q, k] fp32), identical on every rank and equal to ops.l2_search_grouped over the whole gallery: the k
+    nearest distinct videos, each by its nearest row, -1 / -1 / +inf where there are fewer.
+
+    A local ops.l2_search_grouped_part(id_base = row_base), ONE all_gather of [3, Q, k] int64 per rank -- ids, the bits of the fp64
+    distances, groups --, then ops.l2_search_merge_grouped, whose de-duplicating insertion absorbs the worse entries of a video that
+    several ranks list.  world <= 64.  As with sharded_search, no multi-GPU box has run this: what is tested is the code path at
+    world = 1 and the windowed merge on one card (tests/test_gpu_search_grouped.py)."""
+    if not 1 <= world <= 64:
+        raise ValueError(f"sharded_search_videos: world={world} must be in [1, 64]")
+    k = int(k)
+    nq, n_local = queries.shape[0], index_rows_local.shape[0]
+    if n_local:
+        depth = min(k, n_local)
+        ids, groups, d64, _ = ops.l2_search_grouped_part(index_rows_local, queries, video_ids_local, depth, id_base=int(row_base))
+        ids, d64 = ops.pad_search_part(ids, d64, k)
+        groups = torch.nn.functional.pad(groups, (0, k - depth), value=-1)
+    else:
+        ids = torch.full((nq, k), -1, dtype=torch.int64, device=queries.device)
+        d64 = torch.full((nq, k), float("inf"), dtype=torch.float64, device=queries.device)
+        groups = torch.full((nq, k), -1, dtype=torch.int32, device=queries.device)
+    mine = torch.stack([ids, d64.contiguous().view(torch.int64), groups.to(torch.int64)])      # [3, Q, k]: one buffer, one collective
+    if world > 1:
+        parts = torch.empty((world,) + tuple(mine.shape), dtype=torch.int64, device=mine.device)
+        dist.all_gather_into_tensor(parts, mine.contiguous())
+    else:
+        parts = mine[None]
+    ids, groups, dists = ops.l2_search_merge_grouped(parts[:, 0].contiguous(), parts[:, 1].contiguous().view(torch.float64),
+                                                     parts[:, 2].to(torch.int32).contiguous())
+    return torch.where(ids >= 0, groups.to(torch.int64), ids), ids, dists

@@ -15,6 +15,13 @@ Rows can go away and a query can search part of the gallery; both are one bit pe
     index.remove([17, 42])                            # ids are never reused, nothing is renumbered or compacted
     cats = index.subset(subreddit_of_row == 3)        # bool [ntotal] or ids; reusable across queries
     ids, scores = index.search_text(model, title_tokens, k=10, subset=cats)
+
+A video can own several rows -- a title and its comments, many captions, the chunks of a long video -- and then the k nearest distinct
+VIDEOS are what a query wants, each by its nearest row (vtc_l2_search_grouped: the de-duplication happens inside the scan, exactly):
+
+    index.add(caption_embeddings, video_ids=video_of_caption)      # int [n] in [0, 2^31); a video's rows in any number of calls
+    videos, rows, scores = index.search_videos(queries, k=10)
+    index.remove_videos([7, 9])
 """
 from __future__ import annotations
 
@@ -24,6 +31,22 @@ from .. import _lib as L
 from .. import ops
 
 __all__ = ["VideoIndex", "RowSubset"]
+
+
+def _video_id_tensor(video_ids, n, device, what):
+    """An integer [n] sequence or tensor with values in [0, 2^31) -> int32 [n] on ``device``; anything else raises ValueError (a
+    device-to-host read when n > 0)."""
+    v = torch.as_tensor(video_ids)
+    if v.numel() == 0 and not n:                               # an empty list has no dtype to speak of
+        return torch.empty(0, dtype=torch.int32, device=device)
+    if v.dtype == torch.bool or v.is_floating_point() or v.is_complex():
+        raise ValueError(f"VideoIndex.{what}: video_ids must be integers, got {v.dtype}")
+    if n is not None and tuple(v.shape) != (n,):
+        raise ValueError(f"VideoIndex.{what}: video_ids must be [{n}], one per row, got {tuple(v.shape)}")
+    v = v.to(device=device).reshape(-1)
+    if v.numel() and (int(v.min()) < 0 or int(v.max()) >= 2 ** 31):
+        raise ValueError(f"VideoIndex.{what}: video_ids must be in [0, 2^31), got {int(v.min())} .. {int(v.max())}")
+    return v.to(torch.int32)
 
 
 def _id_tensor(ids, ntotal, device, what):
@@ -101,6 +124,7 @@ class VideoIndex:
         self._n_live = 0
         self._generation = 0                # bumped by add / remove / load_state_dict: what a RowSubset's cached words are valid for
         self._words = None                  # (generation, packed words of _live)
+        self._video_ids = None              # int32 [capacity] on the device once the first non-empty add passed video_ids: a GROUPED index
 
     def __len__(self):
         """The number of live rows."""
@@ -115,6 +139,16 @@ class VideoIndex:
     def live_mask(self):
         """bool [ntotal] on the device (a copy): False for a removed row."""
         return torch.ones(self._n, dtype=torch.bool, device=self.device) if self._live is None else self._live.clone()
+
+    @property
+    def grouped(self):
+        """True once the first non-empty ``add`` passed ``video_ids``: every row then has a video id and ``search_videos`` works."""
+        return self._video_ids is not None
+
+    @property
+    def video_ids(self):
+        """int32 [ntotal] on the device (a copy): the video of every row of a grouped index; None for an ungrouped one."""
+        return None if self._video_ids is None else self._video_ids[:self._n].clone()
 
     # ---- rows ----------------------------------------------------------------------------------
     def _prepared(self, x, what, check=True):
@@ -136,16 +170,30 @@ class VideoIndex:
             x = torch.nn.functional.pad(x, (0, self.width - self.dim))
         return x
 
-    def add(self, embeddings):
+    def add(self, embeddings, video_ids=None):
         """Appends [n, dim] fp32 rows; their ids are their positions in insertion order (removed ids are not reused).  Returns the id of
-        the first one, which is ``ntotal`` before the call."""
+        the first one, which is ``ntotal`` before the call.
+        ``video_ids`` (an integer [n] tensor or sequence, values in [0, 2^31)) names the video of every row; one video's rows may come in
+        different calls.  An index is GROUPED iff its first non-empty add passed them, and every later add must do the same as the first:
+        mixing the two forms raises ValueError and changes nothing."""
         x = self._prepared(embeddings, "embeddings")
         first, n = self._n, x.shape[0]
+        vids = None if video_ids is None else _video_id_tensor(video_ids, n, self.device, "add")
+        if n and first and (vids is not None) != self.grouped:
+            raise ValueError("VideoIndex.add: this index " + ("has a video id for every row: pass video_ids" if self.grouped else
+                             "was started without video_ids: its rows have none, so later rows cannot either"))
         if first + n > self._rows.shape[0]:                 # amortised doubling
             grown = torch.empty(max(first + n, 2 * self._rows.shape[0], 1024), self.width, dtype=torch.float32, device=self.device)
             grown[:first] = self._rows[:first]
             self._rows = grown
         self._rows[first:first + n] = x
+        if n and vids is not None:
+            if self._video_ids is None or self._video_ids.shape[0] < self._rows.shape[0]:
+                grown = torch.zeros(self._rows.shape[0], dtype=torch.int32, device=self.device)
+                if self._video_ids is not None:
+                    grown[:first] = self._video_ids[:first]
+                self._video_ids = grown
+            self._video_ids[first:first + n] = vids
         self._n = first + n
         if n:
             self._n_live += n
@@ -170,6 +218,17 @@ class VideoIndex:
             self._n_live -= newly
             self._generation += 1
         return newly
+
+    def remove_videos(self, video_ids):
+        """Removes every live row of these videos (an integer sequence or tensor) and returns how many rows that were.  A video the index
+        does not hold removes nothing.  Reads the count back from the device (a host sync): removal is not the query path."""
+        if not self.grouped:
+            raise ValueError("VideoIndex.remove_videos: the index has no video ids (add(embeddings, video_ids=...))")
+        vids = _video_id_tensor(video_ids, None, self.device, "remove_videos")
+        if vids.numel() == 0 or self._n == 0:
+            return 0
+        rows = torch.nonzero(torch.isin(self._video_ids[:self._n], vids)).reshape(-1)
+        return self.remove(rows)
 
     def subset(self, members):
         """The rows a search may return, as a reusable ``RowSubset``: ``members`` is a bool [ntotal] tensor or int64 ids (a sequence or a
@@ -202,6 +261,8 @@ class VideoIndex:
         state = {"rows": self.rows[:, :self.dim].clone(), "count": self._n, "dim": self.dim, "normalized": self.normalized}
         if self._live is not None:
             state["live"] = self._live.clone()
+        if self.grouped:
+            state["video_ids"] = self.video_ids
         return state
 
     def load_state_dict(self, state):
@@ -218,6 +279,13 @@ class VideoIndex:
             if live.dtype != torch.bool or tuple(live.shape) != (rows.shape[0],):
                 raise ValueError(f"VideoIndex.load_state_dict: live must be bool [{rows.shape[0]}], got {live.dtype} {tuple(live.shape)}")
             live = live.to(self.device).clone()
+        vids = state.get("video_ids")
+        if vids is not None:
+            vids = torch.as_tensor(vids)
+            if vids.dtype != torch.int32 or tuple(vids.shape) != (rows.shape[0],):
+                raise ValueError(f"VideoIndex.load_state_dict: video_ids must be int32 [{rows.shape[0]}], got {vids.dtype} {tuple(vids.shape)}")
+            vids = _video_id_tensor(vids, rows.shape[0], self.device, "load_state_dict").clone()
+        self._video_ids = vids
         self._n = rows.shape[0]
         self._live = live
         self._n_live = self._n if live is None else int(live.sum())
@@ -271,17 +339,49 @@ class VideoIndex:
         ids, dists = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
         return ids, 1.0 - dists / 2.0
 
+    def search_videos(self, queries, k, subset=None):
+        """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of every
+        query, nearest first, each with its nearest live row (the best-matching caption, comment or chunk) and that row's score as
+        ``search`` gives it.  Ties go to the lower row.  Always the scan (vtc_l2_search_grouped; vtc_l2_topk has no grouping), 64 queries
+        per call, with the few-query rules of the masked route: only enqueued, no host sync, and a non-finite query gets a row of
+        -1 / -1 / -inf.  1 <= k <= min(64, len(index)), len counting live ROWS; fewer than k distinct live videos (in the ``subset``, if
+        one is given) give rows that end in -1 / -1 / -inf.  On an ungrouped index it raises ValueError."""
+        if not self.grouped:
+            raise ValueError("VideoIndex.search_videos: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
+        k = int(k)
+        if not 1 <= k <= min(self.MAX_K, self._n_live):
+            raise ValueError(f"VideoIndex.search_videos: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
+            raise ValueError("VideoIndex.search_videos: the subset belongs to another index (build it with this index's subset())")
+        q = self._prepared(queries, "queries", check=False)
+        if q.shape[0] == 0:
+            raise ValueError("VideoIndex.search_videos: no queries")
+        words = self._live_words() if subset is None else subset.words()
+        g, vids, step = self.rows, self._video_ids[:self._n], ops.SEARCH_MAX_QUERIES
+        ws = self._workspace(ops.l2_search_grouped_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
+        out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words)[:3] for lo in range(0, q.shape[0], step)]
+        rows, videos, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
+        return torch.where(rows >= 0, videos.to(torch.int64), rows), rows, 1.0 - dists / 2.0
+
+    def search_videos_text(self, model, title_tokens, k, comments=None, subset=None):
+        """``search_text`` for a grouped index: the k nearest distinct videos of text queries given as token ids, as ``search_videos``
+        returns them."""
+        return self.search_videos(self._text_queries(model, title_tokens, comments, "search_videos_text"), k, subset=subset)
+
     def search_text(self, model, title_tokens, k, comments=None, subset=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a
         ``*_finaltf`` model that adapts the text branch (branch_to_adapt_val == "text"), ``comments`` [Q, n_comments, ctx] adapts the
         query through the Context Adapter Module as the wrapper's eval forward does."""
+        return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset)
+
+    def _text_queries(self, model, title_tokens, comments, what):
         if not title_tokens.is_cuda:
-            raise RuntimeError("vtc_amd VideoIndex.search_text: token ids must be on the GPU (no CPU fallback)")
+            raise RuntimeError(f"vtc_amd VideoIndex.{what}: token ids must be on the GPU (no CPU fallback)")
         if comments is not None and getattr(model, "branch_to_adapt_val", None) != "text":
-            raise ValueError("VideoIndex.search_text: comments adapt the query only for a *_finaltf model with branch_to_adapt_val == 'text'")
+            raise ValueError(f"VideoIndex.{what}: comments adapt the query only for a *_finaltf model with branch_to_adapt_val == 'text'")
         feats = model.encode_text(title_tokens)
         if comments is not None:
             b, ncomms, ntoks = comments.shape
             feats_comm = model.encode_text(comments.reshape(b * ncomms, ntoks))
             feats = model._pack()["cam"].forward(feats, feats_comm, comments)
-        return self.search(ops.normalize_rows(feats.float().contiguous()), k, subset=subset)
+        return ops.normalize_rows(feats.float().contiguous())

@@ -460,6 +460,83 @@ def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return
     return ids, dists
 
 
+@on_device
+def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
+                      return_dists: bool = True, ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
+    """The grouped query-time search (vtc_l2_search_grouped): every gallery row belongs to the group ``groups[j]`` (int32 [n], ANY values,
+    rows of a group anywhere), and of the complete (distance, row)-sorted list of the live rows with a finite distance only the FIRST row
+    of every group stays; the first ``depth`` of those are the result -- the ``depth`` nearest distinct groups, each by its nearest row.
+    Returns (ids [Q, depth] int64 = id_base + that row, -1 where fewer groups have a finite distance; groups [Q, depth] int32, -1 there
+    too -- read ``ids`` to tell an empty entry, -1 is a legal group id; dists fp32 or None; nonfinite_bits as l2_search).  ``live`` and
+    ``ws`` as in l2_search, the workspace being ``l2_search_grouped_workspace_bytes``; its head holds the fp64 distances."""
+    gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
+    groups = _gpu(groups, torch.int32, "groups")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise ValueError(f"l2_search_grouped: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if groups.device != gallery.device or tuple(groups.shape) != (ng,):
+        raise ValueError(f"l2_search_grouped: groups must be int32 [{ng}] on {gallery.device} (one id per gallery row), got "
+                         f"{tuple(groups.shape)} on {groups.device}")
+    if live is not None:
+        live = _gpu(live, torch.int32, "live")
+        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
+            raise ValueError(f"l2_search_grouped: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
+                             f"{tuple(live.shape)} on {live.device}")
+    need = L.lib().vtc_l2_search_grouped_workspace_bytes(ng, nq, d, depth)
+    if ws is None:
+        ws = workspace(need, gallery.device)
+    elif need and (ws.numel() < need or ws.device != gallery.device):
+        raise ValueError(f"l2_search_grouped: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on "
+                         f"{gallery.device}")
+    ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
+    out_groups = torch.empty(nq, depth, dtype=torch.int32, device=gallery.device)
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
+    bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
+    L.check(L.lib().vtc_l2_search_grouped(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None,
+                                          groups.data_ptr(), ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
+                                          dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream()), "vtc_l2_search_grouped")
+    return ids, out_groups, dists, bits
+
+
+def l2_search_grouped_workspace_bytes(n_gallery: int, n_queries: int, d: int, depth: int) -> int:
+    """0 for a shape vtc_l2_search_grouped refuses."""
+    return int(L.lib().vtc_l2_search_grouped_workspace_bytes(int(n_gallery), int(n_queries), int(d), int(depth)))
+
+
+@on_device
+def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
+                           live: Optional[torch.Tensor] = None):
+    """One window's share of a grouped search over several: (ids [Q, depth] int64, groups [Q, depth] int32, dists64 [Q, depth] fp64,
+    nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows."""
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    ws = workspace(l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device)
+    ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live)
+    return ids, out_groups, search_dists64(ws, nq, depth), bits
+
+
+@on_device
+def l2_search_merge_grouped(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, groups_parts: torch.Tensor, return_dists: bool = True):
+    """Grouped lists over gallery windows -> the grouped list of their union (vtc_l2_search_merge_grouped): ids_parts [P, Q, depth] int64,
+    dists64_parts fp64 and groups_parts int32 of the same shape (l2_search_grouped_part's outputs, stacked; entries with id -1 are
+    ignored).  Of a group that several parts list, the entry first by (distance, id) stays.  Returns (ids, groups, dists fp32 or None)."""
+    ids_parts, dists64_parts = _gpu(ids_parts, torch.int64, "ids_parts"), _gpu(dists64_parts, torch.float64, "dists64_parts")
+    groups_parts = _gpu(groups_parts, torch.int32, "groups_parts")
+    if ids_parts.dim() != 3 or dists64_parts.shape != ids_parts.shape or groups_parts.shape != ids_parts.shape:
+        raise ValueError(f"l2_search_merge_grouped: [parts, queries, depth] lists expected, got {tuple(ids_parts.shape)}, "
+                         f"{tuple(dists64_parts.shape)} and {tuple(groups_parts.shape)}")
+    n_parts, nq, depth = ids_parts.shape
+    ids = torch.empty(nq, depth, dtype=torch.int64, device=ids_parts.device)
+    out_groups = torch.empty(nq, depth, dtype=torch.int32, device=ids_parts.device)
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=ids_parts.device) if return_dists else None
+    L.check(L.lib().vtc_l2_search_merge_grouped(ids_parts.data_ptr(), dists64_parts.data_ptr(), groups_parts.data_ptr(), n_parts, nq, depth,
+                                                ids.data_ptr(), out_groups.data_ptr(), dists.data_ptr() if dists is not None else None,
+                                                _stream()), "vtc_l2_search_merge_grouped")
+    return ids, out_groups, dists
+
+
 def pad_search_part(ids: torch.Tensor, dists64: torch.Tensor, depth: int):
     """A window's lists widened to ``depth`` columns with empty entries (-1 / +inf): windows with fewer rows than the merged list's depth."""
     short = depth - ids.shape[1]
