@@ -401,7 +401,23 @@ int vtc_l2_search_grouped(const float *gallery, const float *queries, const uint
  * it.  Limits of vtc_l2_search_merge; a null groups_parts / out_groups is refused. */
 int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_parts, const int32_t *groups_parts, int n_parts, int n_queries,
                                 int depth, int64_t *ids, int32_t *out_groups, float *dists, void *stream);
-/* hits[j] += #{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
+/* vtc_l2_search_masked / vtc_l2_search_grouped over a gallery STORED AS IEEE binary16 (uint16 bit patterns, [n_gallery, d], row stride d,
+ * 8-byte aligned; only IEEE half, not bf16): half the bytes a one-query scan streams, half the memory an index holds.  The queries stay
+ * fp32.  D(q, j) is the fp64 sum over k of ((double)queries[q][k] - (double)(float)gallery[j][k])^2, formed with the summation order of
+ * vtc_l2_search -- binary16 -> fp32 is exact, subnormal halves included (they are not flushed) -- so ids, dists and the fp64 distances
+ * at the head of the workspace are, BIT FOR BIT, those of the fp32 entry over the gallery widened to fp32: exact over the rows as
+ * stored, ties to the lower row, the same bits whichever kernel forms the distance.  A half row with a +-inf or NaN has a non-finite
+ * distance: it is never returned and sets bit 1 of nonfinite.  live may be NULL; a dead row is never read.
+ * groups == NULL: the ungrouped search (out_groups is then ignored; workspace vtc_l2_search_workspace_bytes).  groups != NULL: the
+ * grouped search, out_groups is required (workspace vtc_l2_search_grouped_workspace_bytes).  The partial lists in the workspace are fp64
+ * distances and ids, so vtc_l2_search_merge / vtc_l2_search_merge_grouped take windows of half and of fp32 galleries alike.
+ * LIMITS and refusals: those of the fp32 entries (n_queries in [1, 64], depth in [1, min(64, n_gallery)], d a multiple of 64 in
+ * [64, 2048], id_base >= 0, null gallery / queries / ids / ws, a workspace that is too small), and groups given without out_groups.
+ * There is no many-query route for a half gallery: vtc_l2_topk reads fp32 rows. */
+int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_gallery,
+                       int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists,
+                       int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* hits[j] +=#{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);
 /* R@K of BOTH directions of n PAIRED rows (a_i <-> b_i: RecallAtK.result(), model/metric.py:166-187; evaluation/eval.py:117-127) without the

@@ -37,7 +37,23 @@ Per (n_gallery, n_queries, rows per video, layout) one JSON line:
   same_ids_as_collapsed       on the first 10^4 rows: the grouped ids equal the COMPLETE (fp64 distance, row) order of the slice, formed
                               outside the library, collapsed to the first row of every video on the host (asserted; outside the timing)
 `contiguous` gives rows r * v .. r * v + r - 1 to video v (the captions of a video added together); `scattered` permutes that
-assignment over the gallery.  profiles/search_grouped.md holds a run's table."""
+assignment over the gallery.  profiles/search_grouped.md holds a run's table.
+
+With --storage float16 the tool measures the scan over a gallery STORED AS IEEE HALF (ops.l2_search* with a torch.float16 gallery =
+vtc_l2_search_half) against the fp32 scan, alone or with --live / --rows-per-video (default --storage float32: everything above):
+
+    python tools/search_bench.py --storage float16 [--live 1.0,0.1] [--rows-per-video 5] [--queries 1,2,4,8] ...
+
+Per (n_gallery, n_queries, variant) one JSON line:
+  half_us / fp32_us        the scan over the half rows and the fp32 scan over the SAME rows widened to fp32 (the same values, twice the
+                           bytes), same mask and groups, in alternation as above
+  half_over_fp32           ratio of the medians
+  same_bits_as_fp32        ids and fp32 dists of the two are equal (asserted: binary16 -> fp32 is exact)
+  same_ids_as_host         on the first 10^4 rows: the half ids equal the complete fp64 (distance, row) order over the widened rows formed
+                           outside the library, dead rows dropped, collapsed to the first row of every video (asserted; outside the timing)
+  top_depth_agreement      the share of the ids an fp32 index of the UNROUNDED unit rows returns for the same queries (same mask and
+                           groups) that the half index returns too: what rounding the stored rows to 11 bits costs
+profiles/search_half.md holds a run's table."""
 import argparse
 import json
 import os
@@ -135,13 +151,17 @@ def masked_main(args):
     return lines
 
 
-def collapsed_ids(gallery, queries, groups, depth):
-    """The definition, outside the library: per query the full fp64 (distance, row) order, the first row of every group, cut."""
+def collapsed_ids(gallery, queries, groups, depth, live=None):
+    """The definition, outside the library: per query the full fp64 (distance, row) order (of the live rows), the first row of every
+    group, cut."""
     g64, grp = gallery.double(), groups.cpu().numpy()
     out = np.full((queries.shape[0], depth), -1, np.int64)
     for i in range(queries.shape[0]):
         dist = ((g64 - queries[i].double()) ** 2).sum(1)
-        order = torch.sort(dist, stable=True)[1].cpu().numpy()
+        if live is not None:
+            dist = dist[live]                                  # compacted: positions are mapped back below
+        order = torch.sort(dist, stable=True)[1]
+        order = (order if live is None else torch.nonzero(live).reshape(-1)[order]).cpu().numpy()
         _, first = np.unique(grp[order], return_index=True)
         keep = order[np.sort(first)[:depth]]
         out[i, :keep.size] = keep
@@ -193,6 +213,80 @@ def grouped_main(args):
     return lines
 
 
+def half_main(args):
+    """--storage float16: the half scan against the fp32 scan over the same (widened) rows -- plain, with --live, with --rows-per-video."""
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    variants = [("plain", None, None)]
+    if args.live:
+        variants = [(f"live {f}", float(f), None) for f in args.live.split(",")]
+    if args.rows_per_video:
+        variants = [(f"{name}, {r} rows per video" if name != "plain" else f"{r} rows per video", f, int(r))
+                    for name, f, _ in variants for r in args.rows_per_video.split(",")]
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        unrounded = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        half = unrounded.to(torch.float16)
+        wide = half.float()
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(unrounded[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            for name, fraction, rpv in variants:
+                words = flags = groups = None
+                if fraction is not None:
+                    flags = live_mask(ng, fraction, args.live_pattern, gen)
+                    words = ops.row_mask_pack(flags)
+                    assert int(flags.sum()) >= args.depth * (rpv or 1), "fewer live rows than the depth: nothing to compare"
+                if rpv is not None:
+                    groups = (torch.arange(ng, device="cuda") // rpv).to(torch.int32)
+                    if args.video_layout == "scattered":
+                        groups = groups[torch.randperm(ng, device="cuda", generator=gen)].contiguous()
+                    assert ng // rpv >= args.depth, "fewer videos than the depth: nothing to compare"
+                need = (ops.l2_search_grouped_workspace_bytes if rpv else ops.l2_search_workspace_bytes)(ng, nq, args.d, args.depth)
+                ws_h, ws_f = ops.workspace(need, half.device), ops.workspace(need, half.device)
+
+                def search(g, ws, n=None):                     # (ids, dists) of the variant over the first n rows of g
+                    if n is not None:
+                        g, w, gr = g[:n], None if flags is None else ops.row_mask_pack(flags[:n]), None if groups is None else groups[:n].contiguous()
+                    else:
+                        w, gr = words, groups
+                    if gr is None:
+                        return ops.l2_search(g, queries, args.depth, ws=ws, live=w)[:2]
+                    out = ops.l2_search_grouped(g, queries, gr, args.depth, ws=ws, live=w)
+                    return out[0], out[2]
+                entries = [lambda: search(half, ws_h), lambda: search(wide, ws_f)]
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times, outs = [[] for _ in entries], [None, None]
+                for _ in range(args.calls):
+                    for k, fn in enumerate(entries):
+                        us, outs[k] = timed(fn)
+                        times[k].append(us)
+                same_bits = bool(torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]))
+                n_check = min(ng, 10 ** 4)
+                got = search(half, None, n_check)[0].cpu().numpy()
+                host_groups = torch.arange(n_check, device="cuda") if groups is None else groups[:n_check]
+                same_host = bool(np.array_equal(got, collapsed_ids(wide[:n_check], queries, host_groups, args.depth,
+                                                                   None if flags is None else flags[:n_check])))
+                ids_u = search(unrounded, None)[0]
+                ids_h = outs[0][0]
+                agree = float(np.mean([np.isin(a, b).mean() for a, b in zip(ids_u.cpu().numpy(), ids_h.cpu().numpy())]))
+                h, f = stat(times[0]), stat(times[1])
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "variant": name,
+                        "half_us": h, "fp32_us": f, "half_over_fp32": round(h["median"] / f["median"], 3), "passes": passes(nq),
+                        "half_tb_per_s": round(ng * args.d * 2 / (1e6 * h["median"]), 3), "fp32_tb_per_s": round(ng * args.d * 4 / (1e6 * f["median"]), 3),
+                        "same_bits_as_fp32": same_bits, "same_ids_as_host": same_host, "top_depth_agreement": round(agree, 4)}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                assert same_bits, "the half scan and the fp32 scan over the widened rows returned different bits"
+                assert same_host, "the half scan and the host's full fp64 order over the widened rows returned different ids"
+                del ws_h, ws_f
+        del unrounded, half, wide
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -207,9 +301,14 @@ def main(argv=None):
     ap.add_argument("--topk-gathered", action="store_true", help="with --live: also time gather + l2_topk(EXACT) over the live rows")
     ap.add_argument("--rows-per-video", type=str, default=None, help="rows per video, e.g. 1,5,20: measure the grouped scan (see above)")
     ap.add_argument("--video-layout", type=str, default="contiguous", choices=("contiguous", "scattered"))
+    ap.add_argument("--storage", type=str, default="float32", choices=("float32", "float16"),
+                    help="float16: measure the scan over a half gallery against the fp32 scan (see above); works with --live / --rows-per-video")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.storage == "float16":
+        write_out(args.out, half_main(args))
+        return
     if args.live:
         write_out(args.out, masked_main(args))
         return

@@ -112,6 +112,7 @@ SIGNATURES = {
     "vtc_l2_search_grouped_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vtc_l2_search_grouped": (C.c_int, [fp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
     "vtc_l2_search_merge_grouped": (C.c_int, [ip, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp, vp]),
+    "vtc_l2_search_half": (C.c_int, [vp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
     "vtc_recall_hits": (C.c_int, [ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp]),
     "vtc_recall_hits_pair": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp, vp]),
     "vtc_l2_recall_bidir_supported": (C.c_int, [C.c_int, C.c_int]),

@@ -28,6 +28,11 @@
 //                                (part_g) carries the groups to the merge; the grid is the ungrouped scan's.
 //   merge_grouped_kernel<Src>    merge_kernel with GroupLists, for the workgroups' lists (ScanGroupLists) and the caller's (PartGroupLists).
 //
+// vtc_l2_search_half: the masked / grouped search over a gallery stored as IEEE binary16.  half_scan_kernel / half_scan_grouped_kernel
+// are scan_body with the gallery's element type _Float16: the row loader (sweep_common.h, row_piece) reads 8 bytes a lane where the
+// fp32 scan reads 16 and widens them exactly, every lane keeps its columns, and the same statements form the same fp64 bits as the
+// fp32 scan over the widened rows.  The workspace, the lists and both merges do not know how the gallery is stored.
+//
 // Why merging de-duplicated lists is exact, for the waves' lists in the LDS, the workgroups' lists and the caller's windows alike: a
 // group of the union's first `depth` has its overall nearest row in some part.  In that part fewer than `depth` groups have a smaller
 // local minimum (a local minimum is not below the overall one of its group, and fewer than `depth` groups are nearer overall), so that
@@ -247,8 +252,13 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
 // the insertion.  Loads return in order, so when the row's distances are there -- which every step waits for anyway -- the group has
 // arrived: the rejecting path never waits on it, and the insertion never pays a memory round trip of its own, which a lazy load would
 // cost exactly while a wave fills its lists and every row is inserted.  The price is NR load instructions and NR registers a step.
-template <int NQ, int NR, bool MASKED, bool GROUPED>
-__device__ __forceinline__ void scan_body(const float *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
+//
+// G: the gallery's element type.  float is the scan of vtc_l2_search*; _Float16 that of vtc_l2_search_half, over rows stored as IEEE
+// binary16.  Nothing but the row loader differs (sweep_common.h, row_piece): lane l still keeps the columns 4 l .. 4 l + 3 (+ 256 i),
+// loads 8 bytes a piece where the fp32 scan loads 16, widens them exactly and forms the distance with the same statements in the same
+// order -- the same fp64 bits as the fp32 scan over the widened rows.  The mask, the groups and the queries in the LDS are untouched.
+template <int NQ, int NR, bool MASKED, bool GROUPED, typename G>
+__device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
                                           const int *__restrict__ groups, int ng, int nq, int d, int depth, double *__restrict__ part_d,
                                           int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite) {
   extern __shared__ float4 smem4[];
@@ -394,6 +404,21 @@ __global__ __launch_bounds__(256) void search_scan_kernel(const float *__restric
                                                           double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
   scan_body<NQ, NR, MASKED, false>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite);
 }
+// The half gallery's two kernels: the same body with G = _Float16, under names of their own.
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void half_scan_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
+                                                        const unsigned *__restrict__ live, int ng, int nq, int d, int depth,
+                                                        double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, false>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite);
+}
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void half_scan_grouped_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
+                                                                const unsigned *__restrict__ live, const int *__restrict__ groups, int ng,
+                                                                int nq, int d, int depth, double *__restrict__ part_d,
+                                                                int *__restrict__ part_i, int *__restrict__ part_g,
+                                                                int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, true>(gallery, queries, live, groups, ng, nq, d, depth, part_d, part_i, part_g, nonfinite);
+}
 template <int NQ, int NR, bool MASKED>
 __global__ __launch_bounds__(256) void search_grouped_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
                                                                   const unsigned *__restrict__ live, const int *__restrict__ groups, int ng,
@@ -498,8 +523,9 @@ SearchWs search_ws(void *ws, int ng, int nq, int depth, bool grouped = false) {
 
 // The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
 // most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
-template <int NQ, int NR, bool MASKED, bool GROUPED>
-int launch_scan(const float *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
+// G = _Float16: the half gallery's kernels, by the same rule among themselves.
+template <int NQ, int NR, bool MASKED, bool GROUPED, typename G>
+int launch_scan(const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
                 const SearchWs &s, int tiles, int *nonfinite, hipStream_t stream) {
   // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
   static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
@@ -508,8 +534,12 @@ int launch_scan(const float *gallery, const float *queries, const unsigned *live
   std::atomic<int> &slot = resident[dev][d / 64 - 1];
   int per_cu = slot.load(std::memory_order_relaxed);
   if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_scan_kernel<NQ, NR, false>, 256, scan_lds_bytes(NQ, d)) != hipSuccess || per_cu < 1)
-      per_cu = 1;
+    constexpr bool HALF = std::is_same_v<G, _Float16>;
+    auto resident_of = [&](int &n, auto kernel) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, scan_lds_bytes(NQ, d)); };
+    hipError_t e;
+    if constexpr (HALF) e = resident_of(per_cu, half_scan_kernel<NQ, NR, false>);
+    else e = resident_of(per_cu, search_scan_kernel<NQ, NR, false>);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
     // The masked scan runs the unmasked scan's grid (never more than is resident of its own), so both leave the same number of lists.
     // The 8 x 1 tile takes fewer registers with the mask and would fit a fourth workgroup per CU; every wave fills lists of its own
     // before it starts rejecting rows, and with all rows live at 10^5 rows the fourth workgroup put the masked scan 4.5 - 5.8 % behind
@@ -517,18 +547,27 @@ int launch_scan(const float *gallery, const float *queries, const unsigned *live
     // written down in profiles/search_masked.md.
     // The grouped scan follows the same rule: the unmasked, ungrouped scan's grid, never more than is resident of its own.
     int own = per_cu;
-    if (GROUPED) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_grouped_scan_kernel<NQ, NR, MASKED>, 256, scan_lds_bytes(NQ, d)) == hipSuccess &&
-          own >= 1)
-        per_cu = std::min(per_cu, own);
-    } else if (MASKED && hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, search_scan_kernel<NQ, NR, true>, 256, scan_lds_bytes(NQ, d)) == hipSuccess &&
-               own >= 1)
-      per_cu = std::min(per_cu, own);
+    if constexpr (GROUPED) {
+      if constexpr (HALF) e = resident_of(own, half_scan_grouped_kernel<NQ, NR, MASKED>);
+      else e = resident_of(own, search_grouped_scan_kernel<NQ, NR, MASKED>);
+      if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
+    } else if constexpr (MASKED) {
+      if constexpr (HALF) e = resident_of(own, half_scan_kernel<NQ, NR, true>);
+      else e = resident_of(own, search_scan_kernel<NQ, NR, true>);
+      if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
+    }
     slot.store(per_cu, std::memory_order_relaxed);
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  if constexpr (GROUPED)
+  if constexpr (std::is_same_v<G, _Float16>) {
+    if constexpr (GROUPED)
+      hipLaunchKernelGGL((half_scan_grouped_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
+                         live, groups, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
+    else
+      hipLaunchKernelGGL((half_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live, ng,
+                         nq, d, depth, s.part_d, s.part_i, nonfinite);
+  } else if constexpr (GROUPED)
     hipLaunchKernelGGL((search_grouped_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
                        live, groups, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
   else
@@ -536,9 +575,11 @@ int launch_scan(const float *gallery, const float *queries, const unsigned *live
                        nq, d, depth, s.part_d, s.part_i, nonfinite);
   return blocks;
 }
-// the instantiation of the plan's tile shape
-template <bool MASKED, bool GROUPED = false>
-int launch_scan_tile(const SearchPlan &p, const float *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d,
+// the instantiation of the plan's tile shape.  The half scan keeps the fp32 scan's shapes: 8 gallery rows a step for its one- and
+// two-query tiles (a piece of a half row is 8 bytes a lane, so a step has half the bytes in flight) were measured and lost
+// (profiles/search_half.md).
+template <bool MASKED, bool GROUPED = false, typename G>
+int launch_scan_tile(const SearchPlan &p, const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d,
                      int depth, const SearchWs &s, int *nonfinite, hipStream_t stream) {
   if (p.tile_q == 1) return launch_scan<1, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
   if (p.tile_q == 2) return launch_scan<2, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
@@ -653,5 +694,39 @@ extern "C" int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const doubl
                      PartGroupLists{dists_parts, ids_parts, groups_parts, nq, depth, 0}, n_parts, depth, (int64_t)0, ids, out_groups, dists,
                      (double *)nullptr);
   VTC_LAUNCH_CHECK("l2_search_merge_grouped");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_half(const uint16_t *gallery_, const float *queries, const uint32_t *live, const int32_t *groups, int ng, int nq, int d,
+                                  int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
+                                  size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const _Float16 *gallery = reinterpret_cast<const _Float16 *>(gallery_);
+  VTC_CHECK(gallery && queries && ids && (!groups || out_groups), "l2_search_half: null argument");
+  VTC_CHECK(ng >= 1, "l2_search_half: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_half: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search_half: depth=%d must be in [1, min(%d, n_gallery)]", depth,
+            SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search_half: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "l2_search_half: id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth, groups != nullptr);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search_half: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const SearchPlan p = search_plan(nq);
+  int blocks;
+  if (groups)
+    blocks = live ? launch_scan_tile<true, true>(p, gallery, queries, live, groups, ng, nq, d, depth, s, nonfinite, stream)
+                  : launch_scan_tile<false, true>(p, gallery, queries, nullptr, groups, ng, nq, d, depth, s, nonfinite, stream);
+  else
+    blocks = live ? launch_scan_tile<true, false>(p, gallery, queries, live, nullptr, ng, nq, d, depth, s, nonfinite, stream)
+                  : launch_scan_tile<false, false>(p, gallery, queries, nullptr, nullptr, ng, nq, d, depth, s, nonfinite, stream);
+  VTC_LAUNCH_CHECK2("l2_search_half", "scan");
+  if (groups)
+    hipLaunchKernelGGL(merge_grouped_kernel<ScanGroupLists>, dim3(nq), dim3(256), 0, stream, ScanGroupLists{s.part_d, s.part_i, s.part_g, blocks, depth, 0},
+                       blocks, depth, id_base, ids, out_groups, dists, s.dists64);
+  else
+    hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth, id_base,
+                       ids, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search_half", "merge");
   return 0;
 }

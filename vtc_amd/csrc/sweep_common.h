@@ -11,6 +11,16 @@ __device__ __forceinline__ double dist64_step(const float4 a, const float4 b) {
   const double e0 = (double)a.x - (double)b.x, e1 = (double)a.y - (double)b.y, e2 = (double)a.z - (double)b.z, e3 = (double)a.w - (double)b.w;
   return e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
 }
+// A lane's piece of a GALLERY row: the four columns at p, as the fp32 values the distance is formed of.  An fp32 row gives them as they
+// are (the 16-byte load every caller has always made).  A row stored as IEEE binary16 (the query-time search's half galleries) gives
+// the same four columns widened -- 8 bytes loaded, four v_cvt_f32_f16; binary16 -> fp32 is exact, subnormals included, so the float4
+// is bit for bit what the fp32 load returns from the widened row and everything after it is shared.
+__device__ __forceinline__ float4 row_piece(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 row_piece(const _Float16 *p) {
+  typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+  const half4_t h = *reinterpret_cast<const half4_t *>(p);
+  return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+}
 // fp64 sum_k (q_k - g_k)^2 of NB (query row, gallery row) pairs by the whole wave: qrow(u) / grow(u) are pair u's rows.  Per pair a lane adds
 // the steps of its chunks in ascending k, then the xor butterfly leaves every lane with the same bits.  EVERY kernel that forms a distance --
 // the re-rank, the fallback, the rescan, the recall-only finish, the full-rank sweep -- does it through this loop (the wrappers below), so a
@@ -26,7 +36,7 @@ __device__ __forceinline__ void wave_dist64_core(QRow qrow, GRow grow, int d, in
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       a[u] = *reinterpret_cast<const float4 *>(qrow(u) + c);
-      b[u] = *reinterpret_cast<const float4 *>(grow(u) + c);
+      b[u] = row_piece(grow(u) + c);
     }
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
@@ -61,8 +71,9 @@ __device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, 
 }
 // the NB consecutive query rows qs[0 .. NB) (row stride d; global memory or LDS) against the NR gallery rows jj[] (valid indices, as above):
 // out[u * NR + r] = query u, gallery row jj[r].  The query-time search (search.hip): its tile of queries stays put while the gallery streams by.
-template <int NB, int NR = 1>
-__device__ __forceinline__ void wave_dist64_queries(const float *qs, const float *__restrict__ gallery, const int (&jj)[NR], int d, int lane,
+// G is the gallery's element type, float or _Float16 (row_piece); the queries are fp32 either way.
+template <int NB, int NR = 1, typename G = float>
+__device__ __forceinline__ void wave_dist64_queries(const float *qs, const G *__restrict__ gallery, const int (&jj)[NR], int d, int lane,
                                                     double (&out)[NB * NR]) {
   wave_dist64_core<NB * NR>([&](int p) { return qs + (size_t)(p / NR) * d; }, [&](int p) { return gallery + (size_t)jj[p % NR] * d; }, d, lane, out);
 }

@@ -471,7 +471,8 @@ def sharded_rank_stats(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor,
 
 def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int, world: int):
     """Query-time search over a gallery that is row-sharded across ranks: this rank stores the rows [row_base, row_base + n_local) of the
-    index (fp32 [n_local, d], d % 64 == 0) and every rank holds the same queries [Q <= 64, d].  Returns (ids [Q, k] int64 -- global row
+    index (fp32 or torch.float16 [n_local, d], d % 64 == 0 -- half rows are searched as stored, ops.l2_search; the partial lists are fp64
+    either way) and every rank holds the same fp32 queries [Q <= 64, d].  Returns (ids [Q, k] int64 -- global row
     ids --, dists [Q, k] fp32), identical on every rank and equal to ops.l2_search over the whole gallery.
 
     A local ops.l2_search_part(id_base = row_base), ONE all_gather of the partial lists -- ids and fp64 distances in one int64 buffer
@@ -498,8 +499,8 @@ def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch
 
 def sharded_search_videos(index_rows_local: torch.Tensor, video_ids_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int,
                           world: int):
-    """``sharded_search`` for a gallery with several rows per video: this rank stores the rows [row_base, row_base + n_local) and their
-    video ids (int32 [n_local]); a video's rows may lie on different ranks.  Returns (video_ids [Q, k] int64, row_ids [Q, k] int64 --
+    """``sharded_search`` for a gallery with several rows per video: this rank stores the rows [row_base, row_base + n_local), fp32 or
+    torch.float16 as there, and their video ids (int32 [n_local]); a video's rows may lie on different ranks.  Returns (video_ids [Q, k] int64, row_ids [Q, k] int64 --
     global row ids --, dists [Q, k] fp32), identical on every rank and equal to ops.l2_search_grouped over the whole gallery: the k
     nearest distinct videos, each by its nearest row, -1 / -1 / +inf where there are fewer.
 

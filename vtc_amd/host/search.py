@@ -22,6 +22,14 @@ VIDEOS are what a query wants, each by its nearest row (vtc_l2_search_grouped: t
     index.add(caption_embeddings, video_ids=video_of_caption)      # int [n] in [0, 2^31); a video's rows in any number of calls
     videos, rows, scores = index.search_videos(queries, k=10)
     index.remove_videos([7, 9])
+
+The rows can be stored as IEEE half, half the memory and half the bytes a one-query search streams (vtc_l2_search_half):
+
+    index = VideoIndex(512, storage=torch.float16)    # or: index = fp32_index.converted(torch.float16)
+
+A stored row is then the unit row rounded to nearest-even to the 11 significant bits of binary16 per component.  The search stays exact
+over the rows AS STORED: the fp64 distances of the fp32 queries and the widened half rows, bit for bit what an fp32 index holding those
+widened rows returns.
 """
 from __future__ import annotations
 
@@ -91,7 +99,12 @@ class VideoIndex:
     """A gallery of fp32 rows on the GPU with exact nearest-row search.  Ids are positions in insertion order and are never reused:
     ``ntotal`` counts the rows ever added, ``len(index)`` the live ones, ``remove`` only clears a row's bit (no compaction, no
     renumbering; the memory stays).  With nothing removed and no ``subset`` a search is routed as the constants below say; otherwise it
-    is the masked scan (vtc_l2_search_masked) for any number of queries, in slices of 64 -- vtc_l2_topk has no mask."""
+    is the masked scan (vtc_l2_search_masked) for any number of queries, in slices of 64 -- vtc_l2_topk has no mask.
+    ``storage=torch.float16`` keeps the rows as IEEE half (``index.storage``): ``add`` normalises in fp32 and rounds to nearest-even, so
+    a stored row is the unit row rounded to 11 significant bits per component, and every search is exact over those stored rows (scores
+    are 1 - D/2 of them).  A half index ALWAYS searches with the scan (vtc_l2_search_half), in slices of 64 queries and by the masked
+    route's rules: vtc_l2_topk reads fp32 rows, so ROUTE_TOPK_MIN_QUERIES does not apply, and many-query batches are slower than on
+    an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries).  ``converted`` moves an index over."""
     #: queries per call from which search() goes through ops.l2_topk(precision=SWEEP_EXACT) instead of ops.l2_search (which takes up to
     #: 64).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
     #: vtc_l2_topk): the scan's time grows with the number of queries (one gallery pass per started tile of 8), vtc_l2_topk's does not.
@@ -104,8 +117,9 @@ class VideoIndex:
     #: as at 1 and 2, than at 8 and 12: unexplained, that entry is not changed here.  13 - 15 queries were not measured.)
     ROUTE_TOPK_MIN_QUERIES = 12
     MAX_K = 64                # one list entry per lane of a wavefront, as everywhere in the sweeps
+    STORAGE = {"float32": torch.float32, "float16": torch.float16}      # the state dict's names of the storage dtypes
 
-    def __init__(self, dim, device="cuda", normalized=False):
+    def __init__(self, dim, device="cuda", normalized=False, storage=torch.float32):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError(f"vtc_amd VideoIndex: the index lives on the GPU (got {device}); this package has no CPU path")
@@ -117,7 +131,10 @@ class VideoIndex:
         self.width = self.dim + -self.dim % 64          # zero-padded to the sweep's granule of 64 columns (host/metric.py pads alike)
         self.device = device
         self.normalized = bool(normalized)
-        self._rows = torch.empty(0, self.width, dtype=torch.float32, device=device)       # capacity rows; the first _n are the index
+        if storage not in self.STORAGE.values():
+            raise ValueError(f"VideoIndex: storage={storage} must be torch.float32 or torch.float16")
+        self.storage = storage
+        self._rows = torch.empty(0, self.width, dtype=storage, device=device)       # capacity rows; the first _n are the index
         self._n = 0
         self._ws = None
         self._live = None                   # bool [ntotal] on the device once a row was removed; None: every row is live
@@ -151,10 +168,12 @@ class VideoIndex:
         return None if self._video_ids is None else self._video_ids[:self._n].clone()
 
     # ---- rows ----------------------------------------------------------------------------------
-    def _prepared(self, x, what, check=True):
+    def _prepared(self, x, what, check=True, stored=False):
         """fp32 [n, dim] on the index's device -> unit rows (unless the index was built as ``normalized``), zero-padded to ``width``;
         with ``check``, NaN / inf rows are rejected as the eval entry points reject them (ops.nonfinite_bits: a 4-byte device-to-host
-        read, so a host sync)."""
+        read, so a host sync).  ``stored``: the rows as the index keeps them -- for half storage rounded to nearest-even AFTER the fp32
+        normalisation and BEFORE the check, which then sees what the rounding made of them (a component above 65504 of a
+        ``normalized`` index's row has become inf)."""
         x = torch.as_tensor(x)
         if x.dim() != 2 or x.shape[1] != self.dim:
             raise ValueError(f"VideoIndex: {what} must be [n, {self.dim}], got {tuple(x.shape)}")
@@ -163,27 +182,30 @@ class VideoIndex:
             return x.new_zeros(0, self.width)
         if not self.normalized:
             x = ops.normalize_rows(x)
+        if stored and self.storage != torch.float32:
+            x = x.to(self.storage).float()                     # rounded; widened again (exactly) for the check and the padding
         if check and ops.nonfinite_bits(x, x):
             raise ValueError(f"VideoIndex: non-finite values in the {what}" + ("" if self.normalized else " (after normalisation: a NaN, an inf "
                              "or an all-zero row)") + " -- such a row has no distance to anything")
         if self.width != self.dim:
             x = torch.nn.functional.pad(x, (0, self.width - self.dim))
-        return x
+        return x.to(self.storage) if stored else x
 
     def add(self, embeddings, video_ids=None):
         """Appends [n, dim] fp32 rows; their ids are their positions in insertion order (removed ids are not reused).  Returns the id of
-        the first one, which is ``ntotal`` before the call.
+        the first one, which is ``ntotal`` before the call.  A half index normalises in fp32 as an fp32 one does and then rounds to
+        nearest-even (``.to(torch.float16)``); the non-finite check runs on the rounded rows.
         ``video_ids`` (an integer [n] tensor or sequence, values in [0, 2^31)) names the video of every row; one video's rows may come in
         different calls.  An index is GROUPED iff its first non-empty add passed them, and every later add must do the same as the first:
         mixing the two forms raises ValueError and changes nothing."""
-        x = self._prepared(embeddings, "embeddings")
+        x = self._prepared(embeddings, "embeddings", stored=True)
         first, n = self._n, x.shape[0]
         vids = None if video_ids is None else _video_id_tensor(video_ids, n, self.device, "add")
         if n and first and (vids is not None) != self.grouped:
             raise ValueError("VideoIndex.add: this index " + ("has a video id for every row: pass video_ids" if self.grouped else
                              "was started without video_ids: its rows have none, so later rows cannot either"))
         if first + n > self._rows.shape[0]:                 # amortised doubling
-            grown = torch.empty(max(first + n, 2 * self._rows.shape[0], 1024), self.width, dtype=torch.float32, device=self.device)
+            grown = torch.empty(max(first + n, 2 * self._rows.shape[0], 1024), self.width, dtype=self.storage, device=self.device)
             grown[:first] = self._rows[:first]
             self._rows = grown
         self._rows[first:first + n] = x
@@ -254,11 +276,15 @@ class VideoIndex:
 
     @property
     def rows(self):
-        """The stored rows [ntotal, width] (a view), removed ones included."""
+        """The stored rows [ntotal, width] (a view) in the storage dtype, removed ones included."""
         return self._rows[:self._n]
 
     def state_dict(self):
+        """The rows in the storage dtype; a half index writes "storage": "float16" beside them.  An fp32 index's state has the keys it
+        always had -- a state without "storage" IS fp32 (``load_state_dict`` also takes an explicit "float32")."""
         state = {"rows": self.rows[:, :self.dim].clone(), "count": self._n, "dim": self.dim, "normalized": self.normalized}
+        if self.storage != torch.float32:
+            state["storage"] = {v: k for k, v in self.STORAGE.items()}[self.storage]
         if self._live is not None:
             state["live"] = self._live.clone()
         if self.grouped:
@@ -266,11 +292,20 @@ class VideoIndex:
         return state
 
     def load_state_dict(self, state):
+        """A state whose storage differs from the index's raises ValueError (``converted`` changes the storage); rows are taken bit
+        for bit, never rounded or normalised again."""
+        storage = state.get("storage", "float32")
+        if self.STORAGE.get(storage) != self.storage:
+            raise ValueError(f"VideoIndex.load_state_dict: the state's storage is {storage}, the index's {self.storage} "
+                             "(load it into an index of that storage; converted() changes it)")
         rows = torch.as_tensor(state["rows"])
+        if storage != "float32" and rows.dtype != self.storage:
+            raise ValueError(f"VideoIndex.load_state_dict: a {storage} state holds {rows.dtype} rows")
         if int(state.get("dim", self.dim)) != self.dim or rows.dim() != 2 or rows.shape[1] != self.dim or int(state["count"]) != rows.shape[0]:
             raise ValueError(f"VideoIndex.load_state_dict: rows {tuple(rows.shape)}, count {state.get('count')} do not fit dim {self.dim}")
-        rows = rows.to(device=self.device, dtype=torch.float32)
-        if rows.shape[0] and ops.nonfinite_bits(rows.contiguous(), rows.contiguous()):
+        rows = rows.to(device=self.device, dtype=self.storage)
+        wide = rows.float().contiguous()
+        if rows.shape[0] and ops.nonfinite_bits(wide, wide):
             raise ValueError("VideoIndex.load_state_dict: non-finite values in the stored rows")
         self._rows = torch.nn.functional.pad(rows, (0, self.width - self.dim)).contiguous()     # stored rows are final: not normalised again
         live = state.get("live")
@@ -291,6 +326,23 @@ class VideoIndex:
         self._n_live = self._n if live is None else int(live.sum())
         self._generation += 1
 
+    def converted(self, storage):
+        """A new index of ``storage`` (torch.float32 or torch.float16) with the same ids, ``ntotal``, live mask and video ids: fp32 ->
+        half rounds every stored row to nearest-even, half -> fp32 widens exactly, the same storage gives a copy.  This index is not
+        changed; RowSubsets belong to the index they were built on."""
+        other = VideoIndex(self.dim, device=self.device, normalized=self.normalized, storage=storage)
+        rows = self.rows.to(other.storage)
+        if other.storage != self.storage and self._n:
+            wide = rows.float().contiguous()                   # fp32 -> half can only overflow for a ``normalized`` index's rows
+            if ops.nonfinite_bits(wide, wide):
+                raise ValueError(f"VideoIndex.converted: a stored row has a component that {storage} cannot hold")
+        other._rows = rows.clone() if rows.data_ptr() == self._rows.data_ptr() else rows.contiguous()
+        other._n, other._n_live = self._n, self._n_live
+        other._live = None if self._live is None else self._live.clone()
+        other._video_ids = None if self._video_ids is None else self._video_ids[:self._n].clone()
+        other._generation += 1
+        return other
+
     # ---- search --------------------------------------------------------------------------------
     def _workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes:
@@ -307,11 +359,16 @@ class VideoIndex:
         non-finite one raises ValueError: vtc_l2_topk has no defined answer for such a row.
         After a ``remove``, or with a ``subset`` (a RowSubset of this index), only the live members are searched: the masked scan for any
         number of queries, 64 per call, with the few-query rule for a non-finite query (a row of -1 / -inf, no raise, no read) and no host
-        sync.  A subset with fewer than k live members gives rows that end in -1 / -inf."""
+        sync.  A subset with fewer than k live members gives rows that end in -1 / -inf.
+        A half index (``storage=torch.float16``) takes that route for EVERY search -- the scan over the stored half rows
+        (vtc_l2_search_half), 64 queries per call, only enqueued, a non-finite query a row of -1 / -inf -- whatever the number of
+        queries: vtc_l2_topk reads fp32 rows.  Batches of many queries are therefore slower than on an fp32 index
+        (profiles/search.md: 4.5 x at 64 queries).  The scores are 1 - D/2 over the stored rows, each the unit row rounded to
+        binary16's 11 significant bits per component."""
         k = int(k)
         if not 1 <= k <= min(self.MAX_K, self._n_live):
             raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
-        if subset is not None or self._live is not None:
+        if subset is not None or self._live is not None or self.storage != torch.float32:
             return self._search_masked(queries, k, subset)
         scan = 0 < len(queries) < min(self.ROUTE_TOPK_MIN_QUERIES, ops.SEARCH_MAX_QUERIES + 1)
         q = self._prepared(queries, "queries", check=not scan)
@@ -332,7 +389,7 @@ class VideoIndex:
         q = self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
             raise ValueError("VideoIndex.search: no queries")
-        words = self._live_words() if subset is None else subset.words()
+        words = self._live_words() if subset is None else subset.words()      # None on a half index with every row live: no mask
         g, step = self.rows, ops.SEARCH_MAX_QUERIES
         ws = self._workspace(ops.l2_search_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
         out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
@@ -344,7 +401,7 @@ class VideoIndex:
         query, nearest first, each with its nearest live row (the best-matching caption, comment or chunk) and that row's score as
         ``search`` gives it.  Ties go to the lower row.  Always the scan (vtc_l2_search_grouped; vtc_l2_topk has no grouping), 64 queries
         per call, with the few-query rules of the masked route: only enqueued, no host sync, and a non-finite query gets a row of
-        -1 / -1 / -inf.  1 <= k <= min(64, len(index)), len counting live ROWS; fewer than k distinct live videos (in the ``subset``, if
+        -1 / -1 / -inf.  A half index searches its stored half rows the same way (vtc_l2_search_half).  1 <= k <= min(64, len(index)), len counting live ROWS; fewer than k distinct live videos (in the ``subset``, if
         one is given) give rows that end in -1 / -1 / -inf.  On an ungrouped index it raises ValueError."""
         if not self.grouped:
             raise ValueError("VideoIndex.search_videos: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")

@@ -362,6 +362,14 @@ def l2_topk_bidir(a: torch.Tensor, b: torch.Tensor, depth: int, precision: int =
 SEARCH_MAX_QUERIES = 64       # vtc_l2_search's limit; more queries go through l2_topk
 
 
+def _search_gallery(gallery: torch.Tensor) -> torch.Tensor:
+    """The gallery of a query-time search: fp32, or IEEE half (vtc_l2_search_half); every other dtype raises TypeError."""
+    gallery = _gpu(gallery, None, "gallery")
+    if gallery.dtype not in (torch.float32, torch.float16):
+        raise TypeError(f"vtc_amd: gallery must be torch.float32 or torch.float16, got {gallery.dtype}")
+    return gallery
+
+
 @on_device
 def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
               ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
@@ -371,8 +379,11 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     caller's ``ws`` of at least ``l2_search_workspace_bytes`` the fp64 distances of the result are ``search_dists64(ws, Q, depth)``.
     ``live`` (vtc_l2_search_masked): packed int32 words [ceil(n / 32)] on the gallery's device (``row_mask_pack``), row j takes part iff bit
     j & 31 of word j >> 5 is set.  The result is that of the search over the live rows alone, with their original row numbers; a dead
-    row is neither read nor counted in nonfinite_bits.  ``depth`` is still bounded by the physical row count."""
-    gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
+    row is neither read nor counted in nonfinite_bits.  ``depth`` is still bounded by the physical row count.
+    A ``torch.float16`` gallery (vtc_l2_search_half) is searched as stored: the distances are the fp64 ones of the fp32 queries and the
+    half rows widened to fp32, which is exact -- every output, the fp64 distances in ``ws`` included, has the bits of this call over
+    ``gallery.float()``.  The queries stay fp32; any other gallery dtype raises TypeError."""
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     ng, d = gallery.shape
     nq = queries.shape[0]
     if queries.shape[1] != d:
@@ -392,7 +403,10 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
     tail = (int(id_base), ids.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    if live is None:
+    if gallery.dtype == torch.float16:
+        L.check(L.lib().vtc_l2_search_half(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, None, ng, nq,
+                                           d, depth, tail[0], tail[1], None, *tail[2:]), "vtc_l2_search_half")
+    elif live is None:
         L.check(L.lib().vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, *tail), "vtc_l2_search")
     else:
         L.check(L.lib().vtc_l2_search_masked(gallery.data_ptr(), queries.data_ptr(), live.data_ptr(), ng, nq, d, depth, *tail),
@@ -436,7 +450,8 @@ def search_dists64(ws: torch.Tensor, n_queries: int, depth: int) -> torch.Tensor
 def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None):
     """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
     l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list).
-    ``live``: the window's own packed row mask (bit 0 of word 0 is the window's first row), as l2_search takes it."""
+    ``live``: the window's own packed row mask (bit 0 of word 0 is the window's first row), as l2_search takes it.  The window may be
+    fp32 or ``torch.float16``; the fp64 lists do not depend on how the rows are stored, so l2_search_merge takes both."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
@@ -468,8 +483,9 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     of every group stays; the first ``depth`` of those are the result -- the ``depth`` nearest distinct groups, each by its nearest row.
     Returns (ids [Q, depth] int64 = id_base + that row, -1 where fewer groups have a finite distance; groups [Q, depth] int32, -1 there
     too -- read ``ids`` to tell an empty entry, -1 is a legal group id; dists fp32 or None; nonfinite_bits as l2_search).  ``live`` and
-    ``ws`` as in l2_search, the workspace being ``l2_search_grouped_workspace_bytes``; its head holds the fp64 distances."""
-    gallery, queries = _gpu(gallery, torch.float32, "gallery"), _gpu(queries, torch.float32, "queries")
+    ``ws`` as in l2_search, the workspace being ``l2_search_grouped_workspace_bytes``; its head holds the fp64 distances.  A
+    ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``."""
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     groups = _gpu(groups, torch.int32, "groups")
     ng, d = gallery.shape
     nq = queries.shape[0]
@@ -493,10 +509,11 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     out_groups = torch.empty(nq, depth, dtype=torch.int32, device=gallery.device)
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
-    L.check(L.lib().vtc_l2_search_grouped(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None,
-                                          groups.data_ptr(), ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
-                                          dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream()), "vtc_l2_search_grouped")
+    fn, name = ((L.lib().vtc_l2_search_half, "vtc_l2_search_half") if gallery.dtype == torch.float16 else
+                (L.lib().vtc_l2_search_grouped, "vtc_l2_search_grouped"))          # the two take the same arguments
+    L.check(fn(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, groups.data_ptr(), ng, nq, d, depth,
+               int(id_base), ids.data_ptr(), out_groups.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(),
+               ws.data_ptr(), ws.numel(), _stream()), name)
     return ids, out_groups, dists, bits
 
 
@@ -509,7 +526,7 @@ def l2_search_grouped_workspace_bytes(n_gallery: int, n_queries: int, d: int, de
 def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
                            live: Optional[torch.Tensor] = None):
     """One window's share of a grouped search over several: (ids [Q, depth] int64, groups [Q, depth] int32, dists64 [Q, depth] fp64,
-    nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows."""
+    nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows.  fp32 or ``torch.float16`` rows."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device)
