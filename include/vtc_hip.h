@@ -417,6 +417,43 @@ int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_pa
 int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_gallery,
                        int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists,
                        int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* RANGE SEARCH: every row of a stored gallery that lies within a threshold of a query, however many rows that is (near-duplicate
+ * detection before a video is added, "everything that matches this title", counting matches).  vtc_l2_search cannot stand in: its depth
+ * is capped at 64 and a depth guessed too small truncates silently.
+ * D(q, j) is the fp64 squared distance of fp32 query q and gallery row j as vtc_l2_search forms it (the one device function of the
+ * sweeps: the bits that call leaves at the head of its workspace for the pair), for an fp32 gallery and for a half gallery widened
+ * exactly (gallery_is_half != 0: IEEE binary16 bit patterns, as vtc_l2_search_half takes them).  Row j is a HIT of query q iff
+ *   its bit of `live` is set (live == NULL: every row; the mask of vtc_l2_search_masked, only read), and
+ *   D(q, j) is finite, and
+ *   D(q, j) <= radius2[q], compared in fp64 (radius2: double [n_queries], device).
+ * No sum of another order decides membership.  A query that holds a NaN / inf has no hits and sets bit 2 of nonfinite[0] (int32, device,
+ * may be NULL, ORed into as by vtc_l2_search); a live gallery row that holds one is never a hit and sets bit 1; a dead row is not read
+ * and sets nothing.  A radius2 that is NaN or negative gives no hits, +inf gives every live finite row.
+ *
+ * vtc_l2_range_count: ONE pass over the gallery per tile of queries (vtc_l2_search's tiles) and a small prefix launch; nothing is read
+ * back by the host.  Writes lims (int64 [n_queries + 1], device): lims[0] = 0, lims[q + 1] - lims[q] = the hits of query q.  WORKSPACE
+ * HEAD: after the call the first n_queries * ceil(n_gallery / 32) uint32 of the workspace are the HIT WORDS, query-major, in
+ * vtc_row_mask_pack's format: word w of query q is at [q * ceil(n_gallery / 32) + w], its bit b is row 32 w + b, the bits past
+ * n_gallery are 0.  The words of one query are a valid `live` argument of vtc_l2_search_masked / vtc_l2_search_half ("the nearest k
+ * among the rows within the threshold").  Behind them the workspace holds counts the fill pass needs.
+ *
+ * vtc_l2_range_fill: after vtc_l2_range_count, with the same gallery, queries, shape and workspace (untouched in between) and the lims
+ * it wrote.  For every hit, at p = lims[q] + (the rank of the row among q's hits, ASCENDING ROW ORDER) when p < capacity:
+ *   ids[p] (int64) = id_base + row,  dists[p] (fp32, may be NULL) = (float) D,  dists64[p] (double, may be NULL) = D.
+ * Positions at or past `capacity` are not written: a truncated result, never a store out of bounds.  D is formed again by the same
+ * function -- bit-equal to what the count pass compared.  Gallery rows are read only where a hit word is non-zero, in chunks of 512
+ * rows.  One launch; the order of the result does not depend on the grid (no atomic decides a position).
+ *
+ * LIMITS (refused with a status + vtc_last_error, nothing is launched): 1 <= n_queries <= 64, d % 64 == 0 and 64 <= d <= 2048,
+ * n_gallery >= 1, capacity >= 0, id_base >= 0 with id_base + n_gallery an int64, non-null gallery / queries / radius2 / lims / ids / ws,
+ * ws_bytes >= vtc_l2_range_workspace_bytes(...), which is 0 for arguments the calls refuse.
+ * NOT PROVIDED: a grouped (distinct-video) range search, sharding over devices, more than 64 queries per call (slice them). */
+size_t vtc_l2_range_workspace_bytes(int n_gallery, int n_queries, int d);
+int vtc_l2_range_count(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const double *radius2,
+                       int n_gallery, int n_queries, int d, int64_t *lims, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+int vtc_l2_range_fill(const void *gallery, int gallery_is_half, const float *queries, int n_gallery, int n_queries, int d,
+                      const int64_t *lims, int64_t capacity, int64_t id_base, int64_t *ids, float *dists, double *dists64, void *ws,
+                      size_t ws_bytes, void *stream);
 /* hits[j] +=#{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);

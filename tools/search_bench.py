@@ -53,7 +53,23 @@ Per (n_gallery, n_queries, variant) one JSON line:
                            outside the library, dead rows dropped, collapsed to the first row of every video (asserted; outside the timing)
   top_depth_agreement      the share of the ids an fp32 index of the UNROUNDED unit rows returns for the same queries (same mask and
                            groups) that the half index returns too: what rounding the stored rows to 11 bits costs
-profiles/search_half.md holds a run's table."""
+profiles/search_half.md holds a run's table.
+
+With --hits (or --min-score) the tool measures the RANGE search (ops.l2_range_count / vtc_l2_range_fill) against the scan:
+
+    python tools/search_bench.py --hits 100,10000,all [--storage float16] [--queries 1,8,64] ...
+    python tools/search_bench.py --min-score 0.9 ...
+
+Per (n_gallery, n_queries, hits) one JSON line:
+  count_us / scan_us       the count pass (one gallery pass + the prefix launch; lims and the hit words, nothing fetched) and
+                           ops.l2_search at --depth over the same gallery (fp32 or half as --storage says), in alternation as above
+  count_over_scan          ratio of the medians: the count pass streams the scan's bytes and does less per row
+  fill_us, fill_over_count vtc_l2_range_fill into preallocated outputs (ids, fp32 dists), timed in the same alternation
+  hits_per_query           the mean number of hits; --hits N takes, per query, the radius halfway between its N-th and (N + 1)-th
+                           nearest rows by an fp32 matrix product (about N hits; the count is what the device found), `all` is +inf,
+                           --min-score s is radius 2 (1 - s) for every query
+  same_hits_as_host        on the first 10^4 rows: lims and ids equal the fp64 membership formed outside the library (asserted)
+profiles/search_range.md holds a run's table."""
 import argparse
 import json
 import os
@@ -287,6 +303,75 @@ def half_main(args):
     return lines
 
 
+def range_main(args):
+    """--hits / --min-score: the range search's count pass against the scan, and the fill pass relative to the count pass."""
+    lib = L.lib()
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    levels = [("min_score", float(x)) for x in args.min_score.split(",")] if args.min_score else [("hits", x) for x in args.hits.split(",")]
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        gallery = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        if args.storage == "float16":
+            gallery = gallery.to(torch.float16)
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(gallery[pick].float() + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            ws_s = ops.workspace(lib.vtc_l2_search_workspace_bytes(ng, nq, args.d, args.depth), gallery.device)
+            ws_r = ops.workspace(ops.l2_range_workspace_bytes(ng, nq, args.d), gallery.device)
+            approx = None
+            for kind, level in levels:
+                if kind == "min_score":
+                    radius2 = torch.full((nq,), 2.0 * (1.0 - level), dtype=torch.float64, device="cuda")
+                elif level == "all":
+                    radius2 = torch.full((nq,), float("inf"), dtype=torch.float64, device="cuda")
+                else:
+                    if approx is None:
+                        approx = 2.0 - 2.0 * (queries @ gallery.float().t())           # [Q, n] fp32: only places the radius
+                    low = torch.topk(approx, int(level) + 1, dim=1, largest=False)[0]
+                    radius2 = ((low[:, -1].double() + low[:, -2].double()) / 2).contiguous()
+                lims = ops.l2_range_count(gallery, queries, radius2, ws=ws_r)
+                total = int(lims[-1])
+                ids = torch.empty(total, dtype=torch.int64, device="cuda")
+                dists = torch.empty(total, dtype=torch.float32, device="cuda")
+                stream = torch.cuda.current_stream().cuda_stream
+
+                def fill():
+                    L.check(lib.vtc_l2_range_fill(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), ng, nq, args.d,
+                                                  lims.data_ptr(), total, 0, ids.data_ptr(), dists.data_ptr(), None, ws_r.data_ptr(), ws_r.numel(),
+                                                  stream), "vtc_l2_range_fill")
+                scan = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws_s)                                # noqa: E731
+                count = lambda: ops.l2_range_count(gallery, queries, radius2, ws=ws_r)                             # noqa: E731
+                entries = [scan, count, fill]                  # fill follows a count over the same radius in the same workspace
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times = [[] for _ in entries]
+                for _ in range(args.calls):
+                    for t, fn in zip(times, entries):
+                        t.append(timed(fn)[0])
+                n_check = min(ng, 10 ** 4)
+                got = ops.l2_range_search(gallery[:n_check], queries, radius2, max_results=nq * n_check)
+                g64 = gallery[:n_check].double()
+                member = torch.stack([((g64 - queries[i].double()) ** 2).sum(1) <= radius2[i] for i in range(nq)])
+                want_lims = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), member.sum(1).cumsum(0)])
+                same = bool(torch.equal(got[0], want_lims) and torch.equal(got[1], torch.nonzero(member)[:, 1]))
+                sc, c, f = stat(times[0]), stat(times[1]), stat(times[2])
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "storage": args.storage,
+                        kind: level, "hits_per_query": round(total / nq, 1), "count_us": c, "scan_us": sc, "fill_us": f,
+                        "count_over_scan": round(c["median"] / sc["median"], 3), "fill_over_count": round(f["median"] / c["median"], 3),
+                        "passes": passes(nq), "gallery_tb_per_s": round(ng * args.d * gallery.element_size() / (1e6 * c["median"]), 3),
+                        "same_hits_as_host": same}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                assert same, "the range search and the host's fp64 membership differ on the first 10^4 rows"
+                del ids, dists
+            del ws_s, ws_r, approx
+        del gallery
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -303,9 +388,15 @@ def main(argv=None):
     ap.add_argument("--video-layout", type=str, default="contiguous", choices=("contiguous", "scattered"))
     ap.add_argument("--storage", type=str, default="float32", choices=("float32", "float16"),
                     help="float16: measure the scan over a half gallery against the fp32 scan (see above); works with --live / --rows-per-video")
+    ap.add_argument("--hits", type=str, default=None, help="hits per query, e.g. 100,10000,all: measure the range search (see above)")
+    ap.add_argument("--min-score", type=str, default=None, help="score thresholds, e.g. 0.9,0.5: the range search at radius 2 (1 - s)")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.hits or args.min_score:
+        assert not (args.live or args.rows_per_video), "the range mode has no --live / --rows-per-video variants"
+        write_out(args.out, range_main(args))
+        return
     if args.storage == "float16":
         write_out(args.out, half_main(args))
         return

@@ -113,6 +113,10 @@ SIGNATURES = {
     "vtc_l2_search_grouped": (C.c_int, [fp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
     "vtc_l2_search_merge_grouped": (C.c_int, [ip, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp, vp]),
     "vtc_l2_search_half": (C.c_int, [vp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
+    # range search (range.hip): count = one gallery pass -> lims + hit words in the workspace; fill = ids / dists of the hits
+    "vtc_l2_range_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_range_count": (C.c_int, [vp, C.c_int, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),
+    "vtc_l2_range_fill": (C.c_int, [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int64, ip, fp, fp, vp, C.c_size_t, vp]),
     "vtc_recall_hits": (C.c_int, [ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp]),
     "vtc_recall_hits_pair": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp, vp]),
     "vtc_l2_recall_bidir_supported": (C.c_int, [C.c_int, C.c_int]),

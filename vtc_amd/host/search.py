@@ -30,6 +30,13 @@ The rows can be stored as IEEE half, half the memory and half the bytes a one-qu
 A stored row is then the unit row rounded to nearest-even to the 11 significant bits of binary16 per component.  The search stays exact
 over the rows AS STORED: the fp64 distances of the fp32 queries and the widened half rows, bit for bit what an fp32 index holding those
 widened rows returns.
+
+Every search above returns the nearest k, k <= 64.  The other question -- WHICH rows score at least s, however many -- is the range
+search (vtc_l2_range_count / vtc_l2_range_fill: the same fp64 distances, compared with the threshold in fp64):
+
+    lims, ids, scores = index.range_search(queries, min_score=0.9)     # query i's hits: ids[lims[i]:lims[i + 1]], nearest first
+    counts = index.range_count(queries, min_score=0.9)                 # how many, without fetching them: no host sync
+    near = index.range_subset(query, min_score=0.8)                    # the hits of one query as a RowSubset: filters chain
 """
 from __future__ import annotations
 
@@ -430,6 +437,92 @@ class VideoIndex:
         ``*_finaltf`` model that adapts the text branch (branch_to_adapt_val == "text"), ``comments`` [Q, n_comments, ctx] adapts the
         query through the Context Adapter Module as the wrapper's eval forward does."""
         return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset)
+
+    # ---- range search ----------------------------------------------------------------------------
+    def _range_setup(self, queries, min_score, subset, what):
+        """(prepared queries [Q, width], radius2 as Q Python doubles, the packed words of the rows that take part or None)."""
+        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
+            raise ValueError(f"VideoIndex.{what}: the subset belongs to another index (build it with this index's subset())")
+        if self._n == 0:
+            raise ValueError(f"VideoIndex.{what}: the index is empty")
+        q = self._prepared(queries, "queries", check=False)
+        if q.shape[0] == 0:
+            raise ValueError(f"VideoIndex.{what}: no queries")
+        if isinstance(min_score, torch.Tensor):
+            min_score = min_score.detach().cpu().double().reshape(-1).tolist() if min_score.dim() else float(min_score)
+        if isinstance(min_score, (int, float)):
+            scores = [float(min_score)] * q.shape[0]
+        else:
+            scores = [float(s) for s in min_score]
+            if len(scores) != q.shape[0]:
+                raise ValueError(f"VideoIndex.{what}: min_score must be a float or one per query ({q.shape[0]}), got {len(scores)}")
+        radius2 = [2.0 * (1.0 - s) for s in scores]             # score = 1 - D / 2, in Python doubles
+        words = self._live_words() if subset is None else subset.words()
+        return q, radius2, words
+
+    def range_search(self, queries, min_score, subset=None, sort=True, max_results=1 << 22):
+        """EVERY live row that scores at least ``min_score`` against a query, however many: (lims [Q + 1] int64, ids [total] int64,
+        scores [total] fp32) on the device, query i's hits being [lims[i], lims[i + 1]).  ``min_score``: a float, or one per query; a row
+        is a hit iff its fp64 squared distance D <= 2 (1 - min_score) (computed in Python doubles, compared in fp64 on the device), and
+        scores = 1 - D / 2 as ``search`` returns them.  ``sort=True`` orders every query's hits nearest first, by (fp64 distance, row);
+        ``sort=False`` leaves them in ascending row order.  Exact (vtc_l2_range_count / vtc_l2_range_fill): the distances are the bits
+        ``search`` compares, over the stored rows of a half index.  Removed rows and ``subset`` are honoured as in ``search``; any number
+        of queries, 64 per call.  A non-finite query has no hits.
+        One host sync per 64 queries: the number of hits is read back before the result is allocated, and more than ``max_results`` in
+        total raise ValueError before that allocation (``range_count`` tells the size without fetching)."""
+        q, radius2, words = self._range_setup(queries, min_score, subset, "range_search")
+        g, step = self.rows, ops.SEARCH_MAX_QUERIES
+        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], step), self.width))
+        lims, ids, dists, total = [torch.zeros(1, dtype=torch.int64, device=self.device)], [], [], 0
+        for lo in range(0, q.shape[0], step):
+            l, i, d32, d64 = ops.l2_range_search(g, q[lo:lo + step], radius2[lo:lo + step], live=words, max_results=int(max_results) - total,
+                                                 return_dists64=True, ws=ws)
+            if sort and i.numel():
+                n_q = l.shape[0] - 1
+                seg = torch.repeat_interleave(torch.arange(n_q, device=self.device), l[1:] - l[:-1], output_size=i.numel())
+                order = torch.argsort(d64, stable=True)         # rows ascend inside a segment: stable sorts keep (distance, row)
+                order = order[torch.argsort(seg[order], stable=True)]
+                i, d32 = i[order], d32[order]
+            lims.append(l[1:] + total)
+            ids.append(i)
+            dists.append(d32)
+            total += i.numel()
+        return torch.cat(lims), torch.cat(ids), 1.0 - torch.cat(dists) / 2.0
+
+    def range_count(self, queries, min_score, subset=None):
+        """int64 [Q] on the device: how many live rows (of the ``subset``) score at least ``min_score`` against every query -- the sizes
+        of ``range_search``'s segments without fetching them.  Only enqueued: no host sync."""
+        q, radius2, words = self._range_setup(queries, min_score, subset, "range_count")
+        g, step = self.rows, ops.SEARCH_MAX_QUERIES
+        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], step), self.width))
+        out = []
+        for lo in range(0, q.shape[0], step):
+            l = ops.l2_range_count(g, q[lo:lo + step], radius2[lo:lo + step], live=words, ws=ws)
+            out.append(l[1:] - l[:-1])
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+    def range_search_text(self, model, title_tokens, min_score, comments=None, **kw):
+        """``range_search`` of text queries given as token ids, encoded as ``search_text`` encodes them."""
+        return self.range_search(self._text_queries(model, title_tokens, comments, "range_search_text"), min_score, **kw)
+
+    def range_subset(self, query, min_score, subset=None):
+        """The live rows (of ``subset``) that score at least ``min_score`` against ONE query ([dim] or [1, dim]), as a ``RowSubset`` of
+        this index built from the count pass's hit words: ``search(q, k, subset=index.range_subset(q, s))`` is the nearest k among the
+        rows scoring at least s, and subsets chain.  Only enqueued: no host sync."""
+        query = torch.as_tensor(query)
+        if query.dim() == 1:
+            query = query[None]
+        if query.dim() != 2 or query.shape[0] != 1:
+            raise ValueError(f"VideoIndex.range_subset: one query ([{self.dim}] or [1, {self.dim}]), got {tuple(query.shape)}")
+        q, radius2, words = self._range_setup(query, min_score, subset, "range_subset")
+        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, 1, self.width))
+        ops.l2_range_count(self.rows, q, radius2, live=words, ws=ws)
+        hit = ops.range_hit_words(ws, self._n, 1)[0].clone()
+        shifts = torch.arange(32, dtype=torch.int32, device=self.device)
+        flags = ((hit[:, None] >> shifts[None]) & 1).reshape(-1)[:self._n].to(torch.uint8).contiguous()
+        out = RowSubset(self, flags)
+        out._words, out._generation = hit, self._generation     # the hit words ARE the packed flags, dead rows already out
+        return out
 
     def _text_queries(self, model, title_tokens, comments, what):
         if not title_tokens.is_cuda:

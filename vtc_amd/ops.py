@@ -446,6 +446,104 @@ def search_dists64(ws: torch.Tensor, n_queries: int, depth: int) -> torch.Tensor
     return ws[:n_queries * depth * 8].view(torch.float64).view(n_queries, depth)
 
 
+def l2_range_workspace_bytes(n_gallery: int, n_queries: int, d: int) -> int:
+    """0 for a shape vtc_l2_range_count / vtc_l2_range_fill refuse."""
+    return int(L.lib().vtc_l2_range_workspace_bytes(int(n_gallery), int(n_queries), int(d)))
+
+
+def range_hit_words(ws: torch.Tensor, n_gallery: int, n_queries: int) -> torch.Tensor:
+    """The hit words [Q, ceil(n / 32)] int32 of the last l2_range_count that ran in ``ws`` (a view of the workspace's head: the next call
+    overwrites it).  Row q is ``row_mask_pack``'s format: a valid ``live`` of l2_search."""
+    nw = (n_gallery + 31) // 32
+    return ws[:n_queries * nw * 4].view(torch.int32).view(n_queries, nw)
+
+
+def _range_args(gallery, queries, radius2, live, ws, what):
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise ValueError(f"{what}: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if isinstance(radius2, torch.Tensor) and radius2.is_cuda:
+        radius2 = _gpu(radius2, torch.float64, "radius2")
+    elif isinstance(radius2, (int, float)):
+        radius2 = torch.full((nq,), float(radius2), dtype=torch.float64, device=gallery.device)      # a fill launch: no copy, no sync
+    else:
+        # host values: through pinned memory and an asynchronous copy, so that the count pass stays free of host syncs
+        radius2 = torch.as_tensor(radius2, dtype=torch.float64).reshape(-1).pin_memory().to(gallery.device, non_blocking=True)
+    if radius2.device != gallery.device or tuple(radius2.shape) != (nq,):
+        raise ValueError(f"{what}: radius2 must be a float or float64 [{nq}] (one squared radius per query), got {tuple(radius2.shape)}")
+    if live is not None:
+        live = _gpu(live, torch.int32, "live")
+        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
+            raise ValueError(f"{what}: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
+                             f"{tuple(live.shape)} on {live.device}")
+    need = L.lib().vtc_l2_range_workspace_bytes(ng, nq, d)
+    if ws is None:
+        ws = workspace(need, gallery.device)
+    elif need and (ws.numel() < need or ws.device != gallery.device):
+        # never a silent fresh workspace: the hit words stay in the tensor the caller passed
+        raise ValueError(f"{what}: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on {gallery.device}")
+    return gallery, queries, radius2, live, ws
+
+
+def _range_count(gallery, queries, radius2, live, ws):
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    lims = torch.empty(nq + 1, dtype=torch.int64, device=gallery.device)
+    bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
+    L.check(L.lib().vtc_l2_range_count(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                       live.data_ptr() if live is not None else None, radius2.data_ptr(), ng, nq, d, lims.data_ptr(),
+                                       bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_range_count")
+    return lims, bits
+
+
+@on_device
+def l2_range_count(gallery: torch.Tensor, queries: torch.Tensor, radius2, live: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                   return_bits: bool = False):
+    """Range search, the count pass alone (vtc_l2_range_count): ``lims`` int64 [Q + 1] on the device, lims[0] = 0 and lims[q + 1] - lims[q]
+    the number of gallery rows with a finite fp64 squared distance D <= radius2[q] to query q (at most 64 queries).  Only enqueued: no
+    host sync.  ``radius2``: a float, or float64 [Q].  ``live``: packed row mask as ``l2_search`` takes it.  A ``torch.float16`` gallery
+    is searched as stored.  With a caller's ``ws`` (``l2_range_workspace_bytes``) the hit words are ``range_hit_words(ws, n, Q)``.
+    ``return_bits``: also the non-finite word (device int32 [1]: 1 = a live gallery row holds a NaN / inf, 2 = a query does)."""
+    gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, "l2_range_count")
+    lims, bits = _range_count(gallery, queries, radius2, live, ws)
+    return (lims, bits) if return_bits else lims
+
+
+@on_device
+def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live: Optional[torch.Tensor] = None, id_base: int = 0,
+                    max_results: int = 1 << 22, return_dists64: bool = False, return_words: bool = False, ws: Optional[torch.Tensor] = None):
+    """Range search (vtc_l2_range_count + vtc_l2_range_fill): EVERY gallery row with a finite fp64 squared distance D <= radius2[q] to
+    query q, for at most 64 queries.  Returns (lims int64 [Q + 1], ids int64 [total] = id_base + row, dists fp32 [total] = (float) D
+    [, dists64 float64 [total]] [, words int32 [Q, ceil(n / 32)]]), all on the device: query q's hits are [lims[q], lims[q + 1]), in
+    ascending row order.  ``words`` are the hit words, a copy; words[q] is a valid ``live`` of ``l2_search``.
+    ONE host sync: lims[-1] is read back between the two passes, because the size of the output depends on the data.  A total above
+    ``max_results`` raises ValueError BEFORE anything is allocated for it (``l2_range_count`` tells the size without fetching).
+    ``radius2`` / ``live`` / a ``torch.float16`` gallery: as ``l2_range_count``."""
+    gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, "l2_range_search")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    lims, _ = _range_count(gallery, queries, radius2, live, ws)
+    total = int(lims[-1])                                     # the one device-to-host read
+    if total > int(max_results):
+        raise ValueError(f"l2_range_search: {total} rows lie within the radius, max_results={int(max_results)} (raise it, tighten the radius, "
+                         "or count with l2_range_count)")
+    dev = gallery.device
+    ids = torch.empty(total, dtype=torch.int64, device=dev)
+    dists = torch.empty(total, dtype=torch.float32, device=dev)
+    dists64 = torch.empty(total, dtype=torch.float64, device=dev) if return_dists64 else None
+    L.check(L.lib().vtc_l2_range_fill(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), ng, nq, d, lims.data_ptr(),
+                                      total, int(id_base), ids.data_ptr(), dists.data_ptr(), dists64.data_ptr() if return_dists64 else None,
+                                      ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_range_fill")
+    out = (lims, ids, dists)
+    if return_dists64:
+        out += (dists64,)
+    if return_words:
+        out += (range_hit_words(ws, ng, nq).clone(),)
+    return out
+
+
 @on_device
 def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None):
     """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
