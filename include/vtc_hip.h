@@ -417,6 +417,34 @@ int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_pa
 int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_gallery,
                        int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists,
                        int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* SEARCH AFTER A CURSOR: results beyond depth 64, one page at a time.  The search order of a query is the total order of its live rows
+ * with a finite distance by the key (D(q, j), j) -- fp64 distance, then row.  For every query q the call returns the `depth` rows whose
+ * key lies STRICTLY AFTER the cursor key (after_d[q], after_i[q]) (double [n_queries] and int64 [n_queries], device, only read):
+ *   row j is admitted iff D(q, j) > after_d[q], or D(q, j) == after_d[q] and id_base + j > after_i[q], both compared exactly;
+ * everything else -- ids, dists, the tail of -1 / +inf, nonfinite, the fp64 distances at the head of the workspace, `live` (NULL: every
+ * row), id_base -- is vtc_l2_search_masked's (gallery_is_half == 0, fp32 rows) or vtc_l2_search_half's without groups (gallery_is_half
+ * != 0, IEEE binary16 bit patterns).  The call keeps no state.  With (after_d, after_i) = the last fp64 distance and id of the previous
+ * page, the pages concatenated ARE the ranking to any depth, bit for bit what one deeper search would return: the previous page holds
+ * exactly the keys up to its last one, so the next starts at its successor.  That needs after_d[q] to have the bits the scan forms for
+ * the cursor row: take it from the head of the previous call's workspace, or from vtc_l2_pair_dists64 -- not from the fp32 dists.
+ * after_d[q] = -inf admits every row (the call is then the plain search); +inf or a NaN admits none: the row of that query is empty.
+ * after_i[q] is any int64: a cursor row below id_base lies before every row of this window at an equal distance, one at or above
+ * id_base + n_gallery after them, so the windows of one gallery take the SAME cursor and vtc_l2_search_merge merges their lists.  The
+ * cursor row need not be live: a cursor survives the removal of its row.
+ * Two launches on the grid of vtc_l2_search; one gallery pass per tile of queries, whatever the cursor.
+ * LIMITS and refusals: those of vtc_l2_search_masked, and after_d / after_i must be non-null; the workspace is
+ * vtc_l2_search_workspace_bytes(...).  The grouped search has no cursor. */
+int vtc_l2_search_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const double *after_d,
+                        const int64_t *after_i, int n_gallery, int n_queries, int d, int depth, int64_t id_base, int64_t *ids, float *dists,
+                        int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* out[q] (double [n_queries], device) = D(queries[q], gallery row rows[q] - id_base): the fp64 squared distance of ONE pair per query,
+ * formed by the device function of every search -- the bits vtc_l2_search* leaves in its workspace for that pair, so a valid after_d.
+ * rows: int64 [n_queries], device.  rows[q] == -1, or any id outside [id_base, id_base + n_gallery), gives out[q] = +inf and reads no
+ * gallery memory: never a fault.  THE ROW IS READ WHETHER OR NOT IT IS LIVE -- there is no mask; a row removed from an index keeps its
+ * memory.  A query that holds a NaN / inf gives a non-finite out[q].  Any n_queries >= 1; one launch, one wave per query.
+ * Refused: null gallery / queries / rows / out, n_gallery < 1, n_queries < 1, d not a multiple of 64 in [64, 2048], id_base < 0. */
+int vtc_l2_pair_dists64(const void *gallery, int gallery_is_half, const float *queries, const int64_t *rows, int n_gallery, int n_queries,
+                        int d, int64_t id_base, double *out, void *stream);
 /* RANGE SEARCH: every row of a stored gallery that lies within a threshold of a query, however many rows that is (near-duplicate
  * detection before a video is added, "everything that matches this title", counting matches).  vtc_l2_search cannot stand in: its depth
  * is capped at 64 and a depth guessed too small truncates silently.

@@ -69,7 +69,29 @@ Per (n_gallery, n_queries, hits) one JSON line:
                            nearest rows by an fp32 matrix product (about N hits; the count is what the device found), `all` is +inf,
                            --min-score s is radius 2 (1 - s) for every query
   same_hits_as_host        on the first 10^4 rows: lims and ids equal the fp64 membership formed outside the library (asserted)
-profiles/search_range.md holds a run's table."""
+profiles/search_range.md holds a run's table.
+
+With --after-pages P the tool measures the CURSOR scan (ops.l2_search(after=...) = vtc_l2_search_after) against the plain scan:
+
+    python tools/search_bench.py --after-pages 10 [--deep-k 256,1024] [--baseline-lib OTHER/libvtc_hip.so] [--queries 1,8,64] ...
+
+Per (n_gallery, n_queries) one JSON line:
+  plain_us                 ops.l2_search at --depth, no cursor
+  after_first_us           the cursor scan with the cursor (-inf, -1): it admits every row, the result is the plain search's (asserted)
+  after_deep_us            the cursor scan with the cursor on every query's (64 P)-th neighbour (found by chaining P pages of 64, outside
+                           the timing): the rows before the cursor pass the depth-th key's compare for the whole scan and are turned
+                           away by the cursor's
+  baseline_plain_us        with --baseline-lib: the same ops.l2_search bound to ANOTHER build of the library (the commit before a change
+                           to the scan) for the call, so both builds' plain scans run behind the same host code -- all entries in
+                           alternation as above
+  *_over_plain             ratios of the medians (baseline: plain_over_baseline)
+  same_ids_as_host         on the first 10^4 rows: the page after the (64 P)-th neighbour equals that slice of the complete fp64
+                           (distance, row) order formed outside the library (asserted; outside the timing)
+and per (n_gallery, n_queries, k of --deep-k) one more:
+  deep_us / range_us       VideoIndex.search_deep(queries, k) and VideoIndex.range_search at, per query, the score of its k-th neighbour
+                           (about k hits; sorted, its host sync inside the timing), in alternation
+  range_hits_per_query     what the range search returned
+profiles/search_after.md holds a run's table."""
 import argparse
 import json
 import os
@@ -372,6 +394,106 @@ def range_main(args):
     return lines
 
 
+def after_main(args):
+    """--after-pages: the cursor scan against the plain scan (and another build's plain scan); search_deep against range_search."""
+    import ctypes as C
+
+    from vtc_amd.host.search import VideoIndex
+    lib = L.lib()
+    base = None
+    if args.baseline_lib:
+        base = C.CDLL(os.path.abspath(args.baseline_lib))
+        for name, (res, argtypes) in L.SIGNATURES.items():    # the entries the other build has, with this tree's signatures
+            if hasattr(base, name):
+                getattr(base, name).restype, getattr(base, name).argtypes = res, argtypes
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    deep_pages, lines = int(args.after_pages), []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        gallery = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        index = VideoIndex(args.d, normalized=True)
+        index.add(gallery)
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(gallery[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            need = lib.vtc_l2_search_workspace_bytes(ng, nq, args.d, args.depth)
+            ws = [ops.workspace(need, gallery.device) for _ in range(4)]
+
+            def cursor_after(g, pages):                        # the key of every query's (64 pages)-th neighbour in g
+                ws64 = ops.workspace(lib.vtc_l2_search_workspace_bytes(g.shape[0], nq, args.d, 64), g.device)
+                after = None
+                for _ in range(pages):
+                    ids = ops.l2_search(g, queries, 64, ws=ws64, after=after)[0]
+                    after = (ops.search_dists64(ws64, nq, 64)[:, -1].clone(), ids[:, -1].clone())
+                return after
+            first = (torch.full((nq,), float("-inf"), dtype=torch.float64, device="cuda"), torch.full((nq,), -1, dtype=torch.int64, device="cuda"))
+            deep = cursor_after(gallery, deep_pages)
+            plain = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws[0])                                  # noqa: E731
+            after_first = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws[1], after=first)              # noqa: E731
+            after_deep = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws[2], after=deep)                # noqa: E731
+
+            def baseline():                                    # the same ops.l2_search, bound to the other build for the call
+                mine, L._lib = L._lib, base
+                try:
+                    return ops.l2_search(gallery, queries, args.depth, ws=ws[3])
+                finally:
+                    L._lib = mine
+            entries = [plain, after_first, after_deep] + ([baseline] if base else [])
+            for _ in range(args.warmup):
+                for fn in entries:
+                    fn()
+            torch.cuda.synchronize()
+            times, outs = [[] for _ in entries], [None] * len(entries)
+            for _ in range(args.calls):
+                for k, fn in enumerate(entries):
+                    us, outs[k] = timed(fn)
+                    times[k].append(us)
+            same_first = all(bool(torch.equal(outs[0][i], o[i])) for o in outs[1:2] + outs[3:] for i in (0, 1))
+            n_check = min(ng, 10 ** 4)
+            small = gallery[:n_check]
+            got = ops.l2_search(small, queries, args.depth, after=cursor_after(small, deep_pages))[0]
+            g64 = small.double()
+            want = torch.stack([torch.sort(((g64 - queries[i].double()) ** 2).sum(1), stable=True)[1][64 * deep_pages:64 * deep_pages + args.depth]
+                                for i in range(nq)])
+            same_host = bool(torch.equal(got, want))
+            st = [stat(t) for t in times]
+            line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "cursor_at": 64 * deep_pages,
+                    "plain_us": st[0], "after_first_us": st[1], "after_deep_us": st[2],
+                    "after_first_over_plain": round(st[1]["median"] / st[0]["median"], 3),
+                    "after_deep_over_plain": round(st[2]["median"] / st[0]["median"], 3), "passes": passes(nq),
+                    "same_as_plain": same_first, "same_ids_as_host": same_host}
+            if base:
+                line["baseline_plain_us"] = st[3]
+                line["plain_over_baseline"] = round(st[0]["median"] / st[3]["median"], 3)
+                line["after_first_over_baseline"] = round(st[1]["median"] / st[3]["median"], 3)
+                line["after_deep_over_baseline"] = round(st[2]["median"] / st[3]["median"], 3)
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            assert same_first, "the cursor scan at (-inf, -1) (or the baseline build) and the plain scan returned different bits"
+            assert same_host, "the page after the cursor and the host's full fp64 order differ on the first 10^4 rows"
+            del ws
+            for k in [int(x) for x in args.deep_k.split(",") if x]:
+                min_score = index.search_deep(queries, k)[1][:, -1].double().cpu().tolist()
+                entries = [lambda: index.search_deep(queries, k), lambda: index.range_search(queries, min_score, max_results=1 << 26)]
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times, outs = [[], []], [None, None]
+                for _ in range(args.calls):
+                    for j, fn in enumerate(entries):
+                        us, outs[j] = timed(fn)
+                        times[j].append(us)
+                dp, rg = stat(times[0]), stat(times[1])
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "calls": args.calls, "search_deep_k": k, "deep_us": dp, "range_us": rg,
+                        "deep_over_range": round(dp["median"] / rg["median"], 3), "deep_passes": passes(nq) * -(-k // 64),
+                        "range_hits_per_query": round(outs[1][1].numel() / nq, 1)}
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+        del gallery, index
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -390,9 +512,17 @@ def main(argv=None):
                     help="float16: measure the scan over a half gallery against the fp32 scan (see above); works with --live / --rows-per-video")
     ap.add_argument("--hits", type=str, default=None, help="hits per query, e.g. 100,10000,all: measure the range search (see above)")
     ap.add_argument("--min-score", type=str, default=None, help="score thresholds, e.g. 0.9,0.5: the range search at radius 2 (1 - s)")
+    ap.add_argument("--after-pages", type=int, default=None, help="P: measure the cursor scan, the cursor on the (64 P)-th neighbour (see above)")
+    ap.add_argument("--deep-k", type=str, default="256,1024", help="with --after-pages: k of VideoIndex.search_deep against range_search")
+    ap.add_argument("--baseline-lib", type=str, default=None, help="with --after-pages: another build of libvtc_hip.so whose vtc_l2_search is timed too")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.after_pages is not None:
+        assert args.after_pages >= 1 and not (args.live or args.rows_per_video or args.hits or args.min_score or args.storage != "float32"), \
+            "the cursor mode measures the plain fp32 scan's variants only"
+        write_out(args.out, after_main(args))
+        return
     if args.hits or args.min_score:
         assert not (args.live or args.rows_per_video), "the range mode has no --live / --rows-per-video variants"
         write_out(args.out, range_main(args))

@@ -33,6 +33,13 @@
 // fp32 scan reads 16 and widens them exactly, every lane keeps its columns, and the same statements form the same fp64 bits as the
 // fp32 scan over the widened rows.  The workspace, the lists and both merges do not know how the gallery is stored.
 //
+// vtc_l2_search_after: the `depth` nearest rows strictly AFTER a cursor key (D*, row*) of the search order, per query -- the next page of
+// a search, to any depth, by chaining each page's last key.  search_after_scan_kernel / half_after_scan_kernel are scan_body with AFTER:
+// a row that has passed `beats` is offered only if its key lies after the query's cursor (one compare pair, in scalar registers like the
+// depth-th key), so the rejecting path of the steady state is the one compare it was.  The lists and merge_kernel<ScanLists> do not
+// care which rows were admitted.  The cursor's distance has to carry the bits the scan compares: it is the fp64 value of an earlier
+// search's workspace, or vtc_l2_pair_dists64's (pair_dists64_kernel, one wave per query through the same wave_dist64_core).
+//
 // Why merging de-duplicated lists is exact, for the waves' lists in the LDS, the workgroups' lists and the caller's windows alike: a
 // group of the union's first `depth` has its overall nearest row in some part.  In that part fewer than `depth` groups have a smaller
 // local minimum (a local minimum is not below the overall one of its group, and fewer than `depth` groups are nearer overall), so that
@@ -257,10 +264,20 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
 // binary16.  Nothing but the row loader differs (sweep_common.h, row_piece): lane l still keeps the columns 4 l .. 4 l + 3 (+ 256 i),
 // loads 8 bytes a piece where the fp32 scan loads 16, widens them exactly and forms the distance with the same statements in the same
 // order -- the same fp64 bits as the fp32 scan over the widened rows.  The mask, the groups and the queries in the LDS are untouched.
-template <int NQ, int NR, bool MASKED, bool GROUPED, typename G>
+//
+// AFTER: query u of the tile has a cursor (cd[u], cr[u]) -- the fp64 distance after_d[q] and the cursor row after_i[q] as a LOCAL row,
+// clamp(after_i[q] - id_base, -1, ng): a cursor row in an earlier window is before every row of this one at an equal distance (-1), one
+// in a later window after them (ng).  Both are wave-uniform and live in scalar registers as (tau, tau_i) do.  A row is offered to query
+// u only if cv > cd[u] || (cv == cd[u] && row > cr[u]), asked AFTER `beats`: a row that does not beat the depth-th still costs one
+// compare.  A NaN cd[u] admits nothing, -inf everything (the plain search), +inf nothing.  Without AFTER the three arguments are not
+// looked at and not a statement of the cursor is compiled.
+template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, typename G>
 __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
                                           const int *__restrict__ groups, int ng, int nq, int d, int depth, double *__restrict__ part_d,
-                                          int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite) {
+                                          int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite,
+                                          const double *__restrict__ after_d = nullptr, const int64_t *__restrict__ after_i = nullptr,
+                                          int64_t id_base = 0) {
+  static_assert(!(AFTER && GROUPED), "the grouped scan has no cursor");
   extern __shared__ float4 smem4[];
   float *qt = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -293,6 +310,17 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
 #pragma unroll
   for (int u = 0; u < NQ; ++u) wl[u].init(EMPTY_ROW);
   bool gallery_bad = false;
+  [[maybe_unused]] double cd[NQ];                          // the cursors of the tile's queries (AFTER)
+  [[maybe_unused]] int cr[NQ];
+  if constexpr (AFTER) {
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const int q = min(q0 + u, nq - 1);                   // a slot past the last query is dead: its cursor is never asked
+      const long long a = after_i[q];
+      cd[u] = uniform_f64(after_d[q]);
+      cr[u] = uniform_of(a < id_base ? -1 : (int)min(a - id_base, (long long)ng));
+    }
+  }
   const long long n_groups = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
   // The mask word of step s's rows, as loaded: every lane reads the same address with an ordinary (vector) load, which returns in order
   // -- requested a step ahead, before that step's gallery rows, it has arrived by the time they have and is never waited for on its own.
@@ -336,6 +364,9 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
           const double cv = dist[u * NR + r];
           if (!(cv < INFINITY)) gallery_bad = true;
           else if (!((dead >> u) & 1) && wl[u].beats(cv, jj[r])) {
+            if constexpr (AFTER) {
+              if (!(cv > cd[u] || (cv == cd[u] && jj[r] > cr[u]))) continue;      // at or before the cursor (or a NaN cursor)
+            }
             if constexpr (GROUPED) wl[u].insert(cv, jj[r], uniform_of(gv[r]), lane, depth);
             else wl[u].insert(cv, jj[r], lane, depth);
           }
@@ -410,6 +441,45 @@ __global__ __launch_bounds__(256) void half_scan_kernel(const _Float16 *__restri
                                                         const unsigned *__restrict__ live, int ng, int nq, int d, int depth,
                                                         double *__restrict__ part_d, int *__restrict__ part_i, int *__restrict__ nonfinite) {
   scan_body<NQ, NR, MASKED, false>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite);
+}
+// The cursor scans (vtc_l2_search_after): the same body with AFTER, under names of their own, with the cursors and the window's id_base.
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void search_after_scan_kernel(const float *__restrict__ gallery, const float *__restrict__ queries,
+                                                                const unsigned *__restrict__ live, const double *__restrict__ after_d,
+                                                                const int64_t *__restrict__ after_i, int64_t id_base, int ng, int nq, int d,
+                                                                int depth, double *__restrict__ part_d, int *__restrict__ part_i,
+                                                                int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, false, true>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite, after_d, after_i,
+                                         id_base);
+}
+template <int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void half_after_scan_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
+                                                              const unsigned *__restrict__ live, const double *__restrict__ after_d,
+                                                              const int64_t *__restrict__ after_i, int64_t id_base, int ng, int nq, int d,
+                                                              int depth, double *__restrict__ part_d, int *__restrict__ part_i,
+                                                              int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, false, true>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite, after_d, after_i,
+                                         id_base);
+}
+// out[q] = D(queries[q], gallery[rows[q] - id_base]), the fp64 distance with the bits the scans form (the same wave_dist64_core), one
+// wave per query; +inf for a row id outside [id_base, id_base + ng) -- -1 included -- whose memory is not touched.  The row is read
+// WHETHER OR NOT IT IS LIVE: there is no mask here, a removed row keeps its memory (VideoIndex), and a cursor may stand on one.  The
+// query is read as it is: one with a NaN / inf gives a non-finite out[q], which as a cursor admits nothing.
+template <typename G>
+__global__ __launch_bounds__(256) void pair_dists64_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                           const int64_t *__restrict__ rows, int ng, int nq, int d, int64_t id_base,
+                                                           double *__restrict__ out) {
+  const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;                                     // wave-uniform
+  const long long row = uniform_of((long long)rows[q]);
+  double v = INFINITY;
+  if (row >= id_base && row - id_base < ng) {
+    const int jj[1] = {(int)(row - id_base)};
+    double dist[1];
+    wave_dist64_queries<1, 1>(queries + (size_t)q * d, gallery, jj, d, lane, dist);
+    v = dist[0];
+  }
+  if (lane == 0) out[q] = v;
 }
 template <int NQ, int NR, bool MASKED>
 __global__ __launch_bounds__(256) void half_scan_grouped_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
@@ -523,10 +593,15 @@ SearchWs search_ws(void *ws, int ng, int nq, int depth, bool grouped = false) {
 
 // The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
 // most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
-// G = _Float16: the half gallery's kernels, by the same rule among themselves.
-template <int NQ, int NR, bool MASKED, bool GROUPED, typename G>
+// G = _Float16: the half gallery's kernels, by the same rule among themselves.  AFTER: the cursor scan, `after` its three arguments.
+struct AfterArgs {
+  const double *d;
+  const int64_t *i;
+  int64_t id_base;
+};
+template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, typename G>
 int launch_scan(const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
-                const SearchWs &s, int tiles, int *nonfinite, hipStream_t stream) {
+                const SearchWs &s, int tiles, int *nonfinite, hipStream_t stream, const AfterArgs &after = {}) {
   // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
   static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
   int dev = 0;
@@ -546,8 +621,13 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
     // the unmasked one instead of 3.4 - 3.6 %.  It was 2.5 % faster at 10^6 rows and 4 - 12 % on partly live masks there: the trade is
     // written down in profiles/search_masked.md.
     // The grouped scan follows the same rule: the unmasked, ungrouped scan's grid, never more than is resident of its own.
+    // The cursor scan too, masked or not.
     int own = per_cu;
-    if constexpr (GROUPED) {
+    if constexpr (AFTER) {
+      if constexpr (HALF) e = resident_of(own, half_after_scan_kernel<NQ, NR, MASKED>);
+      else e = resident_of(own, search_after_scan_kernel<NQ, NR, MASKED>);
+      if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
+    } else if constexpr (GROUPED) {
       if constexpr (HALF) e = resident_of(own, half_scan_grouped_kernel<NQ, NR, MASKED>);
       else e = resident_of(own, search_grouped_scan_kernel<NQ, NR, MASKED>);
       if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
@@ -560,7 +640,14 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  if constexpr (std::is_same_v<G, _Float16>) {
+  if constexpr (AFTER) {
+    if constexpr (std::is_same_v<G, _Float16>)
+      hipLaunchKernelGGL((half_after_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live,
+                         after.d, after.i, after.id_base, ng, nq, d, depth, s.part_d, s.part_i, nonfinite);
+    else
+      hipLaunchKernelGGL((search_after_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
+                         live, after.d, after.i, after.id_base, ng, nq, d, depth, s.part_d, s.part_i, nonfinite);
+  } else if constexpr (std::is_same_v<G, _Float16>) {
     if constexpr (GROUPED)
       hipLaunchKernelGGL((half_scan_grouped_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
                          live, groups, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
@@ -578,13 +665,16 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
 // the instantiation of the plan's tile shape.  The half scan keeps the fp32 scan's shapes: 8 gallery rows a step for its one- and
 // two-query tiles (a piece of a half row is 8 bytes a lane, so a step has half the bytes in flight) were measured and lost
 // (profiles/search_half.md).
-template <bool MASKED, bool GROUPED = false, typename G>
+template <bool MASKED, bool GROUPED = false, bool AFTER = false, typename G>
 int launch_scan_tile(const SearchPlan &p, const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d,
-                     int depth, const SearchWs &s, int *nonfinite, hipStream_t stream) {
-  if (p.tile_q == 1) return launch_scan<1, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 2) return launch_scan<2, 4, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 4) return launch_scan<4, 2, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
-  return launch_scan<8, 1, MASKED, GROUPED>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream);
+                     int depth, const SearchWs &s, int *nonfinite, hipStream_t stream, const AfterArgs &after = {}) {
+  if (p.tile_q == 1)
+    return launch_scan<1, 4, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+  if (p.tile_q == 2)
+    return launch_scan<2, 4, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+  if (p.tile_q == 4)
+    return launch_scan<4, 2, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+  return launch_scan<8, 1, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
 }
 
 // words[w] bit b = (flags[32 w + b] != 0) & and_mask[w] bit b: a thread per row, a ballot per wave -- 64 rows, two words, written by
@@ -728,5 +818,59 @@ extern "C" int vtc_l2_search_half(const uint16_t *gallery_, const float *queries
     hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth, id_base,
                        ids, dists, s.dists64);
   VTC_LAUNCH_CHECK2("l2_search_half", "merge");
+  return 0;
+}
+
+// The cursor search of either storage: the scan of vtc_l2_search_masked / vtc_l2_search_half with AFTER, then the merge every search runs.
+template <typename G>
+static int search_after(const G *gallery, const float *queries, const uint32_t *live, const AfterArgs &after, int ng, int nq, int d, int depth,
+                        int64_t *ids, float *dists, int *nonfinite, const SearchWs &s, hipStream_t stream) {
+  const SearchPlan p = search_plan(nq);
+  const int blocks = live ? launch_scan_tile<true, false, true>(p, gallery, queries, live, nullptr, ng, nq, d, depth, s, nonfinite, stream, after)
+                          : launch_scan_tile<false, false, true>(p, gallery, queries, nullptr, nullptr, ng, nq, d, depth, s, nonfinite, stream, after);
+  VTC_LAUNCH_CHECK2("l2_search_after", "scan");
+  hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth,
+                     after.id_base, ids, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search_after", "merge");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const double *after_d,
+                                   const int64_t *after_i, int ng, int nq, int d, int depth, int64_t id_base, int64_t *ids, float *dists,
+                                   int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && ids && after_d && after_i, "l2_search_after: null argument");
+  VTC_CHECK(ng >= 1, "l2_search_after: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_after: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search_after: depth=%d must be in [1, min(%d, n_gallery)]", depth,
+            SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search_after: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "l2_search_after: id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search_after: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const AfterArgs after{after_d, after_i, id_base};
+  if (gallery_is_half)
+    return search_after(reinterpret_cast<const _Float16 *>(gallery), queries, live, after, ng, nq, d, depth, ids, dists, nonfinite, s, stream);
+  return search_after(reinterpret_cast<const float *>(gallery), queries, live, after, ng, nq, d, depth, ids, dists, nonfinite, s, stream);
+}
+
+extern "C" int vtc_l2_pair_dists64(const void *gallery, int gallery_is_half, const float *queries, const int64_t *rows, int ng, int nq, int d,
+                                   int64_t id_base, double *out, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && rows && out, "l2_pair_dists64 (the search's cursor distances): null argument");
+  VTC_CHECK(ng >= 1, "l2_pair_dists64 (the search's cursor distances): n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1, "l2_pair_dists64 (the search's cursor distances): n_queries=%d must be at least 1", nq);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_pair_dists64 (the search's cursor distances): d=%d must be a multiple of 64 in [64, %d]",
+            d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng,
+            "l2_pair_dists64 (the search's cursor distances): id_base=%lld must be non-negative (and id_base + n_gallery an int64)", (long long)id_base);
+  if (gallery_is_half)
+    hipLaunchKernelGGL(pair_dists64_kernel<_Float16>, dim3(cdiv(nq, 4)), dim3(256), 0, stream, reinterpret_cast<const _Float16 *>(gallery), queries,
+                       rows, ng, nq, d, id_base, out);
+  else
+    hipLaunchKernelGGL(pair_dists64_kernel<float>, dim3(cdiv(nq, 4)), dim3(256), 0, stream, reinterpret_cast<const float *>(gallery), queries, rows,
+                       ng, nq, d, id_base, out);
+  VTC_LAUNCH_CHECK("l2_pair_dists64");
   return 0;
 }

@@ -469,7 +469,8 @@ def sharded_rank_stats(feats_a_local: torch.Tensor, feats_b_local: torch.Tensor,
     return rank_statistics(rank_a, k_vals), rank_statistics(rank_b, k_vals)
 
 
-def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int, world: int):
+def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int, world: int, after=None,
+                   return_dists64: bool = False):
     """Query-time search over a gallery that is row-sharded across ranks: this rank stores the rows [row_base, row_base + n_local) of the
     index (fp32 or torch.float16 [n_local, d], d % 64 == 0 -- half rows are searched as stored, ops.l2_search; the partial lists are fp64
     either way) and every rank holds the same fp32 queries [Q <= 64, d].  Returns (ids [Q, k] int64 -- global row
@@ -477,13 +478,18 @@ def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch
 
     A local ops.l2_search_part(id_base = row_base), ONE all_gather of the partial lists -- ids and fp64 distances in one int64 buffer
     [2, Q, k] per rank: the fp32 distances alone would break ties that the fp64 values decide --, then ops.l2_search_merge.  A rank with
-    fewer than k rows (none, too) sends a list padded with -1 / +inf; world <= 64 (the merge's limit on parts).  No multi-GPU box has
-    run this: what is tested is the code path at world = 1 and the windowed merge on one card (tests/test_gpu_search.py)."""
+    fewer than k rows (none, too) sends a list padded with -1 / +inf; world <= 64 (the merge's limit on parts).
+    ``after``: the cursor of ops.l2_search, ``(d64 [Q] float64, ids [Q] int64)`` in GLOBAL ids and the same on every rank; every rank
+    passes it to its ops.l2_search_part, and the merged list is the page after that key.  ``return_dists64`` adds the merged list's
+    fp64 distances [Q, k] as a third output -- gathered from the parts' lists, bit for bit -- so ``(d64[:, -1], ids[:, -1])`` is the
+    next cursor without computing anything again.
+    No multi-GPU box has run this: what is tested is the code path at world = 1 and the windowed merge on one card
+    (tests/test_gpu_search.py, tests/test_gpu_search_after.py)."""
     if not 1 <= world <= 64:
         raise ValueError(f"sharded_search: world={world} must be in [1, 64]")
     nq, n_local = queries.shape[0], index_rows_local.shape[0]
     if n_local:
-        ids, d64, _ = ops.l2_search_part(index_rows_local, queries, min(int(k), n_local), id_base=int(row_base))
+        ids, d64, _ = ops.l2_search_part(index_rows_local, queries, min(int(k), n_local), id_base=int(row_base), after=after)
         ids, d64 = ops.pad_search_part(ids, d64, int(k))
     else:
         ids = torch.full((nq, int(k)), -1, dtype=torch.int64, device=queries.device)
@@ -494,7 +500,14 @@ def sharded_search(index_rows_local: torch.Tensor, row_base: int, queries: torch
         dist.all_gather_into_tensor(parts, mine.contiguous())
     else:
         parts = mine[None]
-    return ops.l2_search_merge(parts[:, 0].contiguous(), parts[:, 1].contiguous().view(torch.float64))
+    ids_parts, d64_parts = parts[:, 0].contiguous(), parts[:, 1].contiguous().view(torch.float64)
+    ids, dists = ops.l2_search_merge(ids_parts, d64_parts)
+    if not return_dists64:
+        return ids, dists
+    # the fp64 value of every merged entry: the one part entry with its id (ids are unique across parts; an empty entry finds none)
+    flat_ids, flat_d64 = ids_parts.permute(1, 0, 2).reshape(nq, -1), d64_parts.permute(1, 0, 2).reshape(nq, -1)      # [Q, P * k]
+    where = (flat_ids[:, None, :] == ids[:, :, None]).to(torch.uint8).argmax(dim=2)                                  # [Q, k]
+    return ids, dists, torch.where(ids >= 0, flat_d64.gather(1, where), torch.full_like(dists, float("inf"), dtype=torch.float64))
 
 
 def sharded_search_videos(index_rows_local: torch.Tensor, video_ids_local: torch.Tensor, row_base: int, queries: torch.Tensor, k: int, rank: int,

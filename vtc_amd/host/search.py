@@ -37,6 +37,13 @@ search (vtc_l2_range_count / vtc_l2_range_fill: the same fp64 distances, compare
     lims, ids, scores = index.range_search(queries, min_score=0.9)     # query i's hits: ids[lims[i]:lims[i + 1]], nearest first
     counts = index.range_count(queries, min_score=0.9)                 # how many, without fetching them: no host sync
     near = index.range_subset(query, min_score=0.8)                    # the hits of one query as a RowSubset: filters chain
+
+Between the two lies "the next page", and a ranking deeper than 64 -- a re-ranker, a hard-negative miner, recall at 100 or 1000.  The
+search order is a total order on (fp64 distance, row), so "the k nearest rows after row r" is well defined and needs no state
+(vtc_l2_search_after: a cursor in the scan):
+
+    ids2, scores2 = index.search(queries, 10, after=ids[:, -1])        # the next 10 of every query; chain as long as needed
+    ids, scores = index.search_deep(queries, 500)                      # the exact 500 nearest: pages of 64, concatenated
 """
 from __future__ import annotations
 
@@ -357,7 +364,7 @@ class VideoIndex:
             self._ws = ops.workspace(nbytes, self.device)
         return self._ws
 
-    def search(self, queries, k, subset=None):
+    def search(self, queries, k, subset=None, after=None):
         """(ids [Q, k] int64, scores [Q, k] fp32), both on the device: the k nearest stored rows of every query, nearest first, and
         score = 1 - |q - g|^2 / 2, the cosine for unit rows.  1 <= k <= min(64, len(index)), len being the live rows.
         Fewer than ROUTE_TOPK_MIN_QUERIES queries -- batch 1 is the design point -- are only enqueued: no device-to-host read, no host
@@ -371,10 +378,21 @@ class VideoIndex:
         (vtc_l2_search_half), 64 queries per call, only enqueued, a non-finite query a row of -1 / -inf -- whatever the number of
         queries: vtc_l2_topk reads fp32 rows.  Batches of many queries are therefore slower than on an fp32 index
         (profiles/search.md: 4.5 x at 64 queries).  The scores are 1 - D/2 over the stored rows, each the unit row rounded to
-        binary16's 11 significant bits per component."""
+        binary16's 11 significant bits per component.
+        ``after`` (an int64 [Q] tensor of row ids, typically ``ids[:, -1]`` of the previous page): the k nearest rows that come AFTER
+        that row in the query's search order -- by (fp64 distance, row), the order every search returns -- so the pages chained by their
+        last ids are, concatenated, the exact ranking to any depth, without repeats or gaps.  Stateless: the cursor's distance is formed
+        again from the stored row (vtc_l2_pair_dists64, the bits the scan compares), then the cursor scan runs (vtc_l2_search_after) for
+        any number of queries, 64 per call, by the masked route's rules: only enqueued, no host sync, a non-finite query a row of
+        -1 / -inf.  So an id cannot be validated: -1 (the previous page was not full: there is nothing after it) or an id outside
+        [0, ntotal) gives that query a row of -1 / -inf and leaves the others alone -- chaining past the end returns empty pages, it
+        never starts over.  The cursor row need not be live nor a member of ``subset``: a page token survives a ``remove``.  Each page
+        costs a gallery pass per started tile of 8 queries, however deep the cursor is.  ``after=None`` changes nothing above."""
         k = int(k)
         if not 1 <= k <= min(self.MAX_K, self._n_live):
             raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+        if after is not None:
+            return self._search_masked(queries, k, subset, after)
         if subset is not None or self._live is not None or self.storage != torch.float32:
             return self._search_masked(queries, k, subset)
         scan = 0 < len(queries) < min(self.ROUTE_TOPK_MIN_QUERIES, ops.SEARCH_MAX_QUERIES + 1)
@@ -390,7 +408,7 @@ class VideoIndex:
             ids, dists = ops.l2_topk(g, q, k, precision=L.SWEEP_EXACT, ws=ws)
         return ids, 1.0 - dists / 2.0
 
-    def _search_masked(self, queries, k, subset):
+    def _search_masked(self, queries, k, subset, after=None):
         if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
             raise ValueError("VideoIndex.search: the subset belongs to another index (build it with this index's subset())")
         q = self._prepared(queries, "queries", check=False)
@@ -399,9 +417,48 @@ class VideoIndex:
         words = self._live_words() if subset is None else subset.words()      # None on a half index with every row live: no mask
         g, step = self.rows, ops.SEARCH_MAX_QUERIES
         ws = self._workspace(ops.l2_search_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
-        out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
+        if after is not None:
+            after = torch.as_tensor(after)
+            if after.dtype != torch.int64 or tuple(after.shape) != (q.shape[0],):
+                raise ValueError(f"VideoIndex.search: after must be an int64 [{q.shape[0]}] tensor of row ids, one per query, got "
+                                 f"{after.dtype} {tuple(after.shape)}")
+            after = after.to(self.device).contiguous()
+            out = []
+            for lo in range(0, q.shape[0], step):
+                rows = after[lo:lo + step]
+                cursor = (ops.l2_pair_dists64(g, q[lo:lo + step], rows), rows)      # +inf for an id that is no row: nothing comes after it
+                out.append(ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, after=cursor)[:2])
+        else:
+            out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
         ids, dists = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
         return ids, 1.0 - dists / 2.0
+
+    def search_deep(self, queries, k, subset=None):
+        """``search`` without the limit of 64: (ids [Q, k] int64, scores [Q, k] fp32) for any 1 <= k <= len(index), the exact k nearest
+        live rows (of ``subset``) of every query, nearest first.  Page 1 is ``search(queries, min(k, 64), subset)`` by whatever route
+        that takes, with its rules for non-finite queries and host syncs; every further page of 64 is
+        ``search(..., after=ids[:, -1])`` of the page before, only enqueued, and the pages are concatenated.  Fewer than k members
+        give rows that end in -1 / -inf.
+        THE COST: one gallery pass per 64 results per started tile of 8 queries -- k = 1024 for 8 queries is 16 passes over the
+        gallery, for 64 queries 128.  That is right for a few hundred neighbours of a few queries.  For thousands of results, or
+        whenever a score threshold is known, ``range_search`` is the tool: ONE pass per tile of queries however many rows come back,
+        at the price of one host sync, a sort of the hits and a result whose size the data decides.  Measured
+        (profiles/search_after.md, d = 512, one query over 10^6 rows): k = 256 takes 1.84 ms and k = 1024 7.3 ms, ``range_search`` at
+        the k-th neighbour's score 0.58 and 0.59 ms -- it is the better tool from k = 256 on whenever a threshold is known.
+        From ROUTE_TOPK_MIN_QUERIES queries on, page 1 of an fp32 index with every row live is ``search``'s vtc_l2_topk call, whose
+        routing was measured at depth 11; at k = 64 it takes 29 ms over 10^5 rows and 290 ms over 10^6 (the scan: 2 and 14 ms) and
+        dominates the call.  For deep rankings of many queries pass fewer than that per call."""
+        k = int(k)
+        if not 1 <= k <= self._n_live:
+            raise ValueError(f"VideoIndex.search_deep: k={k} must be in [1, len(index) = {self._n_live}]")
+        pages = [self.search(queries, min(k, self.MAX_K), subset=subset)]
+        got = pages[0][0].shape[1]
+        while got < k:
+            pages.append(self.search(queries, min(k - got, self.MAX_K), subset=subset, after=pages[-1][0][:, -1]))
+            got += pages[-1][0].shape[1]
+        if len(pages) == 1:
+            return pages[0]
+        return torch.cat([p[0] for p in pages], dim=1), torch.cat([p[1] for p in pages], dim=1)
 
     def search_videos(self, queries, k, subset=None):
         """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of every
@@ -432,11 +489,11 @@ class VideoIndex:
         returns them."""
         return self.search_videos(self._text_queries(model, title_tokens, comments, "search_videos_text"), k, subset=subset)
 
-    def search_text(self, model, title_tokens, k, comments=None, subset=None):
+    def search_text(self, model, title_tokens, k, comments=None, subset=None, after=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a
         ``*_finaltf`` model that adapts the text branch (branch_to_adapt_val == "text"), ``comments`` [Q, n_comments, ctx] adapts the
-        query through the Context Adapter Module as the wrapper's eval forward does."""
-        return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset)
+        query through the Context Adapter Module as the wrapper's eval forward does.  ``after``: the cursor of ``search``, the next page."""
+        return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset, after=after)
 
     # ---- range search ----------------------------------------------------------------------------
     def _range_setup(self, queries, min_score, subset, what):

@@ -372,7 +372,7 @@ def _search_gallery(gallery: torch.Tensor) -> torch.Tensor:
 
 @on_device
 def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
-              ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
+              ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, after=None):
     """Query-time search (vtc_l2_search): the exact ``depth`` nearest gallery rows of at most 64 queries, by the fp64 squared distances of
     the fp32 rows, ties to the lower row.  Returns (ids [Q, depth] int64 = id_base + row, -1 where fewer rows have a finite distance;
     dists [Q, depth] fp32 or None; nonfinite_bits, a device int32 [1]: 1 = the gallery holds a NaN / inf, 2 = the queries do).  With a
@@ -382,12 +382,23 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     row is neither read nor counted in nonfinite_bits.  ``depth`` is still bounded by the physical row count.
     A ``torch.float16`` gallery (vtc_l2_search_half) is searched as stored: the distances are the fp64 ones of the fp32 queries and the
     half rows widened to fp32, which is exact -- every output, the fp64 distances in ``ws`` included, has the bits of this call over
-    ``gallery.float()``.  The queries stay fp32; any other gallery dtype raises TypeError."""
+    ``gallery.float()``.  The queries stay fp32; any other gallery dtype raises TypeError.
+    ``after`` (vtc_l2_search_after): a cursor per query, ``(after_d64 [Q] float64, after_ids [Q] int64)`` on the gallery's device; only
+    the rows whose key (fp64 distance, id_base + row) lies strictly after it are returned -- the next page of a search whose previous
+    page ended in that key.  ``after_d64`` must carry the bits the scan forms: ``search_dists64(ws, Q, depth)[:, -1]`` of the previous
+    page (cloned: the next call overwrites it) or ``l2_pair_dists64``; -inf is the plain search, +inf / NaN an empty row.  The cursor
+    row need not be live; with ``id_base`` the ids are global, so every window of a gallery takes the same cursor.  None: the call
+    above, unchanged."""
     gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     ng, d = gallery.shape
     nq = queries.shape[0]
     if queries.shape[1] != d:
         raise ValueError(f"l2_search: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if after is not None:
+        after_d, after_i = _gpu(after[0], torch.float64, "after_d64"), _gpu(after[1], torch.int64, "after_ids")
+        if after_d.device != gallery.device or after_i.device != gallery.device or tuple(after_d.shape) != (nq,) or tuple(after_i.shape) != (nq,):
+            raise ValueError(f"l2_search: after must be (float64 [{nq}], int64 [{nq}]) on {gallery.device}, got {tuple(after_d.shape)} on "
+                             f"{after_d.device} and {tuple(after_i.shape)} on {after_i.device}")
     if live is not None:
         live = _gpu(live, torch.int32, "live")
         if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
@@ -403,7 +414,11 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
     tail = (int(id_base), ids.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    if gallery.dtype == torch.float16:
+    if after is not None:
+        L.check(L.lib().vtc_l2_search_after(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                            live.data_ptr() if live is not None else None, after_d.data_ptr(), after_i.data_ptr(), ng, nq, d,
+                                            depth, *tail), "vtc_l2_search_after")
+    elif gallery.dtype == torch.float16:
         L.check(L.lib().vtc_l2_search_half(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, None, ng, nq,
                                            d, depth, tail[0], tail[1], None, *tail[2:]), "vtc_l2_search_half")
     elif live is None:
@@ -434,6 +449,27 @@ def row_mask_pack(flags: torch.Tensor, and_mask: Optional[torch.Tensor] = None) 
     L.check(L.lib().vtc_row_mask_pack(flags.data_ptr(), n, and_mask.data_ptr() if and_mask is not None else None, words.data_ptr(), _stream()),
             "vtc_row_mask_pack")
     return words
+
+
+@on_device
+def l2_pair_dists64(gallery: torch.Tensor, queries: torch.Tensor, rows: torch.Tensor, id_base: int = 0) -> torch.Tensor:
+    """float64 [Q] on the device (vtc_l2_pair_dists64): the fp64 squared distance of query q and the gallery row ``rows[q] - id_base``,
+    one pair per query, with the bits ``l2_search`` leaves in its workspace for that pair -- what ``l2_search(after=...)`` takes as the
+    cursor's distance when only the cursor's id is at hand.  ``rows``: int64 [Q]; -1, or any id outside [id_base, id_base + n), gives
+    +inf and reads nothing.  The row is read whether or not any mask calls it live.  fp32 or ``torch.float16`` gallery; any Q >= 1."""
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
+    rows = _gpu(rows, torch.int64, "rows")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise ValueError(f"l2_pair_dists64: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if rows.device != gallery.device or tuple(rows.shape) != (nq,):
+        raise ValueError(f"l2_pair_dists64: rows must be int64 [{nq}] on {gallery.device} (one per query), got {tuple(rows.shape)} on "
+                         f"{rows.device}")
+    out = torch.empty(nq, dtype=torch.float64, device=gallery.device)
+    L.check(L.lib().vtc_l2_pair_dists64(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), rows.data_ptr(), ng, nq, d,
+                                        int(id_base), out.data_ptr(), _stream()), "vtc_l2_pair_dists64")
+    return out
 
 
 def l2_search_workspace_bytes(n_gallery: int, n_queries: int, d: int, depth: int) -> int:
@@ -545,15 +581,17 @@ def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live:
 
 
 @on_device
-def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None):
+def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None,
+                   after=None):
     """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
     l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list).
     ``live``: the window's own packed row mask (bit 0 of word 0 is the window's first row), as l2_search takes it.  The window may be
-    fp32 or ``torch.float16``; the fp64 lists do not depend on how the rows are stored, so l2_search_merge takes both."""
+    fp32 or ``torch.float16``; the fp64 lists do not depend on how the rows are stored, so l2_search_merge takes both.
+    ``after``: the cursor of l2_search in GLOBAL ids, the same pair for every window -- the merged lists are then the page after it."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
-    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live)
+    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live, after=after)
     return ids, search_dists64(ws, nq, depth), bits
 
 
