@@ -437,6 +437,28 @@ int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint
 int vtc_l2_search_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const double *after_d,
                         const int64_t *after_i, int n_gallery, int n_queries, int d, int depth, int64_t id_base, int64_t *ids, float *dists,
                         int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* SEARCH EXCLUDING ONE ROW OR ONE GROUP PER QUERY: "more like this" (the nearest rows of a stored row, that row left out) and hard
+ * negatives (the nearest videos of text q other than its own video), for a whole batch in one call.  exclude: int64 [n_queries], device,
+ * only read.  DEFINITION: take the search order of query q -- its live rows with a finite distance by (D(q, j), j) -- or, with groups, the
+ * grouped order of vtc_l2_search_grouped (that order with every row deleted that is not the first of its group); DELETE the excluded
+ * rows; THEN cut to `depth` (after the cursor, where one is given):
+ *   groups == NULL: query q never gets the one row with id_base + j == exclude[q];
+ *   groups != NULL: query q never gets a row with (int64) groups[j] == exclude[q] -- the whole group is deleted BEFORE the groups are
+ *                   de-duplicated, so the result is the grouped search of the gallery without that group's rows.
+ * A value that no row / no group has excludes nothing: -1 or any id outside [id_base, id_base + n_gallery) for rows, any value outside
+ * int32 for groups (every int32, -1 included, is a legal group, which is why the key is an int64).  The windows of one gallery take the
+ * SAME exclude (global ids / groups) and vtc_l2_search_merge / vtc_l2_search_merge_grouped merge their lists unchanged.
+ * after_d / after_i: NULL together (no cursor), or the cursor of vtc_l2_search_after, ungrouped only; the cursor may stand on the excluded
+ * row itself (its key is a key like any other), the page then starts right after it.  gallery_is_half / live (NULL: every row) / ids /
+ * dists / nonfinite / the fp64 distances at the head of the workspace: as vtc_l2_search_after, and out_groups as vtc_l2_search_grouped.
+ * The excluded key is one more compare per query on a row that has already beaten the depth-th entry: the gallery is read once.
+ * LIMITS and refusals: those of vtc_l2_search_after (groups == NULL; workspace vtc_l2_search_workspace_bytes) or vtc_l2_search_grouped
+ * (workspace vtc_l2_search_grouped_workspace_bytes, out_groups required); exclude must be non-null; after_d without after_i or the
+ * reverse, and a cursor together with groups, are refused.  A refused call launches nothing. */
+int vtc_l2_search_excluding(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                            const int64_t *exclude, const double *after_d, const int64_t *after_i, int n_gallery, int n_queries, int d,
+                            int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
+                            size_t ws_bytes, void *stream);
 /* out[q] (double [n_queries], device) = D(queries[q], gallery row rows[q] - id_base): the fp64 squared distance of ONE pair per query,
  * formed by the device function of every search -- the bits vtc_l2_search* leaves in its workspace for that pair, so a valid after_d.
  * rows: int64 [n_queries], device.  rows[q] == -1, or any id outside [id_base, id_base + n_gallery), gives out[q] = +inf and reads no

@@ -91,7 +91,25 @@ and per (n_gallery, n_queries, k of --deep-k) one more:
   deep_us / range_us       VideoIndex.search_deep(queries, k) and VideoIndex.range_search at, per query, the score of its k-th neighbour
                            (about k hits; sorted, its host sync inside the timing), in alternation
   range_hits_per_query     what the range search returned
-profiles/search_after.md holds a run's table."""
+profiles/search_after.md holds a run's table.
+
+With --exclude the tool measures the EXCLUDING scan (ops.l2_search(exclude=...) / ops.l2_search_grouped(exclude=...) =
+vtc_l2_search_excluding) against the same call without ``exclude`` -- the scans that were there before it:
+
+    python tools/search_bench.py --exclude [--queries 1,8,64] [--rows-per-video 5] ...
+
+Per (n_gallery, n_queries, storage float32 / float16, ungrouped / grouped at --rows-per-video rows per video) one JSON line:
+  excluding_us / plain_us   the excluding scan and the same search without ``exclude``, in alternation as above.  Every query excludes
+                            its own NEAREST row (ungrouped) or the video of that row (grouped): the key every wave meets and has to
+                            turn away while its lists fill, the case "more like this" and a hard-negative miner produce
+  excluding_over_plain      ratio of the medians
+  cursor_us                 ungrouped only: the cursor scan with the cursor (-inf, -1) and no ``exclude`` (vtc_l2_search_after), in the
+                            same alternation -- the ungrouped excluding scan IS that scan plus the excluded row, so this splits its
+                            distance from the plain scan into the cursor's share and the excluded key's (excluding_over_cursor)
+  slower_than_spread        the excluding median exceeds the plain median by more than the plain scan's own max - min
+  same_as_masked            the excluding result equals, bit for bit, the masked search with the excluded rows' bits cleared, query by
+                            query (asserted; outside the timing)
+profiles/search_exclude.md holds a run's table."""
 import argparse
 import json
 import os
@@ -494,6 +512,74 @@ def after_main(args):
     return lines
 
 
+def exclude_main(args):
+    """--exclude: the excluding scan against the same search without an excluded key, fp32 and half, ungrouped and grouped."""
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    rpv = int((args.rows_per_video or "5").split(",")[0])
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        rows32 = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        storages = {"float32": rows32, "float16": rows32.to(torch.float16)}
+        groups = (torch.arange(ng, device="cuda") // rpv).to(torch.int32)
+        assert ng // rpv > args.depth, "fewer videos than the depth: nothing to compare"
+        flags = torch.ones(ng, dtype=torch.uint8, device="cuda")
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(rows32[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            for storage, gallery in storages.items():
+                for grouped in (False, True):
+                    need = (ops.l2_search_grouped_workspace_bytes if grouped else ops.l2_search_workspace_bytes)(ng, nq, args.d, args.depth)
+                    ws_x, ws_p = ops.workspace(need, gallery.device), ops.workspace(need, gallery.device)
+
+                    def search(ws, exclude=None, q=queries, live=None, after=None):      # (ids, dists)
+                        if grouped:
+                            out = ops.l2_search_grouped(gallery, q, groups, args.depth, ws=ws, live=live, exclude=exclude)
+                            return out[0], out[2]
+                        return ops.l2_search(gallery, q, args.depth, ws=ws, live=live, exclude=exclude, after=after)[:2]
+                    nearest = search(None)[0][:, 0].clone()        # every query's nearest row: the key it excludes
+                    exclude = groups[nearest].to(torch.int64) if grouped else nearest
+                    entries = [lambda: search(ws_x, exclude), lambda: search(ws_p)]
+                    if not grouped:
+                        ws_c = ops.workspace(need, gallery.device)
+                        first = (torch.full((nq,), float("-inf"), dtype=torch.float64, device="cuda"),
+                                 torch.full((nq,), -1, dtype=torch.int64, device="cuda"))
+                        entries.append(lambda: search(ws_c, after=first))
+                    for _ in range(args.warmup):
+                        for fn in entries:
+                            fn()
+                    torch.cuda.synchronize()
+                    times, outs = [[] for _ in entries], [None] * len(entries)
+                    for _ in range(args.calls):
+                        for k, fn in enumerate(entries):
+                            us, outs[k] = timed(fn)
+                            times[k].append(us)
+                    same = True
+                    for u in range(nq):
+                        f = flags.clone()
+                        f[(groups == exclude[u]) if grouped else exclude[u]] = 0
+                        want = search(None, q=queries[u:u + 1], live=ops.row_mask_pack(f))
+                        same = same and bool(torch.equal(outs[0][0][u], want[0][0]) and torch.equal(outs[0][1][u], want[1][0]))
+                    changed = not bool((outs[0][0][:, 0] == outs[1][0][:, 0]).any())
+                    x, pl = stat(times[0]), stat(times[1])
+                    line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "storage": storage,
+                            "variant": f"grouped, {rpv} rows per video" if grouped else "ungrouped", "excluding_us": x, "plain_us": pl,
+                            "excluding_over_plain": round(x["median"] / pl["median"], 3),
+                            "slower_than_spread": bool(x["median"] - pl["median"] > pl["max"] - pl["min"]), "passes": passes(nq),
+                            "gallery_tb_per_s": round(ng * args.d * gallery.element_size() / (1e6 * x["median"]), 3),
+                            "same_as_masked": same, "nearest_left_out": changed}
+                    if not grouped:
+                        line["cursor_us"] = stat(times[2])
+                        line["excluding_over_cursor"] = round(x["median"] / line["cursor_us"]["median"], 3)
+                        del ws_c
+                    print(json.dumps(line), flush=True)
+                    lines.append(line)
+                    assert same and changed, "the excluding scan and the masked search without the excluded rows returned different bits"
+                    del ws_x, ws_p
+        del rows32, storages
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -514,10 +600,16 @@ def main(argv=None):
     ap.add_argument("--min-score", type=str, default=None, help="score thresholds, e.g. 0.9,0.5: the range search at radius 2 (1 - s)")
     ap.add_argument("--after-pages", type=int, default=None, help="P: measure the cursor scan, the cursor on the (64 P)-th neighbour (see above)")
     ap.add_argument("--deep-k", type=str, default="256,1024", help="with --after-pages: k of VideoIndex.search_deep against range_search")
+    ap.add_argument("--exclude", action="store_true",
+                    help="measure the excluding scan against the same search without an excluded key, fp32 and half, ungrouped and grouped (see above)")
     ap.add_argument("--baseline-lib", type=str, default=None, help="with --after-pages: another build of libvtc_hip.so whose vtc_l2_search is timed too")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.exclude:
+        assert not (args.live or args.hits or args.min_score or args.after_pages is not None), "the excluding mode takes --rows-per-video only"
+        write_out(args.out, exclude_main(args))
+        return
     if args.after_pages is not None:
         assert args.after_pages >= 1 and not (args.live or args.rows_per_video or args.hits or args.min_score or args.storage != "float32"), \
             "the cursor mode measures the plain fp32 scan's variants only"

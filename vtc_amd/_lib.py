@@ -117,6 +117,9 @@ SIGNATURES = {
     "vtc_l2_search_after": (C.c_int, [vp, C.c_int, fp, ip, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, fp, ip, vp, C.c_size_t,
                                       vp]),
     "vtc_l2_pair_dists64": (C.c_int, [vp, C.c_int, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int64, fp, vp]),
+    # the excluding search: one row (ungrouped, with or without a cursor) or one group (grouped) per query that it is never offered
+    "vtc_l2_search_excluding": (C.c_int, [vp, C.c_int, fp, ip, ip, ip, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp,
+                                          C.c_size_t, vp]),
     # range search (range.hip): count = one gallery pass -> lims + hit words in the workspace; fill = ids / dists of the hits
     "vtc_l2_range_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vtc_l2_range_count": (C.c_int, [vp, C.c_int, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),

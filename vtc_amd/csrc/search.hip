@@ -40,6 +40,14 @@
 // care which rows were admitted.  The cursor's distance has to carry the bits the scan compares: it is the fp64 value of an earlier
 // search's workspace, or vtc_l2_pair_dists64's (pair_dists64_kernel, one wave per query through the same wave_dist64_core).
 //
+// vtc_l2_search_excluding: every query names ONE row (ungrouped) or one group (grouped) that it is never offered -- "more like this"
+// without the row itself, hard negatives without the text's own video, for a whole tile of queries in the one gallery pass.
+// excluding_scan_kernel / excluding_grouped_scan_kernel are scan_body with EXCL: the query's excluded key in scalar registers, compared
+// after `beats` (and after the cursor) with the row or with the row's group, so the rejecting path stays the one compare.  Deleting a
+// row -- or every row of a group, BEFORE the lists de-duplicate -- from the candidates is deleting it from the order: the lists, both
+// merges and the window merges stay what they are.  The ungrouped kernel is the cursor scan with EXCL (a null cursor is -inf, the plain
+// search), so an exclusion pages like any search.
+//
 // Why merging de-duplicated lists is exact, for the waves' lists in the LDS, the workgroups' lists and the caller's windows alike: a
 // group of the union's first `depth` has its overall nearest row in some part.  In that part fewer than `depth` groups have a smaller
 // local minimum (a local minimum is not below the overall one of its group, and fewer than `depth` groups are nearer overall), so that
@@ -271,13 +279,21 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
 // u only if cv > cd[u] || (cv == cd[u] && row > cr[u]), asked AFTER `beats`: a row that does not beat the depth-th still costs one
 // compare.  A NaN cd[u] admits nothing, -inf everything (the plain search), +inf nothing.  Without AFTER the three arguments are not
 // looked at and not a statement of the cursor is compiled.
-template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, typename G>
+//
+// EXCL: query u of the tile has one key it is never offered (vtc_l2_search_excluding) -- ungrouped the LOCAL row ex[u] (exclude[q] -
+// id_base inside the window, else -1, which no row is), grouped the group ex[u] as an int64 (a value outside int32 is no group: every
+// int32, -1 included, is a legal one).  Wave-uniform, in scalar registers like the cursor, and asked after `beats` and after the cursor:
+// the rejecting path of the steady state stays the one compare.  The ungrouped excluding scan is always a cursor scan (AFTER): a null
+// after_d is the cursor -inf, the plain search, so there is one excluding kernel where the plain and the cursor scan are two.  Without
+// EXCL `exclude` is not looked at and not a statement of it is compiled.
+template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, bool EXCL = false, typename G>
 __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
                                           const int *__restrict__ groups, int ng, int nq, int d, int depth, double *__restrict__ part_d,
                                           int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite,
                                           const double *__restrict__ after_d = nullptr, const int64_t *__restrict__ after_i = nullptr,
-                                          int64_t id_base = 0) {
+                                          int64_t id_base = 0, const int64_t *__restrict__ exclude = nullptr) {
   static_assert(!(AFTER && GROUPED), "the grouped scan has no cursor");
+  static_assert(!EXCL || AFTER != GROUPED, "the excluding scans: the cursor scan, or the grouped scan");
   extern __shared__ float4 smem4[];
   float *qt = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -316,9 +332,25 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
       const int q = min(q0 + u, nq - 1);                   // a slot past the last query is dead: its cursor is never asked
+      if constexpr (EXCL) {
+        if (!after_d) {                                    // no cursor (uniform for the grid): -inf, the plain search
+          cd[u] = -INFINITY;
+          cr[u] = -1;
+          continue;
+        }
+      }
       const long long a = after_i[q];
       cd[u] = uniform_f64(after_d[q]);
       cr[u] = uniform_of(a < id_base ? -1 : (int)min(a - id_base, (long long)ng));
+    }
+  }
+  [[maybe_unused]] std::conditional_t<GROUPED, long long, int> ex[NQ];      // the excluded group / local row of the tile's queries (EXCL)
+  if constexpr (EXCL) {
+#pragma unroll
+    for (int u = 0; u < NQ; ++u) {
+      const long long e = uniform_of((long long)exclude[min(q0 + u, nq - 1)]);
+      if constexpr (GROUPED) ex[u] = e;
+      else ex[u] = e >= id_base && e - id_base < ng ? (int)(e - id_base) : -1;      // jj[r] is a row of the window: never -1
     }
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
@@ -367,7 +399,14 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
             if constexpr (AFTER) {
               if (!(cv > cd[u] || (cv == cd[u] && jj[r] > cr[u]))) continue;      // at or before the cursor (or a NaN cursor)
             }
-            if constexpr (GROUPED) wl[u].insert(cv, jj[r], uniform_of(gv[r]), lane, depth);
+            if constexpr (EXCL && GROUPED) {
+              const int cg = uniform_of(gv[r]);
+              if ((long long)cg == ex[u]) continue;        // a row of the query's excluded group
+              wl[u].insert(cv, jj[r], cg, lane, depth);
+            } else if constexpr (EXCL) {
+              if (jj[r] == ex[u]) continue;                // the query's excluded row
+              wl[u].insert(cv, jj[r], lane, depth);
+            } else if constexpr (GROUPED) wl[u].insert(cv, jj[r], uniform_of(gv[r]), lane, depth);
             else wl[u].insert(cv, jj[r], lane, depth);
           }
         }
@@ -460,6 +499,27 @@ __global__ __launch_bounds__(256) void half_after_scan_kernel(const _Float16 *__
                                                               int *__restrict__ nonfinite) {
   scan_body<NQ, NR, MASKED, false, true>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite, after_d, after_i,
                                          id_base);
+}
+// The excluding scans (vtc_l2_search_excluding): the same body with EXCL, under names of their own, the gallery's element type a
+// template argument.  excluding_scan_kernel is the cursor scan plus the excluded row (a null after_d: no cursor);
+// excluding_grouped_scan_kernel the grouped scan plus the excluded group.
+template <typename G, int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void excluding_scan_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                             const unsigned *__restrict__ live, const double *__restrict__ after_d,
+                                                             const int64_t *__restrict__ after_i, const int64_t *__restrict__ exclude,
+                                                             int64_t id_base, int ng, int nq, int d, int depth, double *__restrict__ part_d,
+                                                             int *__restrict__ part_i, int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, false, true, true>(gallery, queries, live, nullptr, ng, nq, d, depth, part_d, part_i, nullptr, nonfinite, after_d,
+                                               after_i, id_base, exclude);
+}
+template <typename G, int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void excluding_grouped_scan_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                                     const unsigned *__restrict__ live, const int *__restrict__ groups,
+                                                                     const int64_t *__restrict__ exclude, int ng, int nq, int d, int depth,
+                                                                     double *__restrict__ part_d, int *__restrict__ part_i,
+                                                                     int *__restrict__ part_g, int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, true, false, true>(gallery, queries, live, groups, ng, nq, d, depth, part_d, part_i, part_g, nonfinite, nullptr, nullptr,
+                                               0, exclude);
 }
 // out[q] = D(queries[q], gallery[rows[q] - id_base]), the fp64 distance with the bits the scans form (the same wave_dist64_core), one
 // wave per query; +inf for a row id outside [id_base, id_base + ng) -- -1 included -- whose memory is not touched.  The row is read
@@ -594,12 +654,14 @@ SearchWs search_ws(void *ws, int ng, int nq, int depth, bool grouped = false) {
 // The scan's grid is persistent: as many workgroups as are resident at once (what the registers and the LDS of this tile shape allow, at
 // most four per CU), never more than the workspace has lists for or the gallery has groups of four row steps.  Returns the grid's x.
 // G = _Float16: the half gallery's kernels, by the same rule among themselves.  AFTER: the cursor scan, `after` its three arguments.
+// EXCL: the excluding scans, `after.exclude` the excluded keys (and after.d / after.i null where there is no cursor).
 struct AfterArgs {
   const double *d;
   const int64_t *i;
   int64_t id_base;
+  const int64_t *exclude = nullptr;
 };
-template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, typename G>
+template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, bool EXCL = false, typename G>
 int launch_scan(const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
                 const SearchWs &s, int tiles, int *nonfinite, hipStream_t stream, const AfterArgs &after = {}) {
   // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
@@ -621,9 +683,13 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
     // the unmasked one instead of 3.4 - 3.6 %.  It was 2.5 % faster at 10^6 rows and 4 - 12 % on partly live masks there: the trade is
     // written down in profiles/search_masked.md.
     // The grouped scan follows the same rule: the unmasked, ungrouped scan's grid, never more than is resident of its own.
-    // The cursor scan too, masked or not.
+    // The cursor scan too, masked or not, and the excluding scans.
     int own = per_cu;
-    if constexpr (AFTER) {
+    if constexpr (EXCL) {
+      if constexpr (GROUPED) e = resident_of(own, excluding_grouped_scan_kernel<G, NQ, NR, MASKED>);
+      else e = resident_of(own, excluding_scan_kernel<G, NQ, NR, MASKED>);
+      if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
+    } else if constexpr (AFTER) {
       if constexpr (HALF) e = resident_of(own, half_after_scan_kernel<NQ, NR, MASKED>);
       else e = resident_of(own, search_after_scan_kernel<NQ, NR, MASKED>);
       if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
@@ -640,7 +706,14 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  if constexpr (AFTER) {
+  if constexpr (EXCL) {
+    if constexpr (GROUPED)
+      hipLaunchKernelGGL((excluding_grouped_scan_kernel<G, NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery,
+                         queries, live, groups, after.exclude, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
+    else
+      hipLaunchKernelGGL((excluding_scan_kernel<G, NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries,
+                         live, after.d, after.i, after.exclude, after.id_base, ng, nq, d, depth, s.part_d, s.part_i, nonfinite);
+  } else if constexpr (AFTER) {
     if constexpr (std::is_same_v<G, _Float16>)
       hipLaunchKernelGGL((half_after_scan_kernel<NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live,
                          after.d, after.i, after.id_base, ng, nq, d, depth, s.part_d, s.part_i, nonfinite);
@@ -665,16 +738,16 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
 // the instantiation of the plan's tile shape.  The half scan keeps the fp32 scan's shapes: 8 gallery rows a step for its one- and
 // two-query tiles (a piece of a half row is 8 bytes a lane, so a step has half the bytes in flight) were measured and lost
 // (profiles/search_half.md).
-template <bool MASKED, bool GROUPED = false, bool AFTER = false, typename G>
+template <bool MASKED, bool GROUPED = false, bool AFTER = false, bool EXCL = false, typename G>
 int launch_scan_tile(const SearchPlan &p, const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d,
                      int depth, const SearchWs &s, int *nonfinite, hipStream_t stream, const AfterArgs &after = {}) {
   if (p.tile_q == 1)
-    return launch_scan<1, 4, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+    return launch_scan<1, 4, MASKED, GROUPED, AFTER, EXCL>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
   if (p.tile_q == 2)
-    return launch_scan<2, 4, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+    return launch_scan<2, 4, MASKED, GROUPED, AFTER, EXCL>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
   if (p.tile_q == 4)
-    return launch_scan<4, 2, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
-  return launch_scan<8, 1, MASKED, GROUPED, AFTER>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+    return launch_scan<4, 2, MASKED, GROUPED, AFTER, EXCL>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
+  return launch_scan<8, 1, MASKED, GROUPED, AFTER, EXCL>(gallery, queries, live, groups, ng, nq, d, depth, s, p.tiles, nonfinite, stream, after);
 }
 
 // words[w] bit b = (flags[32 w + b] != 0) & and_mask[w] bit b: a thread per row, a ballot per wave -- 64 rows, two words, written by
@@ -873,4 +946,54 @@ extern "C" int vtc_l2_pair_dists64(const void *gallery, int gallery_is_half, con
                        ng, nq, d, id_base, out);
   VTC_LAUNCH_CHECK("l2_pair_dists64");
   return 0;
+}
+
+// The excluding search of either storage: the cursor scan (ungrouped; no cursor is the cursor -inf) or the grouped scan with EXCL, then
+// the merge every search runs -- the lists do not know which rows were admitted.
+template <typename G>
+static int search_excluding(const G *gallery, const float *queries, const uint32_t *live, const int32_t *groups, const AfterArgs &args, int ng,
+                            int nq, int d, int depth, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, const SearchWs &s,
+                            hipStream_t stream) {
+  const SearchPlan p = search_plan(nq);
+  int blocks;
+  if (groups)
+    blocks = live ? launch_scan_tile<true, true, false, true>(p, gallery, queries, live, groups, ng, nq, d, depth, s, nonfinite, stream, args)
+                  : launch_scan_tile<false, true, false, true>(p, gallery, queries, nullptr, groups, ng, nq, d, depth, s, nonfinite, stream, args);
+  else
+    blocks = live ? launch_scan_tile<true, false, true, true>(p, gallery, queries, live, nullptr, ng, nq, d, depth, s, nonfinite, stream, args)
+                  : launch_scan_tile<false, false, true, true>(p, gallery, queries, nullptr, nullptr, ng, nq, d, depth, s, nonfinite, stream, args);
+  VTC_LAUNCH_CHECK2("l2_search_excluding", "scan");
+  if (groups)
+    hipLaunchKernelGGL(merge_grouped_kernel<ScanGroupLists>, dim3(nq), dim3(256), 0, stream, ScanGroupLists{s.part_d, s.part_i, s.part_g, blocks, depth, 0},
+                       blocks, depth, args.id_base, ids, out_groups, dists, s.dists64);
+  else
+    hipLaunchKernelGGL(merge_kernel<ScanLists>, dim3(nq), dim3(256), 0, stream, ScanLists{s.part_d, s.part_i, blocks, depth, 0}, blocks, depth,
+                       args.id_base, ids, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search_excluding", "merge");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_excluding(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                                       const int64_t *exclude, const double *after_d, const int64_t *after_i, int ng, int nq, int d, int depth,
+                                       int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
+                                       size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && ids && exclude && (!groups || out_groups), "l2_search_excluding: null argument");
+  VTC_CHECK(!after_d == !after_i, "l2_search_excluding: after_d and after_i are given together or not at all");
+  VTC_CHECK(!(groups && after_d), "l2_search_excluding: the grouped search has no cursor (after_d / after_i with groups)");
+  VTC_CHECK(ng >= 1, "l2_search_excluding: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_excluding: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search_excluding: depth=%d must be in [1, min(%d, n_gallery)]", depth,
+            SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search_excluding: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "l2_search_excluding: id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth, groups != nullptr);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search_excluding: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const AfterArgs args{after_d, after_i, id_base, exclude};
+  if (gallery_is_half)
+    return search_excluding(reinterpret_cast<const _Float16 *>(gallery), queries, live, groups, args, ng, nq, d, depth, ids, out_groups, dists,
+                            nonfinite, s, stream);
+  return search_excluding(reinterpret_cast<const float *>(gallery), queries, live, groups, args, ng, nq, d, depth, ids, out_groups, dists, nonfinite,
+                          s, stream);
 }

@@ -44,6 +44,14 @@ search order is a total order on (fp64 distance, row), so "the k nearest rows af
 
     ids2, scores2 = index.search(queries, 10, after=ids[:, -1])        # the next 10 of every query; chain as long as needed
     ids, scores = index.search_deep(queries, 500)                      # the exact 500 nearest: pages of 64, concatenated
+
+And a query can name ONE row, or one video, that it must not be given -- the row it was taken from ("more like this"), the video a
+training text belongs to (hard negatives).  A per-query compare in the scan, for a whole batch in one gallery pass per tile of 8
+(vtc_l2_search_excluding; a ``subset`` holds for the whole batch and cannot say this):
+
+    ids, scores = index.similar(row_ids, 10)                           # the nearest rows of STORED rows, each without itself
+    videos, rows, scores = index.similar_videos(row_ids, 10)           # grouped: the nearest other videos of a row's video
+    videos, rows, scores = index.search_videos(text_queries, 10, exclude_videos=video_of_text)      # hard negatives
 """
 from __future__ import annotations
 
@@ -118,7 +126,10 @@ class VideoIndex:
     a stored row is the unit row rounded to 11 significant bits per component, and every search is exact over those stored rows (scores
     are 1 - D/2 of them).  A half index ALWAYS searches with the scan (vtc_l2_search_half), in slices of 64 queries and by the masked
     route's rules: vtc_l2_topk reads fp32 rows, so ROUTE_TOPK_MIN_QUERIES does not apply, and many-query batches are slower than on
-    an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries).  ``converted`` moves an index over."""
+    an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries).  ``converted`` moves an index over.
+    ``exclude`` / ``exclude_videos`` (one row or one video per query that it is never given), ``similar`` and ``similar_videos`` (the
+    neighbours of a stored row without itself / without its own video) are the excluding scan (vtc_l2_search_excluding), by the same
+    rules: any number of queries in slices of 64, only enqueued."""
     #: queries per call from which search() goes through ops.l2_topk(precision=SWEEP_EXACT) instead of ops.l2_search (which takes up to
     #: 64).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
     #: vtc_l2_topk): the scan's time grows with the number of queries (one gallery pass per started tile of 8), vtc_l2_topk's does not.
@@ -364,7 +375,7 @@ class VideoIndex:
             self._ws = ops.workspace(nbytes, self.device)
         return self._ws
 
-    def search(self, queries, k, subset=None, after=None):
+    def search(self, queries, k, subset=None, after=None, exclude=None):
         """(ids [Q, k] int64, scores [Q, k] fp32), both on the device: the k nearest stored rows of every query, nearest first, and
         score = 1 - |q - g|^2 / 2, the cosine for unit rows.  1 <= k <= min(64, len(index)), len being the live rows.
         Fewer than ROUTE_TOPK_MIN_QUERIES queries -- batch 1 is the design point -- are only enqueued: no device-to-host read, no host
@@ -387,12 +398,17 @@ class VideoIndex:
         -1 / -inf.  So an id cannot be validated: -1 (the previous page was not full: there is nothing after it) or an id outside
         [0, ntotal) gives that query a row of -1 / -inf and leaves the others alone -- chaining past the end returns empty pages, it
         never starts over.  The cursor row need not be live nor a member of ``subset``: a page token survives a ``remove``.  Each page
-        costs a gallery pass per started tile of 8 queries, however deep the cursor is.  ``after=None`` changes nothing above."""
+        costs a gallery pass per started tile of 8 queries, however deep the cursor is.  ``after=None`` changes nothing above.
+        ``exclude`` (an int64 [Q] tensor of row ids): query q is never given row ``exclude[q]`` -- its search order with that row
+        deleted, then cut (vtc_l2_search_excluding).  -1, or an id outside [0, ntotal), excludes nothing.  The call is then always the
+        scan, by the masked route's rules: slices of 64 queries, only enqueued, no host sync, a non-finite query a row of -1 / -inf.  It
+        composes with ``subset``, removed rows, half storage and ``after`` (the cursor may be the excluded row).  A query with fewer
+        than k admissible rows ends in -1 / -inf.  ``exclude=None`` changes nothing above."""
         k = int(k)
         if not 1 <= k <= min(self.MAX_K, self._n_live):
             raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
-        if after is not None:
-            return self._search_masked(queries, k, subset, after)
+        if after is not None or exclude is not None:
+            return self._search_masked(queries, k, subset, after, exclude)
         if subset is not None or self._live is not None or self.storage != torch.float32:
             return self._search_masked(queries, k, subset)
         scan = 0 < len(queries) < min(self.ROUTE_TOPK_MIN_QUERIES, ops.SEARCH_MAX_QUERIES + 1)
@@ -408,12 +424,24 @@ class VideoIndex:
             ids, dists = ops.l2_topk(g, q, k, precision=L.SWEEP_EXACT, ws=ws)
         return ids, 1.0 - dists / 2.0
 
-    def _search_masked(self, queries, k, subset, after=None):
+    def _per_query_ids(self, ids, n_queries, name, what):
+        """An int64 tensor with one entry per query (``n_queries`` None: any number >= 1) -> on the index's device, contiguous; anything
+        else raises ValueError.  The VALUES are not read: no host sync."""
+        ok = isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and ids.dim() == 1
+        if not ok or (ids.shape[0] < 1 if n_queries is None else ids.shape[0] != n_queries):
+            got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
+            raise ValueError(f"VideoIndex.{what}: {name} must be an int64 [{n_queries or 'Q >= 1'}] tensor, one per query, got {got}")
+        return ids.to(self.device).contiguous()
+
+    def _search_masked(self, queries, k, subset, after=None, exclude=None, stored=False):
+        """``stored``: the queries are stored rows [Q, width] widened to fp32 (``similar``) and are searched as they are."""
         if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
             raise ValueError("VideoIndex.search: the subset belongs to another index (build it with this index's subset())")
-        q = self._prepared(queries, "queries", check=False)
+        q = queries if stored else self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
             raise ValueError("VideoIndex.search: no queries")
+        if exclude is not None:
+            exclude = self._per_query_ids(exclude, q.shape[0], "exclude", "search")
         words = self._live_words() if subset is None else subset.words()      # None on a half index with every row live: no mask
         g, step = self.rows, ops.SEARCH_MAX_QUERIES
         ws = self._workspace(ops.l2_search_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
@@ -427,13 +455,16 @@ class VideoIndex:
             for lo in range(0, q.shape[0], step):
                 rows = after[lo:lo + step]
                 cursor = (ops.l2_pair_dists64(g, q[lo:lo + step], rows), rows)      # +inf for an id that is no row: nothing comes after it
-                out.append(ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, after=cursor)[:2])
+                out.append(ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, after=cursor,
+                                         exclude=None if exclude is None else exclude[lo:lo + step])[:2])
+        elif exclude is not None:
+            out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, exclude=exclude[lo:lo + step])[:2] for lo in range(0, q.shape[0], step)]
         else:
             out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
         ids, dists = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
         return ids, 1.0 - dists / 2.0
 
-    def search_deep(self, queries, k, subset=None):
+    def search_deep(self, queries, k, subset=None, exclude=None):
         """``search`` without the limit of 64: (ids [Q, k] int64, scores [Q, k] fp32) for any 1 <= k <= len(index), the exact k nearest
         live rows (of ``subset``) of every query, nearest first.  Page 1 is ``search(queries, min(k, 64), subset)`` by whatever route
         that takes, with its rules for non-finite queries and host syncs; every further page of 64 is
@@ -447,53 +478,106 @@ class VideoIndex:
         the k-th neighbour's score 0.58 and 0.59 ms -- it is the better tool from k = 256 on whenever a threshold is known.
         From ROUTE_TOPK_MIN_QUERIES queries on, page 1 of an fp32 index with every row live is ``search``'s vtc_l2_topk call, whose
         routing was measured at depth 11; at k = 64 it takes 29 ms over 10^5 rows and 290 ms over 10^6 (the scan: 2 and 14 ms) and
-        dominates the call.  For deep rankings of many queries pass fewer than that per call."""
+        dominates the call.  For deep rankings of many queries pass fewer than that per call.
+        ``exclude``: ``search``'s, passed on every page -- the ranking without that row, what a hard-negative miner asks for; every
+        page, the first included, is then the scan."""
         k = int(k)
         if not 1 <= k <= self._n_live:
             raise ValueError(f"VideoIndex.search_deep: k={k} must be in [1, len(index) = {self._n_live}]")
-        pages = [self.search(queries, min(k, self.MAX_K), subset=subset)]
+        pages = [self.search(queries, min(k, self.MAX_K), subset=subset, exclude=exclude)]
         got = pages[0][0].shape[1]
         while got < k:
-            pages.append(self.search(queries, min(k - got, self.MAX_K), subset=subset, after=pages[-1][0][:, -1]))
+            pages.append(self.search(queries, min(k - got, self.MAX_K), subset=subset, after=pages[-1][0][:, -1], exclude=exclude))
             got += pages[-1][0].shape[1]
         if len(pages) == 1:
             return pages[0]
         return torch.cat([p[0] for p in pages], dim=1), torch.cat([p[1] for p in pages], dim=1)
 
-    def search_videos(self, queries, k, subset=None):
+    def search_videos(self, queries, k, subset=None, exclude_videos=None):
         """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of every
         query, nearest first, each with its nearest live row (the best-matching caption, comment or chunk) and that row's score as
         ``search`` gives it.  Ties go to the lower row.  Always the scan (vtc_l2_search_grouped; vtc_l2_topk has no grouping), 64 queries
         per call, with the few-query rules of the masked route: only enqueued, no host sync, and a non-finite query gets a row of
         -1 / -1 / -inf.  A half index searches its stored half rows the same way (vtc_l2_search_half).  1 <= k <= min(64, len(index)), len counting live ROWS; fewer than k distinct live videos (in the ``subset``, if
-        one is given) give rows that end in -1 / -1 / -inf.  On an ungrouped index it raises ValueError."""
+        one is given) give rows that end in -1 / -1 / -inf.  On an ungrouped index it raises ValueError.
+        ``exclude_videos`` (an int64 [Q] tensor of video ids): query q is never given a row of the video ``exclude_videos[q]`` -- the
+        nearest OTHER videos, the hard negatives of a (text, video) pair (vtc_l2_search_excluding).  -1, or a video the index does not
+        hold, excludes nothing.  ``None`` changes nothing above."""
+        return self._search_videos(queries, k, subset, exclude_videos, "search_videos")
+
+    def _search_videos(self, queries, k, subset, exclude, what, stored=False):
         if not self.grouped:
-            raise ValueError("VideoIndex.search_videos: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
+            raise ValueError(f"VideoIndex.{what}: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
         k = int(k)
         if not 1 <= k <= min(self.MAX_K, self._n_live):
-            raise ValueError(f"VideoIndex.search_videos: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+            raise ValueError(f"VideoIndex.{what}: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
         if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
-            raise ValueError("VideoIndex.search_videos: the subset belongs to another index (build it with this index's subset())")
-        q = self._prepared(queries, "queries", check=False)
+            raise ValueError(f"VideoIndex.{what}: the subset belongs to another index (build it with this index's subset())")
+        q = queries if stored else self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
-            raise ValueError("VideoIndex.search_videos: no queries")
+            raise ValueError(f"VideoIndex.{what}: no queries")
+        if exclude is not None:
+            exclude = self._per_query_ids(exclude, q.shape[0], "exclude_videos", what)
         words = self._live_words() if subset is None else subset.words()
         g, vids, step = self.rows, self._video_ids[:self._n], ops.SEARCH_MAX_QUERIES
         ws = self._workspace(ops.l2_search_grouped_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
-        out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words)[:3] for lo in range(0, q.shape[0], step)]
+        if exclude is None:
+            out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words)[:3] for lo in range(0, q.shape[0], step)]
+        else:
+            out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words, exclude=exclude[lo:lo + step])[:3]
+                   for lo in range(0, q.shape[0], step)]
         rows, videos, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
         return torch.where(rows >= 0, videos.to(torch.int64), rows), rows, 1.0 - dists / 2.0
 
-    def search_videos_text(self, model, title_tokens, k, comments=None, subset=None):
+    def search_videos_text(self, model, title_tokens, k, comments=None, subset=None, exclude_videos=None):
         """``search_text`` for a grouped index: the k nearest distinct videos of text queries given as token ids, as ``search_videos``
-        returns them."""
-        return self.search_videos(self._text_queries(model, title_tokens, comments, "search_videos_text"), k, subset=subset)
+        returns them.  ``exclude_videos``: ``search_videos``'s."""
+        return self.search_videos(self._text_queries(model, title_tokens, comments, "search_videos_text"), k, subset=subset,
+                                  exclude_videos=exclude_videos)
 
-    def search_text(self, model, title_tokens, k, comments=None, subset=None, after=None):
+    # ---- more like this --------------------------------------------------------------------------
+    def _stored_queries(self, ids, what):
+        """(ids int64 [Q] on the device, the STORED rows ids[q] widened to fp32 [Q, width]).  The gather is clamped into the index and the
+        query of an id outside [0, ntotal) becomes a row of NaN -- which every search answers with -1 / -inf -- without a host read."""
+        ids = self._per_query_ids(ids, None, "ids", what)
+        if self._n == 0:
+            raise ValueError(f"VideoIndex.{what}: the index is empty")
+        inside = (ids >= 0) & (ids < self._n)
+        q = self.rows[ids.clamp(0, self._n - 1)].float()                 # half -> fp32 is exact, the zero padding included
+        return ids, torch.where(inside[:, None], q, q.new_full((), float("nan"))).contiguous()
+
+    def similar(self, ids, k, subset=None, after=None):
+        """MORE LIKE THIS: (ids [Q, k] int64, scores [Q, k] fp32), the k nearest rows of the STORED row ``ids[q]`` (an int64 [Q]
+        tensor of row ids), that row itself left out -- ``search`` with the stored row as the query and ``exclude=ids``.  The query is
+        the row as the index keeps it, never normalised again: a half index's row widened exactly, zero padding included.  So a
+        bit-equal duplicate of the row scores exactly 1 and IS returned: it is another row.  The query row need not be live nor a
+        member of ``subset`` (the neighbours are).  ``after``: ``search``'s cursor, the next page.  An id outside [0, ntotal) (-1
+        included) cannot be validated without a host read: that query comes back as -1 / -inf and the others are left alone.  Any
+        number of queries, 64 per call, only enqueued.  1 <= k <= min(64, len(index)); fewer than k other rows end in -1 / -inf."""
+        k = int(k)
+        if not 1 <= k <= min(self.MAX_K, self._n_live):
+            raise ValueError(f"VideoIndex.similar: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+        ids, q = self._stored_queries(ids, "similar")
+        return self._search_masked(q, k, subset, after, ids, stored=True)
+
+    def similar_videos(self, ids, k, subset=None):
+        """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of the
+        STORED row ``ids[q]`` -- ROW ids, for example the ``rows`` a ``search_videos`` call returned -- with every row of that row's
+        own video left out; otherwise ``search_videos`` with the stored row as the query (as ``similar`` takes it).  An id outside
+        [0, ntotal) gives -1 / -1 / -inf.  On an ungrouped index it raises ValueError.  A query given as a whole VIDEO, all of its
+        rows merged into one ranking, is out of scope: call this per row and merge as the application sees fit."""
+        if not self.grouped:
+            raise ValueError("VideoIndex.similar_videos: the index has no video ids (add(embeddings, video_ids=...)); similar() returns rows")
+        ids, q = self._stored_queries(ids, "similar_videos")
+        own = self._video_ids[:self._n][ids.clamp(0, self._n - 1)].to(torch.int64)
+        return self._search_videos(q, k, subset, own, "similar_videos", stored=True)
+
+    def search_text(self, model, title_tokens, k, comments=None, subset=None, after=None, exclude=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a
         ``*_finaltf`` model that adapts the text branch (branch_to_adapt_val == "text"), ``comments`` [Q, n_comments, ctx] adapts the
-        query through the Context Adapter Module as the wrapper's eval forward does.  ``after``: the cursor of ``search``, the next page."""
-        return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset, after=after)
+        query through the Context Adapter Module as the wrapper's eval forward does.  ``after``: the cursor of ``search``, the next page.
+        ``exclude``: ``search``'s, a row per query that it is never given."""
+        return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset, after=after, exclude=exclude)
 
     # ---- range search ----------------------------------------------------------------------------
     def _range_setup(self, queries, min_score, subset, what):

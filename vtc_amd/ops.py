@@ -370,9 +370,17 @@ def _search_gallery(gallery: torch.Tensor) -> torch.Tensor:
     return gallery
 
 
+def _exclude_arg(exclude, nq, device, what):
+    """The excluded keys of an excluding search: an int64 [Q] tensor on the gallery's device, anything else raises ValueError."""
+    if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64 or tuple(exclude.shape) != (nq,) or exclude.device != device:
+        got = f"{exclude.dtype} {tuple(exclude.shape)} on {exclude.device}" if isinstance(exclude, torch.Tensor) else type(exclude).__name__
+        raise ValueError(f"{what}: exclude must be an int64 [{nq}] tensor on {device} (one row or group per query), got {got}")
+    return exclude.contiguous()
+
+
 @on_device
 def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
-              ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, after=None):
+              ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, after=None, exclude: Optional[torch.Tensor] = None):
     """Query-time search (vtc_l2_search): the exact ``depth`` nearest gallery rows of at most 64 queries, by the fp64 squared distances of
     the fp32 rows, ties to the lower row.  Returns (ids [Q, depth] int64 = id_base + row, -1 where fewer rows have a finite distance;
     dists [Q, depth] fp32 or None; nonfinite_bits, a device int32 [1]: 1 = the gallery holds a NaN / inf, 2 = the queries do).  With a
@@ -388,7 +396,11 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     page ended in that key.  ``after_d64`` must carry the bits the scan forms: ``search_dists64(ws, Q, depth)[:, -1]`` of the previous
     page (cloned: the next call overwrites it) or ``l2_pair_dists64``; -inf is the plain search, +inf / NaN an empty row.  The cursor
     row need not be live; with ``id_base`` the ids are global, so every window of a gallery takes the same cursor.  None: the call
-    above, unchanged."""
+    above, unchanged.
+    ``exclude`` (vtc_l2_search_excluding): int64 [Q] on the gallery's device; query q is never given the row with the GLOBAL id
+    ``exclude[q]`` -- the search order with that row deleted, then cut.  -1, or any id outside [id_base, id_base + n), excludes nothing.
+    It composes with ``live``, a half gallery and ``after`` (the cursor may stand on the excluded row).  A wrong dtype, shape or device
+    raises ValueError.  None: the call above, unchanged."""
     gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     ng, d = gallery.shape
     nq = queries.shape[0]
@@ -399,6 +411,8 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
         if after_d.device != gallery.device or after_i.device != gallery.device or tuple(after_d.shape) != (nq,) or tuple(after_i.shape) != (nq,):
             raise ValueError(f"l2_search: after must be (float64 [{nq}], int64 [{nq}]) on {gallery.device}, got {tuple(after_d.shape)} on "
                              f"{after_d.device} and {tuple(after_i.shape)} on {after_i.device}")
+    if exclude is not None:
+        exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search")
     if live is not None:
         live = _gpu(live, torch.int32, "live")
         if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
@@ -414,7 +428,13 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
     tail = (int(id_base), ids.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    if after is not None:
+    if exclude is not None:
+        L.check(L.lib().vtc_l2_search_excluding(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                                live.data_ptr() if live is not None else None, None, exclude.data_ptr(),
+                                                after_d.data_ptr() if after is not None else None,
+                                                after_i.data_ptr() if after is not None else None, ng, nq, d, depth, tail[0], tail[1], None,
+                                                *tail[2:]), "vtc_l2_search_excluding")
+    elif after is not None:
         L.check(L.lib().vtc_l2_search_after(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
                                             live.data_ptr() if live is not None else None, after_d.data_ptr(), after_i.data_ptr(), ng, nq, d,
                                             depth, *tail), "vtc_l2_search_after")
@@ -582,16 +602,17 @@ def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live:
 
 @on_device
 def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None,
-                   after=None):
+                   after=None, exclude: Optional[torch.Tensor] = None):
     """One window's share of a search over several: (ids [Q, depth] int64, dists64 [Q, depth] fp64, nonfinite_bits) -- what
     l2_search_merge takes.  ``depth`` is capped at the window's rows by the caller (a window may hold fewer rows than the merged list).
     ``live``: the window's own packed row mask (bit 0 of word 0 is the window's first row), as l2_search takes it.  The window may be
     fp32 or ``torch.float16``; the fp64 lists do not depend on how the rows are stored, so l2_search_merge takes both.
-    ``after``: the cursor of l2_search in GLOBAL ids, the same pair for every window -- the merged lists are then the page after it."""
+    ``after``: the cursor of l2_search in GLOBAL ids, the same pair for every window -- the merged lists are then the page after it.
+    ``exclude``: the excluded rows of l2_search in GLOBAL ids, the same tensor for every window -- the merged lists then exclude them."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
-    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live, after=after)
+    ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live, after=after, exclude=exclude)
     return ids, search_dists64(ws, nq, depth), bits
 
 
@@ -613,14 +634,18 @@ def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return
 
 @on_device
 def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
-                      return_dists: bool = True, ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None):
+                      return_dists: bool = True, ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None,
+                      exclude: Optional[torch.Tensor] = None):
     """The grouped query-time search (vtc_l2_search_grouped): every gallery row belongs to the group ``groups[j]`` (int32 [n], ANY values,
     rows of a group anywhere), and of the complete (distance, row)-sorted list of the live rows with a finite distance only the FIRST row
     of every group stays; the first ``depth`` of those are the result -- the ``depth`` nearest distinct groups, each by its nearest row.
     Returns (ids [Q, depth] int64 = id_base + that row, -1 where fewer groups have a finite distance; groups [Q, depth] int32, -1 there
     too -- read ``ids`` to tell an empty entry, -1 is a legal group id; dists fp32 or None; nonfinite_bits as l2_search).  ``live`` and
     ``ws`` as in l2_search, the workspace being ``l2_search_grouped_workspace_bytes``; its head holds the fp64 distances.  A
-    ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``."""
+    ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``.
+    ``exclude`` (vtc_l2_search_excluding): int64 [Q] on the gallery's device; query q is never given a row of the GROUP ``exclude[q]`` --
+    the grouped search of the gallery without that group's rows.  A value outside int32 is no group and excludes nothing (-1 is a legal
+    group).  A wrong dtype, shape or device raises ValueError.  None: the call above, unchanged."""
     gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     groups = _gpu(groups, torch.int32, "groups")
     ng, d = gallery.shape
@@ -645,6 +670,14 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     out_groups = torch.empty(nq, depth, dtype=torch.int32, device=gallery.device)
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
+    if exclude is not None:
+        exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
+        L.check(L.lib().vtc_l2_search_excluding(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                                live.data_ptr() if live is not None else None, groups.data_ptr(), exclude.data_ptr(), None, None,
+                                                ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
+                                                dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _stream()), "vtc_l2_search_excluding")
+        return ids, out_groups, dists, bits
     fn, name = ((L.lib().vtc_l2_search_half, "vtc_l2_search_half") if gallery.dtype == torch.float16 else
                 (L.lib().vtc_l2_search_grouped, "vtc_l2_search_grouped"))          # the two take the same arguments
     L.check(fn(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, groups.data_ptr(), ng, nq, d, depth,
@@ -660,13 +693,14 @@ def l2_search_grouped_workspace_bytes(n_gallery: int, n_queries: int, d: int, de
 
 @on_device
 def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
-                           live: Optional[torch.Tensor] = None):
+                           live: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None):
     """One window's share of a grouped search over several: (ids [Q, depth] int64, groups [Q, depth] int32, dists64 [Q, depth] fp64,
-    nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows.  fp32 or ``torch.float16`` rows."""
+    nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows.  fp32 or ``torch.float16`` rows.
+    ``exclude``: the excluded groups of l2_search_grouped, the same tensor for every window."""
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device)
-    ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live)
+    ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live, exclude=exclude)
     return ids, out_groups, search_dists64(ws, nq, depth), bits
 
 
