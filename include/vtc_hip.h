@@ -433,7 +433,8 @@ int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint
  * cursor row need not be live: a cursor survives the removal of its row.
  * Two launches on the grid of vtc_l2_search; one gallery pass per tile of queries, whatever the cursor.
  * LIMITS and refusals: those of vtc_l2_search_masked, and after_d / after_i must be non-null; the workspace is
- * vtc_l2_search_workspace_bytes(...).  The grouped search has no cursor. */
+ * vtc_l2_search_workspace_bytes(...).  The grouped search has no cursor (of this entry: pages of distinct videos are
+ * vtc_l2_search_grouped_after below, which needs a pass of its own first). */
 int vtc_l2_search_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const double *after_d,
                         const int64_t *after_i, int n_gallery, int n_queries, int d, int depth, int64_t id_base, int64_t *ids, float *dists,
                         int *nonfinite, void *ws, size_t ws_bytes, void *stream);
@@ -454,7 +455,8 @@ int vtc_l2_search_after(const void *gallery, int gallery_is_half, const float *q
  * The excluded key is one more compare per query on a row that has already beaten the depth-th entry: the gallery is read once.
  * LIMITS and refusals: those of vtc_l2_search_after (groups == NULL; workspace vtc_l2_search_workspace_bytes) or vtc_l2_search_grouped
  * (workspace vtc_l2_search_grouped_workspace_bytes, out_groups required); exclude must be non-null; after_d without after_i or the
- * reverse, and a cursor together with groups, are refused.  A refused call launches nothing. */
+ * reverse, and a cursor together with groups, are refused (vtc_l2_search_grouped_after takes both, and an excluded group with them).
+ * A refused call launches nothing. */
 int vtc_l2_search_excluding(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
                             const int64_t *exclude, const double *after_d, const int64_t *after_i, int n_gallery, int n_queries, int d,
                             int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws,
@@ -467,6 +469,43 @@ int vtc_l2_search_excluding(const void *gallery, int gallery_is_half, const floa
  * Refused: null gallery / queries / rows / out, n_gallery < 1, n_queries < 1, d not a multiple of 64 in [64, 2048], id_base < 0. */
 int vtc_l2_pair_dists64(const void *gallery, int gallery_is_half, const float *queries, const int64_t *rows, int n_gallery, int n_queries,
                         int d, int64_t id_base, double *out, void *stream);
+/* PAGES OF DISTINCT VIDEOS: the grouped search after a cursor, to any depth.  For query q the ADMISSIBLE rows are the live rows (of
+ * `live`; NULL: every row) with a finite D(q, j), minus the rows with (int64) groups[j] == exclude[q] where exclude is given.  K(q, g) is
+ * the smallest key (D(q, j), id_base + j) over the admissible rows of group g; the grouped order of q is the groups with an admissible
+ * row sorted by K.  vtc_l2_search_grouped_after returns the first `depth` groups of that order with K(q, g) STRICTLY AFTER the cursor
+ * key (after_d[q], after_i[q]) -- K.d > after_d[q], or K.d == after_d[q] and K.row > after_i[q], compared exactly -- each with its
+ * nearest row and that row's distance; ids / out_groups / dists / the tail of -1 / -1 / +inf / nonfinite / the fp64 distances at the
+ * head of the workspace are vtc_l2_search_grouped's.  With the cursor = the last (fp64 distance, id) of the previous page -- the fp64
+ * value from the workspace or from vtc_l2_pair_dists64, never the fp32 dists -- the pages concatenated ARE the grouped order, bit for
+ * bit, without repeats or gaps.  after_d[q] = -inf admits everything (the call is then vtc_l2_search_grouped), +inf or a NaN nothing;
+ * the cursor row need not be live, and an id that is no row of the gallery is a key like any other (vtc_l2_pair_dists64 gives it +inf:
+ * an empty page).
+ * WHY TWO CALLS.  "After row r" is a compare on a row's own key; "the video's nearest row lies after r" is not: a row after the cursor
+ * belongs on the page only if NO admissible row of its group lies at or before the cursor, and such a row can be anywhere in the
+ * gallery.  So vtc_l2_group_mark_before makes one pass and sets bit g of ban[q] for every group g with a live row of finite distance at
+ * or before the cursor -- ban: uint32 [n_queries][ceil(n_groups / 32)] in device memory of the caller, vtc_l2_group_ban_words(...)
+ * words, bit g & 31 of word g >> 5 -- and vtc_l2_search_grouped_after drops the rows of the groups whose bit is set.  The mark pass
+ * ONLY ORs: the caller zeroes the buffer (or carries bits forward: every group already returned may be marked by hand).  exclude is not
+ * looked at by the mark pass: an excluded group is dropped by the scan anyway.
+ * GROUP IDS ARE DENSE HERE: groups[j] in [0, n_groups), because the bitmap is indexed by the group.  A row whose group lies outside
+ * that range marks nothing and is never returned.  (vtc_l2_search_grouped and the other grouped entries take any int32 and stay as
+ * they are.)
+ * WINDOWS: the cursor and the ids are global as in vtc_l2_search_after, the windows of one gallery take the SAME cursor and mark into
+ * the SAME ban buffer, and EVERY window must be marked before ANY window is scanned -- a group's row before the cursor may lie in
+ * another window.  vtc_l2_search_merge_grouped then merges the windows' pages unchanged.
+ * Cost: two gallery passes per tile of queries (the mark pass keeps no lists), the scan's two launches plus one.
+ * LIMITS and refusals: those of vtc_l2_search_grouped and vtc_l2_search_after (the mark pass has no depth); n_groups in [1, 2^31);
+ * ban, after_d, after_i and groups must be non-null, exclude may be NULL (no group); the workspace is
+ * vtc_l2_search_grouped_workspace_bytes(...).  vtc_l2_group_ban_words is 0 for n_queries outside [1, 64] or n_groups < 1.  A refused
+ * call launches nothing. */
+size_t vtc_l2_group_ban_words(int n_queries, int n_groups);
+int vtc_l2_group_mark_before(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                             int n_groups, const double *after_d, const int64_t *after_i, int n_gallery, int n_queries, int d,
+                             int64_t id_base, uint32_t *ban, void *stream);
+int vtc_l2_search_grouped_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                                int n_groups, const uint32_t *ban, const int64_t *exclude, const double *after_d, const int64_t *after_i,
+                                int n_gallery, int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups,
+                                float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* RANGE SEARCH: every row of a stored gallery that lies within a threshold of a query, however many rows that is (near-duplicate
  * detection before a video is added, "everything that matches this title", counting matches).  vtc_l2_search cannot stand in: its depth
  * is capped at 64 and a depth guessed too small truncates silently.

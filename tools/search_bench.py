@@ -109,7 +109,26 @@ Per (n_gallery, n_queries, storage float32 / float16, ungrouped / grouped at --r
   slower_than_spread        the excluding median exceeds the plain median by more than the plain scan's own max - min
   same_as_masked            the excluding result equals, bit for bit, the masked search with the excluded rows' bits cleared, query by
                             query (asserted; outside the timing)
-profiles/search_exclude.md holds a run's table."""
+profiles/search_exclude.md holds a run's table.
+
+With --grouped-after P the tool measures a stateless PAGE OF VIDEOS (ops.l2_search_grouped(after=..., n_groups=...) =
+vtc_l2_group_mark_before + vtc_l2_search_grouped_after) against ops.l2_search_grouped of the same shape:
+
+    python tools/search_bench.py --grouped-after 1 [--rows-per-video 5] [--queries 1,2,4,8] [--baseline-lib OTHER/libvtc_hip.so] ...
+
+Per (n_gallery, n_queries, storage float32 / float16) one JSON line:
+  page_us / grouped_us      the stateless page -- a zeroed bitmap, the mark pass, the page scan, the merge -- with the cursor on the last
+                            row of every query's (64 P)-th video (found by chaining P pages of 64, outside the timing), and
+                            ops.l2_search_grouped at --depth, in alternation as above
+  page_over_grouped         ratio of the medians
+  mark_us / scan_us         the two halves on their own: ops.l2_group_mark_before (its torch.zeros included) and the page scan with the
+                            bitmap given, in the same alternation
+  same_ids_as_host          on the first 10^4 rows: the page equals that slice of the grouped order formed outside the library in fp64
+                            (asserted; outside the timing)
+  with --baseline-lib, for the entries that were there before (ops.l2_search, l2_search(live=) with every row live, l2_search_grouped, the
+  excluding scans ungrouped and grouped, the cursor scan at (-inf, -1)): NAME_us, NAME_baseline_us -- the same call bound to ANOTHER
+  build of the library (the parent commit) -- and NAME_over_baseline, all in the one alternation
+profiles/search_grouped_after.md holds a run's table."""
 import argparse
 import json
 import os
@@ -580,6 +599,112 @@ def exclude_main(args):
     return lines
 
 
+def grouped_after_main(args):
+    """--grouped-after: a stateless page of videos against the grouped scan; the older entries against another build."""
+    import ctypes as C
+    base = None
+    if args.baseline_lib:
+        base = C.CDLL(os.path.abspath(args.baseline_lib))
+        for name, (res, argtypes) in L.SIGNATURES.items():    # the entries the other build has, with this tree's signatures
+            if hasattr(base, name):
+                getattr(base, name).restype, getattr(base, name).argtypes = res, argtypes
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    rpv = int((args.rows_per_video or "5").split(",")[0])
+    pages, lines = int(args.grouped_after), []
+
+    def cursor_after(g, q, groups, n_groups, n_pages):         # the key of the last row of every query's (64 n_pages)-th video in g
+        ws64 = ops.workspace(ops.l2_search_grouped_workspace_bytes(g.shape[0], q.shape[0], args.d, 64), g.device)
+        after = None
+        for _ in range(n_pages):
+            ids = ops.l2_search_grouped(g, q, groups, 64, ws=ws64, after=after, n_groups=n_groups)[0]
+            after = (ops.search_dists64(ws64, q.shape[0], 64)[:, -1].clone(), ids[:, -1].clone())
+        return after
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        rows32 = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        storages = {"float32": rows32, "float16": rows32.to(torch.float16)}
+        groups = (torch.arange(ng, device="cuda") // rpv).to(torch.int32)
+        n_groups = -(-ng // rpv)
+        assert n_groups > 64 * pages + args.depth, "fewer videos than the page reaches"
+        all_live = ops.row_mask_pack(torch.ones(ng, dtype=torch.uint8, device="cuda"))
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(rows32[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            for storage, gallery in storages.items():
+                need = ops.l2_search_grouped_workspace_bytes(ng, nq, args.d, args.depth)
+                cursor = cursor_after(gallery, queries, groups, n_groups, pages)
+                ban = ops.l2_group_mark_before(gallery, queries, groups, n_groups, cursor)
+                first = (torch.full((nq,), float("-inf"), dtype=torch.float64, device="cuda"), torch.full((nq,), -1, dtype=torch.int64, device="cuda"))
+                nearest = ops.l2_search(gallery, queries, 1)[0][:, 0].clone()
+                own = groups[nearest].to(torch.int64)
+                new = {"page": lambda ws: ops.l2_search_grouped(gallery, queries, groups, args.depth, ws=ws, after=cursor, n_groups=n_groups),
+                       "mark": lambda ws: ops.l2_group_mark_before(gallery, queries, groups, n_groups, cursor),
+                       "scan": lambda ws: ops.l2_search_grouped(gallery, queries, groups, args.depth, ws=ws, after=cursor, n_groups=n_groups, ban=ban)}
+                old = {"grouped": lambda ws: ops.l2_search_grouped(gallery, queries, groups, args.depth, ws=ws),
+                       "search": lambda ws: ops.l2_search(gallery, queries, args.depth, ws=ws),
+                       "masked": lambda ws: ops.l2_search(gallery, queries, args.depth, ws=ws, live=all_live),
+                       "cursor": lambda ws: ops.l2_search(gallery, queries, args.depth, ws=ws, after=first),
+                       "excluding": lambda ws: ops.l2_search(gallery, queries, args.depth, ws=ws, exclude=nearest),
+                       "excluding_grouped": lambda ws: ops.l2_search_grouped(gallery, queries, groups, args.depth, ws=ws, exclude=own)}
+
+                def bound(fn, lib_, ws):                       # the same host code, bound to `lib_` for the call
+                    def call():
+                        mine, L._lib = L._lib, lib_
+                        try:
+                            return fn(ws)
+                        finally:
+                            L._lib = mine
+                    return call
+                names, entries = [], []
+                for name, fn in list(new.items()) + list(old.items()):
+                    names.append(name)
+                    entries.append(bound(fn, L.lib(), ops.workspace(need, gallery.device)))
+                    if base and name in old:
+                        names.append(name + "_baseline")
+                        entries.append(bound(fn, base, ops.workspace(need, gallery.device)))
+                for _ in range(args.warmup):
+                    for fn in entries:
+                        fn()
+                torch.cuda.synchronize()
+                times, outs = [[] for _ in entries], [None] * len(entries)
+                for _ in range(args.calls):
+                    for k, fn in enumerate(entries):
+                        us, outs[k] = timed(fn)
+                        times[k].append(us)
+                st = {n: stat(t) for n, t in zip(names, times)}
+                out = dict(zip(names, outs))
+                same_halves = all(bool(torch.equal(a, b)) for a, b in zip(out["page"][:3], out["scan"][:3]))
+                same_base = all(bool(torch.equal(a, b)) for n in old if base for a, b in zip(out[n][:2], out[n + "_baseline"][:2]))
+                n_check = min(ng, 10 ** 4)
+                small, small_groups = gallery[:n_check], groups[:n_check].contiguous()
+                got = ops.l2_search_grouped(small, queries, small_groups, args.depth, n_groups=n_groups,
+                                            after=cursor_after(small, queries, small_groups, n_groups, pages))[0].cpu().numpy()
+                g64, host_groups, want = small.double(), small_groups.cpu().numpy(), []
+                for i in range(nq):
+                    order = torch.sort(((g64 - queries[i].double()) ** 2).sum(1), stable=True)[1].cpu().numpy()
+                    firsts = np.sort(np.unique(host_groups[order], return_index=True)[1])      # the first row of every video, in order
+                    want.append(order[firsts][64 * pages:64 * pages + args.depth])
+                same_host = bool(np.array_equal(got, np.stack(want)))
+                line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "storage": storage,
+                        "rows_per_video": rpv, "cursor_at_video": 64 * pages, "passes": passes(nq)}
+                for n in names:
+                    line[n + "_us"] = st[n]
+                line["page_over_grouped"] = round(st["page"]["median"] / st["grouped"]["median"], 3)
+                line["mark_over_grouped"] = round(st["mark"]["median"] / st["grouped"]["median"], 3)
+                line["scan_over_grouped"] = round(st["scan"]["median"] / st["grouped"]["median"], 3)
+                if base:
+                    for n in old:
+                        line[n + "_over_baseline"] = round(st[n]["median"] / st[n + "_baseline"]["median"], 3)
+                line.update({"page_is_mark_then_scan": same_halves, "same_as_baseline": same_base, "same_ids_as_host": same_host})
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                assert same_halves and same_base, "the stateless page and its two halves, or the two builds, returned different bits"
+                assert same_host, "the page after the cursor and the host's fp64 grouped order differ on the first 10^4 rows"
+                del entries
+        del rows32, storages
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--galleries", type=str, default="100000,1000000")
@@ -602,10 +727,18 @@ def main(argv=None):
     ap.add_argument("--deep-k", type=str, default="256,1024", help="with --after-pages: k of VideoIndex.search_deep against range_search")
     ap.add_argument("--exclude", action="store_true",
                     help="measure the excluding scan against the same search without an excluded key, fp32 and half, ungrouped and grouped (see above)")
-    ap.add_argument("--baseline-lib", type=str, default=None, help="with --after-pages: another build of libvtc_hip.so whose vtc_l2_search is timed too")
+    ap.add_argument("--baseline-lib", type=str, default=None,
+                    help="with --after-pages / --grouped-after: another build of libvtc_hip.so whose older entries are timed too")
+    ap.add_argument("--grouped-after", type=int, default=None,
+                    help="P: measure a stateless page of videos, the cursor on the (64 P)-th video, against the grouped scan (see above)")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.grouped_after is not None:
+        assert args.grouped_after >= 1 and not (args.live or args.hits or args.min_score or args.after_pages is not None or args.exclude), \
+            "the page mode takes --rows-per-video and --baseline-lib only"
+        write_out(args.out, grouped_after_main(args))
+        return
     if args.exclude:
         assert not (args.live or args.hits or args.min_score or args.after_pages is not None), "the excluding mode takes --rows-per-video only"
         write_out(args.out, exclude_main(args))

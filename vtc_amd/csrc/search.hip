@@ -48,6 +48,15 @@
 // merges and the window merges stay what they are.  The ungrouped kernel is the cursor scan with EXCL (a null cursor is -inf, the plain
 // search), so an exclusion pages like any search.
 //
+// vtc_l2_group_mark_before / vtc_l2_search_grouped_after: the next page of the GROUPED order -- the `depth` nearest distinct videos whose
+// nearest admissible row lies strictly after a cursor key.  One scan cannot decide that: a row after the cursor counts only if no row of
+// its group lies at or before the cursor, and such a row may be in any wave's share.  Two passes and a per-query bitmap of groups can:
+// videos_page_mark_kernel walks the gallery as the scan does and ORs bit groups[row] of ban[q] for every live row with a finite distance
+// at or before q's cursor (no lists, no merge); videos_page_scan_kernel is scan_body with GROUPED, AFTER and EXCL, which drops a row whose
+// group's bit is set -- one more test on the insertion path, after `beats`, the cursor and the excluded group (nullable here).  Banned
+// groups are deleted from the candidates before the lists de-duplicate, as an excluded group is, so the argument below holds unchanged.
+// The groups of these two entries are DENSE, [0, n_groups): the bitmap is indexed by them.
+//
 // Why merging de-duplicated lists is exact, for the waves' lists in the LDS, the workgroups' lists and the caller's windows alike: a
 // group of the union's first `depth` has its overall nearest row in some part.  In that part fewer than `depth` groups have a smaller
 // local minimum (a local minimum is not below the overall one of its group, and fewer than `depth` groups are nearer overall), so that
@@ -286,14 +295,25 @@ constexpr size_t scan_lds_bytes(int nq_tile, int d) {
 // the rejecting path of the steady state stays the one compare.  The ungrouped excluding scan is always a cursor scan (AFTER): a null
 // after_d is the cursor -inf, the plain search, so there is one excluding kernel where the plain and the cursor scan are two.  Without
 // EXCL `exclude` is not looked at and not a statement of it is compiled.
+//
+// GROUPED && AFTER (with EXCL): the PAGE scan of vtc_l2_search_grouped_after.  The grouped order has no cursor a row could be asked
+// about by itself: a row after the cursor belongs on the page only if NO admissible row of its group lies at or before the cursor, and
+// such a row can be in any wave's share.  So a pass before this one (videos_page_mark_kernel) has set bit g of ban[q] for every group g
+// with such a row, and a row that has passed `beats`, the cursor compare and the excluded group is dropped when its group's bit is set
+// -- one ordinary load of the word on the insertion path only, every lane the one address -- or when its group is outside [0, n_grp),
+// which has no bit.  The cursor compare stays although a complete ban implies it: it is scalar and saves the load.  `exclude` may be
+// null here (no group: a value outside int32), so there is one page scan where the grouped scan and its excluding form are two.  A
+// banned group's rows are deleted from the candidates BEFORE the lists de-duplicate, as an excluded group's are: the lists, the LDS
+// layout, the merges and the workspace are what they were.
 template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, bool EXCL = false, typename G>
 __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
                                           const int *__restrict__ groups, int ng, int nq, int d, int depth, double *__restrict__ part_d,
                                           int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite,
                                           const double *__restrict__ after_d = nullptr, const int64_t *__restrict__ after_i = nullptr,
-                                          int64_t id_base = 0, const int64_t *__restrict__ exclude = nullptr) {
-  static_assert(!(AFTER && GROUPED), "the grouped scan has no cursor");
-  static_assert(!EXCL || AFTER != GROUPED, "the excluding scans: the cursor scan, or the grouped scan");
+                                          int64_t id_base = 0, const int64_t *__restrict__ exclude = nullptr,
+                                          const unsigned *__restrict__ ban = nullptr, int n_grp = 0) {
+  static_assert(!(AFTER && GROUPED) || EXCL, "the grouped scan with a cursor is the page scan: it carries the (nullable) excluded group");
+  static_assert(!EXCL || AFTER || GROUPED, "the excluding scans: the cursor scan, the grouped scan, or both (the page scan)");
   extern __shared__ float4 smem4[];
   float *qt = reinterpret_cast<float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -348,11 +368,14 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
   if constexpr (EXCL) {
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
-      const long long e = uniform_of((long long)exclude[min(q0 + u, nq - 1)]);
+      long long e;
+      if constexpr (GROUPED && AFTER) e = exclude ? uniform_of((long long)exclude[min(q0 + u, nq - 1)]) : INT64_MIN;      // null: no group
+      else e = uniform_of((long long)exclude[min(q0 + u, nq - 1)]);
       if constexpr (GROUPED) ex[u] = e;
       else ex[u] = e >= id_base && e - id_base < ng ? (int)(e - id_base) : -1;      // jj[r] is a row of the window: never -1
     }
   }
+  [[maybe_unused]] const size_t ban_words = ((size_t)(unsigned)n_grp + 31) >> 5;      // words of a query's row of `ban` (PAGE)
   const long long n_groups = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
   // The mask word of step s's rows, as loaded: every lane reads the same address with an ordinary (vector) load, which returns in order
   // -- requested a step ahead, before that step's gallery rows, it has arrived by the time they have and is never waited for on its own.
@@ -402,6 +425,11 @@ __device__ __forceinline__ void scan_body(const G *__restrict__ gallery, const f
             if constexpr (EXCL && GROUPED) {
               const int cg = uniform_of(gv[r]);
               if ((long long)cg == ex[u]) continue;        // a row of the query's excluded group
+              if constexpr (AFTER) {                       // PAGE: a group outside [0, n_grp) has no bit, a banned one a row at or before the cursor
+                if ((unsigned)cg >= (unsigned)n_grp) continue;
+                const unsigned bw = ban[(size_t)(q0 + u) * ban_words + ((unsigned)cg >> 5)];      // q0 + u < nq: the query is not dead
+                if ((uniform_of((int)bw) >> (cg & 31)) & 1) continue;
+              }
               wl[u].insert(cv, jj[r], cg, lane, depth);
             } else if constexpr (EXCL) {
               if (jj[r] == ex[u]) continue;                // the query's excluded row
@@ -520,6 +548,108 @@ __global__ __launch_bounds__(256) void excluding_grouped_scan_kernel(const G *__
                                                                      int *__restrict__ part_g, int *__restrict__ nonfinite) {
   scan_body<NQ, NR, MASKED, true, false, true>(gallery, queries, live, groups, ng, nq, d, depth, part_d, part_i, part_g, nonfinite, nullptr, nullptr,
                                                0, exclude);
+}
+// The page scan (vtc_l2_search_grouped_after): the same body with GROUPED, AFTER and EXCL -- the cursor, the ban bitmap of the mark
+// pass and the excluded group, which may be null.
+template <typename G, int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void videos_page_scan_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                               const unsigned *__restrict__ live, const int *__restrict__ groups, int n_grp,
+                                                               const unsigned *__restrict__ ban, const int64_t *__restrict__ exclude,
+                                                               const double *__restrict__ after_d, const int64_t *__restrict__ after_i,
+                                                               int64_t id_base, int ng, int nq, int d, int depth, double *__restrict__ part_d,
+                                                               int *__restrict__ part_i, int *__restrict__ part_g, int *__restrict__ nonfinite) {
+  scan_body<NQ, NR, MASKED, true, true, true>(gallery, queries, live, groups, ng, nq, d, depth, part_d, part_i, part_g, nonfinite, after_d, after_i,
+                                              id_base, exclude, ban, n_grp);
+}
+// The mark pass (vtc_l2_group_mark_before): the scan's walk -- the query tile in the LDS, a non-finite query a row of zeros that takes
+// no part, the tile shapes, the mask word of the next step read ahead, a step without a live row issuing no load, the groups loaded
+// before the step's gallery rows -- with the distances of wave_dist64_queries, so the bits the page scan compares.  A live row with a
+// finite distance that lies AT OR BEFORE query u's cursor, the exact negation of the scan's test, sets bit groups[row] of ban[q0 + u]:
+// an atomicOr from one lane, no lists, no merge.  A NaN cursor therefore marks every such row (and admits nothing in the scan), -inf
+// none.  A group outside [0, n_grp) marks nothing: it is checked before the address is formed.  The pass only ORs.
+template <typename G, int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void videos_page_mark_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                               const unsigned *__restrict__ live, const int *__restrict__ groups, int n_grp,
+                                                               const double *__restrict__ after_d, const int64_t *__restrict__ after_i,
+                                                               int64_t id_base, int ng, int nq, int d, unsigned *__restrict__ ban) {
+  extern __shared__ float4 smem4[];
+  float *qt = reinterpret_cast<float *>(smem4);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q0 = blockIdx.y * NQ;
+  const int d4 = d >> 2;
+  unsigned bad_bits = 0;
+  for (int x = tid; x < NQ * d4; x += 256) {
+    const int u = x / d4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q0 + u < nq) v = reinterpret_cast<const float4 *>(queries + (size_t)(q0 + u) * d)[x - u * d4];
+    if (!(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w))) bad_bits |= 1u << u;
+    smem4[x] = v;
+  }
+  unsigned dead = 0;                                       // bit u: query q0 + u marks nothing (uniform for the workgroup)
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    const int bad = __syncthreads_or((bad_bits >> u) & 1);
+    if (bad || q0 + u >= nq) dead |= 1u << u;
+    if (bad) {
+      for (int x = tid; x < d4; x += 256) smem4[u * d4 + x] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __syncthreads();
+  double cd[NQ];                                           // the cursors, as the scan holds them
+  int cr[NQ];
+#pragma unroll
+  for (int u = 0; u < NQ; ++u) {
+    const int q = min(q0 + u, nq - 1);
+    const long long a = after_i[q];
+    cd[u] = uniform_f64(after_d[q]);
+    cr[u] = uniform_of(a < id_base ? -1 : (int)min(a - id_base, (long long)ng));
+  }
+  const size_t ban_words = ((size_t)(unsigned)n_grp + 31) >> 5;
+  const long long n_steps = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
+  auto live_word = [&](long long s) -> unsigned { return live[(s * NR) >> 5]; };
+  auto live_bits = [&](long long s, unsigned word) -> unsigned {
+    const int j0 = (int)(s * NR), left = ng - j0;          // s < n_steps: j0 < ng, left >= 1
+    const unsigned inside = NR == 1 || left >= NR ? (1u << NR) - 1 : (1u << left) - 1;
+    return (unsigned)uniform_of((int)((word >> (j0 & 31)) & inside));
+  };
+  long long s = (long long)blockIdx.x * 4 + wave;
+  unsigned next_word = 0;
+  if constexpr (MASKED) {
+    if (s < n_steps) next_word = live_word(s);
+  }
+  for (; s < n_steps; s += GW) {
+    unsigned bits = 0;
+    if constexpr (MASKED) {
+      bits = live_bits(s, next_word);
+      if (s + GW < n_steps) next_word = live_word(s + GW);
+      if (!bits) continue;                                 // nothing live in this step: no gallery load
+    }
+    int jj[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      if constexpr (MASKED) jj[r] = (int)(s * NR) + (NR == 1 || ((bits >> r) & 1) ? r : __ffs((int)bits) - 1);      // a dead slot: a live row of the step
+      else jj[r] = (int)min(s * NR + r, (long long)ng - 1);                                           // a slot past the gallery: clamped
+    }
+    int gv[NR];                                            // jj[r] is a row of the gallery
+#pragma unroll
+    for (int r = 0; r < NR; ++r) gv[r] = groups[jj[r]];
+    double dist[NQ * NR];
+    wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      if (MASKED ? (bits >> r) & 1 : s * NR + r < ng) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          const double cv = dist[u * NR + r];
+          if (!(cv < INFINITY) || ((dead >> u) & 1)) continue;
+          if (cv > cd[u] || (cv == cd[u] && jj[r] > cr[u])) continue;      // after the cursor: the page scan's business
+          const int cg = uniform_of(gv[r]);
+          if ((unsigned)cg >= (unsigned)n_grp) continue;                  // no bit: checked before the address is formed
+          if (lane == 0) atomicOr(ban + (size_t)(q0 + u) * ban_words + ((unsigned)cg >> 5), 1u << (cg & 31));      // q0 + u < nq: not dead
+        }
+      }
+    }
+  }
 }
 // out[q] = D(queries[q], gallery[rows[q] - id_base]), the fp64 distance with the bits the scans form (the same wave_dist64_core), one
 // wave per query; +inf for a row id outside [id_base, id_base + ng) -- -1 included -- whose memory is not touched.  The row is read
@@ -660,6 +790,8 @@ struct AfterArgs {
   const int64_t *i;
   int64_t id_base;
   const int64_t *exclude = nullptr;
+  const unsigned *ban = nullptr;      // the page scan's bitmap of banned groups and the number of groups it is indexed by
+  int n_grp = 0;
 };
 template <int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER = false, bool EXCL = false, typename G>
 int launch_scan(const G *gallery, const float *queries, const unsigned *live, const int *groups, int ng, int nq, int d, int depth,
@@ -683,9 +815,12 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
     // the unmasked one instead of 3.4 - 3.6 %.  It was 2.5 % faster at 10^6 rows and 4 - 12 % on partly live masks there: the trade is
     // written down in profiles/search_masked.md.
     // The grouped scan follows the same rule: the unmasked, ungrouped scan's grid, never more than is resident of its own.
-    // The cursor scan too, masked or not, and the excluding scans.
+    // The cursor scan too, masked or not, the excluding scans and the page scan.
     int own = per_cu;
-    if constexpr (EXCL) {
+    if constexpr (GROUPED && AFTER) {
+      e = resident_of(own, videos_page_scan_kernel<G, NQ, NR, MASKED>);
+      if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
+    } else if constexpr (EXCL) {
       if constexpr (GROUPED) e = resident_of(own, excluding_grouped_scan_kernel<G, NQ, NR, MASKED>);
       else e = resident_of(own, excluding_scan_kernel<G, NQ, NR, MASKED>);
       if (e == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
@@ -706,7 +841,11 @@ int launch_scan(const G *gallery, const float *queries, const unsigned *live, co
   }
   const long long n_groups = ((long long)ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_groups + 3) / 4);
-  if constexpr (EXCL) {
+  if constexpr (GROUPED && AFTER) {
+    hipLaunchKernelGGL((videos_page_scan_kernel<G, NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery, queries, live,
+                       groups, after.n_grp, after.ban, after.exclude, after.d, after.i, after.id_base, ng, nq, d, depth, s.part_d, s.part_i, s.part_g,
+                       nonfinite);
+  } else if constexpr (EXCL) {
     if constexpr (GROUPED)
       hipLaunchKernelGGL((excluding_grouped_scan_kernel<G, NQ, NR, MASKED>), dim3(blocks, tiles), dim3(256), scan_lds_bytes(NQ, d), stream, gallery,
                          queries, live, groups, after.exclude, ng, nq, d, depth, s.part_d, s.part_i, s.part_g, nonfinite);
@@ -996,4 +1135,94 @@ extern "C" int vtc_l2_search_excluding(const void *gallery, int gallery_is_half,
                             nonfinite, s, stream);
   return search_excluding(reinterpret_cast<const float *>(gallery), queries, live, groups, args, ng, nq, d, depth, ids, out_groups, dists, nonfinite,
                           s, stream);
+}
+
+// ---- pages of distinct videos: the mark pass and the page scan ---------------------------------------------------------------------------
+namespace {
+template <typename G, int NQ, int NR>
+void launch_mark(const G *gallery, const float *queries, const unsigned *live, const int *groups, int n_grp, const AfterArgs &after, int ng, int nq,
+                 int d, int tiles, unsigned *ban, hipStream_t stream) {
+  // the scan's grid without its occupancy question: no lists depend on the number of workgroups, and a workgroup that is not resident
+  // at once only starts later
+  const long long n_steps = ((long long)ng + NR - 1) / NR;
+  const int blocks = (int)std::min<long long>(std::min(search_max_lists(ng), 4 * vtcgemm::num_cus()), (n_steps + 3) / 4);
+  const size_t lds = (size_t)NQ * d * sizeof(float);
+  if (live)
+    hipLaunchKernelGGL((videos_page_mark_kernel<G, NQ, NR, true>), dim3(blocks, tiles), dim3(256), lds, stream, gallery, queries, live, groups, n_grp,
+                       after.d, after.i, after.id_base, ng, nq, d, ban);
+  else
+    hipLaunchKernelGGL((videos_page_mark_kernel<G, NQ, NR, false>), dim3(blocks, tiles), dim3(256), lds, stream, gallery, queries, live, groups, n_grp,
+                       after.d, after.i, after.id_base, ng, nq, d, ban);
+}
+template <typename G>
+void launch_mark_tile(const SearchPlan &p, const G *gallery, const float *queries, const unsigned *live, const int *groups, int n_grp,
+                      const AfterArgs &after, int ng, int nq, int d, unsigned *ban, hipStream_t stream) {
+  if (p.tile_q == 1) return launch_mark<G, 1, 4>(gallery, queries, live, groups, n_grp, after, ng, nq, d, p.tiles, ban, stream);
+  if (p.tile_q == 2) return launch_mark<G, 2, 4>(gallery, queries, live, groups, n_grp, after, ng, nq, d, p.tiles, ban, stream);
+  if (p.tile_q == 4) return launch_mark<G, 4, 2>(gallery, queries, live, groups, n_grp, after, ng, nq, d, p.tiles, ban, stream);
+  return launch_mark<G, 8, 1>(gallery, queries, live, groups, n_grp, after, ng, nq, d, p.tiles, ban, stream);
+}
+// The page scan of either storage, then the grouped merge every grouped search runs.
+template <typename G>
+int search_grouped_after(const G *gallery, const float *queries, const uint32_t *live, const int32_t *groups, const AfterArgs &args, int ng, int nq,
+                         int d, int depth, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, const SearchWs &s, hipStream_t stream) {
+  const SearchPlan p = search_plan(nq);
+  const int blocks = live ? launch_scan_tile<true, true, true, true>(p, gallery, queries, live, groups, ng, nq, d, depth, s, nonfinite, stream, args)
+                          : launch_scan_tile<false, true, true, true>(p, gallery, queries, nullptr, groups, ng, nq, d, depth, s, nonfinite, stream, args);
+  VTC_LAUNCH_CHECK2("l2_search_grouped_after", "scan");
+  hipLaunchKernelGGL(merge_grouped_kernel<ScanGroupLists>, dim3(nq), dim3(256), 0, stream, ScanGroupLists{s.part_d, s.part_i, s.part_g, blocks, depth, 0},
+                     blocks, depth, args.id_base, ids, out_groups, dists, s.dists64);
+  VTC_LAUNCH_CHECK2("l2_search_grouped_after", "merge");
+  return 0;
+}
+}  // namespace
+
+extern "C" size_t vtc_l2_group_ban_words(int n_queries, int n_groups) {
+  if (n_queries < 1 || n_queries > SEARCH_MAX_Q || n_groups < 1) return 0;
+  return (size_t)n_queries * (((size_t)n_groups + 31) / 32);
+}
+
+extern "C" int vtc_l2_group_mark_before(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                                        int n_groups, const double *after_d, const int64_t *after_i, int ng, int nq, int d, int64_t id_base,
+                                        uint32_t *ban, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && groups && after_d && after_i && ban, "l2_group_mark_before (the grouped search's cursor): null argument");
+  VTC_CHECK(ng >= 1, "l2_group_mark_before (the grouped search's cursor): n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_group_mark_before (the grouped search's cursor): n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(n_groups >= 1, "l2_group_mark_before (the grouped search's cursor): n_groups=%d must be in [1, 2^31)", n_groups);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0,
+            "l2_group_mark_before (the grouped search's cursor): d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng,
+            "l2_group_mark_before (the grouped search's cursor): id_base=%lld must be non-negative (and id_base + n_gallery an int64)",
+            (long long)id_base);
+  const AfterArgs args{after_d, after_i, id_base};
+  const SearchPlan p = search_plan(nq);
+  if (gallery_is_half) launch_mark_tile(p, reinterpret_cast<const _Float16 *>(gallery), queries, live, groups, n_groups, args, ng, nq, d, ban, stream);
+  else launch_mark_tile(p, reinterpret_cast<const float *>(gallery), queries, live, groups, n_groups, args, ng, nq, d, ban, stream);
+  VTC_LAUNCH_CHECK("l2_group_mark_before");
+  return 0;
+}
+
+extern "C" int vtc_l2_search_grouped_after(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live,
+                                           const int32_t *groups, int n_groups, const uint32_t *ban, const int64_t *exclude, const double *after_d,
+                                           const int64_t *after_i, int ng, int nq, int d, int depth, int64_t id_base, int64_t *ids,
+                                           int32_t *out_groups, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && groups && ban && after_d && after_i && ids && out_groups, "l2_search_grouped_after: null argument");
+  VTC_CHECK(ng >= 1, "l2_search_grouped_after: n_gallery=%d must be at least 1", ng);
+  VTC_CHECK(nq >= 1 && nq <= SEARCH_MAX_Q, "l2_search_grouped_after: n_queries=%d must be in [1, %d]", nq, SEARCH_MAX_Q);
+  VTC_CHECK(n_groups >= 1, "l2_search_grouped_after: n_groups=%d must be in [1, 2^31)", n_groups);
+  VTC_CHECK(depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng, "l2_search_grouped_after: depth=%d must be in [1, min(%d, n_gallery)]", depth,
+            SEARCH_MAX_DEPTH);
+  VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "l2_search_grouped_after: d=%d must be a multiple of 64 in [64, %d]", d, SEARCH_MAX_D);
+  VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng,
+            "l2_search_grouped_after: id_base=%lld must be non-negative (and id_base + n_gallery an int64)", (long long)id_base);
+  const SearchWs s = search_ws(ws, ng, nq, depth, true);
+  VTC_CHECK(ws && ws_bytes >= s.total, "l2_search_grouped_after: workspace too small (%zu < %zu)", ws_bytes, s.total);
+  const AfterArgs args{after_d, after_i, id_base, exclude, ban, n_groups};
+  if (gallery_is_half)
+    return search_grouped_after(reinterpret_cast<const _Float16 *>(gallery), queries, live, groups, args, ng, nq, d, depth, ids, out_groups, dists,
+                                nonfinite, s, stream);
+  return search_grouped_after(reinterpret_cast<const float *>(gallery), queries, live, groups, args, ng, nq, d, depth, ids, out_groups, dists,
+                              nonfinite, s, stream);
 }

@@ -52,6 +52,15 @@ training text belongs to (hard negatives).  A per-query compare in the scan, for
     ids, scores = index.similar(row_ids, 10)                           # the nearest rows of STORED rows, each without itself
     videos, rows, scores = index.similar_videos(row_ids, 10)           # grouped: the nearest other videos of a row's video
     videos, rows, scores = index.search_videos(text_queries, 10, exclude_videos=video_of_text)      # hard negatives
+
+The grouped order pages too -- recall at 100 or 1000 over videos with several captions, hard negatives below rank 64, a re-ranker's
+few hundred candidate videos.  "The videos after row r" cannot be asked of a row by itself: a row after the cursor counts only if no row
+of its video lies at or before it, anywhere in the gallery.  So a page is two gallery passes, one that marks the videos already behind
+the cursor in a per-query bitmap and the scan that skips them (vtc_l2_group_mark_before / vtc_l2_search_grouped_after), still exact and
+stateless:
+
+    videos2, rows2, scores2 = index.search_videos(queries, 10, after=rows[:, -1])     # the next 10 distinct videos of every query
+    videos, rows, scores = index.search_videos_deep(queries, 300)                      # the exact 300 nearest videos: pages of 64
 """
 from __future__ import annotations
 
@@ -129,7 +138,8 @@ class VideoIndex:
     an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries).  ``converted`` moves an index over.
     ``exclude`` / ``exclude_videos`` (one row or one video per query that it is never given), ``similar`` and ``similar_videos`` (the
     neighbours of a stored row without itself / without its own video) are the excluding scan (vtc_l2_search_excluding), by the same
-    rules: any number of queries in slices of 64, only enqueued."""
+    rules: any number of queries in slices of 64, only enqueued.  ``search_videos(after=)`` and ``search_videos_deep`` page the grouped
+    order (vtc_l2_group_mark_before + vtc_l2_search_grouped_after, two gallery passes a page)."""
     #: queries per call from which search() goes through ops.l2_topk(precision=SWEEP_EXACT) instead of ops.l2_search (which takes up to
     #: 64).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
     #: vtc_l2_topk): the scan's time grows with the number of queries (one gallery pass per started tile of 8), vtc_l2_topk's does not.
@@ -167,6 +177,7 @@ class VideoIndex:
         self._generation = 0                # bumped by add / remove / load_state_dict: what a RowSubset's cached words are valid for
         self._words = None                  # (generation, packed words of _live)
         self._video_ids = None              # int32 [capacity] on the device once the first non-empty add passed video_ids: a GROUPED index
+        self._dense = None                  # (sorted distinct video ids int64 [V], slot of every row int32 [ntotal], V): the paged searches
 
     def __len__(self):
         """The number of live rows."""
@@ -241,6 +252,7 @@ class VideoIndex:
                     grown[:first] = self._video_ids[:first]
                 self._video_ids = grown
             self._video_ids[first:first + n] = vids
+            self._dense = None
         self._n = first + n
         if n:
             self._n_live += n
@@ -346,6 +358,7 @@ class VideoIndex:
                 raise ValueError(f"VideoIndex.load_state_dict: video_ids must be int32 [{rows.shape[0]}], got {vids.dtype} {tuple(vids.shape)}")
             vids = _video_id_tensor(vids, rows.shape[0], self.device, "load_state_dict").clone()
         self._video_ids = vids
+        self._dense = None
         self._n = rows.shape[0]
         self._live = live
         self._n_live = self._n if live is None else int(live.sum())
@@ -493,7 +506,16 @@ class VideoIndex:
             return pages[0]
         return torch.cat([p[0] for p in pages], dim=1), torch.cat([p[1] for p in pages], dim=1)
 
-    def search_videos(self, queries, k, subset=None, exclude_videos=None):
+    def _dense_videos(self):
+        """(uniq int64 [V] sorted, slot int32 [ntotal], V): the videos of the index numbered densely, what the paged grouped search
+        indexes its bitmap by -- video ids themselves stay arbitrary.  Built at the first paged call after an ``add`` or a
+        ``load_state_dict`` (``torch.unique`` reads V back: ONE host sync) and kept until the next; a ``remove`` does not touch it."""
+        if self._dense is None:
+            uniq, slot = torch.unique(self._video_ids[:self._n], return_inverse=True)
+            self._dense = (uniq.to(torch.int64), slot.to(torch.int32).contiguous(), int(uniq.shape[0]))
+        return self._dense
+
+    def search_videos(self, queries, k, subset=None, exclude_videos=None, after=None):
         """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of every
         query, nearest first, each with its nearest live row (the best-matching caption, comment or chunk) and that row's score as
         ``search`` gives it.  Ties go to the lower row.  Always the scan (vtc_l2_search_grouped; vtc_l2_topk has no grouping), 64 queries
@@ -502,10 +524,46 @@ class VideoIndex:
         one is given) give rows that end in -1 / -1 / -inf.  On an ungrouped index it raises ValueError.
         ``exclude_videos`` (an int64 [Q] tensor of video ids): query q is never given a row of the video ``exclude_videos[q]`` -- the
         nearest OTHER videos, the hard negatives of a (text, video) pair (vtc_l2_search_excluding).  -1, or a video the index does not
-        hold, excludes nothing.  ``None`` changes nothing above."""
-        return self._search_videos(queries, k, subset, exclude_videos, "search_videos")
+        hold, excludes nothing.  ``None`` changes nothing above.
+        ``after`` (an int64 [Q] tensor of ROW ids, typically ``rows[:, -1]`` of the previous page): the k nearest distinct videos that
+        come AFTER that row in the query's grouped order -- the videos (with a live row, of ``subset``, not excluded) sorted by the key
+        (fp64 distance, row) of their nearest such row -- so the pages chained by their last rows are, concatenated, that order to any
+        depth, bit for bit, without repeats or gaps.  Stateless and exact: the cursor's distance is formed again from the stored row
+        (vtc_l2_pair_dists64), one gallery pass marks the videos with a row at or before the cursor in a per-query bitmap
+        (vtc_l2_group_mark_before) and the scan skips them (vtc_l2_search_grouped_after): TWO gallery passes per started tile of 8
+        queries, 64 queries per call, only enqueued, a non-finite query a row of -1 / -1 / -inf.  -1 (the previous page was not
+        full) or an id outside [0, ntotal) gives that query an empty page and leaves the others alone.  The cursor row need not be
+        live, nor a member of ``subset``, and may belong to the excluded video.  It composes with ``subset``, removed rows, half
+        storage and ``exclude_videos``.  The bitmap is indexed by a dense numbering of the videos that the index builds at the first
+        paged call after an ``add`` (or ``load_state_dict``) with ``torch.unique``, which reads the number of videos back: ONE host
+        sync then, none at the paged calls after it.  ``after=None`` changes nothing above."""
+        return self._search_videos(queries, k, subset, exclude_videos, "search_videos", after=after)
 
-    def _search_videos(self, queries, k, subset, exclude, what, stored=False):
+    def search_videos_deep(self, queries, k, subset=None, exclude_videos=None):
+        """``search_videos`` without the limit of 64: (video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) for any
+        1 <= k <= len(index) (len counting live ROWS, as the grouped bounds do), the exact k nearest distinct videos of every query.
+        Page 1 is ``search_videos(queries, min(k, 64))``; every further page of 64 is ``search_videos(..., after=rows[:, -1])`` of the
+        page before, only enqueued (after the one host sync of the first paged call since an ``add``), and the pages are concatenated.
+        Fewer than k videos give rows that end in -1 / -1 / -inf.
+        THE COST: TWO gallery passes per page per started tile of 8 queries from page 2 on (one that marks the videos behind the
+        cursor, one that scans; page 1 is one pass) -- k = 1024 for 8 queries is 31 passes over the gallery.  That is right for a few
+        hundred videos of a few queries (profiles/search_grouped_after.md).  For thousands of results, or whenever a score threshold
+        is known, ``range_search`` is the tool: one pass per tile of queries however many rows come back; its hits are rows, which the
+        caller reduces to videos."""
+        k = int(k)
+        if not 1 <= k <= self._n_live:
+            raise ValueError(f"VideoIndex.search_videos_deep: k={k} must be in [1, len(index) = {self._n_live}]")
+        pages = [self.search_videos(queries, min(k, self.MAX_K), subset=subset, exclude_videos=exclude_videos)]
+        got = pages[0][0].shape[1]
+        while got < k:
+            pages.append(self.search_videos(queries, min(k - got, self.MAX_K), subset=subset, exclude_videos=exclude_videos,
+                                            after=pages[-1][1][:, -1]))
+            got += pages[-1][0].shape[1]
+        if len(pages) == 1:
+            return pages[0]
+        return tuple(torch.cat([p[i] for p in pages], dim=1) for i in range(3))
+
+    def _search_videos(self, queries, k, subset, exclude, what, stored=False, after=None):
         if not self.grouped:
             raise ValueError(f"VideoIndex.{what}: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
         k = int(k)
@@ -521,6 +579,20 @@ class VideoIndex:
         words = self._live_words() if subset is None else subset.words()
         g, vids, step = self.rows, self._video_ids[:self._n], ops.SEARCH_MAX_QUERIES
         ws = self._workspace(ops.l2_search_grouped_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
+        if after is not None:
+            after = self._per_query_ids(after, q.shape[0], "after", what)
+            uniq, slot, n_videos = self._dense_videos()
+            if exclude is not None:                            # the excluded VIDEO as its slot; one the index does not hold is no group
+                at = torch.searchsorted(uniq, exclude).clamp(max=n_videos - 1)
+                exclude = torch.where(uniq[at] == exclude, at, torch.full_like(at, 1 << 40))
+            out = []
+            for lo in range(0, q.shape[0], step):
+                rows = after[lo:lo + step]
+                cursor = (ops.l2_pair_dists64(g, q[lo:lo + step], rows), rows)      # +inf for an id that is no row: nothing comes after it
+                out.append(ops.l2_search_grouped(g, q[lo:lo + step], slot, k, ws=ws, live=words, after=cursor, n_groups=n_videos,
+                                                 exclude=None if exclude is None else exclude[lo:lo + step])[:3])
+            rows, slots, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
+            return torch.where(rows >= 0, uniq[slots.clamp(min=0).to(torch.int64)], rows), rows, 1.0 - dists / 2.0
         if exclude is None:
             out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words)[:3] for lo in range(0, q.shape[0], step)]
         else:
@@ -529,11 +601,11 @@ class VideoIndex:
         rows, videos, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
         return torch.where(rows >= 0, videos.to(torch.int64), rows), rows, 1.0 - dists / 2.0
 
-    def search_videos_text(self, model, title_tokens, k, comments=None, subset=None, exclude_videos=None):
+    def search_videos_text(self, model, title_tokens, k, comments=None, subset=None, exclude_videos=None, after=None):
         """``search_text`` for a grouped index: the k nearest distinct videos of text queries given as token ids, as ``search_videos``
-        returns them.  ``exclude_videos``: ``search_videos``'s."""
+        returns them.  ``exclude_videos`` and ``after`` (the next page): ``search_videos``'s."""
         return self.search_videos(self._text_queries(model, title_tokens, comments, "search_videos_text"), k, subset=subset,
-                                  exclude_videos=exclude_videos)
+                                  exclude_videos=exclude_videos, after=after)
 
     # ---- more like this --------------------------------------------------------------------------
     def _stored_queries(self, ids, what):
@@ -560,17 +632,18 @@ class VideoIndex:
         ids, q = self._stored_queries(ids, "similar")
         return self._search_masked(q, k, subset, after, ids, stored=True)
 
-    def similar_videos(self, ids, k, subset=None):
+    def similar_videos(self, ids, k, subset=None, after=None):
         """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of the
         STORED row ``ids[q]`` -- ROW ids, for example the ``rows`` a ``search_videos`` call returned -- with every row of that row's
         own video left out; otherwise ``search_videos`` with the stored row as the query (as ``similar`` takes it).  An id outside
-        [0, ntotal) gives -1 / -1 / -inf.  On an ungrouped index it raises ValueError.  A query given as a whole VIDEO, all of its
-        rows merged into one ranking, is out of scope: call this per row and merge as the application sees fit."""
+        [0, ntotal) gives -1 / -1 / -inf.  On an ungrouped index it raises ValueError.  ``after``: ``search_videos``'s cursor, the next
+        page of other videos (the ``rows[:, -1]`` of the page before), to any depth by chaining.  A query given as a whole VIDEO, all
+        of its rows merged into one ranking, is out of scope: call this per row and merge as the application sees fit."""
         if not self.grouped:
             raise ValueError("VideoIndex.similar_videos: the index has no video ids (add(embeddings, video_ids=...)); similar() returns rows")
         ids, q = self._stored_queries(ids, "similar_videos")
         own = self._video_ids[:self._n][ids.clamp(0, self._n - 1)].to(torch.int64)
-        return self._search_videos(q, k, subset, own, "similar_videos", stored=True)
+        return self._search_videos(q, k, subset, own, "similar_videos", stored=True, after=after)
 
     def search_text(self, model, title_tokens, k, comments=None, subset=None, after=None, exclude=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a

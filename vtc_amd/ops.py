@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import numbers
 from typing import Optional, Sequence
 
 import torch
@@ -632,10 +633,76 @@ def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return
     return ids, dists
 
 
+def _after_arg(after, nq, device, what):
+    """The cursor of a search: (float64 [Q], int64 [Q]) on the gallery's device, anything else raises ValueError."""
+    ok = isinstance(after, (tuple, list)) and len(after) == 2 and all(isinstance(t, torch.Tensor) for t in after)
+    if ok:
+        ok = (after[0].dtype == torch.float64 and after[1].dtype == torch.int64 and
+              all(t.device == device and tuple(t.shape) == (nq,) for t in after))
+    if not ok:
+        got = ", ".join(f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                        for t in (after if isinstance(after, (tuple, list)) else (after,)))
+        raise ValueError(f"{what}: after must be (float64 [{nq}], int64 [{nq}]) on {device}, got ({got})")
+    return after[0].contiguous(), after[1].contiguous()
+
+
+def _n_groups_arg(n_groups, what):
+    if isinstance(n_groups, bool) or not isinstance(n_groups, numbers.Integral) or not 1 <= n_groups < 2 ** 31:
+        raise ValueError(f"{what}: a cursor needs n_groups, an int in [1, 2^31) with every group id in [0, n_groups), got {n_groups!r}")
+    return int(n_groups)
+
+
+def _ban_arg(ban, nq, n_groups, device, what):
+    """The bitmap of banned groups: int32 [Q, ceil(n_groups / 32)] on the gallery's device, contiguous; anything else raises ValueError."""
+    words = (n_groups + 31) // 32
+    if (not isinstance(ban, torch.Tensor) or ban.dtype != torch.int32 or tuple(ban.shape) != (nq, words) or ban.device != device or
+            not ban.is_contiguous()):
+        got = f"{ban.dtype} {tuple(ban.shape)} on {ban.device}" if isinstance(ban, torch.Tensor) else type(ban).__name__
+        raise ValueError(f"{what}: ban must be a contiguous int32 [{nq}, {words}] tensor on {device} (one bit per query and group), got {got}")
+    return ban
+
+
+@on_device
+def l2_group_mark_before(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, n_groups: int, after,
+                         live: Optional[torch.Tensor] = None, id_base: int = 0, ban: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mark pass of a page of the grouped search (vtc_l2_group_mark_before): sets bit g of ``ban[q]`` for every group g that has a
+    live row with a finite distance AT OR BEFORE query q's cursor ``after = (after_d64 [Q] float64, after_ids [Q] int64)`` -- the groups
+    ``l2_search_grouped(after=...)`` must not return again.  ``groups``: int32 [n] with DENSE ids in [0, n_groups); a row whose group is
+    outside the range marks nothing.  ``ban``: int32 [Q, ceil(n_groups / 32)] on the gallery's device, bit g & 31 of word g >> 5; None
+    allocates and zeroes one, a given one is ORed into in place (the windows of one gallery mark into the same buffer, with their
+    ``id_base``).  Returns ``ban``.  One gallery pass per tile of queries, only enqueued; fp32 or ``torch.float16`` gallery.  Wrong
+    dtypes, shapes or devices raise ValueError."""
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
+    groups = _gpu(groups, torch.int32, "groups")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    if queries.shape[1] != d:
+        raise ValueError(f"l2_group_mark_before: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if groups.device != gallery.device or tuple(groups.shape) != (ng,):
+        raise ValueError(f"l2_group_mark_before: groups must be int32 [{ng}] on {gallery.device} (one id per gallery row), got "
+                         f"{tuple(groups.shape)} on {groups.device}")
+    n_groups = _n_groups_arg(n_groups, "l2_group_mark_before")
+    after_d, after_i = _after_arg(after, nq, gallery.device, "l2_group_mark_before")
+    if live is not None:
+        live = _gpu(live, torch.int32, "live")
+        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
+            raise ValueError(f"l2_group_mark_before: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
+                             f"{tuple(live.shape)} on {live.device}")
+    if ban is None:
+        ban = torch.zeros(nq, (n_groups + 31) // 32, dtype=torch.int32, device=gallery.device)
+    else:
+        ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_group_mark_before")
+    L.check(L.lib().vtc_l2_group_mark_before(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                             live.data_ptr() if live is not None else None, groups.data_ptr(), n_groups, after_d.data_ptr(),
+                                             after_i.data_ptr(), ng, nq, d, int(id_base), ban.data_ptr(), _stream()),
+            "vtc_l2_group_mark_before")
+    return ban
+
+
 @on_device
 def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
                       return_dists: bool = True, ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None,
-                      exclude: Optional[torch.Tensor] = None):
+                      exclude: Optional[torch.Tensor] = None, after=None, n_groups: Optional[int] = None, ban: Optional[torch.Tensor] = None):
     """The grouped query-time search (vtc_l2_search_grouped): every gallery row belongs to the group ``groups[j]`` (int32 [n], ANY values,
     rows of a group anywhere), and of the complete (distance, row)-sorted list of the live rows with a finite distance only the FIRST row
     of every group stays; the first ``depth`` of those are the result -- the ``depth`` nearest distinct groups, each by its nearest row.
@@ -645,7 +712,16 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``.
     ``exclude`` (vtc_l2_search_excluding): int64 [Q] on the gallery's device; query q is never given a row of the GROUP ``exclude[q]`` --
     the grouped search of the gallery without that group's rows.  A value outside int32 is no group and excludes nothing (-1 is a legal
-    group).  A wrong dtype, shape or device raises ValueError.  None: the call above, unchanged."""
+    group).  A wrong dtype, shape or device raises ValueError.  None: the call above, unchanged.
+    ``after`` (vtc_l2_search_grouped_after): a cursor per query as in l2_search, ``(after_d64 [Q] float64, after_ids [Q] int64)``; the
+    result is the next page of the grouped order -- the first ``depth`` groups whose NEAREST admissible row's key (fp64 distance,
+    id_base + row) lies strictly after the cursor.  ``n_groups`` is then required and the groups must be DENSE, in [0, n_groups): a
+    bitmap of groups decides which are already behind the cursor, and a row whose group is outside the range is never returned.  With
+    ``ban=None`` the call zeroes such a bitmap and runs the mark pass itself (``l2_group_mark_before``): the stateless call, two gallery
+    passes.  A given ``ban`` (int32 [Q, ceil(n_groups / 32)]) is taken as it is -- the windows of one gallery are all marked into one
+    buffer BEFORE any of them is scanned, and a caller may carry bits forward.  ``exclude`` composes with the cursor (the cursor may
+    stand on a row of the excluded group).  -inf is the plain grouped search, +inf / NaN an empty row.  ``after=None``: the call above,
+    argument for argument (``n_groups`` and ``ban`` are then not looked at)."""
     gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
     groups = _gpu(groups, torch.int32, "groups")
     ng, d = gallery.shape
@@ -670,6 +746,22 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     out_groups = torch.empty(nq, depth, dtype=torch.int32, device=gallery.device)
     dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
+    if after is not None:
+        after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search_grouped")
+        n_groups = _n_groups_arg(n_groups, "l2_search_grouped")
+        if exclude is not None:
+            exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
+        if ban is None:
+            ban = l2_group_mark_before(gallery, queries, groups, n_groups, (after_d, after_i), live=live, id_base=id_base)
+        else:
+            ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_search_grouped")
+        L.check(L.lib().vtc_l2_search_grouped_after(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
+                                                    live.data_ptr() if live is not None else None, groups.data_ptr(), n_groups, ban.data_ptr(),
+                                                    exclude.data_ptr() if exclude is not None else None, after_d.data_ptr(), after_i.data_ptr(),
+                                                    ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
+                                                    dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    _stream()), "vtc_l2_search_grouped_after")
+        return ids, out_groups, dists, bits
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
         L.check(L.lib().vtc_l2_search_excluding(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
@@ -693,14 +785,21 @@ def l2_search_grouped_workspace_bytes(n_gallery: int, n_queries: int, d: int, de
 
 @on_device
 def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
-                           live: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None):
+                           live: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, after=None,
+                           n_groups: Optional[int] = None, ban: Optional[torch.Tensor] = None):
     """One window's share of a grouped search over several: (ids [Q, depth] int64, groups [Q, depth] int32, dists64 [Q, depth] fp64,
     nonfinite_bits) -- what l2_search_merge_grouped takes.  A group's rows may lie in several windows.  fp32 or ``torch.float16`` rows.
-    ``exclude``: the excluded groups of l2_search_grouped, the same tensor for every window."""
+    ``exclude``: the excluded groups of l2_search_grouped, the same tensor for every window.
+    ``after`` / ``n_groups`` / ``ban``: the cursor of l2_search_grouped in GLOBAL ids, the same for every window, and the ONE bitmap that
+    ``l2_group_mark_before`` has filled over EVERY window before the first window is scanned (``ban`` is required here: a window cannot
+    know what lies before the cursor in the others)."""
+    if after is not None and ban is None:
+        raise ValueError("l2_search_grouped_part: a cursor needs the ban bitmap marked over every window (l2_group_mark_before)")
     ng, d = gallery.shape
     nq = queries.shape[0]
     ws = workspace(l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device)
-    ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live, exclude=exclude)
+    ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live, exclude=exclude,
+                                                 after=after, n_groups=n_groups, ban=ban)
     return ids, out_groups, search_dists64(ws, nq, depth), bits
 
 
