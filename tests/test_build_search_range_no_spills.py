@@ -2,8 +2,7 @@
 queries' radii and their hit words in registers inside a loop that is bound by HBM (one query) or by its fp64 arithmetic (more), as the
 scan of tests/test_build_search_no_spills.py does -- a spilled register there is a scratch access per row.  Every instantiation must
 compile without scratch and without spills: the count pass's four tile shapes x masked x {float, _Float16} = 16, the fill pass's two
-(float, _Float16) and the prefix kernel, 19 kernels in all.  None of their names may contain a substring by which the search's kernels
-are counted elsewhere."""
+(float, _Float16) and the prefix kernel, 19 kernels in all."""
 import os
 import shutil
 
@@ -14,7 +13,7 @@ from test_build_search_no_spills import _metadata
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
-TILES = ((1, 4), (2, 4), (4, 2), (8, 1))                  # search_plan's tile shapes: queries x gallery rows of a step
+TILES = ((1, 4), (2, 4), (4, 2), (8, 1))                  # tile_plan's shapes: queries x gallery rows of a step
 GALLERY = {"f": "float", "DF16_": "_Float16"}              # the mangled element types
 
 
@@ -34,5 +33,3 @@ def test_every_range_instantiation_compiles_without_scratch(tmp_path):
     assert len(meta) == 19, sorted(meta)
     for k, m in meta.items():
         assert m["spill"] == 0 and m["scratch"] == 0, (k, m)
-        for taken in ("search_scan_kernel", "search_grouped_scan_kernel", "merge_grouped_kernel", "half_scan"):
-            assert taken not in k, k

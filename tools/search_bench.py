@@ -61,6 +61,9 @@ With --hits (or --min-score) the tool measures the RANGE search (ops.l2_range_co
     python tools/search_bench.py --min-score 0.9 ...
 
 Per (n_gallery, n_queries, hits) one JSON line:
+  count_baseline_us        with --baseline-lib: the same ops.l2_range_count bound to ANOTHER build of the library (the commit before a
+                           change), in the same alternation; count_over_baseline is the ratio of the medians, and both builds must leave
+                           the same lims and hit words (asserted)
   count_us / scan_us       the count pass (one gallery pass + the prefix launch; lims and the hit words, nothing fetched) and
                            ops.l2_search at --depth over the same gallery (fp32 or half as --storage says), in alternation as above
   count_over_scan          ratio of the medians: the count pass streams the scan's bytes and does less per row
@@ -125,8 +128,8 @@ Per (n_gallery, n_queries, storage float32 / float16) one JSON line:
                             bitmap given, in the same alternation
   same_ids_as_host          on the first 10^4 rows: the page equals that slice of the grouped order formed outside the library in fp64
                             (asserted; outside the timing)
-  with --baseline-lib, for the entries that were there before (ops.l2_search, l2_search(live=) with every row live, l2_search_grouped, the
-  excluding scans ungrouped and grouped, the cursor scan at (-inf, -1)): NAME_us, NAME_baseline_us -- the same call bound to ANOTHER
+  with --baseline-lib, for the entries the other build has (ops.l2_search, l2_search(live=) with every row live, l2_search_grouped, the
+  excluding scans ungrouped and grouped, the cursor scan at (-inf, -1), and the page, mark and scan above when it has them): NAME_us, NAME_baseline_us -- the same call bound to ANOTHER
   build of the library (the parent commit) -- and NAME_over_baseline, all in the one alternation
 profiles/search_grouped_after.md holds a run's table."""
 import argparse
@@ -365,6 +368,13 @@ def half_main(args):
 def range_main(args):
     """--hits / --min-score: the range search's count pass against the scan, and the fill pass relative to the count pass."""
     lib = L.lib()
+    base = None
+    if args.baseline_lib:
+        import ctypes as C
+        base = C.CDLL(os.path.abspath(args.baseline_lib))
+        for name, (res, argtypes) in L.SIGNATURES.items():    # the entries the other build has, with this tree's signatures
+            if hasattr(base, name):
+                getattr(base, name).restype, getattr(base, name).argtypes = res, argtypes
     gen = torch.Generator(device="cuda").manual_seed(5)
     levels = [("min_score", float(x)) for x in args.min_score.split(",")] if args.min_score else [("hits", x) for x in args.hits.split(",")]
     lines = []
@@ -401,6 +411,16 @@ def range_main(args):
                 scan = lambda: ops.l2_search(gallery, queries, args.depth, ws=ws_s)                                # noqa: E731
                 count = lambda: ops.l2_range_count(gallery, queries, radius2, ws=ws_r)                             # noqa: E731
                 entries = [scan, count, fill]                  # fill follows a count over the same radius in the same workspace
+                if base:
+                    ws_b = ops.workspace(ops.l2_range_workspace_bytes(ng, nq, args.d), gallery.device)
+
+                    def count_baseline():                      # the same ops.l2_range_count, bound to the other build for the call
+                        mine, L._lib = L._lib, base
+                        try:
+                            return ops.l2_range_count(gallery, queries, radius2, ws=ws_b)
+                        finally:
+                            L._lib = mine
+                    entries.append(count_baseline)
                 for _ in range(args.warmup):
                     for fn in entries:
                         fn()
@@ -421,9 +441,15 @@ def range_main(args):
                         "count_over_scan": round(c["median"] / sc["median"], 3), "fill_over_count": round(f["median"] / c["median"], 3),
                         "passes": passes(nq), "gallery_tb_per_s": round(ng * args.d * gallery.element_size() / (1e6 * c["median"]), 3),
                         "same_hits_as_host": same}
+                if base:
+                    same_base = bool(torch.equal(count(), count_baseline()) and
+                                     torch.equal(ops.range_hit_words(ws_r, ng, nq), ops.range_hit_words(ws_b, ng, nq)))
+                    cb = stat(times[3])
+                    line.update({"count_baseline_us": cb, "count_over_baseline": round(c["median"] / cb["median"], 3), "same_as_baseline": same_base})
                 print(json.dumps(line), flush=True)
                 lines.append(line)
                 assert same, "the range search and the host's fp64 membership differ on the first 10^4 rows"
+                assert not base or same_base, "the two builds' count passes left different lims or hit words"
                 del ids, dists
             del ws_s, ws_r, approx
         del gallery
@@ -658,7 +684,7 @@ def grouped_after_main(args):
                 for name, fn in list(new.items()) + list(old.items()):
                     names.append(name)
                     entries.append(bound(fn, L.lib(), ops.workspace(need, gallery.device)))
-                    if base and name in old:
+                    if base and (name in old or hasattr(base, "vtc_l2_search_grouped_after")):
                         names.append(name + "_baseline")
                         entries.append(bound(fn, base, ops.workspace(need, gallery.device)))
                 for _ in range(args.warmup):
@@ -673,7 +699,10 @@ def grouped_after_main(args):
                 st = {n: stat(t) for n, t in zip(names, times)}
                 out = dict(zip(names, outs))
                 same_halves = all(bool(torch.equal(a, b)) for a, b in zip(out["page"][:3], out["scan"][:3]))
-                same_base = all(bool(torch.equal(a, b)) for n in old if base for a, b in zip(out[n][:2], out[n + "_baseline"][:2]))
+                in_base = [n for n in names if n + "_baseline" in names]
+                same_base = all(bool(torch.equal(a, b)) for n in in_base for a, b in zip(tuple(out[n])[:2] if n != "mark" else (out[n],),
+                                                                                       tuple(out[n + "_baseline"])[:2] if n != "mark" else
+                                                                                       (out[n + "_baseline"],)))
                 n_check = min(ng, 10 ** 4)
                 small, small_groups = gallery[:n_check], groups[:n_check].contiguous()
                 got = ops.l2_search_grouped(small, queries, small_groups, args.depth, n_groups=n_groups,
@@ -692,7 +721,7 @@ def grouped_after_main(args):
                 line["mark_over_grouped"] = round(st["mark"]["median"] / st["grouped"]["median"], 3)
                 line["scan_over_grouped"] = round(st["scan"]["median"] / st["grouped"]["median"], 3)
                 if base:
-                    for n in old:
+                    for n in in_base:
                         line[n + "_over_baseline"] = round(st[n]["median"] / st[n + "_baseline"]["median"], 3)
                 line.update({"page_is_mark_then_scan": same_halves, "same_as_baseline": same_base, "same_ids_as_host": same_host})
                 print(json.dumps(line), flush=True)
@@ -728,7 +757,7 @@ def main(argv=None):
     ap.add_argument("--exclude", action="store_true",
                     help="measure the excluding scan against the same search without an excluded key, fp32 and half, ungrouped and grouped (see above)")
     ap.add_argument("--baseline-lib", type=str, default=None,
-                    help="with --after-pages / --grouped-after: another build of libvtc_hip.so whose older entries are timed too")
+                    help="with --after-pages / --grouped-after / --hits: another build of libvtc_hip.so whose older entries are timed too")
     ap.add_argument("--grouped-after", type=int, default=None,
                     help="P: measure a stateless page of videos, the cursor on the (64 P)-th video, against the grouped scan (see above)")
     args = ap.parse_args(argv)

@@ -22,7 +22,7 @@
 //
 // No atomic decides a position and every word has one writer, so the result does not depend on the grid.  Not here: a grouped
 // (distinct-video) range search, sharding over several devices, more than 64 queries a call.
-#include "sweep_common.h"
+#include "search_walk.h"
 
 #include <algorithm>
 
@@ -32,8 +32,6 @@ using namespace vtcsweep;
 constexpr int RANGE_MAX_Q = 64, RANGE_MAX_D = 2048;
 constexpr int RANGE_MAX_BLOCKS = 1024;        // workgroups of a count pass, at most: the count slots per query in the workspace
 constexpr int CHUNK_WORDS = 16;               // hit words of a fill wave's unit (512 rows): one chunk base each
-
-__device__ __forceinline__ int uniform_of(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Row j is a hit of query q0 + u iff it is live, D is finite and D <= radius2 in fp64.  A query with a NaN / inf, or a slot past the
 // last query, takes radius -1: no distance is <= it.  A NaN or negative radius2 needs no case of its own -- no D >= 0 compares <= it.
@@ -45,31 +43,13 @@ __global__ __launch_bounds__(256) void range_count_kernel(const G *__restrict__ 
   static_assert(32 % NR == 0, "a step's rows lie in one word");
   extern __shared__ float4 smem4[];
   __shared__ int wave_cnt[4][NQ];
-  float *qt = reinterpret_cast<float *>(smem4);
+  const float *qt = reinterpret_cast<const float *>(smem4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.y * NQ;
-  // ---- the query tile -> LDS, as the scan does it: a query with a NaN / inf becomes a row of zeros, so a distance formed below is
-  // non-finite exactly when the GALLERY row holds a NaN / inf.
-  const int d4 = d >> 2;
-  unsigned bad_bits = 0;
-  for (int x = tid; x < NQ * d4; x += 256) {
-    const int u = x / d4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (q0 + u < nq) v = reinterpret_cast<const float4 *>(queries + (size_t)(q0 + u) * d)[x - u * d4];
-    if (!(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w))) bad_bits |= 1u << u;
-    smem4[x] = v;
-  }
+  const unsigned dead = load_query_tile<NQ>(queries, q0, nq, d, smem4, nonfinite);      // the scan's tile: a dead query is a row of zeros
   double r2[NQ];
 #pragma unroll
-  for (int u = 0; u < NQ; ++u) {
-    const int bad = __syncthreads_or((bad_bits >> u) & 1);
-    r2[u] = bad || q0 + u >= nq ? -1.0 : radius2[q0 + u];
-    if (bad) {
-      for (int x = tid; x < d4; x += 256) smem4[u * d4 + x] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (nonfinite && blockIdx.x == 0 && tid == 0) atomicOr(nonfinite, 2);
-    }
-  }
-  __syncthreads();
+  for (int u = 0; u < NQ; ++u) r2[u] = (dead >> u) & 1 ? -1.0 : radius2[q0 + u];
 
   // ---- the pass: a word a unit.  `avail`: the rows of word w that are live and inside the gallery (wave-uniform, a scalar register).
   int count[NQ];
@@ -238,19 +218,6 @@ __global__ __launch_bounds__(256) void range_fill_kernel(const G *__restrict__ g
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-// search.hip's tile shapes (search_plan): queries of a tile (a gallery pass each) x gallery rows of a step
-struct RangePlan {
-  int tile_q, tile_r, tiles;
-};
-RangePlan range_plan(int nq) {
-  RangePlan p;
-  if (nq == 1) p.tile_q = 1, p.tile_r = 4;
-  else if (nq == 2) p.tile_q = 2, p.tile_r = 4;
-  else if (nq <= 4) p.tile_q = 4, p.tile_r = 2;
-  else p.tile_q = 8, p.tile_r = 1;
-  p.tiles = cdiv(nq, p.tile_q);
-  return p;
-}
 bool range_args_ok(int ng, int nq, int d) { return ng >= 1 && nq >= 1 && nq <= RANGE_MAX_Q && d >= 64 && d <= RANGE_MAX_D && d % 64 == 0; }
 int range_words(int ng) { return (int)(((long long)ng + 31) / 32); }
 int range_chunks(int ng) { return cdiv(range_words(ng), CHUNK_WORDS); }
@@ -292,19 +259,16 @@ int launch_count(const G *gallery, const float *queries, const unsigned *live, c
                      range_words(ng), s.words, s.cnt, nonfinite);
   return blocks;
 }
-template <bool MASKED, typename G>
-int launch_count_tile(const RangePlan &p, const G *gallery, const float *queries, const unsigned *live, const double *radius2, int ng, int nq, int d,
-                      const RangeWs &s, int *nonfinite, hipStream_t stream) {
-  if (p.tile_q == 1) return launch_count<1, 4, MASKED>(gallery, queries, live, radius2, ng, nq, d, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 2) return launch_count<2, 4, MASKED>(gallery, queries, live, radius2, ng, nq, d, s, p.tiles, nonfinite, stream);
-  if (p.tile_q == 4) return launch_count<4, 2, MASKED>(gallery, queries, live, radius2, ng, nq, d, s, p.tiles, nonfinite, stream);
-  return launch_count<8, 1, MASKED>(gallery, queries, live, radius2, ng, nq, d, s, p.tiles, nonfinite, stream);
-}
+// the instantiation of the call: the scan's tile shapes (search_walk.h, tile_plan), MASKED by `live`
 template <typename G>
-int launch_count_any(const RangePlan &p, const G *gallery, const float *queries, const unsigned *live, const double *radius2, int ng, int nq, int d,
-                     const RangeWs &s, int *nonfinite, hipStream_t stream) {
-  return live ? launch_count_tile<true>(p, gallery, queries, live, radius2, ng, nq, d, s, nonfinite, stream)
-              : launch_count_tile<false>(p, gallery, queries, nullptr, radius2, ng, nq, d, s, nonfinite, stream);
+int launch_count_of(const G *gallery, const float *queries, const unsigned *live, const double *radius2, int ng, int nq, int d, const RangeWs &s,
+                    int *nonfinite, hipStream_t stream) {
+  const TilePlan p = tile_plan(nq);
+  return with_tile(p, [&](auto tq, auto tr) {
+    constexpr int NQ = decltype(tq)::value, NR = decltype(tr)::value;
+    return live ? launch_count<NQ, NR, true>(gallery, queries, live, radius2, ng, nq, d, s, p.tiles, nonfinite, stream)
+                : launch_count<NQ, NR, false>(gallery, queries, nullptr, radius2, ng, nq, d, s, p.tiles, nonfinite, stream);
+  });
 }
 }  // namespace
 
@@ -322,9 +286,8 @@ extern "C" int vtc_l2_range_count(const void *gallery, int gallery_is_half, cons
   VTC_CHECK(d >= 64 && d <= RANGE_MAX_D && d % 64 == 0, "l2_range_count: d=%d must be a multiple of 64 in [64, %d]", d, RANGE_MAX_D);
   const RangeWs s = range_ws(ws, ng, nq);
   VTC_CHECK(ws && ws_bytes >= s.total, "l2_range_count: workspace too small (%zu < %zu)", ws_bytes, s.total);
-  const RangePlan p = range_plan(nq);
-  const int blocks = gallery_is_half ? launch_count_any(p, (const _Float16 *)gallery, queries, live, radius2, ng, nq, d, s, nonfinite, stream)
-                                     : launch_count_any(p, (const float *)gallery, queries, live, radius2, ng, nq, d, s, nonfinite, stream);
+  const int blocks = gallery_is_half ? launch_count_of((const _Float16 *)gallery, queries, live, radius2, ng, nq, d, s, nonfinite, stream)
+                                     : launch_count_of((const float *)gallery, queries, live, radius2, ng, nq, d, s, nonfinite, stream);
   VTC_LAUNCH_CHECK2("l2_range_count", "count");
   hipLaunchKernelGGL(range_prefix_kernel, dim3(nq), dim3(256), 0, stream, s.words, s.cnt, blocks, range_words(ng), range_chunks(ng),
                      (long long *)lims, s.chunk_base);

@@ -379,6 +379,52 @@ def _exclude_arg(exclude, nq, device, what):
     return exclude.contiguous()
 
 
+def _after_arg(after, nq, device, what):
+    """The cursor of a search: (float64 [Q], int64 [Q]) on the gallery's device, anything else raises ValueError."""
+    ok = isinstance(after, (tuple, list)) and len(after) == 2 and all(isinstance(t, torch.Tensor) for t in after)
+    if ok:
+        ok = (after[0].dtype == torch.float64 and after[1].dtype == torch.int64 and
+              all(t.device == device and tuple(t.shape) == (nq,) for t in after))
+    if not ok:
+        got = ", ".join(f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                        for t in (after if isinstance(after, (tuple, list)) else (after,)))
+        raise ValueError(f"{what}: after must be (float64 [{nq}], int64 [{nq}]) on {device}, got ({got})")
+    return after[0].contiguous(), after[1].contiguous()
+
+
+def _live_arg(live, ng, device, what):
+    """The row mask of a search: packed int32 words [ceil(n / 32)] on the gallery's device, or None."""
+    if live is None:
+        return None
+    live = _gpu(live, torch.int32, "live")
+    if live.device != device or tuple(live.shape) != ((ng + 31) // 32,):
+        raise ValueError(f"{what}: live must be int32 [{(ng + 31) // 32}] on {device} (one bit per gallery row), got "
+                         f"{tuple(live.shape)} on {live.device}")
+    return live
+
+
+def _search_ws_arg(ws, need, device, what):
+    """The workspace of a search: a fresh one, or the caller's -- never a silent fresh one then: the caller reads the fp64 list out of the
+    tensor it passed."""
+    if ws is None:
+        return workspace(need, device)
+    if need and (ws.numel() < need or ws.device != device):
+        raise ValueError(f"{what}: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on {device}")
+    return ws
+
+
+def _search_outputs(nq, depth, device, return_dists, grouped):
+    """(ids, groups or None, dists or None, nonfinite bits) of a search, to be filled by the library."""
+    ids = torch.empty(nq, depth, dtype=torch.int64, device=device)
+    out_groups = torch.empty(nq, depth, dtype=torch.int32, device=device) if grouped else None
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=device) if return_dists else None
+    return ids, out_groups, dists, torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 @on_device
 def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, return_dists: bool = True,
               ws: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, after=None, exclude: Optional[torch.Tensor] = None):
@@ -407,46 +453,28 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     nq = queries.shape[0]
     if queries.shape[1] != d:
         raise ValueError(f"l2_search: gallery rows have {d} columns, queries {queries.shape[1]}")
-    if after is not None:
-        after_d, after_i = _gpu(after[0], torch.float64, "after_d64"), _gpu(after[1], torch.int64, "after_ids")
-        if after_d.device != gallery.device or after_i.device != gallery.device or tuple(after_d.shape) != (nq,) or tuple(after_i.shape) != (nq,):
-            raise ValueError(f"l2_search: after must be (float64 [{nq}], int64 [{nq}]) on {gallery.device}, got {tuple(after_d.shape)} on "
-                             f"{after_d.device} and {tuple(after_i.shape)} on {after_i.device}")
+    after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search") if after is not None else (None, None)
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search")
-    if live is not None:
-        live = _gpu(live, torch.int32, "live")
-        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
-            raise ValueError(f"l2_search: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
-                             f"{tuple(live.shape)} on {live.device}")
-    need = L.lib().vtc_l2_search_workspace_bytes(ng, nq, d, depth)
-    if ws is None:
-        ws = workspace(need, gallery.device)
-    elif need and (ws.numel() < need or ws.device != gallery.device):
-        # never a silent fresh workspace here: the caller reads the fp64 list out of the tensor it passed
-        raise ValueError(f"l2_search: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on {gallery.device}")
-    ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
-    dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
-    bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
-    tail = (int(id_base), ids.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    if exclude is not None:
-        L.check(L.lib().vtc_l2_search_excluding(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                                live.data_ptr() if live is not None else None, None, exclude.data_ptr(),
-                                                after_d.data_ptr() if after is not None else None,
-                                                after_i.data_ptr() if after is not None else None, ng, nq, d, depth, tail[0], tail[1], None,
-                                                *tail[2:]), "vtc_l2_search_excluding")
+    live = _live_arg(live, ng, gallery.device, "l2_search")
+    lib = L.lib()
+    ws = _search_ws_arg(ws, lib.vtc_l2_search_workspace_bytes(ng, nq, d, depth), gallery.device, "l2_search")
+    ids, _, dists, bits = _search_outputs(nq, depth, gallery.device, return_dists, grouped=False)
+    half = int(gallery.dtype == torch.float16)
+    shape = (ng, nq, d, depth, int(id_base), ids.data_ptr())
+    tail = (_ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if exclude is not None:                                    # the narrowest entry that takes the call
+        L.check(lib.vtc_l2_search_excluding(gallery.data_ptr(), half, queries.data_ptr(), _ptr(live), None, exclude.data_ptr(), _ptr(after_d),
+                                            _ptr(after_i), *shape, None, *tail), "vtc_l2_search_excluding")
     elif after is not None:
-        L.check(L.lib().vtc_l2_search_after(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                            live.data_ptr() if live is not None else None, after_d.data_ptr(), after_i.data_ptr(), ng, nq, d,
-                                            depth, *tail), "vtc_l2_search_after")
-    elif gallery.dtype == torch.float16:
-        L.check(L.lib().vtc_l2_search_half(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, None, ng, nq,
-                                           d, depth, tail[0], tail[1], None, *tail[2:]), "vtc_l2_search_half")
+        L.check(lib.vtc_l2_search_after(gallery.data_ptr(), half, queries.data_ptr(), _ptr(live), after_d.data_ptr(), after_i.data_ptr(), *shape,
+                                        *tail), "vtc_l2_search_after")
+    elif half:
+        L.check(lib.vtc_l2_search_half(gallery.data_ptr(), queries.data_ptr(), _ptr(live), None, *shape, None, *tail), "vtc_l2_search_half")
     elif live is None:
-        L.check(L.lib().vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), ng, nq, d, depth, *tail), "vtc_l2_search")
+        L.check(lib.vtc_l2_search(gallery.data_ptr(), queries.data_ptr(), *shape, *tail), "vtc_l2_search")
     else:
-        L.check(L.lib().vtc_l2_search_masked(gallery.data_ptr(), queries.data_ptr(), live.data_ptr(), ng, nq, d, depth, *tail),
-                "vtc_l2_search_masked")
+        L.check(lib.vtc_l2_search_masked(gallery.data_ptr(), queries.data_ptr(), live.data_ptr(), *shape, *tail), "vtc_l2_search_masked")
     return ids, dists, bits
 
 
@@ -633,19 +661,6 @@ def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return
     return ids, dists
 
 
-def _after_arg(after, nq, device, what):
-    """The cursor of a search: (float64 [Q], int64 [Q]) on the gallery's device, anything else raises ValueError."""
-    ok = isinstance(after, (tuple, list)) and len(after) == 2 and all(isinstance(t, torch.Tensor) for t in after)
-    if ok:
-        ok = (after[0].dtype == torch.float64 and after[1].dtype == torch.int64 and
-              all(t.device == device and tuple(t.shape) == (nq,) for t in after))
-    if not ok:
-        got = ", ".join(f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-                        for t in (after if isinstance(after, (tuple, list)) else (after,)))
-        raise ValueError(f"{what}: after must be (float64 [{nq}], int64 [{nq}]) on {device}, got ({got})")
-    return after[0].contiguous(), after[1].contiguous()
-
-
 def _n_groups_arg(n_groups, what):
     if isinstance(n_groups, bool) or not isinstance(n_groups, numbers.Integral) or not 1 <= n_groups < 2 ** 31:
         raise ValueError(f"{what}: a cursor needs n_groups, an int in [1, 2^31) with every group id in [0, n_groups), got {n_groups!r}")
@@ -683,17 +698,13 @@ def l2_group_mark_before(gallery: torch.Tensor, queries: torch.Tensor, groups: t
                          f"{tuple(groups.shape)} on {groups.device}")
     n_groups = _n_groups_arg(n_groups, "l2_group_mark_before")
     after_d, after_i = _after_arg(after, nq, gallery.device, "l2_group_mark_before")
-    if live is not None:
-        live = _gpu(live, torch.int32, "live")
-        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
-            raise ValueError(f"l2_group_mark_before: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
-                             f"{tuple(live.shape)} on {live.device}")
+    live = _live_arg(live, ng, gallery.device, "l2_group_mark_before")
     if ban is None:
         ban = torch.zeros(nq, (n_groups + 31) // 32, dtype=torch.int32, device=gallery.device)
     else:
         ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_group_mark_before")
     L.check(L.lib().vtc_l2_group_mark_before(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                             live.data_ptr() if live is not None else None, groups.data_ptr(), n_groups, after_d.data_ptr(),
+                                             _ptr(live), groups.data_ptr(), n_groups, after_d.data_ptr(),
                                              after_i.data_ptr(), ng, nq, d, int(id_base), ban.data_ptr(), _stream()),
             "vtc_l2_group_mark_before")
     return ban
@@ -731,50 +742,31 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     if groups.device != gallery.device or tuple(groups.shape) != (ng,):
         raise ValueError(f"l2_search_grouped: groups must be int32 [{ng}] on {gallery.device} (one id per gallery row), got "
                          f"{tuple(groups.shape)} on {groups.device}")
-    if live is not None:
-        live = _gpu(live, torch.int32, "live")
-        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
-            raise ValueError(f"l2_search_grouped: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
-                             f"{tuple(live.shape)} on {live.device}")
-    need = L.lib().vtc_l2_search_grouped_workspace_bytes(ng, nq, d, depth)
-    if ws is None:
-        ws = workspace(need, gallery.device)
-    elif need and (ws.numel() < need or ws.device != gallery.device):
-        raise ValueError(f"l2_search_grouped: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on "
-                         f"{gallery.device}")
-    ids = torch.empty(nq, depth, dtype=torch.int64, device=gallery.device)
-    out_groups = torch.empty(nq, depth, dtype=torch.int32, device=gallery.device)
-    dists = torch.empty(nq, depth, dtype=torch.float32, device=gallery.device) if return_dists else None
-    bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
-    if after is not None:
+    live = _live_arg(live, ng, gallery.device, "l2_search_grouped")
+    lib = L.lib()
+    ws = _search_ws_arg(ws, lib.vtc_l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device, "l2_search_grouped")
+    ids, out_groups, dists, bits = _search_outputs(nq, depth, gallery.device, return_dists, grouped=True)
+    half = int(gallery.dtype == torch.float16)
+    head = (queries.data_ptr(), _ptr(live), groups.data_ptr())
+    tail = (ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(), _ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(),
+            _stream())
+    if exclude is not None:
+        exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
+    if after is not None:                                      # the narrowest entry that takes the call
         after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search_grouped")
         n_groups = _n_groups_arg(n_groups, "l2_search_grouped")
-        if exclude is not None:
-            exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
         if ban is None:
             ban = l2_group_mark_before(gallery, queries, groups, n_groups, (after_d, after_i), live=live, id_base=id_base)
         else:
             ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_search_grouped")
-        L.check(L.lib().vtc_l2_search_grouped_after(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                                    live.data_ptr() if live is not None else None, groups.data_ptr(), n_groups, ban.data_ptr(),
-                                                    exclude.data_ptr() if exclude is not None else None, after_d.data_ptr(), after_i.data_ptr(),
-                                                    ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
-                                                    dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    _stream()), "vtc_l2_search_grouped_after")
-        return ids, out_groups, dists, bits
-    if exclude is not None:
-        exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
-        L.check(L.lib().vtc_l2_search_excluding(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                                live.data_ptr() if live is not None else None, groups.data_ptr(), exclude.data_ptr(), None, None,
-                                                ng, nq, d, depth, int(id_base), ids.data_ptr(), out_groups.data_ptr(),
-                                                dists.data_ptr() if dists is not None else None, bits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _stream()), "vtc_l2_search_excluding")
-        return ids, out_groups, dists, bits
-    fn, name = ((L.lib().vtc_l2_search_half, "vtc_l2_search_half") if gallery.dtype == torch.float16 else
-                (L.lib().vtc_l2_search_grouped, "vtc_l2_search_grouped"))          # the two take the same arguments
-    L.check(fn(gallery.data_ptr(), queries.data_ptr(), live.data_ptr() if live is not None else None, groups.data_ptr(), ng, nq, d, depth,
-               int(id_base), ids.data_ptr(), out_groups.data_ptr(), dists.data_ptr() if dists is not None else None, bits.data_ptr(),
-               ws.data_ptr(), ws.numel(), _stream()), name)
+        L.check(lib.vtc_l2_search_grouped_after(gallery.data_ptr(), half, *head, n_groups, ban.data_ptr(), _ptr(exclude), after_d.data_ptr(),
+                                                after_i.data_ptr(), *tail), "vtc_l2_search_grouped_after")
+    elif exclude is not None:
+        L.check(lib.vtc_l2_search_excluding(gallery.data_ptr(), half, *head, exclude.data_ptr(), None, None, *tail), "vtc_l2_search_excluding")
+    elif half:
+        L.check(lib.vtc_l2_search_half(gallery.data_ptr(), *head, *tail), "vtc_l2_search_half")
+    else:
+        L.check(lib.vtc_l2_search_grouped(gallery.data_ptr(), *head, *tail), "vtc_l2_search_grouped")
     return ids, out_groups, dists, bits
 
 
