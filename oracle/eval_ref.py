@@ -82,6 +82,45 @@ def near_ties(features_a: np.ndarray, features_b: np.ndarray, k_vals: Sequence[i
     return n
 
 
+def boundary_gap(features_a: np.ndarray, features_b: np.ndarray, k_vals: Sequence[int] = (1, 5, 10)) -> float:
+    """The smallest fp64 distance gap an R@K outcome of ``recall_at_k(features_a, features_b)`` rests on -- the quantity
+    ``near_ties`` thresholds, taken for every query and every k: a hit (target at 0-based rank r < k) turns into a miss once the row
+    at rank k comes closer than the target, a miss (r >= k) into a hit once the target comes closer than the row at rank k - 1; the
+    gap is the distance between the target and that row.  For a target right at the boundary (r = k - 1 or r = k) this is near_ties'
+    neighbour gap; for the others it is larger, and it is included because several rows crossing a target together also change the
+    outcome.  ``inf`` when no k is below the gallery size.  If every distance moves by less than half of it, no R@K changes."""
+    a = np.ascontiguousarray(features_a, dtype=np.float64)
+    b = np.ascontiguousarray(features_b, dtype=np.float64)
+    d = (b * b).sum(1)[:, None] + (a * a).sum(1)[None, :] - 2.0 * (b @ a.T)
+    ds = np.sort(d, axis=1)
+    gap = np.inf
+    for i in range(b.shape[0]):
+        r = int(np.argsort(d[i], kind="stable").tolist().index(i))
+        for k in k_vals:
+            if r < k and k < a.shape[0]:
+                gap = min(gap, float(ds[i, k] - d[i, i]))
+            elif r >= k:
+                gap = min(gap, float(d[i, i] - ds[i, k - 1]))
+    return gap
+
+
+def table_gap(tensor_v, tensor_t, k_vals: Sequence[int] = (1, 5, 10)) -> float:
+    """boundary_gap over both directions of compute_recall_table (video -> text and text -> video)."""
+    v = np.asarray(tensor_v, dtype=np.float64)
+    t = np.asarray(tensor_t, dtype=np.float64)
+    t = t[:, 0] if t.ndim == 3 else t
+    return min(boundary_gap(v, t, k_vals), boundary_gap(t, v, k_vals))
+
+
+def rank_safety_bound(eps: float, dim: int) -> float:
+    """2 delta: the boundary gap above which two embedding sets that agree within ``eps`` per element give the same R@K table.
+    An embedding moves by at most eps sqrt(D) in L2, so a difference v - t by s = 2 eps sqrt(D); with |v - t| <= 2 (unit captions,
+    video embeddings of norm <= 1) a squared distance moves by at most delta = 4 s + s^2, and the order of two distances is kept
+    when they are 2 delta apart."""
+    s = 2.0 * eps * float(np.sqrt(dim))
+    return 2.0 * (4.0 * s + s * s)
+
+
 def eval_result_dict(res_vis: np.ndarray, res_text: np.ndarray, dtype=np.float32) -> dict:
     """evaluation/eval.py:121-138: both directions, k in {1,5,10}, JSON keys.  ``dtype=np.float64``: ground-truth ranks."""
     t_from_i = recall_at_k(res_vis, res_text, [1, 5, 10], dtype)

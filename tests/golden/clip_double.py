@@ -1,6 +1,6 @@
 """Tests-only stand-in for the un-vendored ``clip`` package (openai/CLIP).
 
-Used ONLY by tests/golden/make_golden.py, in this container, so that the
+Used ONLY by tests/golden/make_golden.py and make_eval_golden.py, in this container, so that the
 reference's own ``model/model.py`` / ``model/timesformer_clip*.py`` import and
 run UNMODIFIED and emit golden vectors.  It is never shipped,
 never imported by the product, and never runs on the GPU box.

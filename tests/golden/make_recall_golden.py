@@ -8,8 +8,8 @@ Run in the build container only (needs the read-only reference checkout):
 ``RecallAtK`` cannot run as shipped here: ``faiss-gpu`` (environment.yml:12) is not installed and needs a GPU, and
 ``collections.Iterable`` (metric.py:106) is gone in Python >= 3.10.  Two stand-ins, for this script only:
   * ``collections.Iterable = collections.abc.Iterable``;
-  * a numpy ``faiss`` module with the four names metric.py touches (GpuIndexFlatConfig, StandardGpuResources,
-    GpuIndexFlatL2.add/.search).  Its search is faiss's published exact-L2 definition (squared L2, fp32, k smallest,
+  * a numpy ``faiss`` module (tests/golden/faiss_double.py) with the four names metric.py touches (GpuIndexFlatConfig,
+    StandardGpuResources, GpuIndexFlatL2.add/.search).  Its search is faiss's published exact-L2 definition (squared L2, fp32, k smallest,
     ascending); ties -- unspecified in faiss -- by lowest index.
 What this pins is everything the reference's OWN code decides: search depth ``max(k)+1`` (:145), the hit rule
 ``target in rp[:k]`` (:153-155), the denominator ``len(features_a)`` (:138,158), ``result()``'s key names and which
@@ -18,12 +18,9 @@ NOT evidence about faiss; the fixture stores inputs and the reference's outputs.
 """
 from __future__ import annotations
 
-import collections
-import collections.abc
 import json
 import os
 import sys
-import types
 
 import numpy as np
 import torch
@@ -32,42 +29,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
 
-collections.Iterable = collections.abc.Iterable          # metric.py:106
+sys.path.insert(0, HERE)
+import faiss_double  # noqa: E402  (the numpy ``faiss`` + ``collections.Iterable``, shared with make_eval_golden.py)
 
-faiss = types.ModuleType("faiss")
-
-
-class GpuIndexFlatConfig:
-    useFloat16 = False
-    device = 0
-
-
-class StandardGpuResources:
-    pass
-
-
-class GpuIndexFlatL2:
-    def __init__(self, res, dim, cfg):
-        assert cfg.useFloat16 is False                    # metric.py:113
-        self.dim, self.x = dim, np.zeros((0, dim), dtype=np.float32)
-
-    def add(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        assert x.shape[1] == self.dim
-        self.x = np.concatenate([self.x, x])
-
-    def search(self, q, k):
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        d = (q * q).sum(1)[:, None] + (self.x * self.x).sum(1)[None, :] - np.float32(2) * (q @ self.x.T)
-        order = np.argsort(d, axis=1, kind="stable")[:, :k]
-        if order.shape[1] < k:                            # faiss pads missing neighbours with -1
-            pad = -np.ones((q.shape[0], k - order.shape[1]), dtype=order.dtype)
-            return np.take_along_axis(d, order, 1), np.concatenate([order, pad], 1)
-        return np.take_along_axis(d, order, 1), order
-
-
-faiss.GpuIndexFlatConfig, faiss.StandardGpuResources, faiss.GpuIndexFlatL2 = GpuIndexFlatConfig, StandardGpuResources, GpuIndexFlatL2
-sys.modules["faiss"] = faiss
+faiss_double.install()
 # the reference's file, loaded as-is by path (importing the ``model`` package would pull in model/model.py -> ``clip``)
 import importlib.util  # noqa: E402
 

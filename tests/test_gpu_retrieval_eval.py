@@ -26,12 +26,13 @@ def test_ragged_chunked_eval_matches_per_video_loop(branch):
     m.load_state_dict(sd, strict=True)
     m = m.eval().cuda()
     m.compute_dtype = torch.float32
-    rng = np.random.default_rng(0)
     videos = []
+    # seeds 120.. / 220.. / 320..: chosen on the CPU, with the oracle alone, so that the oracle embeddings' boundary gap meets 2 delta
+    # on all three branches (100.. / 200.. / 300.. gave 2.8e-4 on the text branch)
     for i, nfr in enumerate([200, 16 * 8, 16 * 13, 50, 16 * 17 + 3, 129]):       # 1..3 chunks, ragged tails
-        fr = A.synth_pixels((nfr, 3, a.image_resolution, a.image_resolution), 100 + i)
-        cap = A.synth_tokens(1, a, 200 + i)[0]
-        com = A.synth_tokens(5, a, 300 + i, empty_frac=0.3) if i % 2 == 0 else None   # real comments or dummies
+        fr = A.synth_pixels((nfr, 3, a.image_resolution, a.image_resolution), 120 + i)
+        cap = A.synth_tokens(1, a, 220 + i)[0]
+        com = A.synth_tokens(5, a, 320 + i, empty_frac=0.3) if i % 2 == 0 else None   # real comments or dummies
         videos.append((fr, cap, com))
     table, v_emb, c_emb = RE.retrieval_evaluation(m, videos, "full-test", "cuda", return_embeddings=True)
     # oracle: the reference's loop, one video at a time
@@ -47,16 +48,17 @@ def test_ragged_chunked_eval_matches_per_video_loop(branch):
     assert (v_emb.cpu() - ref_v).abs().max() < 1e-5 and (c_emb.cpu() - ref_c).abs().max() < 1e-5
     assert not np.allclose(np.linalg.norm(v_emb.cpu().numpy(), axis=1), 1.0, atol=1e-4)      # mean is NOT renormalised
     # ranks: the table is computed from the GPU's embeddings, so hold it to the fp64 ranks of THOSE embeddings without a
-    # near-tie guard (the EXACT sweep's contract), and report how the oracle's own embeddings rank (end-to-end view)
+    # near-tie guard (the EXACT sweep's contract), and to the oracle's own embeddings' ranks (end-to-end view): embeddings within
+    # 1e-5 (asserted above) rank alike when the oracle embeddings' boundary gap is at least 2 delta (E.rank_safety_bound)
     tvr, vtr = E.compute_recall_table(v_emb.cpu(), c_emb.cpu(), np.float64)
     np.testing.assert_array_equal(table["videos full-test split Video to Text"], tvr)
     np.testing.assert_array_equal(table["videos full-test split Text to Video"], vtr)
     tvr_o, vtr_o = E.compute_recall_table(ref_v, ref_c, np.float64)
-    nt = E.near_ties(ref_v.numpy(), ref_c.numpy()) + E.near_ties(ref_c.numpy(), ref_v.numpy())
-    print(f"[parity] chunked eval ({branch}): near ties {nt}; oracle-embedding table {tvr_o.tolist()} / {vtr_o.tolist()}")
-    if nt == 0:       # 6 videos: a 1e-6 gap between neighbours would be the only way the two embedding sets rank differently
-        np.testing.assert_array_equal(table["videos full-test split Video to Text"], tvr_o)
-        np.testing.assert_array_equal(table["videos full-test split Text to Video"], vtr_o)
+    gap, bound = E.table_gap(ref_v.numpy(), ref_c.numpy()), E.rank_safety_bound(1e-5, a.embed_dim)
+    print(f"[parity] chunked eval ({branch}): boundary gap {gap:.3e} (2 delta {bound:.3e}); oracle-embedding table {tvr_o.tolist()} / {vtr_o.tolist()}")
+    assert gap >= bound
+    np.testing.assert_array_equal(table["videos full-test split Video to Text"], tvr_o)
+    np.testing.assert_array_equal(table["videos full-test split Text to Video"], vtr_o)
 
 
 def test_ragged_chunked_eval_vit_b32_bf16_vs_per_video_oracle_loop():
@@ -100,11 +102,12 @@ def test_ragged_chunked_eval_vit_b32_bf16_vs_per_video_oracle_loop():
 
 
 # ---- the drop-in entry point: the reference's module path, signature and DataFrame ----------------------------------
-def _tiny_standin(monkeypatch, n_videos=7):
+def _tiny_standin(monkeypatch, n_videos=7, seed=123):
+    """``seed``: chosen on the CPU, with the oracle alone, so that _check_frame's gap condition holds for the test's model and flags."""
     from vtc_amd.host import datasets as D
     a = A.TINY
     monkeypatch.setattr(D, "VIDEO_STANDIN", dict(D.VIDEO_STANDIN, n_videos=n_videos, min_frames=20, max_frames=16 * 8 * 3,
-                                                 resolution=a.image_resolution, context=a.context_length))
+                                                 resolution=a.image_resolution, context=a.context_length, seed=seed))
     return a
 
 
@@ -120,7 +123,9 @@ def _build(kind, cls_name, a, seed, **ctor):
 
 
 def _check_frame(df, dataset_cls, split, name, forward, needs_comments, branch, **loop_kw):
-    """df (the drop-in's DataFrame) against the oracle's per-video loop over the same stand-in items + the oracle's fp64 ranks."""
+    """df (the drop-in's DataFrame) against the oracle's per-video loop over the same stand-in items + the oracle's fp64 ranks.  The
+    two tables are equal whenever the embeddings agree within 1e-5 (the fp32 bar) and the oracle embeddings' boundary gap is at least
+    2 delta (E.rank_safety_bound); the gap is a property of the chosen data and is asserted, then the tables always compare."""
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -130,10 +135,10 @@ def _check_frame(df, dataset_cls, split, name, forward, needs_comments, branch, 
     want = E.compute_recall_frame(ref_v, ref_c, split, name, np.float64)
     assert list(df.columns) == list(want.columns) == [f"{name} {split} split Video to Text", f"{name} {split} split Text to Video"]
     assert list(df.index) == ["R@1", "R@5", "R@10"]
-    nt = E.near_ties(ref_v.numpy(), ref_c[:, 0].numpy()) + E.near_ties(ref_c[:, 0].numpy(), ref_v.numpy())
-    print(f"[parity] retrieval_evaluation({name}, {split}): near ties {nt}; table\n{df}")
-    if nt == 0:
-        np.testing.assert_array_equal(df.to_numpy(), want.to_numpy())
+    gap, bound = E.table_gap(ref_v.numpy(), ref_c.numpy()), E.rank_safety_bound(1e-5, ref_v.shape[1])
+    print(f"[parity] retrieval_evaluation({name}, {split}): boundary gap {gap:.3e} (2 delta {bound:.3e}); table\n{df}")
+    assert gap >= bound
+    np.testing.assert_array_equal(df.to_numpy(), want.to_numpy())
     vtt, ttv = df.loc["R@10"].tolist()                  # what trainer/trainer.py:162 reads
     assert 0.0 <= vtt <= 100.0 and 0.0 <= ttv <= 100.0
     return ref_v, ref_c
@@ -180,7 +185,7 @@ def test_drop_in_entry_image_models_and_first_frame_only(monkeypatch, cls_name, 
     (model/model.py:333-338, 465-470); ``first_frame_only`` hands them the first frame as a 4-D batch of one (:165-173)."""
     from evaluation.retrieval_evaluation import image_models, retrieval_evaluation, video_models
     from vtc_amd.host import datasets as D
-    a = _tiny_standin(monkeypatch, 6)
+    a = _tiny_standin(monkeypatch, 6, seed={"clip": 124, "clip_finaltf": 123}[kind])      # 123 leaves PretrainedCLIP a gap of 1.8e-4
     cam = kind.endswith("finaltf")
     m, sd = _build(kind, cls_name, a, 73, **(dict(branch_to_adapt_val="text", n_heads=2) if cam else {}))
     assert isinstance(m, image_models) and isinstance(m, video_models)

@@ -201,9 +201,12 @@ def test_wrappers_vs_golden(fname, dtype):
     scale = float(np.exp(np.log(1 / 0.07)))
     report(f"{fname} cos-sim {dtype}", np.abs(sim - g["sim"]).max() / scale, tol)
     np.testing.assert_allclose(np.linalg.norm(fv, axis=-1), 1.0, atol=1e-5)
-    # R@1 ranks of the batch similarity identical to the reference's
-    if np.sort(g["sim"], axis=1)[:, -1].min() - np.sort(g["sim"], axis=1)[:, -2].max() > 0.1:
-        assert np.array_equal(sim.argmax(1), g["sim"].argmax(1))
+    # R@1 ranks of the batch similarity identical to the reference's: every element of sim is within tol * scale of the reference's
+    # (asserted above), so a row's best match stays the best when the reference's row margin is at least twice that.  The margin
+    # is a property of the fixture (every wrap_* fixture has it in both precisions) and is asserted; then the ranks always compare.
+    top = np.sort(g["sim"], axis=1)
+    assert (top[:, -1] - top[:, -2]).min() >= 2 * tol * scale, (fname, (top[:, -1] - top[:, -2]).min(), 2 * tol * scale)
+    assert np.array_equal(sim.argmax(1), g["sim"].argmax(1))
 
 
 def test_cam_at_init_and_branch_isolation():
