@@ -141,7 +141,7 @@ class VideoIndex:
     rules: any number of queries in slices of 64, only enqueued.  ``search_videos(after=)`` and ``search_videos_deep`` page the grouped
     order (vtc_l2_group_mark_before + vtc_l2_search_grouped_after, two gallery passes a page)."""
     #: queries per call from which search() goes through ops.l2_topk(precision=SWEEP_EXACT) instead of ops.l2_search (which takes up to
-    #: 64).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
+    #: 64 per call; an instance that sets the constant above that gets the scan in slices, as every masked search does).  Measured, profiles/search.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 gallery rows, scan vs
     #: vtc_l2_topk): the scan's time grows with the number of queries (one gallery pass per started tile of 8), vtc_l2_topk's does not.
     #:    8 queries   244.4 vs 275.6 (1.13 x)   1 468.9 vs 2 229.0 (1.52 x)   scan faster
     #:    9           358.8 vs 386.6 (1.08 x)   2 818.6 vs 3 768.7 (1.34 x)   scan faster
@@ -417,65 +417,92 @@ class VideoIndex:
         scan, by the masked route's rules: slices of 64 queries, only enqueued, no host sync, a non-finite query a row of -1 / -inf.  It
         composes with ``subset``, removed rows, half storage and ``after`` (the cursor may be the excluded row).  A query with fewer
         than k admissible rows ends in -1 / -inf.  ``exclude=None`` changes nothing above."""
-        k = int(k)
-        if not 1 <= k <= min(self.MAX_K, self._n_live):
-            raise ValueError(f"VideoIndex.search: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
-        if after is not None or exclude is not None:
-            return self._search_masked(queries, k, subset, after, exclude)
-        if subset is not None or self._live is not None or self.storage != torch.float32:
-            return self._search_masked(queries, k, subset)
-        scan = 0 < len(queries) < min(self.ROUTE_TOPK_MIN_QUERIES, ops.SEARCH_MAX_QUERIES + 1)
-        q = self._prepared(queries, "queries", check=not scan)
+        k = self._checked_k(k, "search")
+        plain = after is None and exclude is None and subset is None and self._live is None and self.storage == torch.float32
+        if not (plain and len(queries) >= self.ROUTE_TOPK_MIN_QUERIES):
+            return self._scan(queries, k, subset, after, exclude, "search")      # nothing is read back: no sync
+        q = self._prepared(queries, "queries")
         if q.shape[0] == 0:
             raise ValueError("VideoIndex.search: no queries")
-        g = self.rows
-        if scan:
-            ws = self._workspace(ops.l2_search_workspace_bytes(self._n, q.shape[0], self.width, k))
-            ids, dists, _ = ops.l2_search(g, q, k, ws=ws)         # the word is not read: no sync (a bad query's row is -1 / +inf)
-        else:
-            ws = self._workspace(L.lib().vtc_l2_topk_workspace_bytes(self._n, q.shape[0], self.width, L.SWEEP_EXACT, 0))
-            ids, dists = ops.l2_topk(g, q, k, precision=L.SWEEP_EXACT, ws=ws)
+        ws = self._workspace(L.lib().vtc_l2_topk_workspace_bytes(self._n, q.shape[0], self.width, L.SWEEP_EXACT, 0))
+        ids, dists = ops.l2_topk(self.rows, q, k, precision=L.SWEEP_EXACT, ws=ws)
         return ids, 1.0 - dists / 2.0
 
-    def _per_query_ids(self, ids, n_queries, name, what):
+    def _checked_k(self, k, what, deep=False):
+        """int(k), which must be in [1, min(64, len(index))] -- ``deep``, the paged searches: in [1, len(index)] -- or ValueError."""
+        k = int(k)
+        if not 1 <= k <= (self._n_live if deep else min(self.MAX_K, self._n_live)):
+            most = f"len(index) = {self._n_live}"
+            raise ValueError(f"VideoIndex.{what}: k={k} must be in [1, {most if deep else f'min({self.MAX_K}, {most})'}]")
+        return k
+
+    def _check_subset(self, subset, what):
+        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
+            raise ValueError(f"VideoIndex.{what}: the subset belongs to another index (build it with this index's subset())")
+
+    def _per_query_ids(self, ids, n_queries, name, what, row_ids=False):
         """An int64 tensor with one entry per query (``n_queries`` None: any number >= 1) -> on the index's device, contiguous; anything
-        else raises ValueError.  The VALUES are not read: no host sync."""
+        else raises ValueError.  ``row_ids`` (the cursor of ``search``): whatever ``torch.as_tensor`` makes such a tensor of.  The VALUES
+        are not read: no host sync."""
+        if row_ids:
+            ids = torch.as_tensor(ids)
         ok = isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and ids.dim() == 1
         if not ok or (ids.shape[0] < 1 if n_queries is None else ids.shape[0] != n_queries):
             got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
-            raise ValueError(f"VideoIndex.{what}: {name} must be an int64 [{n_queries or 'Q >= 1'}] tensor, one per query, got {got}")
+            raise ValueError(f"VideoIndex.{what}: {name} must be an int64 [{n_queries or 'Q >= 1'}] tensor{' of row ids' * row_ids}, one per "
+                             f"query, got {got}")
         return ids.to(self.device).contiguous()
 
-    def _search_masked(self, queries, k, subset, after=None, exclude=None, stored=False):
-        """``stored``: the queries are stored rows [Q, width] widened to fp32 (``similar``) and are searched as they are."""
-        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
-            raise ValueError("VideoIndex.search: the subset belongs to another index (build it with this index's subset())")
+    @staticmethod
+    def _sliced(queries, *per_query):
+        """[(queries, *per_query) of one library call]: slices of at most ``ops.SEARCH_MAX_QUERIES`` queries, each with the entries of
+        the same queries of every per-query sequence (None stays None).  THE place where a call's arguments are cut; up to 64 queries
+        are the arguments themselves."""
+        n, step, whole = queries.shape[0], ops.SEARCH_MAX_QUERIES, (queries, *per_query)
+        if n <= step:
+            return [whole]
+        return [tuple(None if t is None else t[lo:lo + step] for t in whole) for lo in range(0, n, step)]
+
+    def _scan(self, queries, k, subset, after, exclude, what, grouped=False, stored=False):
+        """The scan behind every top-k search of rows (``ops.l2_search``) and, ``grouped``, of distinct videos
+        (``ops.l2_search_grouped``): any number of queries in slices of 64, only enqueued.  ``after`` / ``exclude``: one row id (grouped:
+        one row id / one video id) per query or None.  ``stored``: the queries are stored rows [Q, width] widened to fp32 (``similar``)
+        and are searched as they are.  Returns (ids, scores), grouped (videos, rows, scores).  ``what`` names the caller in the messages."""
+        self._check_subset(subset, what)
         q = queries if stored else self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
-            raise ValueError("VideoIndex.search: no queries")
+            raise ValueError(f"VideoIndex.{what}: no queries")
         if exclude is not None:
-            exclude = self._per_query_ids(exclude, q.shape[0], "exclude", "search")
-        words = self._live_words() if subset is None else subset.words()      # None on a half index with every row live: no mask
-        g, step = self.rows, ops.SEARCH_MAX_QUERIES
-        ws = self._workspace(ops.l2_search_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
+            exclude = self._per_query_ids(exclude, q.shape[0], "exclude_videos" if grouped else "exclude", what)
+        words = self._live_words() if subset is None else subset.words()      # None with every row live: no mask
+        ws_bytes = ops.l2_search_grouped_workspace_bytes if grouped else ops.l2_search_workspace_bytes
+        ws = self._workspace(ws_bytes(self._n, min(q.shape[0], ops.SEARCH_MAX_QUERIES), self.width, k))
         if after is not None:
-            after = torch.as_tensor(after)
-            if after.dtype != torch.int64 or tuple(after.shape) != (q.shape[0],):
-                raise ValueError(f"VideoIndex.search: after must be an int64 [{q.shape[0]}] tensor of row ids, one per query, got "
-                                 f"{after.dtype} {tuple(after.shape)}")
-            after = after.to(self.device).contiguous()
-            out = []
-            for lo in range(0, q.shape[0], step):
-                rows = after[lo:lo + step]
-                cursor = (ops.l2_pair_dists64(g, q[lo:lo + step], rows), rows)      # +inf for an id that is no row: nothing comes after it
-                out.append(ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, after=cursor,
-                                         exclude=None if exclude is None else exclude[lo:lo + step])[:2])
-        elif exclude is not None:
-            out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words, exclude=exclude[lo:lo + step])[:2] for lo in range(0, q.shape[0], step)]
-        else:
-            out = [ops.l2_search(g, q[lo:lo + step], k, ws=ws, live=words)[:2] for lo in range(0, q.shape[0], step)]
-        ids, dists = out[0] if len(out) == 1 else (torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out]))
-        return ids, 1.0 - dists / 2.0
+            after = self._per_query_ids(after, q.shape[0], "after", what, row_ids=not grouped)
+        uniq = n_videos = None
+        if grouped and after is None:
+            groups = self._video_ids[:self._n]
+        elif grouped:                                              # a page: the videos by their dense slots, which index its bitmap
+            uniq, groups, n_videos = self._dense_videos()
+            if exclude is not None:                                # the excluded VIDEO as its slot; one the index does not hold is no group
+                at = torch.searchsorted(uniq, exclude).clamp(max=n_videos - 1)
+                exclude = torch.where(uniq[at] == exclude, at, torch.full_like(at, 1 << 40))
+        g, out = self.rows, []
+        # What the call does not have stays None, every argument's default: each slice reaches the library entry of exactly the
+        # arguments that are set (ops: the narrowest entry that takes the call).
+        for qs, cursor, ex in self._sliced(q, after, exclude):
+            if cursor is not None:
+                cursor = (ops.l2_pair_dists64(g, qs, cursor), cursor)          # +inf for an id that is no row: nothing comes after it
+            if grouped:
+                out.append(ops.l2_search_grouped(g, qs, groups, k, ws=ws, live=words, exclude=ex, after=cursor, n_groups=n_videos)[:3])
+            else:
+                out.append(ops.l2_search(g, qs, k, ws=ws, live=words, after=cursor, exclude=ex)[:2])
+        *found, dists = out[0] if len(out) == 1 else [torch.cat(column) for column in zip(*out)]
+        if grouped:                                                # (rows, their videos -- of a page: their slots)
+            rows, videos = found
+            videos = videos.to(torch.int64) if uniq is None else uniq[videos.clamp(min=0).to(torch.int64)]
+            found = torch.where(rows >= 0, videos, rows), rows
+        return (*found, 1.0 - dists / 2.0)
 
     def search_deep(self, queries, k, subset=None, exclude=None):
         """``search`` without the limit of 64: (ids [Q, k] int64, scores [Q, k] fp32) for any 1 <= k <= len(index), the exact k nearest
@@ -494,17 +521,18 @@ class VideoIndex:
         dominates the call.  For deep rankings of many queries pass fewer than that per call.
         ``exclude``: ``search``'s, passed on every page -- the ranking without that row, what a hard-negative miner asks for; every
         page, the first included, is then the scan."""
-        k = int(k)
-        if not 1 <= k <= self._n_live:
-            raise ValueError(f"VideoIndex.search_deep: k={k} must be in [1, len(index) = {self._n_live}]")
-        pages = [self.search(queries, min(k, self.MAX_K), subset=subset, exclude=exclude)]
+        return self._paged(lambda n, after: self.search(queries, n, subset=subset, after=after, exclude=exclude), 0, k, "search_deep")
+
+    def _paged(self, page, cursor_column, k, what):
+        """The pager of ``search_deep`` and ``search_videos_deep``: ``page(n, after)`` is one page of n <= 64 results (after=None: the
+        first), and the last entry of every query in output ``cursor_column`` -- the row ids -- is the cursor of the next."""
+        k = self._checked_k(k, what, deep=True)
+        pages = [page(min(k, self.MAX_K), None)]
         got = pages[0][0].shape[1]
         while got < k:
-            pages.append(self.search(queries, min(k - got, self.MAX_K), subset=subset, after=pages[-1][0][:, -1], exclude=exclude))
+            pages.append(page(min(k - got, self.MAX_K), pages[-1][cursor_column][:, -1]))
             got += pages[-1][0].shape[1]
-        if len(pages) == 1:
-            return pages[0]
-        return torch.cat([p[0] for p in pages], dim=1), torch.cat([p[1] for p in pages], dim=1)
+        return pages[0] if len(pages) == 1 else tuple(torch.cat(column, dim=1) for column in zip(*pages))
 
     def _dense_videos(self):
         """(uniq int64 [V] sorted, slot int32 [ntotal], V): the videos of the index numbered densely, what the paged grouped search
@@ -539,6 +567,11 @@ class VideoIndex:
         sync then, none at the paged calls after it.  ``after=None`` changes nothing above."""
         return self._search_videos(queries, k, subset, exclude_videos, "search_videos", after=after)
 
+    def _search_videos(self, queries, k, subset, exclude, what, stored=False, after=None):
+        if not self.grouped:
+            raise ValueError(f"VideoIndex.{what}: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
+        return self._scan(queries, self._checked_k(k, what), subset, after, exclude, what, grouped=True, stored=stored)
+
     def search_videos_deep(self, queries, k, subset=None, exclude_videos=None):
         """``search_videos`` without the limit of 64: (video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) for any
         1 <= k <= len(index) (len counting live ROWS, as the grouped bounds do), the exact k nearest distinct videos of every query.
@@ -550,56 +583,8 @@ class VideoIndex:
         hundred videos of a few queries (profiles/search_grouped_after.md).  For thousands of results, or whenever a score threshold
         is known, ``range_search`` is the tool: one pass per tile of queries however many rows come back; its hits are rows, which the
         caller reduces to videos."""
-        k = int(k)
-        if not 1 <= k <= self._n_live:
-            raise ValueError(f"VideoIndex.search_videos_deep: k={k} must be in [1, len(index) = {self._n_live}]")
-        pages = [self.search_videos(queries, min(k, self.MAX_K), subset=subset, exclude_videos=exclude_videos)]
-        got = pages[0][0].shape[1]
-        while got < k:
-            pages.append(self.search_videos(queries, min(k - got, self.MAX_K), subset=subset, exclude_videos=exclude_videos,
-                                            after=pages[-1][1][:, -1]))
-            got += pages[-1][0].shape[1]
-        if len(pages) == 1:
-            return pages[0]
-        return tuple(torch.cat([p[i] for p in pages], dim=1) for i in range(3))
-
-    def _search_videos(self, queries, k, subset, exclude, what, stored=False, after=None):
-        if not self.grouped:
-            raise ValueError(f"VideoIndex.{what}: the index has no video ids (add(embeddings, video_ids=...)); search() returns rows")
-        k = int(k)
-        if not 1 <= k <= min(self.MAX_K, self._n_live):
-            raise ValueError(f"VideoIndex.{what}: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
-        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
-            raise ValueError(f"VideoIndex.{what}: the subset belongs to another index (build it with this index's subset())")
-        q = queries if stored else self._prepared(queries, "queries", check=False)
-        if q.shape[0] == 0:
-            raise ValueError(f"VideoIndex.{what}: no queries")
-        if exclude is not None:
-            exclude = self._per_query_ids(exclude, q.shape[0], "exclude_videos", what)
-        words = self._live_words() if subset is None else subset.words()
-        g, vids, step = self.rows, self._video_ids[:self._n], ops.SEARCH_MAX_QUERIES
-        ws = self._workspace(ops.l2_search_grouped_workspace_bytes(self._n, min(q.shape[0], step), self.width, k))
-        if after is not None:
-            after = self._per_query_ids(after, q.shape[0], "after", what)
-            uniq, slot, n_videos = self._dense_videos()
-            if exclude is not None:                            # the excluded VIDEO as its slot; one the index does not hold is no group
-                at = torch.searchsorted(uniq, exclude).clamp(max=n_videos - 1)
-                exclude = torch.where(uniq[at] == exclude, at, torch.full_like(at, 1 << 40))
-            out = []
-            for lo in range(0, q.shape[0], step):
-                rows = after[lo:lo + step]
-                cursor = (ops.l2_pair_dists64(g, q[lo:lo + step], rows), rows)      # +inf for an id that is no row: nothing comes after it
-                out.append(ops.l2_search_grouped(g, q[lo:lo + step], slot, k, ws=ws, live=words, after=cursor, n_groups=n_videos,
-                                                 exclude=None if exclude is None else exclude[lo:lo + step])[:3])
-            rows, slots, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
-            return torch.where(rows >= 0, uniq[slots.clamp(min=0).to(torch.int64)], rows), rows, 1.0 - dists / 2.0
-        if exclude is None:
-            out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words)[:3] for lo in range(0, q.shape[0], step)]
-        else:
-            out = [ops.l2_search_grouped(g, q[lo:lo + step], vids, k, ws=ws, live=words, exclude=exclude[lo:lo + step])[:3]
-                   for lo in range(0, q.shape[0], step)]
-        rows, videos, dists = out[0] if len(out) == 1 else tuple(torch.cat([o[i] for o in out]) for i in range(3))
-        return torch.where(rows >= 0, videos.to(torch.int64), rows), rows, 1.0 - dists / 2.0
+        return self._paged(lambda n, after: self.search_videos(queries, n, subset=subset, exclude_videos=exclude_videos, after=after), 1, k,
+                           "search_videos_deep")
 
     def search_videos_text(self, model, title_tokens, k, comments=None, subset=None, exclude_videos=None, after=None):
         """``search_text`` for a grouped index: the k nearest distinct videos of text queries given as token ids, as ``search_videos``
@@ -626,11 +611,9 @@ class VideoIndex:
         member of ``subset`` (the neighbours are).  ``after``: ``search``'s cursor, the next page.  An id outside [0, ntotal) (-1
         included) cannot be validated without a host read: that query comes back as -1 / -inf and the others are left alone.  Any
         number of queries, 64 per call, only enqueued.  1 <= k <= min(64, len(index)); fewer than k other rows end in -1 / -inf."""
-        k = int(k)
-        if not 1 <= k <= min(self.MAX_K, self._n_live):
-            raise ValueError(f"VideoIndex.similar: k={k} must be in [1, min({self.MAX_K}, len(index) = {self._n_live})]")
+        k = self._checked_k(k, "similar")
         ids, q = self._stored_queries(ids, "similar")
-        return self._search_masked(q, k, subset, after, ids, stored=True)
+        return self._scan(q, k, subset, after, ids, "search", stored=True)      # its messages say VideoIndex.search
 
     def similar_videos(self, ids, k, subset=None, after=None):
         """(video_ids [Q, k] int64, row_ids [Q, k] int64, scores [Q, k] fp32) of a GROUPED index: the k nearest distinct videos of the
@@ -654,9 +637,9 @@ class VideoIndex:
 
     # ---- range search ----------------------------------------------------------------------------
     def _range_setup(self, queries, min_score, subset, what):
-        """(prepared queries [Q, width], radius2 as Q Python doubles, the packed words of the rows that take part or None)."""
-        if subset is not None and (not isinstance(subset, RowSubset) or subset.index is not self):
-            raise ValueError(f"VideoIndex.{what}: the subset belongs to another index (build it with this index's subset())")
+        """([(the prepared queries [<= 64, width] of a slice, their radius2 as Python doubles)], the packed words of the rows that take
+        part or None, the workspace of a slice's call)."""
+        self._check_subset(subset, what)
         if self._n == 0:
             raise ValueError(f"VideoIndex.{what}: the index is empty")
         q = self._prepared(queries, "queries", check=False)
@@ -672,7 +655,8 @@ class VideoIndex:
                 raise ValueError(f"VideoIndex.{what}: min_score must be a float or one per query ({q.shape[0]}), got {len(scores)}")
         radius2 = [2.0 * (1.0 - s) for s in scores]             # score = 1 - D / 2, in Python doubles
         words = self._live_words() if subset is None else subset.words()
-        return q, radius2, words
+        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], ops.SEARCH_MAX_QUERIES), self.width))
+        return self._sliced(q, radius2), words, ws
 
     def range_search(self, queries, min_score, subset=None, sort=True, max_results=1 << 22):
         """EVERY live row that scores at least ``min_score`` against a query, however many: (lims [Q + 1] int64, ids [total] int64,
@@ -684,13 +668,11 @@ class VideoIndex:
         of queries, 64 per call.  A non-finite query has no hits.
         One host sync per 64 queries: the number of hits is read back before the result is allocated, and more than ``max_results`` in
         total raise ValueError before that allocation (``range_count`` tells the size without fetching)."""
-        q, radius2, words = self._range_setup(queries, min_score, subset, "range_search")
-        g, step = self.rows, ops.SEARCH_MAX_QUERIES
-        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], step), self.width))
+        slices, words, ws = self._range_setup(queries, min_score, subset, "range_search")
         lims, ids, dists, total = [torch.zeros(1, dtype=torch.int64, device=self.device)], [], [], 0
-        for lo in range(0, q.shape[0], step):
-            l, i, d32, d64 = ops.l2_range_search(g, q[lo:lo + step], radius2[lo:lo + step], live=words, max_results=int(max_results) - total,
-                                                 return_dists64=True, ws=ws)
+        for q, radius2 in slices:
+            l, i, d32, d64 = ops.l2_range_search(self.rows, q, radius2, live=words, max_results=int(max_results) - total, return_dists64=True,
+                                                 ws=ws)
             if sort and i.numel():
                 n_q = l.shape[0] - 1
                 seg = torch.repeat_interleave(torch.arange(n_q, device=self.device), l[1:] - l[:-1], output_size=i.numel())
@@ -706,12 +688,10 @@ class VideoIndex:
     def range_count(self, queries, min_score, subset=None):
         """int64 [Q] on the device: how many live rows (of the ``subset``) score at least ``min_score`` against every query -- the sizes
         of ``range_search``'s segments without fetching them.  Only enqueued: no host sync."""
-        q, radius2, words = self._range_setup(queries, min_score, subset, "range_count")
-        g, step = self.rows, ops.SEARCH_MAX_QUERIES
-        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], step), self.width))
+        slices, words, ws = self._range_setup(queries, min_score, subset, "range_count")
         out = []
-        for lo in range(0, q.shape[0], step):
-            l = ops.l2_range_count(g, q[lo:lo + step], radius2[lo:lo + step], live=words, ws=ws)
+        for q, radius2 in slices:
+            l = ops.l2_range_count(self.rows, q, radius2, live=words, ws=ws)
             out.append(l[1:] - l[:-1])
         return out[0] if len(out) == 1 else torch.cat(out)
 
@@ -728,8 +708,7 @@ class VideoIndex:
             query = query[None]
         if query.dim() != 2 or query.shape[0] != 1:
             raise ValueError(f"VideoIndex.range_subset: one query ([{self.dim}] or [1, {self.dim}]), got {tuple(query.shape)}")
-        q, radius2, words = self._range_setup(query, min_score, subset, "range_subset")
-        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, 1, self.width))
+        ((q, radius2),), words, ws = self._range_setup(query, min_score, subset, "range_subset")
         ops.l2_range_count(self.rows, q, radius2, live=words, ws=ws)
         hit = ops.range_hit_words(ws, self._n, 1)[0].clone()
         shifts = torch.arange(32, dtype=torch.int32, device=self.device)

@@ -371,6 +371,24 @@ def _search_gallery(gallery: torch.Tensor) -> torch.Tensor:
     return gallery
 
 
+def _search_inputs(what, gallery, queries, groups=None, rows=None):
+    """What every search entry opens with: the gallery (fp32 or half), the queries as fp32 with the gallery's column count and, where the
+    call has one, its ``groups`` (int32, one per gallery row) or ``rows`` (int64, one per query) on the gallery's device.  Returns
+    (gallery, queries, that vector or None, n_gallery, n_queries, d); ``what`` names the caller in every message."""
+    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
+    ng, d = gallery.shape
+    nq = queries.shape[0]
+    vec = groups if rows is None else rows
+    if vec is not None:
+        name, dtype, n, one = ("groups", torch.int32, ng, "one id per gallery row") if rows is None else ("rows", torch.int64, nq, "one per query")
+        vec = _gpu(vec, dtype, name)
+    if queries.shape[1] != d:
+        raise ValueError(f"{what}: gallery rows have {d} columns, queries {queries.shape[1]}")
+    if vec is not None and (vec.device != gallery.device or tuple(vec.shape) != (n,)):
+        raise ValueError(f"{what}: {name} must be {str(dtype)[6:]} [{n}] on {gallery.device} ({one}), got {tuple(vec.shape)} on {vec.device}")
+    return gallery, queries, vec, ng, nq, d
+
+
 def _exclude_arg(exclude, nq, device, what):
     """The excluded keys of an excluding search: an int64 [Q] tensor on the gallery's device, anything else raises ValueError."""
     if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64 or tuple(exclude.shape) != (nq,) or exclude.device != device:
@@ -448,11 +466,7 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     ``exclude[q]`` -- the search order with that row deleted, then cut.  -1, or any id outside [id_base, id_base + n), excludes nothing.
     It composes with ``live``, a half gallery and ``after`` (the cursor may stand on the excluded row).  A wrong dtype, shape or device
     raises ValueError.  None: the call above, unchanged."""
-    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    ng, d = gallery.shape
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise ValueError(f"l2_search: gallery rows have {d} columns, queries {queries.shape[1]}")
+    gallery, queries, _, ng, nq, d = _search_inputs("l2_search", gallery, queries)
     after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search") if after is not None else (None, None)
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search")
@@ -463,7 +477,9 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     half = int(gallery.dtype == torch.float16)
     shape = (ng, nq, d, depth, int(id_base), ids.data_ptr())
     tail = (_ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-    if exclude is not None:                                    # the narrowest entry that takes the call
+    # The narrowest entry that takes the call.  A ladder on purpose: a table of (condition, entry, arguments) forms every entry's
+    # arguments at every call, 2 us of host time on a 50 us call.
+    if exclude is not None:
         L.check(lib.vtc_l2_search_excluding(gallery.data_ptr(), half, queries.data_ptr(), _ptr(live), None, exclude.data_ptr(), _ptr(after_d),
                                             _ptr(after_i), *shape, None, *tail), "vtc_l2_search_excluding")
     elif after is not None:
@@ -506,15 +522,7 @@ def l2_pair_dists64(gallery: torch.Tensor, queries: torch.Tensor, rows: torch.Te
     one pair per query, with the bits ``l2_search`` leaves in its workspace for that pair -- what ``l2_search(after=...)`` takes as the
     cursor's distance when only the cursor's id is at hand.  ``rows``: int64 [Q]; -1, or any id outside [id_base, id_base + n), gives
     +inf and reads nothing.  The row is read whether or not any mask calls it live.  fp32 or ``torch.float16`` gallery; any Q >= 1."""
-    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    rows = _gpu(rows, torch.int64, "rows")
-    ng, d = gallery.shape
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise ValueError(f"l2_pair_dists64: gallery rows have {d} columns, queries {queries.shape[1]}")
-    if rows.device != gallery.device or tuple(rows.shape) != (nq,):
-        raise ValueError(f"l2_pair_dists64: rows must be int64 [{nq}] on {gallery.device} (one per query), got {tuple(rows.shape)} on "
-                         f"{rows.device}")
+    gallery, queries, rows, ng, nq, d = _search_inputs("l2_pair_dists64", gallery, queries, rows=rows)
     out = torch.empty(nq, dtype=torch.float64, device=gallery.device)
     L.check(L.lib().vtc_l2_pair_dists64(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), rows.data_ptr(), ng, nq, d,
                                         int(id_base), out.data_ptr(), _stream()), "vtc_l2_pair_dists64")
@@ -544,11 +552,7 @@ def range_hit_words(ws: torch.Tensor, n_gallery: int, n_queries: int) -> torch.T
 
 
 def _range_args(gallery, queries, radius2, live, ws, what):
-    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    ng, d = gallery.shape
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise ValueError(f"{what}: gallery rows have {d} columns, queries {queries.shape[1]}")
+    gallery, queries, _, ng, nq, d = _search_inputs(what, gallery, queries)
     if isinstance(radius2, torch.Tensor) and radius2.is_cuda:
         radius2 = _gpu(radius2, torch.float64, "radius2")
     elif isinstance(radius2, (int, float)):
@@ -558,17 +562,8 @@ def _range_args(gallery, queries, radius2, live, ws, what):
         radius2 = torch.as_tensor(radius2, dtype=torch.float64).reshape(-1).pin_memory().to(gallery.device, non_blocking=True)
     if radius2.device != gallery.device or tuple(radius2.shape) != (nq,):
         raise ValueError(f"{what}: radius2 must be a float or float64 [{nq}] (one squared radius per query), got {tuple(radius2.shape)}")
-    if live is not None:
-        live = _gpu(live, torch.int32, "live")
-        if live.device != gallery.device or tuple(live.shape) != ((ng + 31) // 32,):
-            raise ValueError(f"{what}: live must be int32 [{(ng + 31) // 32}] on {gallery.device} (one bit per gallery row), got "
-                             f"{tuple(live.shape)} on {live.device}")
-    need = L.lib().vtc_l2_range_workspace_bytes(ng, nq, d)
-    if ws is None:
-        ws = workspace(need, gallery.device)
-    elif need and (ws.numel() < need or ws.device != gallery.device):
-        # never a silent fresh workspace: the hit words stay in the tensor the caller passed
-        raise ValueError(f"{what}: the workspace passed holds {ws.numel()} bytes on {ws.device}, the call needs {need} on {gallery.device}")
+    live = _live_arg(live, ng, gallery.device, what)
+    ws = _search_ws_arg(ws, L.lib().vtc_l2_range_workspace_bytes(ng, nq, d), gallery.device, what)      # the hit words stay in it
     return gallery, queries, radius2, live, ws
 
 
@@ -650,15 +645,25 @@ def l2_search_merge(ids_parts: torch.Tensor, dists64_parts: torch.Tensor, return
     """The lists of searches over disjoint gallery windows -> the list of their union (vtc_l2_search_merge).  ids_parts [P, Q, depth] int64
     and dists64_parts [P, Q, depth] fp64 (l2_search_part's outputs, stacked; entries with id -1 are ignored); returns (ids [Q, depth],
     dists fp32 or None): the first ``depth`` by (distance, id)."""
-    ids_parts, dists64_parts = _gpu(ids_parts, torch.int64, "ids_parts"), _gpu(dists64_parts, torch.float64, "dists64_parts")
-    if ids_parts.dim() != 3 or dists64_parts.shape != ids_parts.shape:
-        raise ValueError(f"l2_search_merge: [parts, queries, depth] lists expected, got {tuple(ids_parts.shape)} and {tuple(dists64_parts.shape)}")
-    n_parts, nq, depth = ids_parts.shape
-    ids = torch.empty(nq, depth, dtype=torch.int64, device=ids_parts.device)
-    dists = torch.empty(nq, depth, dtype=torch.float32, device=ids_parts.device) if return_dists else None
-    L.check(L.lib().vtc_l2_search_merge(ids_parts.data_ptr(), dists64_parts.data_ptr(), n_parts, nq, depth, ids.data_ptr(),
-                                        dists.data_ptr() if dists is not None else None, _stream()), "vtc_l2_search_merge")
-    return ids, dists
+    return _search_merge("l2_search_merge", return_dists, ids_parts, dists64_parts)
+
+
+def _search_merge(what, return_dists, *stacks):
+    """The body of both merges (the entry vtc_<what>): the stacks checked, the outputs allocated, the one library call.  A third stack,
+    the groups, makes it the grouped merge, with a groups output between ids and dists."""
+    kinds = (("ids_parts", torch.int64), ("dists64_parts", torch.float64), ("groups_parts", torch.int32))
+    parts = [_gpu(t, dtype, name) for t, (name, dtype) in zip(stacks, kinds)]
+    grouped = len(parts) == 3
+    if parts[0].dim() != 3 or any(p.shape != parts[0].shape for p in parts[1:]):
+        shapes = [str(tuple(p.shape)) for p in parts]
+        raise ValueError(f"{what}: [parts, queries, depth] lists expected, got {', '.join(shapes[:-1])} and {shapes[-1]}")
+    n_parts, nq, depth = parts[0].shape
+    dev = parts[0].device
+    outs = (torch.empty(nq, depth, dtype=torch.int64, device=dev),) + ((torch.empty(nq, depth, dtype=torch.int32, device=dev),) if grouped else ())
+    dists = torch.empty(nq, depth, dtype=torch.float32, device=dev) if return_dists else None
+    L.check(getattr(L.lib(), "vtc_" + what)(*[p.data_ptr() for p in parts], n_parts, nq, depth, *[o.data_ptr() for o in outs], _ptr(dists),
+                                            _stream()), "vtc_" + what)
+    return (*outs, dists)
 
 
 def _n_groups_arg(n_groups, what):
@@ -687,15 +692,7 @@ def l2_group_mark_before(gallery: torch.Tensor, queries: torch.Tensor, groups: t
     allocates and zeroes one, a given one is ORed into in place (the windows of one gallery mark into the same buffer, with their
     ``id_base``).  Returns ``ban``.  One gallery pass per tile of queries, only enqueued; fp32 or ``torch.float16`` gallery.  Wrong
     dtypes, shapes or devices raise ValueError."""
-    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    groups = _gpu(groups, torch.int32, "groups")
-    ng, d = gallery.shape
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise ValueError(f"l2_group_mark_before: gallery rows have {d} columns, queries {queries.shape[1]}")
-    if groups.device != gallery.device or tuple(groups.shape) != (ng,):
-        raise ValueError(f"l2_group_mark_before: groups must be int32 [{ng}] on {gallery.device} (one id per gallery row), got "
-                         f"{tuple(groups.shape)} on {groups.device}")
+    gallery, queries, groups, ng, nq, d = _search_inputs("l2_group_mark_before", gallery, queries, groups)
     n_groups = _n_groups_arg(n_groups, "l2_group_mark_before")
     after_d, after_i = _after_arg(after, nq, gallery.device, "l2_group_mark_before")
     live = _live_arg(live, ng, gallery.device, "l2_group_mark_before")
@@ -733,15 +730,7 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     buffer BEFORE any of them is scanned, and a caller may carry bits forward.  ``exclude`` composes with the cursor (the cursor may
     stand on a row of the excluded group).  -inf is the plain grouped search, +inf / NaN an empty row.  ``after=None``: the call above,
     argument for argument (``n_groups`` and ``ban`` are then not looked at)."""
-    gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    groups = _gpu(groups, torch.int32, "groups")
-    ng, d = gallery.shape
-    nq = queries.shape[0]
-    if queries.shape[1] != d:
-        raise ValueError(f"l2_search_grouped: gallery rows have {d} columns, queries {queries.shape[1]}")
-    if groups.device != gallery.device or tuple(groups.shape) != (ng,):
-        raise ValueError(f"l2_search_grouped: groups must be int32 [{ng}] on {gallery.device} (one id per gallery row), got "
-                         f"{tuple(groups.shape)} on {groups.device}")
+    gallery, queries, groups, ng, nq, d = _search_inputs("l2_search_grouped", gallery, queries, groups)
     live = _live_arg(live, ng, gallery.device, "l2_search_grouped")
     lib = L.lib()
     ws = _search_ws_arg(ws, lib.vtc_l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device, "l2_search_grouped")
@@ -752,7 +741,7 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
             _stream())
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
-    if after is not None:                                      # the narrowest entry that takes the call
+    if after is not None:                                      # the narrowest entry that takes the call: a ladder, as in l2_search
         after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search_grouped")
         n_groups = _n_groups_arg(n_groups, "l2_search_grouped")
         if ban is None:
@@ -800,19 +789,7 @@ def l2_search_merge_grouped(ids_parts: torch.Tensor, dists64_parts: torch.Tensor
     """Grouped lists over gallery windows -> the grouped list of their union (vtc_l2_search_merge_grouped): ids_parts [P, Q, depth] int64,
     dists64_parts fp64 and groups_parts int32 of the same shape (l2_search_grouped_part's outputs, stacked; entries with id -1 are
     ignored).  Of a group that several parts list, the entry first by (distance, id) stays.  Returns (ids, groups, dists fp32 or None)."""
-    ids_parts, dists64_parts = _gpu(ids_parts, torch.int64, "ids_parts"), _gpu(dists64_parts, torch.float64, "dists64_parts")
-    groups_parts = _gpu(groups_parts, torch.int32, "groups_parts")
-    if ids_parts.dim() != 3 or dists64_parts.shape != ids_parts.shape or groups_parts.shape != ids_parts.shape:
-        raise ValueError(f"l2_search_merge_grouped: [parts, queries, depth] lists expected, got {tuple(ids_parts.shape)}, "
-                         f"{tuple(dists64_parts.shape)} and {tuple(groups_parts.shape)}")
-    n_parts, nq, depth = ids_parts.shape
-    ids = torch.empty(nq, depth, dtype=torch.int64, device=ids_parts.device)
-    out_groups = torch.empty(nq, depth, dtype=torch.int32, device=ids_parts.device)
-    dists = torch.empty(nq, depth, dtype=torch.float32, device=ids_parts.device) if return_dists else None
-    L.check(L.lib().vtc_l2_search_merge_grouped(ids_parts.data_ptr(), dists64_parts.data_ptr(), groups_parts.data_ptr(), n_parts, nq, depth,
-                                                ids.data_ptr(), out_groups.data_ptr(), dists.data_ptr() if dists is not None else None,
-                                                _stream()), "vtc_l2_search_merge_grouped")
-    return ids, out_groups, dists
+    return _search_merge("l2_search_merge_grouped", return_dists, ids_parts, dists64_parts, groups_parts)
 
 
 def pad_search_part(ids: torch.Tensor, dists64: torch.Tensor, depth: int):
