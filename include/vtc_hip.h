@@ -506,6 +506,40 @@ int vtc_l2_search_grouped_after(const void *gallery, int gallery_is_half, const 
                                 int n_groups, const uint32_t *ban, const int64_t *exclude, const double *after_d, const int64_t *after_i,
                                 int n_gallery, int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups,
                                 float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* SET QUERIES: several vectors as ONE query, the minimum over them -- the videos nearest to a video by any of its captions or chunks,
+ * the videos that match a title or any of its comments, any of these paraphrases.
+ * A set query S is m >= 1 vectors, its members.  Its distance to gallery row j is
+ *     E(S, j) = min over the members v of S with only finite components of D(v, j)
+ * D is the fp64 squared distance every search forms (wave_dist64_core: same statements, same bits).
+ *   UNGROUPED ORDER.  The live rows with a finite E, sorted by (E(S, j), j).  The first `depth` are the result.
+ *   GROUPED ORDER.  Take the ungrouped order and delete every row that is not the first of its group.  The first `depth` are the
+ *   result.  This is vtc_l2_search_grouped's sentence with E in place of D.
+ *   EXCLUDED KEY PER SET.  A row when ungrouped, a group when grouped.  It is deleted from the order before the cut, as
+ *   vtc_l2_search_excluding does.  -1, or a key that is not there, excludes nothing.
+ *   NON-FINITE MEMBERS.  A member with a NaN or inf takes no part and sets bit 2 of `nonfinite`.  A set with no finite member returns
+ *   -1 / (-1) / +inf.  Bit 1 means what it means today.
+ *   EQUIVALENCES.  A set of one member is the plain search.  Every output, the fp64 list in the workspace included, has the bits
+ *   vtc_l2_search / _masked / _half / _grouped / _excluding give for that vector.  Repeating a member changes nothing.  That is how the
+ *   host pads ragged sets.
+ *   THERE IS NO CURSOR.  A set search has no `after` and no deep form.  A set larger than one tile of 8 members is scanned as several
+ *   tiles.  A tile knows only its own members' min.  A row that an earlier page returned on tile 1's distance would pass a cursor test
+ *   against tile 2's larger one and come back.  Paging set queries needs the cursor test on the set-wide E, which these entries do not
+ *   have; a range search over sets does not exist either.
+ * queries: float [n_sets * set_size][d], device, set s being the rows [s * set_size, (s + 1) * set_size); all sets of a call have the
+ * same size (pad a smaller one by repeating a member).  live (NULL: every row), groups (NULL: ungrouped; then out_groups is not looked
+ * at), exclude (NULL: none; int64 [n_sets], device, a global row id or a group as vtc_l2_search_excluding reads them), gallery_is_half,
+ * id_base, nonfinite: as in vtc_l2_search_excluding.  ids / out_groups / dists: [n_sets][depth], device; the fp64 distances of the
+ * result are the first region of the workspace, double [n_sets][depth], as in every search.
+ * Cost: one gallery pass per started tile of 8 members per set (a set of 1, 2 or up to 4 members is one tile of that shape), one merge
+ * per set over the lists of all its tiles; the minimum is set_size - 1 fmin on distances the scan forms anyway, and a row that does
+ * not beat the set's depth-th entry costs one compare.  Two launches.
+ * LIMITS and refusals: n_sets >= 1, set_size >= 1, n_sets * set_size <= 64; n_gallery, d, depth, id_base as vtc_l2_search; gallery,
+ * queries and ids non-null, out_groups non-null with groups; the workspace at least vtc_l2_search_sets_workspace_bytes(...), which is 0
+ * for a refused shape.  A refused call launches nothing. */
+size_t vtc_l2_search_sets_workspace_bytes(int n_gallery, int n_sets, int set_size, int d, int depth, int grouped);
+int vtc_l2_search_sets(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
+                       const int64_t *exclude, int n_gallery, int n_sets, int set_size, int d, int depth, int64_t id_base, int64_t *ids,
+                       int32_t *out_groups, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* RANGE SEARCH: every row of a stored gallery that lies within a threshold of a query, however many rows that is (near-duplicate
  * detection before a video is added, "everything that matches this title", counting matches).  vtc_l2_search cannot stand in: its depth
  * is capped at 64 and a depth guessed too small truncates silently.

@@ -125,6 +125,10 @@ SIGNATURES = {
     "vtc_l2_group_mark_before": (C.c_int, [vp, C.c_int, fp, ip, ip, C.c_int, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int64, ip, vp]),
     "vtc_l2_search_grouped_after": (C.c_int, [vp, C.c_int, fp, ip, ip, C.c_int, ip, ip, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip,
                                               fp, ip, vp, C.c_size_t, vp]),
+    # set queries (search_sets.hip): several vectors as one query, the minimum over them
+    "vtc_l2_search_sets_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_search_sets": (C.c_int, [vp, C.c_int, fp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp,
+                                     C.c_size_t, vp]),
     # range search (range.hip): count = one gallery pass -> lims + hit words in the workspace; fill = ids / dists of the hits
     "vtc_l2_range_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vtc_l2_range_count": (C.c_int, [vp, C.c_int, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),

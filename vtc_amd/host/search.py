@@ -61,6 +61,14 @@ stateless:
 
     videos2, rows2, scores2 = index.search_videos(queries, 10, after=rows[:, -1])     # the next 10 distinct videos of every query
     videos, rows, scores = index.search_videos_deep(queries, 300)                      # the exact 300 nearest videos: pages of 64
+
+A query can also be SEVERAL vectors, any of which may match -- a title and its comments, the captions or chunks of a whole video,
+paraphrases.  The set's distance to a row is the minimum over its members, taken inside the scan on distances it forms anyway
+(vtc_l2_search_sets), so nothing is merged, sorted or de-duplicated on the host:
+
+    ids, scores = index.search_any(query_sets, 10)                                     # [S, M, dim]: S queries of M members each
+    videos, rows, scores = index.search_videos_any(query_sets, 10, sizes=[3, 9, 1])    # ragged sets, distinct videos
+    videos, rows, scores = index.similar_to_video(video_ids, 10)                       # the videos nearest to a video, by any of its rows
 """
 from __future__ import annotations
 
@@ -178,6 +186,7 @@ class VideoIndex:
         self._words = None                  # (generation, packed words of _live)
         self._video_ids = None              # int32 [capacity] on the device once the first non-empty add passed video_ids: a GROUPED index
         self._dense = None                  # (sorted distinct video ids int64 [V], slot of every row int32 [ntotal], V): the paged searches
+        self._by_video = None               # (generation, video ids sorted int64 [ntotal], the rows in that order): similar_to_video
 
     def __len__(self):
         """The number of live rows."""
@@ -454,20 +463,22 @@ class VideoIndex:
         return ids.to(self.device).contiguous()
 
     @staticmethod
-    def _sliced(queries, *per_query):
+    def _sliced(queries, *per_query, step=ops.SEARCH_MAX_QUERIES):
         """[(queries, *per_query) of one library call]: slices of at most ``ops.SEARCH_MAX_QUERIES`` queries, each with the entries of
         the same queries of every per-query sequence (None stays None).  THE place where a call's arguments are cut; up to 64 queries
-        are the arguments themselves."""
-        n, step, whole = queries.shape[0], ops.SEARCH_MAX_QUERIES, (queries, *per_query)
+        are the arguments themselves.  ``step``: set queries [S, M, width] are cut into calls of 64 // M sets."""
+        n, whole = queries.shape[0], (queries, *per_query)
         if n <= step:
             return [whole]
         return [tuple(None if t is None else t[lo:lo + step] for t in whole) for lo in range(0, n, step)]
 
-    def _scan(self, queries, k, subset, after, exclude, what, grouped=False, stored=False):
+    def _scan(self, queries, k, subset, after, exclude, what, grouped=False, stored=False, sets=False):
         """The scan behind every top-k search of rows (``ops.l2_search``) and, ``grouped``, of distinct videos
         (``ops.l2_search_grouped``): any number of queries in slices of 64, only enqueued.  ``after`` / ``exclude``: one row id (grouped:
         one row id / one video id) per query or None.  ``stored``: the queries are stored rows [Q, width] widened to fp32 (``similar``)
-        and are searched as they are.  Returns (ids, scores), grouped (videos, rows, scores).  ``what`` names the caller in the messages."""
+        and are searched as they are.  ``sets``: the queries are prepared SET queries [S, M, width] (``_set_queries``), a query being a
+        set: ``ops.l2_search_sets`` in slices of 64 // M sets, ``exclude`` one key per set, no ``after``.  Returns (ids, scores), grouped
+        (videos, rows, scores).  ``what`` names the caller in the messages."""
         self._check_subset(subset, what)
         q = queries if stored else self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
@@ -475,8 +486,12 @@ class VideoIndex:
         if exclude is not None:
             exclude = self._per_query_ids(exclude, q.shape[0], "exclude_videos" if grouped else "exclude", what)
         words = self._live_words() if subset is None else subset.words()      # None with every row live: no mask
-        ws_bytes = ops.l2_search_grouped_workspace_bytes if grouped else ops.l2_search_workspace_bytes
-        ws = self._workspace(ws_bytes(self._n, min(q.shape[0], ops.SEARCH_MAX_QUERIES), self.width, k))
+        step = ops.SEARCH_MAX_QUERIES // q.shape[1] if sets else ops.SEARCH_MAX_QUERIES
+        if sets:
+            ws = self._workspace(ops.l2_search_sets_workspace_bytes(self._n, min(q.shape[0], step), q.shape[1], self.width, k, grouped))
+        else:
+            ws_bytes = ops.l2_search_grouped_workspace_bytes if grouped else ops.l2_search_workspace_bytes
+            ws = self._workspace(ws_bytes(self._n, min(q.shape[0], step), self.width, k))
         if after is not None:
             after = self._per_query_ids(after, q.shape[0], "after", what, row_ids=not grouped)
         uniq = n_videos = None
@@ -490,10 +505,13 @@ class VideoIndex:
         g, out = self.rows, []
         # What the call does not have stays None, every argument's default: each slice reaches the library entry of exactly the
         # arguments that are set (ops: the narrowest entry that takes the call).
-        for qs, cursor, ex in self._sliced(q, after, exclude):
+        for qs, cursor, ex in self._sliced(q, after, exclude, step=step):
             if cursor is not None:
                 cursor = (ops.l2_pair_dists64(g, qs, cursor), cursor)          # +inf for an id that is no row: nothing comes after it
-            if grouped:
+            if sets:
+                found = ops.l2_search_sets(g, qs, k, groups=groups if grouped else None, live=words, exclude=ex, ws=ws)
+                out.append(found[:3] if grouped else (found[0], found[2]))
+            elif grouped:
                 out.append(ops.l2_search_grouped(g, qs, groups, k, ws=ws, live=words, exclude=ex, after=cursor, n_groups=n_videos)[:3])
             else:
                 out.append(ops.l2_search(g, qs, k, ws=ws, live=words, after=cursor, exclude=ex)[:2])
@@ -621,12 +639,145 @@ class VideoIndex:
         own video left out; otherwise ``search_videos`` with the stored row as the query (as ``similar`` takes it).  An id outside
         [0, ntotal) gives -1 / -1 / -inf.  On an ungrouped index it raises ValueError.  ``after``: ``search_videos``'s cursor, the next
         page of other videos (the ``rows[:, -1]`` of the page before), to any depth by chaining.  A query given as a whole VIDEO, all
-        of its rows merged into one ranking, is out of scope: call this per row and merge as the application sees fit."""
+        of its rows merged into one ranking, is ``similar_to_video``."""
         if not self.grouped:
             raise ValueError("VideoIndex.similar_videos: the index has no video ids (add(embeddings, video_ids=...)); similar() returns rows")
         ids, q = self._stored_queries(ids, "similar_videos")
         own = self._video_ids[:self._n][ids.clamp(0, self._n - 1)].to(torch.int64)
         return self._search_videos(q, k, subset, own, "similar_videos", stored=True, after=after)
+
+    # ---- set queries: several vectors as one query ---------------------------------------------------
+    MAX_SET = ops.SEARCH_MAX_QUERIES      # members of a set query: one library call takes 64 vectors
+
+    def _set_queries(self, query_sets, sizes, what):
+        """[S, M, dim] -> the prepared members [S, M, width] (as ``search`` prepares queries, no check: a non-finite member takes no
+        part).  ``sizes``: a HOST sequence of S ints in [1, M], never read from a device; the members at or past ``sizes[s]`` are
+        replaced by member 0 of their set, which changes no output bit (a repeated member is no new candidate)."""
+        x = torch.as_tensor(query_sets)
+        if x.dim() != 3 or x.shape[2] != self.dim or not 1 <= x.shape[1] <= self.MAX_SET:
+            raise ValueError(f"VideoIndex.{what}: query_sets must be [S, M, {self.dim}] with 1 <= M <= {self.MAX_SET} members a set, got "
+                             f"{tuple(x.shape)}")
+        n_sets, m = x.shape[:2]
+        if n_sets == 0:
+            raise ValueError(f"VideoIndex.{what}: no queries")
+        q = self._prepared(x.reshape(n_sets * m, self.dim), "query_sets", check=False).view(n_sets, m, self.width)
+        if sizes is not None:
+            if isinstance(sizes, torch.Tensor) and sizes.is_cuda:
+                raise ValueError(f"VideoIndex.{what}: sizes must be a host sequence of {n_sets} ints (it is not read from a device)")
+            sizes = [int(s) for s in sizes]
+            if len(sizes) != n_sets or not all(1 <= s <= m for s in sizes):
+                raise ValueError(f"VideoIndex.{what}: sizes must be {n_sets} ints in [1, M = {m}], one per set, got {sizes}")
+            if min(sizes) < m:
+                keep = torch.tensor([[j < s for j in range(m)] for s in sizes], device=self.device)
+                q = torch.where(keep[:, :, None], q, q[:, :1]).contiguous()
+        return q
+
+    def _attaining_members(self, q, rows):
+        """int64 [S, k]: for every returned row the LOWEST member of its set that attains E -- the fp64 argmin, over the members, of
+        the pair distances with the scan's bits (ops.l2_pair_dists64; a non-finite member counts as +inf), -1 where the row is -1.
+        One launch over S * k * M pairs (their member vectors are gathered: S * k * M * width floats) plus torch ops, no host sync."""
+        (n_sets, m, width), k = q.shape, rows.shape[1]
+        pairs = ops.l2_pair_dists64(self.rows, q[:, None].expand(n_sets, k, m, width).reshape(-1, width),
+                                    rows[:, :, None].expand(n_sets, k, m).reshape(-1)).view(n_sets, k, m)
+        pairs = torch.where(torch.isfinite(pairs), pairs, pairs.new_full((), float("inf")))
+        return torch.where(rows >= 0, torch.argmin(pairs, dim=2), rows)
+
+    def _search_sets(self, q, k, subset, exclude, what, grouped, return_members):
+        if q.shape[1] == 1:      # a set of one member IS the plain search, bit for bit, and that scan is 1 - 4 % faster (profiles/search_sets.md)
+            out = self._scan(q[:, 0], k, subset, None, exclude, what, grouped=grouped, stored=True)
+        else:
+            out = self._scan(q, k, subset, None, exclude, what, grouped=grouped, stored=True, sets=True)
+        return (*out, self._attaining_members(q, out[1] if grouped else out[0])) if return_members else out
+
+    def search_any(self, query_sets, k, sizes=None, subset=None, exclude=None, return_members=False):
+        """SET QUERIES: (ids [S, k] int64, scores [S, k] fp32) for ``query_sets`` [S, M, dim], 1 <= M <= 64 -- S queries, each a SET of
+        M member vectors, any of which may match: a title and its comments, the captions or chunks of a video, paraphrases.  A set's
+        distance to a row is E = the MINIMUM over its members of the fp64 squared distance ``search`` forms, the result the k live
+        rows (of ``subset``) with the smallest (E, row), and score = 1 - E / 2: the best score any member reaches.  The minimum is
+        taken inside the scan (vtc_l2_search_sets), not merged on the host: no sync, no sort, every row once.  The members are
+        prepared as ``search`` prepares queries; a non-finite one takes no part, a set of only such members is a row of -1 / -inf.
+        ``sizes``: a host sequence of S ints in [1, M] for ragged sets -- set s is its first ``sizes[s]`` members (the rest are
+        overwritten by member 0, which changes nothing).  ``exclude``: an int64 [S] device tensor, ONE row per set that it is never
+        given.  ``return_members=True`` appends an int64 [S, k] tensor: the member that attains E for the returned row (the lowest
+        on a tie), -1 where the row is -1; one more small launch (vtc_l2_pair_dists64), no sync.
+        Sets are cut into calls of 64 // M sets, only enqueued.  THE COST: one gallery pass per started tile of 8 members per set
+        -- what M separate queries cost, less their lists.  1 <= k <= min(64, len(index)).
+        THERE IS NO ``after=`` and no deep form.  A set of more than 8 members is scanned as several tiles and a tile knows only its
+        own members' minimum: a row an earlier page returned on one tile's distance would pass a cursor test against another tile's
+        larger one and come back.  Paging needs the cursor test on the set-wide E, which the scan does not have."""
+        k = self._checked_k(k, "search_any")
+        return self._search_sets(self._set_queries(query_sets, sizes, "search_any"), k, subset, exclude, "search_any", False, return_members)
+
+    def search_videos_any(self, query_sets, k, sizes=None, subset=None, exclude_videos=None, return_members=False):
+        """``search_any`` of a GROUPED index: (video_ids [S, k] int64, row_ids [S, k] int64, scores [S, k] fp32), the k nearest distinct
+        videos of every set, each by the row and the member that are nearest, as ``search_videos`` returns them.
+        ``exclude_videos``: an int64 [S] device tensor, one VIDEO per set none of whose rows it is given.  ``sizes``,
+        ``return_members`` (the member that attains the returned row's distance), the cost and the missing ``after=``:
+        ``search_any``'s.  On an ungrouped index it raises ValueError."""
+        if not self.grouped:
+            raise ValueError("VideoIndex.search_videos_any: the index has no video ids (add(embeddings, video_ids=...)); search_any() returns rows")
+        k = self._checked_k(k, "search_videos_any")
+        return self._search_sets(self._set_queries(query_sets, sizes, "search_videos_any"), k, subset, exclude_videos, "search_videos_any", True,
+                                 return_members)
+
+    def _rows_by_video(self):
+        """(the video ids of the rows, sorted, int64 [ntotal]; the rows in that order, int64 [ntotal]): a video's LIVE rows are one run,
+        in ascending row order (a stable sort), and the dead rows lie behind every video id.  O(ntotal) memory whatever the number of
+        videos asked for; sorted once per ``add`` / ``remove`` / ``load_state_dict`` and kept; no host sync."""
+        if self._by_video is None or self._by_video[0] != self._generation:
+            vid = self._video_ids[:self._n].to(torch.int64)
+            if self._live is not None:
+                vid = torch.where(self._live, vid, vid.new_full((), 1 << 40))
+            self._by_video = (self._generation, *torch.sort(vid, stable=True))
+        return self._by_video[1:]
+
+    def similar_to_video(self, video_ids, k, subset=None, return_members=False):
+        """THE VIDEOS NEAREST TO A VIDEO, by any of its rows: (video_ids [V, k] int64, row_ids [V, k] int64, scores [V, k] fp32) of a
+        GROUPED index.  For every entry of ``video_ids`` (an integer [V] sequence or tensor) the query SET is the video's LIVE stored
+        rows as the index keeps them -- a half index's rows widened exactly, nothing normalised again -- in ascending row order, and
+        every row of that video is left out: ``search_videos_any`` with ``exclude_videos=video_ids``.  A video the index does not hold,
+        or one with no live row, gives -1 / -1 / -inf and leaves the others alone.  A video with more than 64 live rows raises
+        ValueError.  ``return_members`` appends the position, among the video's live rows, of the row that attains the distance.
+        Finding the videos' rows is a binary search in the rows sorted by video -- sorted once per ``add`` / ``remove`` and kept,
+        O(ntotal) memory whatever V is -- and reads the largest count back: ONE host sync per call; the searches are only enqueued,
+        64 // (that count) videos a call.  No ``after=``: see ``search_any``."""
+        if not self.grouped:
+            raise ValueError("VideoIndex.similar_to_video: the index has no video ids (add(embeddings, video_ids=...)); similar() returns rows")
+        k = self._checked_k(k, "similar_to_video")
+        v = torch.as_tensor(video_ids)
+        if v.dtype == torch.bool or v.is_floating_point() or v.is_complex() or v.dim() != 1 or v.shape[0] < 1:
+            raise ValueError(f"VideoIndex.similar_to_video: video_ids must be an integer [V >= 1] sequence or tensor, got {v.dtype} {tuple(v.shape)}")
+        v = v.to(device=self.device, dtype=torch.int64)
+        n = self._n
+        by_video, order = self._rows_by_video()
+        lo, hi = torch.searchsorted(by_video, v), torch.searchsorted(by_video, v, right=True)
+        count = torch.where((v >= 0) & (v < 2 ** 31), hi - lo, torch.zeros_like(lo))   # what is no video id has no rows
+        most = int(count.max())                                                          # the one host sync
+        if most > self.MAX_SET:
+            raise ValueError(f"VideoIndex.similar_to_video: a video has {most} live rows, a set query takes at most {self.MAX_SET} members")
+        m = max(most, 1)
+        rows = order[(lo[:, None] + torch.arange(m, device=self.device)[None]).clamp(max=n - 1)]      # [V, m]; past the count: replaced below
+        member = torch.arange(m, device=self.device)[None] < count[:, None]
+        rows = torch.where(member, rows, rows[:, :1])                                    # padded by member 0, as ``sizes`` pads
+        q = self.rows[rows.reshape(-1)].float().view(v.shape[0], m, self.width)           # half -> fp32 is exact
+        q = torch.where((count > 0)[:, None, None], q, q.new_full((), float("nan"))).contiguous()      # no live row: no member
+        return self._search_sets(q, k, subset, v, "similar_to_video", True, return_members)
+
+    def search_any_text(self, model, tokens, k, **kw):
+        """``search_any`` of text given as token ids [S, M, ctx] -- a title and its comments as separate vectors, any of which may
+        match: model.encode_text on the flattened tokens, normalisation, the set search.  ``**kw``: ``search_any``'s."""
+        return self.search_any(self._text_sets(model, tokens, "search_any_text"), k, **kw)
+
+    def search_videos_any_text(self, model, tokens, k, **kw):
+        """``search_videos_any`` of text given as token ids [S, M, ctx] -- a title and its comments as separate vectors, any of which may
+        match -- on a grouped index.  ``**kw``: ``search_videos_any``'s."""
+        return self.search_videos_any(self._text_sets(model, tokens, "search_videos_any_text"), k, **kw)
+
+    def _text_sets(self, model, tokens, what):
+        if tokens.dim() != 3:
+            raise ValueError(f"VideoIndex.{what}: tokens must be [S, M, ctx], got {tuple(tokens.shape)}")
+        n_sets, m, ctx = tokens.shape
+        return self._text_queries(model, tokens.reshape(n_sets * m, ctx), None, what).view(n_sets, m, -1)
 
     def search_text(self, model, title_tokens, k, comments=None, subset=None, after=None, exclude=None):
         """The k nearest videos of text queries given as token ids [Q, ctx]: model.encode_text + normalisation + search.  For a

@@ -765,6 +765,48 @@ def l2_search_grouped_workspace_bytes(n_gallery: int, n_queries: int, d: int, de
 
 
 @on_device
+def l2_search_sets(gallery: torch.Tensor, query_sets: torch.Tensor, depth: int, groups: Optional[torch.Tensor] = None,
+                   live: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, id_base: int = 0, return_dists: bool = True,
+                   ws: Optional[torch.Tensor] = None):
+    """SET QUERIES (vtc_l2_search_sets): ``query_sets`` [S, M, d] is S queries of M member vectors each, and a set's distance to gallery row
+    j is E(S, j) = the minimum, over its members with only finite components, of the fp64 squared distance every search forms.  Returns
+    (ids [S, depth] int64, groups [S, depth] int32 or None, dists [S, depth] fp32 or None, nonfinite_bits): ungrouped the live rows with a
+    finite E by (E, row), cut to ``depth``; with ``groups`` (int32 [n], as l2_search_grouped) that order with every row deleted that is not
+    the first of its group -- the ``depth`` nearest distinct groups.  ``exclude``: int64 [S] on the gallery's device, ONE key per set,
+    a global row id ungrouped and a group grouped, deleted from the order before the cut; -1, or a key that is not there, excludes nothing.
+    A member with a NaN / inf takes no part (bit 2 of nonfinite_bits); a set with no finite member is a row of -1 / (-1) / +inf.  A set of
+    one member is l2_search / l2_search_grouped of that vector, bit for bit; repeating a member changes nothing, which is how ragged sets
+    are padded.  ``live``, ``id_base``, a ``torch.float16`` gallery and ``ws`` as in l2_search: with a caller's ``ws`` of at least
+    ``l2_search_sets_workspace_bytes`` the fp64 distances are ``search_dists64(ws, S, depth)``.  S * M <= 64, otherwise ValueError.
+    One gallery pass per started tile of 8 members per set.  There is no ``after``: a set of several tiles has no cursor a tile could test
+    (include/vtc_hip.h)."""
+    query_sets = _gpu(query_sets, torch.float32, "query_sets")
+    if query_sets.dim() != 3 or query_sets.shape[0] < 1 or query_sets.shape[1] < 1:
+        raise ValueError(f"l2_search_sets: query_sets must be [S, M, d] with S, M >= 1, got {tuple(query_sets.shape)}")
+    n_sets, set_size = query_sets.shape[:2]
+    if n_sets * set_size > SEARCH_MAX_QUERIES:
+        raise ValueError(f"l2_search_sets: {n_sets} sets of {set_size} members are {n_sets * set_size} vectors, a call takes at most "
+                         f"{SEARCH_MAX_QUERIES}")
+    gallery, queries, groups, ng, _, d = _search_inputs("l2_search_sets", gallery, query_sets.reshape(n_sets * set_size, -1), groups)
+    live = _live_arg(live, ng, gallery.device, "l2_search_sets")
+    if exclude is not None:
+        exclude = _exclude_arg(exclude, n_sets, gallery.device, "l2_search_sets")
+    lib = L.lib()
+    ws = _search_ws_arg(ws, lib.vtc_l2_search_sets_workspace_bytes(ng, n_sets, set_size, d, depth, int(groups is not None)), gallery.device,
+                        "l2_search_sets")
+    ids, out_groups, dists, bits = _search_outputs(n_sets, depth, gallery.device, return_dists, grouped=groups is not None)
+    L.check(lib.vtc_l2_search_sets(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), _ptr(live), _ptr(groups),
+                                   _ptr(exclude), ng, n_sets, set_size, d, depth, int(id_base), ids.data_ptr(), _ptr(out_groups), _ptr(dists),
+                                   bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_search_sets")
+    return ids, out_groups, dists, bits
+
+
+def l2_search_sets_workspace_bytes(n_gallery: int, n_sets: int, set_size: int, d: int, depth: int, grouped: bool = False) -> int:
+    """0 for a shape vtc_l2_search_sets refuses."""
+    return int(L.lib().vtc_l2_search_sets_workspace_bytes(int(n_gallery), int(n_sets), int(set_size), int(d), int(depth), int(bool(grouped))))
+
+
+@on_device
 def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups: torch.Tensor, depth: int, id_base: int = 0,
                            live: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None, after=None,
                            n_groups: Optional[int] = None, ban: Optional[torch.Tensor] = None):
