@@ -413,10 +413,35 @@ int vtc_l2_search_merge_grouped(const int64_t *ids_parts, const double *dists_pa
  * distances and ids, so vtc_l2_search_merge / vtc_l2_search_merge_grouped take windows of half and of fp32 galleries alike.
  * LIMITS and refusals: those of the fp32 entries (n_queries in [1, 64], depth in [1, min(64, n_gallery)], d a multiple of 64 in
  * [64, 2048], id_base >= 0, null gallery / queries / ids / ws, a workspace that is too small), and groups given without out_groups.
- * There is no many-query route for a half gallery: vtc_l2_topk reads fp32 rows. */
+ * There is no many-query route for a half gallery through vtc_l2_topk, which reads fp32 rows: the one for a half gallery is
+ * vtc_l2_search_many_half below. */
 int vtc_l2_search_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_gallery,
                        int n_queries, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists,
                        int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* MANY queries over a half gallery.  DEFINITION: the result is that of vtc_l2_search_half with groups == NULL on the same arguments, BIT
+ * FOR BIT -- ids, dists, the n_queries * depth doubles at the head of the workspace, the bits ORed into nonfinite, the -1 / +inf tails,
+ * the whole -1 row of a non-finite query, a dead row influencing nothing (not even bit 1), live == NULL meaning every row, id_base --
+ * so vtc_l2_search_merge takes its windows unchanged.  The entry has no specification of its own.
+ * MECHANISM (search_many.hip): four launches whatever the data, no host synchronisation, no allocation, nothing read back.  A prologue
+ * over the QUERIES splits them into fp16 hi + lo (scaled by a power of two); ONE pass streams the gallery through
+ * v_mfma_f32_16x16x32_f16 -- the stored rows are the operand, |g|^2 is formed from the loaded tile -- for an approximate distance A with
+ * |A - D| <= eps = kappa (|q|^2 + max|g|^2) + 1e-35, kappa = (6 d + 8) 2^-24 + 2^-20 (derived in search_many.hip), and keeps per query
+ * the cdepth = min(64, n_gallery, max(32, depth + 21)) smallest; a finish forms the candidates' fp64 distances with the scan's own device
+ * function, orders them by (D, row) and accepts the list where the bound proves that every row outside it lies STRICTLY behind the
+ * depth-th found (or the list is every live finite row).  A query the bound cannot certify -- near-duplicates deeper than the list,
+ * magnitudes beyond fp16 / fp32 range or too small for the split, an A that overflowed while D is finite -- is finished on the device
+ * by an exact fp64 scan of the live rows (one workgroup per such query: slow, and normally there is none).  A tile of 16 rows none of
+ * which is live issues no gallery load.
+ * COST: one gallery pass per call for up to 64 queries (the scan: one per 8); measured in profiles/search_many.md.
+ * THE COUNTER: behind the fp64 head -- at byte align256(n_queries * depth * 8) of the workspace -- one int32 holds the number of
+ * queries of this call that the fallback finished (the workspace is carved in 256-byte steps).
+ * LIMITS and refusals (a status, vtc_last_error, nothing launched): those of vtc_l2_search_half, and depth <= 32 (at least 21 spare
+ * ranks in a lane-per-entry list); 1 <= n_queries <= 64 (more: slice them).  The workspace is vtc_l2_search_many_workspace_bytes(...),
+ * 0 for a refused shape; it does not grow with n_queries x n_gallery (no distance matrix: at most 1024 lists of cdepth per query).
+ * NOT PROVIDED: groups; cursor, exclude and sets; fp32 galleries, masked or not; more than 64 queries per pass; depth above 32. */
+size_t vtc_l2_search_many_workspace_bytes(int n_gallery, int n_queries, int d, int depth);
+int vtc_l2_search_many_half(const uint16_t *gallery, const float *queries, const uint32_t *live, int n_gallery, int n_queries, int d,
+                            int depth, int64_t id_base, int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* SEARCH AFTER A CURSOR: results beyond depth 64, one page at a time.  The search order of a query is the total order of its live rows
  * with a finite distance by the key (D(q, j), j) -- fp64 distance, then row.  For every query q the call returns the `depth` rows whose
  * key lies STRICTLY AFTER the cursor key (after_d[q], after_i[q]) (double [n_queries] and int64 [n_queries], device, only read):

@@ -113,6 +113,9 @@ SIGNATURES = {
     "vtc_l2_search_grouped": (C.c_int, [fp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
     "vtc_l2_search_merge_grouped": (C.c_int, [ip, fp, ip, C.c_int, C.c_int, C.c_int, ip, ip, fp, vp]),
     "vtc_l2_search_half": (C.c_int, [vp, fp, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t, vp]),
+    # many queries over a half gallery (search_many.hip): an MFMA candidate pass, finished exactly -- vtc_l2_search_half's bits
+    "vtc_l2_search_many_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_search_many_half": (C.c_int, [vp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, fp, ip, vp, C.c_size_t, vp]),
     # the cursor search: the rows after a (fp64 distance, id) key, and the fp64 distance of one pair per query
     "vtc_l2_search_after": (C.c_int, [vp, C.c_int, fp, ip, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, fp, ip, vp, C.c_size_t,
                                       vp]),

@@ -1,0 +1,513 @@
+// search_many.hip -- vtc_l2_search_many_half: the top-`depth` of MANY queries (up to 64 a pass) over a gallery stored as IEEE binary16.
+// The result is vtc_l2_search_half's without groups, bit for bit (include/vtc_hip.h); only the way there differs.  The scan of search.hip
+// forms every (query, row) distance in fp64, which at 64 queries is all it does: 8 gallery passes of fp64 arithmetic.  A half row already
+// IS an fp16 MFMA operand, so here the gallery is streamed ONCE through v_mfma_f32_16x16x32_f16 for an APPROXIMATE distance A, a few more
+// candidates than were asked for are kept, and the scheme of the sweeps' exact finish (sweep_topk.hip: exact_rerank_kernel /
+// exact_fallback_kernel) makes the answer exact again.  Four launches, whatever the data:
+//
+//   many_prep_kernel      a wave per query: |q|^2, the power-of-two scale s, the fp16 (hi, lo) split of s q laid out as the MFMA's B
+//                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.
+//   many_pass_kernel      the candidate pass.  A workgroup is one wave per 16 queries; every wave walks the workgroup's tiles of 16 gallery
+//                         rows (round-robin over the grid), loads a row tile straight from global memory into A fragments -- a lane's 16
+//                         bytes are 8 consecutive halves of one row, no LDS, no conversion -- one item ahead of the one it multiplies,
+//                         and keeps its queries' B fragments in the LDS (up to 512 columns: 32 KB a wave; a longer row reloads its
+//                         part of them per item).  |g|^2 comes from the loaded fragments (v_dot2_f32_f16).  Per query the wave keeps
+//                         the C = cdepth smallest (A, row) in a sorted list in the LDS, an entry per lane, and writes it to the
+//                         workspace.  The waves of a workgroup read the same rows (the second to fourth from the caches): a list
+//                         per (workgroup, query) is what bounds the number of insertions, the pass's other cost.
+//   many_finish_kernel    a workgroup per query merges the workgroups' lists to the C best candidates and A_out, the value no row
+//                         outside the list lies below; wave 0 forms the fp64 distances D of the candidates by wave_dist64_core -- the
+//                         bits the scan forms -- orders them by (D, row), writes the first `depth`, and CERTIFIES the list:
+//                             the list is every live finite row (A_out = +inf),  or  A_out - eps > D_depth   (strictly),
+//                         since |A - D| <= eps puts every row outside the list strictly behind the depth-th found, exact ties included.
+//                         A query that is not certified is appended to the flagged list.
+//   many_fallback_kernel  the flagged queries only (normally none): a workgroup per query scans the live rows in fp64 with the scan's
+//                         list insertion, and overwrites the query's row of the result.
+//
+// THE BOUND.  A(q, j) = fl(fl(qn + gn) - 2 acc / s) with qn, gn the fp32 squared norms and acc the MFMA's fp32 sum over k of
+// g_k hi_k + g_k lo_k, where x = s q, hi = fl16(x), lo = fl16(x - hi) and s = 2^(13 - e) puts the largest |x_k| into [2^13, 2^14)
+// (scaling by a power of two is exact).  With u = 2^-24, S = |q|^2 + |g|^2, |q||g| <= S / 2:
+//   split      x_k - hi_k is exact in fp32 and |x_k - hi_k - lo_k| <= 2^-22 |x_k| while hi_k and lo_k are normal halves.  A subnormal one is
+//              a component below 2^-27 of the largest; even if the matrix core FLUSHED a subnormal operand (it does not: the tests'
+//              subnormal rows), that is an absolute 2^-13 per component, sum_k |g_k| 2^-13 <= 2^-13 sqrt(d) |g| <= 2^-20.5 |x||g| as
+//              |x| >= 2^13 and d <= 2048.  Together < 2^-20 |q||g| on the dot product, 2^-20 S on the distance.
+//   MFMA       2 d exact fp16 x fp16 products summed in fp32, in an order and with an internal rounding the hardware does not
+//              promise: two units a term, 4 d u |q||g| on the dot product, 4 d u S on the distance.
+//   norms      gn: d / 2 dot2 steps of two roundings and the two lane adds, qn: d fused steps and the butterfly: <= 2 d u S together.
+//   epilogue   fl(qn + gn) and the final fused multiply-add, each one rounding of a value <= 2 S: <= 8 u S with slack.
+//   range      acc / s, qn and the scaled components may UNDERFLOW for queries far below fp32's normal range: an absolute 1e-35, far
+//              above d 2^-149.  Overflow is not bounded but detected: a live row with a finite norm whose A is not finite flags the query.
+// So |A - D| <= eps(q) = many_kappa(d) (qn + max_j gn) + 1e-35 with many_kappa(d) = (6 d + 8) 2^-24 + 2^-20, the maximum over the LIVE
+// rows with a FINITE norm (a row with a NaN / inf is never a candidate, and a dead one is never looked at).
+#include "search_scan.h"
+
+namespace {
+using namespace vtcsweep;
+
+constexpr int MANY_MAX_DEPTH = 32;     // at least 21 spare ranks in a lane-per-entry list
+constexpr int MANY_KC = 512;           // columns of a K chunk: 16 MFMA steps, 32 KB of B fragments a wave
+constexpr int MANY_KS = MANY_KC / 32;
+constexpr int MANY_MAX_BLOCKS = 1024;  // workgroups of the pass at most (four one-wave workgroups a CU): lists per query in the workspace
+constexpr int QF_DEAD = 1, QF_FALLBACK = 2;
+
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+
+inline float many_kappa(int d) { return (6.0f * d + 8.0f) / 16777216.0f + 1.0f / 1048576.0f; }
+inline int many_cdepth(int depth, int ng) { return std::min(std::min(64, ng), std::max(32, depth + 21)); }      // exact_cdepth's rule
+inline int many_qgroups(int nq) { return cdiv(nq, 16); }
+// workgroups of the pass the workspace has lists for: a workgroup of g waves holds g x 32 KB of the LDS, so 4 / g fit a CU
+inline int many_max_blocks(int ng, int nq) {
+  const int g = many_qgroups(nq), per_cu = g == 1 ? 4 : (g == 2 ? 2 : 1);      // 40 KB a wave with its lists: 160 KiB a CU
+  return (int)std::min<long long>(MANY_MAX_BLOCKS / 4 * per_cu, ((long long)ng + 15) / 16);
+}
+
+struct ManyWs {
+  double *dists64;      // [nq][depth]: the documented head
+  int *flags;           // flags[0]: the queries the fallback finished (the documented counter); flags[1 ..]: which
+  uint4 *qimg;          // [qgroups][d / 32][hi, lo][64 lanes]: B fragments
+  float *qn, *inv_s;    // [64]
+  int *qflag;           // [64]
+  float *gmax;          // [blocks]
+  int *over;            // [blocks][64]
+  float *list_a;        // [nq][cdepth][blocks]
+  int *list_i;
+  size_t total;
+};
+ManyWs many_ws(void *ws, int ng, int nq, int d, int depth) {
+  Bump b(ws);
+  ManyWs s;
+  const size_t blocks = many_max_blocks(ng, nq), entries = (size_t)nq * many_cdepth(depth, ng);
+  s.dists64 = (double *)b.take((size_t)nq * depth * sizeof(double));
+  s.flags = (int *)b.take((1 + SEARCH_MAX_Q) * sizeof(int));
+  s.qimg = (uint4 *)b.take((size_t)many_qgroups(nq) * 16 * d * 2 * sizeof(_Float16));
+  s.qn = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
+  s.inv_s = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
+  s.qflag = (int *)b.take(SEARCH_MAX_Q * sizeof(int));
+  s.gmax = (float *)b.take(blocks * sizeof(float));
+  s.over = (int *)b.take(blocks * SEARCH_MAX_Q * sizeof(int));
+  s.list_a = (float *)b.take(entries * blocks * sizeof(float));
+  s.list_i = (int *)b.take(entries * blocks * sizeof(int));
+  s.total = b.off;
+  return s;
+}
+
+// One wave per query slot (16 x qgroups of them; a slot past the last query is a dead row of zeros, as a query with a NaN / inf is).
+__global__ __launch_bounds__(64) void many_prep_kernel(const float *__restrict__ queries, int nq, int d, uint4 *__restrict__ qimg,
+                                                       float *__restrict__ qn, float *__restrict__ inv_s, int *__restrict__ qflag,
+                                                       int *__restrict__ flags, int *__restrict__ nonfinite) {
+  const int q = blockIdx.x, lane = threadIdx.x;
+  if (q == 0 && lane == 0) flags[0] = 0;
+  const float *row = queries + (size_t)min(q, nq - 1) * d;
+  float m = 0.f, n2 = 0.f;
+  bool bad = false;
+  for (int c = lane * 4; c < d; c += 256) {
+    const float4 v = *reinterpret_cast<const float4 *>(row + c);
+    bad = bad || !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
+    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    n2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, n2))));
+  }
+  const bool nonfin = __ballot(bad) != 0, dead = nonfin || q >= nq;
+  m = wave_max(dead ? 0.f : m);
+  n2 = wave_sum(n2);
+  int flag = dead ? QF_DEAD : 0, e = 13;                   // m == 0: s = 1
+  if (m > 0.f) e = ilogbf(m);
+  int se = 13 - e;                                         // s = 2^se puts m into [2^13, 2^14)
+  if (se > 126) {                                          // a query below 2^-113: s would leave fp32, the split has no bound
+    se = 126;
+    flag |= QF_FALLBACK;
+  }
+  const float s = __int_as_float((se + 127) << 23);
+  if (lane == 0) {
+    qn[q] = dead ? 0.f : n2;
+    inv_s[q] = __int_as_float((127 - se) << 23);
+    qflag[q] = flag;
+    if (nonfin && q < nq && nonfinite) atomicOr(nonfinite, 2);
+  }
+  // the B fragment of MFMA step ks: lane (kq, u) = 16 kq + u holds the 8 halves k = 32 ks + 8 kq .. + 7 of query u of the group
+  const int grp = q >> 4, u = q & 15;
+  for (int b = lane; b < d / 8; b += 64) {
+    f16x8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float x = dead ? 0.f : row[b * 8 + j] * s;
+      hi[j] = (_Float16)x;
+      lo[j] = (_Float16)(x - (float)hi[j]);
+    }
+    const int ks = b >> 2, kq = b & 3;
+    const size_t o = ((size_t)(grp * (d / 32) + ks) * 2) * 64 + kq * 16 + u;
+    qimg[o] = __builtin_bit_cast(uint4, hi);
+    qimg[o + 64] = __builtin_bit_cast(uint4, lo);
+  }
+}
+
+// The sorted candidate list of one query: entry e on lane e, ascending A, kept in the LDS ([list][lane], a float and an int: 512 bytes a
+// list, 8 KB a wave) so that the list a candidate belongs to is an ADDRESS -- sixteen lists in registers are sixteen copies of the
+// insertion behind a branch tree, and took 1.8 times as long per added query (profiles/search_many.md).  Rows arrive in ascending
+// order, so a strict compare keeps the lower row of a tie.  tau is the C-th entry (+inf until C rows have come): no row outside the
+// list lies below it.
+constexpr int MANY_LIST_BYTES = 16 * 64 * (int)(sizeof(float) + sizeof(int));      // of a wave
+// lane l's value on lane l + 1: the DPP wave shift, a move instead of __shfl_up's trip through the LDS crossbar (lane 0 keeps its own)
+__device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+// offers the wave-uniform candidate (cv, ci) to the list (la, li) = this lane's entry of it; returns the list's tau afterwards
+__device__ __forceinline__ float many_offer(float *la, int *li, float cv, int ci, int lane, int cdepth) {
+  float a = *la;
+  int i = *li;
+  const float cur = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), cdepth - 1));
+  if (!(cv < cur)) return cur;                             // an earlier row of this step may have lowered tau
+  const int pos = __popcll(__ballot(a <= cv));
+  const float ua = __builtin_bit_cast(float, wave_shr1(__builtin_bit_cast(int, a)));
+  const int ui = wave_shr1(i);
+  if (lane > pos) { a = ua; i = ui; }
+  if (lane == pos) { a = cv; i = ci; }
+  *la = a;
+  *li = i;
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), cdepth - 1));
+}
+
+template <bool MASKED, int NKS>
+__global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restrict__ gallery, const unsigned *__restrict__ live,
+                                                        const uint4 *__restrict__ qimg, const float *__restrict__ qn_all,
+                                                        const float *__restrict__ inv_s_all, const int *__restrict__ qflag, int ng, int nq, int d,
+                                                        int cdepth, float *__restrict__ list_a, int *__restrict__ list_i,
+                                                        float *__restrict__ gmax_out, int *__restrict__ over_out, int *__restrict__ nonfinite) {
+  extern __shared__ uint4 smem_many[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;        // wave: the group of 16 queries
+  const int u = lane & 15, kq = lane >> 4;
+  // an item of the walk is NKS MFMA steps of a tile (a template parameter: the loads of an item are then unconditional and the
+  // compiler counts them, so waiting for one item's fragments leaves the next item's in flight); d = 32 NKS nchunks.  Up to 512
+  // columns the wave's whole B image is RESIDENT in the LDS; a longer row reloads the item's part of it per item.
+  const int nchunks = d / (32 * NKS);
+  const bool resident = d <= MANY_KC;
+  const int img_vecs = (resident ? d / 32 : NKS) * 2 * 64;  // of a wave; the waves' lists follow the images
+  uint4 *img = smem_many + (size_t)wave * img_vecs;
+  float *la = reinterpret_cast<float *>(smem_many + (size_t)(blockDim.x >> 6) * img_vecs) + wave * (16 * 64 * 2) + lane;
+  int *li = reinterpret_cast<int *>(la + 16 * 64);       // la[64 v] / li[64 v]: this lane's entry of list v
+  const uint4 *gimg = qimg + (size_t)wave * (d / 32) * 2 * 64;
+  if (resident)
+    for (int x = lane; x < d / 32 * 2 * 64; x += 64) img[x] = gimg[x];
+  __syncthreads();
+
+  const int q = wave * 16 + u;                             // the lane's query: column u of the MFMA's result
+  const float qn = qn_all[q], m2inv_s = -2.f * inv_s_all[q];
+  const bool qdead = (qflag[q] & QF_DEAD) != 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) la[64 * v] = INFINITY, li[64 * v] = EMPTY_ROW;
+  float tau = INFINITY;                                    // of the lane's query
+  bool over = false, gallery_bad = false;
+  float gmax = 0.f;
+
+  // The walk: workgroup b takes the tiles b, b + G, ... and SKIPS a tile none of whose rows is live before anything of it is loaded, so
+  // every item that is loaded is multiplied: the loads of an item are unconditional, the compiler counts them, and waiting for one
+  // item's fragments leaves the next item's in flight.  The mask word of a tile (its address is uniform: a scalar load, which the
+  // vector loads' counter does not see) is read one tile ahead; only a run of dead tiles is searched word by word.
+  const long long n_tiles = ((long long)ng + 15) / 16, G = gridDim.x;
+  auto word_at = [&](long long t) -> unsigned {           // the 16 mask bits of tile t, as loaded
+    if constexpr (!MASKED) return 0xffffu;
+    if (t >= n_tiles) return 0;
+    return live[t >> 1] >> ((t & 1) * 16);
+  };
+  auto bits_at = [&](long long t, unsigned word) -> unsigned {      // ... of its rows inside the gallery, wave-uniform; 0 past the end
+    if (t >= n_tiles) return 0;
+    const long long left = (long long)ng - t * 16;
+    const unsigned inside = left >= 16 ? 0xffffu : (1u << left) - 1;
+    return (unsigned)uniform_of((int)(word & inside));
+  };
+  // the A fragments of an item: lane (kq, u) holds row u of the tile, halves 32 ks + 8 kq .. + 7 of the chunk.  A dead row (or one past
+  // the gallery) is pointed at a live row of the tile: its memory is not read, its results are dropped.  bits != 0.
+  auto load_frags = [&](long long t, int chunk, unsigned bits, f16x8 (&ga)[NKS]) {
+    const long long row = t * 16 + (((bits >> u) & 1) ? u : __ffs((int)bits) - 1);
+    const _Float16 *p = gallery + (size_t)row * d + chunk * (NKS * 32) + kq * 8;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) ga[ks] = *reinterpret_cast<const f16x8 *>(p + ks * 32);
+  };
+
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float nrm = 0.f;
+  auto compute = [&](long long t, int chunk, unsigned bits, const f16x8 (&ga)[NKS]) {
+    if (!resident) {                                       // every wave of the workgroup walks the same items
+      __syncthreads();
+      for (int x = lane; x < NKS * 2 * 64; x += 64) img[x] = gimg[(size_t)chunk * NKS * 2 * 64 + x];
+      __syncthreads();
+    }
+    const uint4 *bi = img + (resident ? chunk * NKS * 2 * 64 : 0) + lane;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      const f16x8 bh = __builtin_bit_cast(f16x8, bi[(ks * 2) * 64]), bl = __builtin_bit_cast(f16x8, bi[(ks * 2 + 1) * 64]);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bl, acc, 0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const half2_t h = {ga[ks][2 * j], ga[ks][2 * j + 1]};
+        nrm = __builtin_amdgcn_fdot2(h, h, nrm, false);
+      }
+    }
+    if (chunk != nchunks - 1) return;
+    // ---- the tile's epilogue: acc[i] = query u x row 4 kq + i of the tile
+    nrm += __shfl_xor(nrm, 16, 64);
+    nrm += __shfl_xor(nrm, 32, 64);                        // every lane: |g|^2 of row u
+    const bool row_live = (bits >> u) & 1, row_fin = fabsf(nrm) < INFINITY;
+    if (row_live && !row_fin) gallery_bad = true;
+    if (row_live && row_fin) gmax = fmaxf(gmax, nrm);
+    const int row0 = (int)(t * 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = 4 * kq + i;
+      const float gn = __shfl(nrm, r, 64);
+      const float A = fmaf(m2inv_s, acc[i], qn + gn);
+      const bool cand = ((bits >> r) & 1) && fabsf(gn) < INFINITY && !qdead;
+      const bool fin = fabsf(A) < INFINITY;
+      if (cand && !fin) over = true;                       // D is finite, A is not: the query goes to the fallback
+      unsigned long long m = __ballot(cand && fin && A < tau);
+      while (m) {
+        const int from = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const float cv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, A), from));
+        const int ci = row0 + 4 * (from >> 4) + i, v = from & 15;
+        const float t = many_offer(la + 64 * v, li + 64 * v, cv, ci, lane, cdepth);      // v is wave-uniform
+        if (u == v) tau = t;
+      }
+    }
+    acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    nrm = 0.f;
+  };
+
+  // two fragment sets: the loads of the next item are in flight while this one is multiplied.  After the last item the loads are
+  // issued once more for the item itself (a live tile) and dropped, which keeps their number fixed.
+  f16x8 fa[NKS], fb[NKS];
+  long long tc = blockIdx.x;
+  unsigned bc = bits_at(tc, word_at(tc));
+  while (tc < n_tiles && !bc) {
+    tc += G;
+    bc = bits_at(tc, word_at(tc));
+  }
+  if (tc < n_tiles) {                                      // uniform for the workgroup
+    unsigned w1 = word_at(tc + G);
+    int chunk = 0;
+    load_frags(tc, 0, bc, fa);
+    auto step = [&](const f16x8 (&cur)[NKS], f16x8 (&nxt)[NKS]) -> bool {
+      long long tn = tc;
+      unsigned bn = bc;
+      int cn = chunk + 1;
+      if (cn == nchunks) {
+        cn = 0;
+        tn = tc + G;
+        bn = bits_at(tn, w1);
+        while (tn < n_tiles && !bn) {
+          tn += G;
+          bn = bits_at(tn, word_at(tn));
+        }
+        w1 = word_at(tn + G);
+      }
+      const bool last = tn >= n_tiles;
+      if (last) load_frags(tc, chunk, bc, nxt);
+      else load_frags(tn, cn, bn, nxt);
+      compute(tc, chunk, bc, cur);
+      tc = tn, bc = bn, chunk = cn;
+      return !last;
+    };
+    while (step(fa, fb) && step(fb, fa)) {
+    }
+  }
+
+  if (wave == 0) {
+    const float g = wave_max(gmax);
+    if (lane == 0) gmax_out[blockIdx.x] = g;
+    if (nonfinite && __ballot(gallery_bad) && lane == 0) atomicOr(nonfinite, 1);
+  }
+  const unsigned long long ov = __ballot(over);
+  if (kq == 0 && q < nq) over_out[(size_t)blockIdx.x * SEARCH_MAX_Q + q] = ((ov >> u) & 0x0001000100010001ull) != 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int qq = wave * 16 + v;
+    if (qq < nq && lane < cdepth) {
+      const size_t o = ((size_t)qq * cdepth + lane) * gridDim.x + blockIdx.x;
+      list_a[o] = la[64 * v];
+      list_i[o] = li[64 * v];
+    }
+  }
+}
+
+// the lists the pass wrote, [query][entry][workgroup], as merge_lists reads them
+struct ManyLists {
+  const float *a;
+  const int *i;
+  int nlists, cdepth, q;
+  template <bool GROUPED>
+  __device__ __forceinline__ void get(int l, int e, double &cv, long long &ci, int &cg) const {
+    const size_t o = ((size_t)q * cdepth + e) * nlists + l;
+    cv = a[o];
+    ci = i[o];
+  }
+};
+
+__global__ __launch_bounds__(256) void many_finish_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries, ManyLists src,
+                                                          const float *__restrict__ qn, const int *__restrict__ qflag,
+                                                          const float *__restrict__ gmax_parts, const int *__restrict__ over_parts, int ng, int d,
+                                                          int depth, float kappa, int64_t id_base, int64_t *__restrict__ ids,
+                                                          float *__restrict__ dists, double *__restrict__ dists64, int *__restrict__ flags) {
+  __shared__ double sd[4][64];
+  __shared__ long long si[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = blockIdx.x, cdepth = src.cdepth, nlists = src.nlists;
+  src.q = q;
+  const int flag = qflag[q];
+  SortedList<long long, EMPTY_ID, false> wl;
+  wl.init();
+  if (!(flag & QF_DEAD)) merge_lists(wl, src, nlists, wave * 64, 256, cdepth, lane);
+  sd[wave][lane] = wl.bd;
+  si[wave][lane] = wl.bi;
+  __syncthreads();
+  if (wave != 0) return;
+  merge_lists(wl, LdsLists<long long>{&sd[1][0], &si[1][0], nullptr}, 3, 0, 64, cdepth, lane);
+  // the C best candidates by (A, row), lane e the e-th; nothing outside the list lies below a_out
+  const double a_out = __shfl(wl.bd, cdepth - 1, 64);
+  float gmax = 0.f;
+  bool over = false;
+  for (int l = lane; l < nlists; l += 64) {
+    gmax = fmaxf(gmax, gmax_parts[l]);
+    over = over || over_parts[(size_t)l * SEARCH_MAX_Q + q] != 0;
+  }
+  gmax = wave_max(gmax);
+  over = __ballot(over) != 0;
+  const int my = lane < cdepth && wl.bi != EMPTY_ID ? (int)wl.bi : -1;
+  const int n_cand = __popcll(__ballot(my >= 0));
+  double md = INFINITY;
+  constexpr int NB = 8;
+  const float *qrow = queries + (size_t)q * d;
+  for (int c0 = 0; c0 < n_cand; c0 += NB) {                // the candidates are the first n_cand lanes
+    int rows[NB];
+    double out[NB];
+#pragma unroll
+    for (int v = 0; v < NB; ++v) rows[v] = max(__shfl(my, min(c0 + v, 63), 64), 0);      // an absent slot reads row 0, dropped below
+    wave_dist64_core<NB>([&](int) { return qrow; }, [&](int v) { return gallery + (size_t)rows[v] * d; }, d, lane, out);
+#pragma unroll
+    for (int v = 0; v < NB; ++v)
+      if (lane == c0 + v) md = out[v];
+  }
+  if (my < 0) md = INFINITY;
+  int rank = 0;
+  for (int c = 0; c < n_cand; ++c) {
+    const double od = __shfl(md, c, 64);
+    const int oi = __shfl(my, c, 64);
+    if (od < md || (od == md && oi < my)) ++rank;
+  }
+  if (my >= 0 && rank < depth) {
+    const size_t o = (size_t)q * depth + rank;
+    ids[o] = id_base + my;
+    if (dists) dists[o] = (float)md;
+    dists64[o] = md;
+  }
+  if (lane >= n_cand && lane < depth) {                    // fewer candidates than depth: the tail (a dead query: the whole row)
+    const size_t o = (size_t)q * depth + lane;
+    ids[o] = -1;
+    if (dists) dists[o] = INFINITY;
+    dists64[o] = INFINITY;
+  }
+  if (flag & QF_DEAD) return;
+  const unsigned long long last = __ballot(my >= 0 && rank == depth - 1);
+  const double d_depth = last ? __shfl(md, __ffsll((long long)last) - 1, 64) : (double)INFINITY;
+  const double eps = (double)kappa * ((double)qn[q] + (double)gmax) * (1.0 + 1e-6) + 1e-35;
+  const bool whole = !(a_out < INFINITY) || n_cand >= ng;  // fewer than C candidates exist, or every row is one: nothing is outside
+  const bool sure = !over && !(flag & QF_FALLBACK) && (whole || a_out - eps > d_depth);
+  if (!sure && lane == 0) flags[1 + atomicAdd(flags, 1)] = q;
+}
+
+// The flagged queries: exact_fallback_kernel's scan over the LIVE rows of the half gallery -- fp64 distances by the sweeps' one loop,
+// four rows a step and wave, (D, row) insertion, a row with a non-finite distance rejected -- sixteen waves a query.
+__global__ __launch_bounds__(1024) void many_fallback_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
+                                                             const unsigned *__restrict__ live, int ng, int d, int depth, int64_t id_base,
+                                                             const int *__restrict__ flags, int64_t *__restrict__ ids, float *__restrict__ dists,
+                                                             double *__restrict__ dists64) {
+  __shared__ double sd[16][64];
+  __shared__ long long si[16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_flagged = flags[0];
+  for (int f = blockIdx.x; f < n_flagged; f += gridDim.x) {        // uniform for the workgroup; normally zero trips
+    const int q = flags[1 + f];
+    const float *qrow = queries + (size_t)q * d;
+    SortedList<int, EMPTY_ROW, false> wl;
+    wl.init();
+    for (long long j0 = (long long)wave * 4; j0 < ng; j0 += 64) {
+      unsigned bits = ng - j0 >= 4 ? 0xfu : (1u << (ng - j0)) - 1;
+      if (live) bits &= (unsigned)uniform_of((int)(live[j0 >> 5] >> (j0 & 31)));
+      if (!bits) continue;
+      int jj[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) jj[r] = (int)j0 + (((bits >> r) & 1) ? r : __ffs((int)bits) - 1);
+      double dist[4];
+      wave_dist64_queries<1, 4>(qrow, gallery, jj, d, lane, dist);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if ((bits >> r) & 1) wl.offer(dist[r], jj[r], 0, lane, depth);
+    }
+    sd[wave][lane] = wl.bd;
+    si[wave][lane] = wl.bi == EMPTY_ROW ? EMPTY_ID : (long long)wl.bi;
+    __syncthreads();
+    if (wave == 0) {
+      SortedList<long long, EMPTY_ID, false> m;
+      m.init();
+      merge_lists(m, LdsLists<long long>{&sd[0][0], &si[0][0], nullptr}, 16, 0, 64, depth, lane);
+      if (lane < depth) {
+        const size_t o = (size_t)q * depth + lane;
+        const bool empty = m.bi == EMPTY_ID;
+        ids[o] = empty ? -1 : id_base + m.bi;
+        if (dists) dists[o] = empty ? INFINITY : (float)m.bd;
+        dists64[o] = empty ? (double)INFINITY : m.bd;
+      }
+    }
+    __syncthreads();                                       // sd / si are reused by the next flagged query
+  }
+}
+
+bool many_args_ok(int ng, int nq, int d, int depth) { return search_args_ok(ng, nq, d, depth) && depth <= MANY_MAX_DEPTH; }
+}  // namespace
+
+extern "C" size_t vtc_l2_search_many_workspace_bytes(int n_gallery, int n_queries, int d, int depth) {
+  if (!many_args_ok(n_gallery, n_queries, d, depth)) return 0;
+  return many_ws(nullptr, n_gallery, n_queries, d, depth).total;
+}
+
+extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *queries, const uint32_t *live, int ng, int nq, int d, int depth,
+                                       int64_t id_base, int64_t *ids, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream_) {
+  const char *name = "l2_search_many_half";
+  hipStream_t stream = (hipStream_t)stream_;
+  VTC_CHECK(gallery && queries && ids, "%s: null argument", name);
+  if (check_shape(name, ng, nq, SEARCH_MAX_Q, " (more queries: slice them)", nullptr, &depth, d, id_base)) return 1;
+  VTC_CHECK(depth <= MANY_MAX_DEPTH, "%s: depth=%d must be at most %d (deeper: vtc_l2_search_half)", name, depth, MANY_MAX_DEPTH);
+  const size_t need = many_ws(nullptr, ng, nq, d, depth).total;
+  VTC_CHECK(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", name, ws_bytes, need);
+
+  const ManyWs s = many_ws(ws, ng, nq, d, depth);
+  const _Float16 *g = reinterpret_cast<const _Float16 *>(gallery);
+  const int qg = many_qgroups(nq), cdepth = many_cdepth(depth, ng);
+  const int per_cu = qg == 1 ? 4 : (qg == 2 ? 2 : 1);
+  const int blocks = std::min(many_max_blocks(ng, nq), per_cu * vtcgemm::num_cus());
+  const int ksteps = d / 32, nks = ksteps % 16 == 0 ? 16 : (ksteps % 8 == 0 ? 8 : (ksteps % 4 == 0 ? 4 : 2));      // d % 64 == 0: ksteps is even
+  const size_t lds = (size_t)qg * ((d <= MANY_KC ? ksteps : nks) * 2 * 64 * sizeof(uint4) + MANY_LIST_BYTES);      // at most all 160 KiB of a CU
+  // the pass of this call: MASKED by `live`, NKS the largest of 16, 8, 4, 2 MFMA steps an item that divides the row
+  auto pass = [&](auto masked, auto steps) -> int {
+    constexpr bool MASKED = decltype(masked)::value;
+    constexpr int NKS = decltype(steps)::value;
+    static PerDeviceOnce attr;
+    if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&many_pass_kernel<MASKED, NKS>), 4 * (MANY_KS * 2 * 64 * (int)sizeof(uint4) + MANY_LIST_BYTES), name)) return 1;
+    hipLaunchKernelGGL((many_pass_kernel<MASKED, NKS>), dim3(blocks), dim3(64 * qg), lds, stream, g, live, s.qimg, s.qn, s.inv_s, s.qflag, ng, nq, d,
+                       cdepth, s.list_a, s.list_i, s.gmax, s.over, nonfinite);
+    return 0;
+  };
+  auto pass_of = [&](auto masked) -> int {
+    if (nks == 16) return pass(masked, std::integral_constant<int, 16>{});
+    if (nks == 8) return pass(masked, std::integral_constant<int, 8>{});
+    if (nks == 4) return pass(masked, std::integral_constant<int, 4>{});
+    return pass(masked, std::integral_constant<int, 2>{});
+  };
+
+  hipLaunchKernelGGL(many_prep_kernel, dim3(qg * 16), dim3(64), 0, stream, queries, nq, d, s.qimg, s.qn, s.inv_s, s.qflag, s.flags, nonfinite);
+  VTC_LAUNCH_CHECK2(name, "prep");
+  if (live ? pass_of(std::true_type{}) : pass_of(std::false_type{})) return 1;
+  VTC_LAUNCH_CHECK2(name, "pass");
+  hipLaunchKernelGGL(many_finish_kernel, dim3(nq), dim3(256), 0, stream, g, queries, ManyLists{s.list_a, s.list_i, blocks, cdepth, 0}, s.qn, s.qflag,
+                     s.gmax, s.over, ng, d, depth, many_kappa(d), id_base, ids, dists, s.dists64, s.flags);
+  VTC_LAUNCH_CHECK2(name, "finish");
+  hipLaunchKernelGGL(many_fallback_kernel, dim3(nq), dim3(1024), 0, stream, g, queries, live, ng, d, depth, id_base, s.flags, ids, dists, s.dists64);
+  VTC_LAUNCH_CHECK2(name, "fallback");
+  return 0;
+}

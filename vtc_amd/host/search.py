@@ -143,7 +143,9 @@ class VideoIndex:
     a stored row is the unit row rounded to 11 significant bits per component, and every search is exact over those stored rows (scores
     are 1 - D/2 of them).  A half index ALWAYS searches with the scan (vtc_l2_search_half), in slices of 64 queries and by the masked
     route's rules: vtc_l2_topk reads fp32 rows, so ROUTE_TOPK_MIN_QUERIES does not apply, and many-query batches are slower than on
-    an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries).  ``converted`` moves an index over.
+    an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries) -- through ``search``.  ``search_many``
+    is the batch form: the same result, and on a half index with k <= 32 one pass of the stored rows through the matrix cores per 64
+    queries with an exact fp64 finish (vtc_l2_search_many_half, profiles/search_many.md).  ``converted`` moves an index over.
     ``exclude`` / ``exclude_videos`` (one row or one video per query that it is never given), ``similar`` and ``similar_videos`` (the
     neighbours of a stored row without itself / without its own video) are the excluding scan (vtc_l2_search_excluding), by the same
     rules: any number of queries in slices of 64, only enqueued.  ``search_videos(after=)`` and ``search_videos_deep`` page the grouped
@@ -159,6 +161,18 @@ class VideoIndex:
     #: 12 is the first count at which vtc_l2_topk wins by more than 5 %.  (vtc_l2_topk takes 40 - 70 % longer at 9, 10 and 11 queries,
     #: as at 1 and 2, than at 8 and 12: unexplained, that entry is not changed here.  13 - 15 queries were not measured.)
     ROUTE_TOPK_MIN_QUERIES = 12
+    #: queries per call from which search_many() on a HALF index goes through ops.l2_search_many (k <= 32) instead of the scan.
+    #: Measured, profiles/search_many.md (d = 512, depth 11, medians of 30 alternating calls; us at 10^5 / 10^6 half rows, new entry vs
+    #: the scan over the same rows; in brackets under a random 50 % mask):
+    #:    8 queries   209.0 vs 242.8 (1.16 x) [188.4 vs 186.8, 0.99 x]       386.1 vs  1 454.5 (3.77 x) [2.45 x]   level at 10^5 masked
+    #:    9           221.1 vs 362.8 (1.64 x) [199.5 vs 264.6, 1.33 x]       420.5 vs  2 595.3 (6.17 x) [3.86 x]   new entry faster
+    #:   12           252.5 vs 381.6 (1.51 x) [223.4 vs 274.4, 1.23 x]       482.6 vs  2 639.5 (5.47 x) [3.48 x]   new entry faster
+    #:   16           298.4 vs 415.4 (1.39 x) [1.19 x]                       579.2 vs  2 740.7 (4.73 x) [3.09 x]   new entry faster
+    #:   32           355.4 vs 746.6 (2.10 x) [1.72 x]                       717.3 vs  5 197.7 (7.25 x) [4.62 x]   new entry faster
+    #:   64           400.1 vs 1 408.0 (3.52 x) [2.67 x]                     882.8 vs 10 088.7 (11.4 x) [7.05 x]   new entry faster
+    #: 9 is the first count from which the new entry wins by more than 5 % at both sizes, masked or not (9 is from the tool's second
+    #: run, --queries 8,9,10,11,12, where 10 and 11 won as well): the scan starts its second gallery pass there.
+    ROUTE_MANY_MIN_QUERIES = 9
     MAX_K = 64                # one list entry per lane of a wavefront, as everywhere in the sweeps
     STORAGE = {"float32": torch.float32, "float16": torch.float16}      # the state dict's names of the storage dtypes
 
@@ -435,6 +449,25 @@ class VideoIndex:
             raise ValueError("VideoIndex.search: no queries")
         ws = self._workspace(L.lib().vtc_l2_topk_workspace_bytes(self._n, q.shape[0], self.width, L.SWEEP_EXACT, 0))
         ids, dists = ops.l2_topk(self.rows, q, k, precision=L.SWEEP_EXACT, ws=ws)
+        return ids, 1.0 - dists / 2.0
+
+    def search_many(self, queries, k, subset=None):
+        """``search(queries, k, subset)`` for a BATCH: the same (ids [Q, k], scores [Q, k]), bit for bit, on every index.  On a half
+        index with k <= 32 and at least ROUTE_MANY_MIN_QUERIES queries the slices of 64 go through vtc_l2_search_many_half -- one
+        pass of the stored half rows through the matrix cores per slice and an exact fp64 finish, where ``search`` scans the gallery
+        once per 8 queries -- by the masked route's rules: removed rows and ``subset`` honoured, only enqueued, no host sync, a
+        non-finite query a row of -1 / -inf.  In every other case (an fp32 index, k above 32, fewer queries) the call IS ``search``."""
+        k = self._checked_k(k, "search_many")
+        if self.storage != torch.float16 or k > ops.SEARCH_MANY_MAX_DEPTH or len(queries) < self.ROUTE_MANY_MIN_QUERIES:
+            return self.search(queries, k, subset=subset)
+        self._check_subset(subset, "search_many")
+        q = self._prepared(queries, "queries", check=False)
+        words = self._live_words() if subset is None else subset.words()
+        # the last slice may need MORE than a full one: fewer queries a workgroup, more workgroups, more lists
+        sizes = {min(q.shape[0], ops.SEARCH_MAX_QUERIES), q.shape[0] % ops.SEARCH_MAX_QUERIES} - {0}
+        ws = self._workspace(max(ops.l2_search_many_workspace_bytes(self._n, s, self.width, k) for s in sizes))
+        out = [ops.l2_search_many(self.rows, qs, k, live=words, ws=ws)[:2] for (qs,) in self._sliced(q)]
+        ids, dists = out[0] if len(out) == 1 else [torch.cat(column) for column in zip(*out)]
         return ids, 1.0 - dists / 2.0
 
     def _checked_k(self, k, what, deep=False):

@@ -494,6 +494,44 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     return ids, dists, bits
 
 
+SEARCH_MANY_MAX_DEPTH = 32    # vtc_l2_search_many_half's limit: 21 spare ranks in a lane-per-entry candidate list
+
+
+@on_device
+def l2_search_many(gallery_half: torch.Tensor, queries: torch.Tensor, depth: int, id_base: int = 0, live: Optional[torch.Tensor] = None,
+                   return_dists: bool = True, ws: Optional[torch.Tensor] = None, nonfinite: Optional[torch.Tensor] = None):
+    """``l2_search`` of a ``torch.float16`` gallery for MANY queries (vtc_l2_search_many_half): at most 64 queries, depth <= 32, the same
+    (ids, dists or None, nonfinite_bits) with the same bits -- the fp64 distances ``search_dists64(ws, Q, depth)`` of a caller's ``ws``
+    (at least ``l2_search_many_workspace_bytes``) included -- by ONE pass of the gallery through the matrix cores and an exact fp64 finish
+    instead of a scan per 8 queries.  ``live``: ``l2_search``'s mask.  ``nonfinite``: the int32 [1] device word the bits are ORed into
+    (None: a fresh zero word).  ``search_many_stats(ws, Q, depth)`` tells how many queries needed the exact fallback scan.  An fp32
+    gallery raises ValueError: the pass multiplies the stored half rows as they are.  Only enqueued."""
+    gallery, queries, _, ng, nq, d = _search_inputs("l2_search_many", gallery_half, queries)
+    if gallery.dtype != torch.float16:
+        raise ValueError(f"l2_search_many: the gallery must be torch.float16 (the stored rows are the matrix cores' operand), got {gallery.dtype}")
+    live = _live_arg(live, ng, gallery.device, "l2_search_many")
+    lib = L.lib()
+    ws = _search_ws_arg(ws, lib.vtc_l2_search_many_workspace_bytes(ng, nq, d, depth), gallery.device, "l2_search_many")
+    ids, _, dists, bits = _search_outputs(nq, depth, gallery.device, return_dists, grouped=False)
+    if nonfinite is not None:
+        bits = _gpu(nonfinite, torch.int32, "nonfinite")
+    L.check(lib.vtc_l2_search_many_half(gallery.data_ptr(), queries.data_ptr(), _ptr(live), ng, nq, d, depth, int(id_base), ids.data_ptr(),
+                                        _ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_search_many_half")
+    return ids, dists, bits
+
+
+def l2_search_many_workspace_bytes(n_gallery: int, n_queries: int, d: int, depth: int) -> int:
+    """0 for a shape vtc_l2_search_many_half refuses."""
+    return int(L.lib().vtc_l2_search_many_workspace_bytes(int(n_gallery), int(n_queries), int(d), int(depth)))
+
+
+def search_many_stats(ws: torch.Tensor, n_queries: int, depth: int) -> dict:
+    """What the last ``l2_search_many`` on workspace ``ws`` left behind its fp64 head (include/vtc_hip.h): ``fallback_queries``, the
+    queries of that call that the error bound could not certify and the exact fallback scan finished.  A device-to-host read."""
+    at = (n_queries * depth * 8 + 255) // 256 * 256
+    return {"fallback_queries": int(ws[at:at + 4].view(torch.int32).item())}
+
+
 @on_device
 def row_mask_pack(flags: torch.Tensor, and_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Row flags (uint8 or bool [n], non-zero = the row takes part) -> the int32 words [ceil(n / 32)] l2_search's ``live`` takes
