@@ -244,16 +244,10 @@ RangeWs range_ws(void *ws, int ng, int nq) {
 template <int NQ, int NR, bool MASKED, typename G>
 int launch_count(const G *gallery, const float *queries, const unsigned *live, const double *radius2, int ng, int nq, int d, const RangeWs &s,
                  int tiles, int *nonfinite, hipStream_t stream) {
-  static std::atomic<int> resident[64][RANGE_MAX_D / 64];      // per instantiation, LDS (d / 64) and device: asked once
+  static ResidentTable resident;                           // of this instantiation
+  static_assert(RANGE_MAX_D / 64 == 32, "ResidentTable's columns");
   const size_t lds = (size_t)NQ * d * sizeof(float);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  std::atomic<int> &slot = resident[dev][d / 64 - 1];
-  int per_cu = slot.load(std::memory_order_relaxed);
-  if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, range_count_kernel<NQ, NR, MASKED, G>, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    slot.store(per_cu, std::memory_order_relaxed);
-  }
+  const int per_cu = resident_per_cu(resident, d, [&] { return max_resident(range_count_kernel<NQ, NR, MASKED, G>, lds, 1); });
   const int blocks = std::max(1, std::min(range_max_blocks(ng), std::min(per_cu, 4) * vtcgemm::num_cus()));
   hipLaunchKernelGGL((range_count_kernel<NQ, NR, MASKED, G>), dim3(blocks, tiles), dim3(256), lds, stream, gallery, queries, live, radius2, ng, nq, d,
                      range_words(ng), s.words, s.cnt, nonfinite);

@@ -2,8 +2,8 @@
 // The result is vtc_l2_search_half's without groups, bit for bit (include/vtc_hip.h); only the way there differs.  The scan of search.hip
 // forms every (query, row) distance in fp64, which at 64 queries is all it does: 8 gallery passes of fp64 arithmetic.  A half row already
 // IS an fp16 MFMA operand, so here the gallery is streamed ONCE through v_mfma_f32_16x16x32_f16 for an APPROXIMATE distance A, a few more
-// candidates than were asked for are kept, and the scheme of the sweeps' exact finish (sweep_topk.hip: exact_rerank_kernel /
-// exact_fallback_kernel) makes the answer exact again.  Four launches, whatever the data:
+// candidates than were asked for are kept, and the exact finish the sweeps use too (exact_list.h: the fp64 re-rank of the candidates, the
+// brute-force scan behind an uncertified list) makes the answer exact again.  Four launches, whatever the data:
 //
 //   many_prep_kernel      a wave per query: |q|^2, the power-of-two scale s, the fp16 (hi, lo) split of s q laid out as the MFMA's B
 //                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.
@@ -16,13 +16,13 @@
 //                         workspace.  The waves of a workgroup read the same rows (the second to fourth from the caches): a list
 //                         per (workgroup, query) is what bounds the number of insertions, the pass's other cost.
 //   many_finish_kernel    a workgroup per query merges the workgroups' lists to the C best candidates and A_out, the value no row
-//                         outside the list lies below; wave 0 forms the fp64 distances D of the candidates by wave_dist64_core -- the
-//                         bits the scan forms -- orders them by (D, row), writes the first `depth`, and CERTIFIES the list:
+//                         outside the list lies below; wave 0 forms the fp64 distances D of the candidates and their order by (D, row)
+//                         (rerank64: the bits the scan forms), writes the first `depth`, and CERTIFIES the list:
 //                             the list is every live finite row (A_out = +inf),  or  A_out - eps > D_depth   (strictly),
 //                         since |A - D| <= eps puts every row outside the list strictly behind the depth-th found, exact ties included.
 //                         A query that is not certified is appended to the flagged list.
-//   many_fallback_kernel  the flagged queries only (normally none): a workgroup per query scans the live rows in fp64 with the scan's
-//                         list insertion, and overwrites the query's row of the result.
+//   many_fallback_kernel  the flagged queries only (normally none): a workgroup per query scans the live rows in fp64 (fallback_scan, with
+//                         the scan's list insertion), and overwrites the query's row of the result.
 //
 // THE BOUND.  A(q, j) = fl(fl(qn + gn) - 2 acc / s) with qn, gn the fp32 squared norms and acc the MFMA's fp32 sum over k of
 // g_k hi_k + g_k lo_k, where x = s q, hi = fl16(x), lo = fl16(x - hi) and s = 2^(13 - e) puts the largest |x_k| into [2^13, 2^14)
@@ -39,6 +39,7 @@
 //              above d 2^-149.  Overflow is not bounded but detected: a live row with a finite norm whose A is not finite flags the query.
 // So |A - D| <= eps(q) = many_kappa(d) (qn + max_j gn) + 1e-35 with many_kappa(d) = (6 d + 8) 2^-24 + 2^-20, the maximum over the LIVE
 // rows with a FINITE norm (a row with a NaN / inf is never a candidate, and a dead one is never looked at).
+#include "exact_list.h"
 #include "search_scan.h"
 
 namespace {
@@ -53,7 +54,6 @@ constexpr int QF_DEAD = 1, QF_FALLBACK = 2;
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
 inline float many_kappa(int d) { return (6.0f * d + 8.0f) / 16777216.0f + 1.0f / 1048576.0f; }
-inline int many_cdepth(int depth, int ng) { return std::min(std::min(64, ng), std::max(32, depth + 21)); }      // exact_cdepth's rule
 inline int many_qgroups(int nq) { return cdiv(nq, 16); }
 // workgroups of the pass the workspace has lists for: a workgroup of g waves holds g x 32 KB of the LDS, so 4 / g fit a CU
 inline int many_max_blocks(int ng, int nq) {
@@ -76,7 +76,7 @@ struct ManyWs {
 ManyWs many_ws(void *ws, int ng, int nq, int d, int depth) {
   Bump b(ws);
   ManyWs s;
-  const size_t blocks = many_max_blocks(ng, nq), entries = (size_t)nq * many_cdepth(depth, ng);
+  const size_t blocks = many_max_blocks(ng, nq), entries = (size_t)nq * exact_cdepth(depth, ng);
   s.dists64 = (double *)b.take((size_t)nq * depth * sizeof(double));
   s.flags = (int *)b.take((1 + SEARCH_MAX_Q) * sizeof(int));
   s.qimg = (uint4 *)b.take((size_t)many_qgroups(nq) * 16 * d * 2 * sizeof(_Float16));
@@ -369,27 +369,9 @@ __global__ __launch_bounds__(256) void many_finish_kernel(const _Float16 *__rest
   gmax = wave_max(gmax);
   over = __ballot(over) != 0;
   const int my = lane < cdepth && wl.bi != EMPTY_ID ? (int)wl.bi : -1;
-  const int n_cand = __popcll(__ballot(my >= 0));
-  double md = INFINITY;
-  constexpr int NB = 8;
-  const float *qrow = queries + (size_t)q * d;
-  for (int c0 = 0; c0 < n_cand; c0 += NB) {                // the candidates are the first n_cand lanes
-    int rows[NB];
-    double out[NB];
-#pragma unroll
-    for (int v = 0; v < NB; ++v) rows[v] = max(__shfl(my, min(c0 + v, 63), 64), 0);      // an absent slot reads row 0, dropped below
-    wave_dist64_core<NB>([&](int) { return qrow; }, [&](int v) { return gallery + (size_t)rows[v] * d; }, d, lane, out);
-#pragma unroll
-    for (int v = 0; v < NB; ++v)
-      if (lane == c0 + v) md = out[v];
-  }
-  if (my < 0) md = INFINITY;
-  int rank = 0;
-  for (int c = 0; c < n_cand; ++c) {
-    const double od = __shfl(md, c, 64);
-    const int oi = __shfl(my, c, 64);
-    if (od < md || (od == md && oi < my)) ++rank;
-  }
+  const int n_cand = __popcll(__ballot(my >= 0));          // the candidates are the first n_cand lanes
+  double md;
+  const int rank = rerank64(queries + (size_t)q * d, gallery, my, n_cand, d, lane, md);
   if (my >= 0 && rank < depth) {
     const size_t o = (size_t)q * depth + rank;
     ids[o] = id_base + my;
@@ -411,8 +393,8 @@ __global__ __launch_bounds__(256) void many_finish_kernel(const _Float16 *__rest
   if (!sure && lane == 0) flags[1 + atomicAdd(flags, 1)] = q;
 }
 
-// The flagged queries: exact_fallback_kernel's scan over the LIVE rows of the half gallery -- fp64 distances by the sweeps' one loop,
-// four rows a step and wave, (D, row) insertion, a row with a non-finite distance rejected -- sixteen waves a query.
+// The flagged queries: the brute-force scan over the LIVE rows of the half gallery, a row with a non-finite distance rejected (fallback_scan,
+// exact_list.h) -- sixteen waves a query.
 __global__ __launch_bounds__(1024) void many_fallback_kernel(const _Float16 *__restrict__ gallery, const float *__restrict__ queries,
                                                              const unsigned *__restrict__ live, int ng, int d, int depth, int64_t id_base,
                                                              const int *__restrict__ flags, int64_t *__restrict__ ids, float *__restrict__ dists,
@@ -423,37 +405,8 @@ __global__ __launch_bounds__(1024) void many_fallback_kernel(const _Float16 *__r
   const int n_flagged = flags[0];
   for (int f = blockIdx.x; f < n_flagged; f += gridDim.x) {        // uniform for the workgroup; normally zero trips
     const int q = flags[1 + f];
-    const float *qrow = queries + (size_t)q * d;
-    SortedList<int, EMPTY_ROW, false> wl;
-    wl.init();
-    for (long long j0 = (long long)wave * 4; j0 < ng; j0 += 64) {
-      unsigned bits = ng - j0 >= 4 ? 0xfu : (1u << (ng - j0)) - 1;
-      if (live) bits &= (unsigned)uniform_of((int)(live[j0 >> 5] >> (j0 & 31)));
-      if (!bits) continue;
-      int jj[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) jj[r] = (int)j0 + (((bits >> r) & 1) ? r : __ffs((int)bits) - 1);
-      double dist[4];
-      wave_dist64_queries<1, 4>(qrow, gallery, jj, d, lane, dist);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if ((bits >> r) & 1) wl.offer(dist[r], jj[r], 0, lane, depth);
-    }
-    sd[wave][lane] = wl.bd;
-    si[wave][lane] = wl.bi == EMPTY_ROW ? EMPTY_ID : (long long)wl.bi;
-    __syncthreads();
-    if (wave == 0) {
-      SortedList<long long, EMPTY_ID, false> m;
-      m.init();
-      merge_lists(m, LdsLists<long long>{&sd[0][0], &si[0][0], nullptr}, 16, 0, 64, depth, lane);
-      if (lane < depth) {
-        const size_t o = (size_t)q * depth + lane;
-        const bool empty = m.bi == EMPTY_ID;
-        ids[o] = empty ? -1 : id_base + m.bi;
-        if (dists) dists[o] = empty ? INFINITY : (float)m.bd;
-        dists64[o] = empty ? (double)INFINITY : m.bd;
-      }
-    }
+    const auto m = fallback_scan<true, 16>(queries + (size_t)q * d, gallery, live, ng, d, depth, &sd[0][0], &si[0][0]);
+    if (wave == 0) write_result_row(m, q, depth, lane, id_base, ids, dists, dists64);
     __syncthreads();                                       // sd / si are reused by the next flagged query
   }
 }
@@ -478,7 +431,7 @@ extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *que
 
   const ManyWs s = many_ws(ws, ng, nq, d, depth);
   const _Float16 *g = reinterpret_cast<const _Float16 *>(gallery);
-  const int qg = many_qgroups(nq), cdepth = many_cdepth(depth, ng);
+  const int qg = many_qgroups(nq), cdepth = exact_cdepth(depth, ng);
   const int per_cu = qg == 1 ? 4 : (qg == 2 ? 2 : 1);
   const int blocks = std::min(many_max_blocks(ng, nq), per_cu * vtcgemm::num_cus());
   const int ksteps = d / 32, nks = ksteps % 16 == 0 ? 16 : (ksteps % 8 == 0 ? 8 : (ksteps % 4 == 0 ? 4 : 2));      // d % 64 == 0: ksteps is even

@@ -4,7 +4,7 @@
 // driver (run_search); the kernels keep internal linkage, so each file holds only the instantiations its entries launch --
 // tests/test_build_search_no_spills.py pins search.hip's by name and number, and the SET ones live in search_sets.hip.
 #pragma once
-#include "search_walk.h"
+#include "exact_list.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -14,96 +14,8 @@ using namespace vtcsweep;
 
 constexpr int SEARCH_MAX_Q = 64, SEARCH_MAX_DEPTH = 64, SEARCH_MAX_D = 2048, SEARCH_MAX_PARTS = 64;
 constexpr int SEARCH_MAX_BLOCKS = 1024;       // workgroups of a scan (4 per CU on a 256-CU part): the number of lists per query in the workspace
-constexpr int EMPTY_ROW = 0x7fffffff;         // index of an empty list slot (distance +inf)
-constexpr long long EMPTY_ID = 0x7fffffffffffffffll;
 
-// A sorted list of (fp64 distance, index) keys, one entry per lane, ascending; the first `depth` lanes are the list, (tau, tau_i) its last
-// key, wave-uniform.  Empty slots hold (+inf, EMPTY).  Ungrouped, the insertion is exact_fallback_kernel's `offer` (sweep_topk.hip).
-//
-// GROUPED: every entry carries the group id of its row (bg), and over all 64 lanes -- not only the first `depth` -- no two non-empty
-// entries share a group.  An empty slot is known by its index (EMPTY), never by bg: every int is a legal group id.  A candidate that has
-// passed `beats` meets the lane p_old that holds its group, if any (one more ballot):
-//   that entry is before the candidate         -> the candidate is dropped;
-//   otherwise, with pos the candidate's place  -> the lanes (pos, p_old] take their left neighbour's entry, lane pos the candidate, the
-//                                                 lanes above p_old keep theirs: the group's old entry is the one that leaves;
-//   no lane holds the group                    -> p_old = 63, the ungrouped shift of everything above pos.
-// Entries only ever move towards higher lanes, so what lies past the depth-th never comes back: a row that does not beat the depth-th
-// changes nothing of the first `depth`, whether its group is held (by an entry that is then not worse than the depth-th, or by one
-// past it) or not -- `beats` is the ungrouped list's one compare.  A group no lane holds has no row so far that was before the depth-th
-// key of its time (it would still be held, or has left over lane 63 behind 64 closer groups), and that key only falls: inserting is right.
-template <bool GROUPED>
-struct EntryGroup {
-  int bg;
-};
-template <>
-struct EntryGroup<false> {};
-template <typename I, I EMPTY, bool GROUPED>
-struct SortedList : EntryGroup<GROUPED> {
-  static constexpr bool grouped = GROUPED;
-  double bd, tau;
-  I bi, tau_i;
-  __device__ __forceinline__ void init() {
-    bd = tau = INFINITY;
-    bi = tau_i = EMPTY;
-    if constexpr (GROUPED) this->bg = 0;
-  }
-  // wave-uniform candidate: is it finite and before the depth-th entry?
-  __device__ __forceinline__ bool beats(double cv, I ci) const { return cv < INFINITY && (cv < tau || (cv == tau && ci < tau_i)); }
-  // cg: the candidate's group, not looked at without GROUPED
-  __device__ __forceinline__ void insert(double cv, I ci, int cg, int lane, int depth) {
-    const bool less = bd < cv || (bd == cv && bi < ci);
-    const int pos = __popcll(__ballot(less));              // <= depth - 1: the candidate is before the depth-th
-    if constexpr (GROUPED) {
-      const unsigned long long held = __ballot(bi != EMPTY && this->bg == cg);
-      const int p_old = held ? __ffsll((long long)held) - 1 : 63;
-      if (p_old < pos) return;                             // the lanes below pos are the entries before the candidate (wave-uniform)
-      const double ud = __shfl_up(bd, 1, 64);
-      const I ui = __shfl_up(bi, 1, 64);
-      const int ug = __shfl_up(this->bg, 1, 64);
-      if (lane > pos && lane <= p_old) { bd = ud; bi = ui; this->bg = ug; }
-      if (lane == pos) { bd = cv; bi = ci; this->bg = cg; }
-    } else {
-      const double ud = __shfl_up(bd, 1, 64);
-      const I ui = __shfl_up(bi, 1, 64);
-      if (lane > pos) { bd = ud; bi = ui; }
-      if (lane == pos) { bd = cv; bi = ci; }
-    }
-    tau = uniform_f64(__shfl(bd, depth - 1, 64));
-    tau_i = uniform_of(__shfl(bi, depth - 1, 64));
-  }
-  __device__ __forceinline__ void offer(double cv, I ci, int cg, int lane, int depth) {
-    if (beats(cv, ci)) insert(cv, ci, cg, lane, depth);
-  }
-};
-
-// Merges the sorted lists list0, list0 + stride, ... < nlists into wl, 64 lists at a time: lane l follows list l0 + l entry by entry
-// (src.get<grouped>(list, e, cv, ci, cg): the entry, cv = +inf for an empty one, cg its group for a grouped list) and drops out at the
-// first entry that does not beat the current depth-th -- the rest of a sorted list cannot either.  The entries that do are offered one
-// by one; an entry that beats the depth-th but whose group a better entry holds is dropped by the insertion and the lane goes on.
-template <typename List, typename Src>
-__device__ __forceinline__ void merge_lists(List &wl, Src src, int nlists, int list0, int stride, int depth, int lane) {
-  for (int l0 = list0; l0 < nlists; l0 += stride) {       // wave-uniform
-    const int l = l0 + lane;
-    bool alive = l < nlists;
-    for (int e = 0; e < depth; ++e) {
-      double cv = INFINITY;
-      long long ci = EMPTY_ID;
-      int cg = 0;
-      if (alive) src.template get<List::grouped>(l, e, cv, ci, cg);
-      alive = alive && wl.beats(cv, ci);
-      unsigned long long m = __ballot(alive);
-      if (!m) break;
-      while (m) {
-        const int from = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if constexpr (List::grouped) wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), __shfl(cg, from, 64), lane, depth);
-        else wl.offer(__shfl(cv, from, 64), __shfl(ci, from, 64), 0, lane, depth);
-      }
-    }
-  }
-}
-
-// The three places lists are read from.  Each carries the entries' groups (g / sg), which only get<true> reads.
+// The places lists are read from, besides the LDS (LdsLists, exact_list.h).  Each carries the entries' groups (g), which only get<true> reads.
 // the lists the scan's workgroups wrote: [query][entry][list], so that the 64 lanes of a merge step read neighbours
 struct ScanLists {
   static constexpr bool groups_out = true;                // a grouped merge of these writes out_groups
@@ -144,20 +56,6 @@ struct PartLists {
     if constexpr (GROUPED) cg = g[o];
   }
 };
-// the four waves' lists of a workgroup in the LDS: sd / si / sg [4][64].  I: how the index is kept there (below).
-template <typename I>
-struct LdsLists {
-  const double *sd;
-  const I *si;
-  const int *sg;
-  template <bool GROUPED>
-  __device__ __forceinline__ void get(int l, int e, double &cv, long long &ci, int &cg) const {
-    cv = sd[l * 64 + e];
-    ci = si[l * 64 + e];                                   // an empty entry's distance is +inf: it is never offered
-    if constexpr (GROUPED) cg = sg[l * 64 + e];
-  }
-};
-
 // LDS of the scan: the query tile, then (re-used) the waves' lists of the tile's queries -- SET: of the tile's one set -- 16 bytes an entry
 constexpr size_t scan_lds_bytes(int nq_tile, int d, bool set = false) {
   const size_t tile = (size_t)nq_tile * d * sizeof(float), lists = (size_t)(set ? 1 : nq_tile) * 4 * 64 * (sizeof(double) + sizeof(long long));
@@ -377,7 +275,7 @@ __global__ __launch_bounds__(256) void merge_kernel(Src src, int nlists, int dep
   __syncthreads();
   if (wave != 0) return;
   merge_lists(wl, LdsLists<long long>{&sd[1][0], &si[1][0], GROUPED ? &sg[1][0] : nullptr}, 3, 0, 64, depth, lane);
-  if (lane < depth) {
+  if (lane < depth) {                                      // write_result_row's block, with the group in its place
     const size_t o = (size_t)q * depth + lane;
     const bool empty = wl.bi == EMPTY_ID;
     ids[o] = empty ? -1 : id_base + wl.bi;
@@ -422,22 +320,15 @@ SearchWs search_ws(void *ws, int ng, int nq, int depth, bool grouped, int tiles 
 // SET: the same rule among the set scans, whose plain one is the baseline; `tiles` is then sets x tiles of a set.
 template <typename G, int NQ, int NR, bool MASKED, bool GROUPED, bool AFTER, bool EXCL, bool SET>
 int launch_scan(const ScanArgs &a, int tiles, hipStream_t stream) {
-  // resident workgroups per CU: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device -- asked once, as num_cus() is
-  static std::atomic<int> resident[64][SEARCH_MAX_D / 64];
+  static ResidentTable resident;                          // of this instantiation
+  static_assert(SEARCH_MAX_D / 64 == 32, "ResidentTable's columns");
   const size_t lds = scan_lds_bytes(NQ, a.d, SET);
   using GT = std::conditional_t<SET, SetOf<G>, G>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  std::atomic<int> &slot = resident[dev][a.d / 64 - 1];
-  int per_cu = slot.load(std::memory_order_relaxed);
-  if (per_cu == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, scan_kernel<GT, NQ, NR, false, false, false, false>, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-    if constexpr (MASKED || GROUPED || AFTER || EXCL) {
-      int own = per_cu;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&own, scan_kernel<GT, NQ, NR, MASKED, GROUPED, AFTER, EXCL>, 256, lds) == hipSuccess && own >= 1) per_cu = std::min(per_cu, own);
-    }
-    slot.store(per_cu, std::memory_order_relaxed);
-  }
+  const int per_cu = resident_per_cu(resident, a.d, [&] {
+    int n = max_resident(scan_kernel<GT, NQ, NR, false, false, false, false>, lds, 1);
+    if constexpr (MASKED || GROUPED || AFTER || EXCL) n = std::min(n, max_resident(scan_kernel<GT, NQ, NR, MASKED, GROUPED, AFTER, EXCL>, lds, n));
+    return n;
+  });
   const long long n_steps = ((long long)a.ng + NR - 1) / NR;
   const int blocks = (int)std::min<long long>(std::min(search_max_lists(a.ng), std::min(per_cu, 4) * vtcgemm::num_cus()), (n_steps + 3) / 4);
   hipLaunchKernelGGL((scan_kernel<GT, NQ, NR, MASKED, GROUPED, AFTER, EXCL>), dim3(blocks, tiles), dim3(256), lds, stream,

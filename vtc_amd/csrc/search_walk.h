@@ -1,6 +1,6 @@
 // search_walk.h -- how the query-time kernels walk a stored gallery (search.hip's scan and mark pass, range.hip's count pass): the tile of
 // queries in the LDS, the cursors of a page, the rows of a step under a row mask, and the tile shapes.  One copy, so that the three kernels
-// cannot drift.
+// cannot drift.  Host side, the cached question how many workgroups of a persistent grid a CU holds (resident_per_cu).
 #pragma once
 #include "sweep_common.h"
 
@@ -139,6 +139,28 @@ auto with_tile(const TilePlan &p, F f) {
   if (p.tile_q == 2) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
   if (p.tile_q == 4) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});
   return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{});
+}
+
+// Resident workgroups per CU of a persistent grid's kernel: a property of the instantiation, its LDS (d / 64 = 1 .. 32) and the device --
+// asked once, as num_cus() is, and kept in a table the launch site holds as a static of its own.  ask() puts the question (max_resident).
+using ResidentTable = std::atomic<int>[64][32];
+template <typename Ask>
+int resident_per_cu(ResidentTable &table, int d, Ask ask) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  std::atomic<int> &slot = table[dev][d / 64 - 1];
+  int per_cu = slot.load(std::memory_order_relaxed);
+  if (per_cu == 0) {
+    per_cu = ask();
+    slot.store(per_cu, std::memory_order_relaxed);
+  }
+  return per_cu;
+}
+// workgroups of 256 threads and `lds` bytes of `kernel` a CU holds at once; `otherwise` when the runtime does not say
+template <typename K>
+int max_resident(K kernel, size_t lds, int otherwise) {
+  int n = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, lds) == hipSuccess && n >= 1 ? n : otherwise;
 }
 
 }  // namespace vtcsweep

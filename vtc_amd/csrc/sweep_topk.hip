@@ -6,6 +6,7 @@
 // Two paths.  The distance-matrix path (every precision; below): WaveList, row / column top-k, merge, and for VTC_SWEEP_EXACT the fp64
 // re-rank of the BF16X3 lists with a brute-force fallback.  The block-minima path (VTC_SWEEP_EXACT at >= 1 024 gallery rows, depth <= 32,
 // default blocking; "block-minima path" below): no matrix, certified candidate sets from per-block keys, re-rank, rescan.
+// The fp64 list, the re-rank and the brute-force scan of both paths' finish are exact_list.h's, shared with the query-time searches.
 // The recall-only finish is sweep_recall.hip, the full-rank sweep sweep_rank.hip; what all share, sweep_front.hip / sweep_common.h.
 //
 // Distance-matrix pipeline (per block of query rows, the fp32 distance matrix "tiled in HBM" as
@@ -22,7 +23,7 @@
 //      (wave-uniform), so after warm-up almost every step is load + compare + ballot; the rare
 //      insertion is a ballot/popcount rank + one shuffle.  Order is (distance, index)
 //      lexicographic => ties resolve to the lowest gallery index, independent of scan order.
-#include "sweep_common.h"
+#include "exact_list.h"
 
 #include <algorithm>
 
@@ -573,31 +574,9 @@ __global__ __launch_bounds__(256) void exact_rerank_kernel(const RerankArgs PA, 
   const float *q = queries + (size_t)r * d;
   const int n_list = cand_n ? cand_n[r] : cdepth;
   const int64_t my = lane < n_list ? cand[(size_t)r * cdepth + lane] : -1;
-  double md = INFINITY;
-  // Eight candidates at a time (one at a time the kernel was a chain of 32 dependent gather latencies), by the sweeps' one distance
-  // loop: the fallback kernel forms the same doubles.  An absent slot reads row 0; its result is dropped.
   const int n_loop = cand_n ? (n_list > 0 ? n_list : 0) : cdepth;      // wave-uniform
-  constexpr int NB = 8;                                                // candidates per step
-  for (int c0 = 0; c0 < n_loop; c0 += NB) {
-    long long jj[NB], rows[NB];
-    double sacc[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      jj[u] = c0 + u < n_loop ? __shfl((long long)my, c0 + u, 64) : -1;      // wave-uniform
-      rows[u] = jj[u] < 0 ? 0 : jj[u];
-    }
-    wave_dist64_rows(q, gallery, rows, d, lane, sacc);
-#pragma unroll
-    for (int u = 0; u < NB; ++u)
-      if (jj[u] >= 0 && lane == c0 + u) md = sacc[u];
-  }
-  // rank among the candidates by (fp64 distance, index); absent slots sort last
-  int rank = 0;
-  for (int c = 0; c < n_loop; ++c) {
-    const double od = __shfl(md, c, 64);
-    const long long oi = __shfl((long long)my, c, 64);
-    if (oi >= 0 && (od < md || (od == md && oi < (long long)my))) ++rank;
-  }
+  double md;
+  const int rank = rerank64(q, gallery, (long long)my, n_loop, d, lane, md);
   if (lane < cdepth && my >= 0 && rank < depth) {
     ids[(size_t)r * depth + rank] = my;
     if (dists) dists[(size_t)r * depth + rank] = (float)md;
@@ -617,45 +596,20 @@ __global__ __launch_bounds__(256) void exact_rerank_kernel(const RerankArgs PA, 
   }
 }
 
-// Flagged rows only (dense near-ties: duplicates in the gallery): fp64 brute force over the whole gallery, one
-// workgroup per row, a sorted (distance, index) list per wave (one entry per lane), merged by wave 0.
+// Flagged rows only (dense near-ties: duplicates in the gallery): fp64 brute force over the whole gallery, one workgroup per row
+// (fallback_scan, exact_list.h; a gallery row at +inf is a row).
 __global__ __launch_bounds__(256) void exact_fallback_kernel(const float *__restrict__ queries, const float *__restrict__ gallery, int ng,
                                                              int d, int depth, const int *__restrict__ flags, int64_t *__restrict__ ids,
                                                              float *__restrict__ dists) {
   __shared__ double sd[4][64];
-  __shared__ int si[4][64];
+  __shared__ long long si[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_flagged = flags[0];
   for (int f = blockIdx.x; f < n_flagged; f += gridDim.x) {   // uniform for the workgroup; normally zero trips
-  const int r = flags[1 + f];
-  const float *q = queries + (size_t)r * d;
-  double bd = INFINITY;
-  int bi = 0x7fffffff;
-  auto offer = [&](double cv, int ci) {                   // wave-uniform candidate
-    const double tau = __shfl(bd, depth - 1, 64);
-    const int tau_i = __shfl(bi, depth - 1, 64);
-    if (!(cv < tau || (cv == tau && ci < tau_i))) return;
-    const bool less = bd < cv || (bd == cv && bi < ci);
-    const int pos = __popcll(__ballot(less));
-    const double ud = __shfl_up(bd, 1, 64);
-    const int ui = __shfl_up(bi, 1, 64);
-    if (lane > pos) { bd = ud; bi = ui; }
-    if (lane == pos) { bd = cv; bi = ci; }
-  };
-  for (int j = wave; j < ng; j += 4) offer(wave_dist64(q, gallery + (size_t)j * d, d, lane), j);
-  sd[wave][lane] = bd;
-  si[wave][lane] = bi;
-  __syncthreads();
-  if (wave == 0) {
-    for (int w = 1; w < 4; ++w)
-      for (int e = 0; e < depth; ++e)
-        if (si[w][e] != 0x7fffffff) offer(sd[w][e], si[w][e]);
-    if (lane < depth) {
-      ids[(size_t)r * depth + lane] = bi == 0x7fffffff ? -1 : (int64_t)bi;
-      if (dists) dists[(size_t)r * depth + lane] = (float)bd;
-    }
-  }
-  __syncthreads();                                         // sd / si are reused by the next flagged row
+    const int r = flags[1 + f];
+    const auto m = fallback_scan<false, 4>(queries + (size_t)r * d, gallery, nullptr, ng, d, depth, &sd[0][0], &si[0][0]);
+    if (wave == 0) write_result_row(m, r, depth, lane, 0, ids, dists, nullptr);
+    __syncthreads();                                         // sd / si are reused by the next flagged row
   }
 }
 
@@ -701,19 +655,8 @@ __global__ __launch_bounds__(256) void block_rescan_kernel(const RescanArgs PA, 
     const int r = flags[1 + f];
     const float *q = queries + (size_t)r * d;
     const float th = theta[r];
-    double bd = INFINITY;
-    int bi = 0x7fffffff;
-    auto offer = [&](double cv, int ci) {                   // wave-uniform candidate
-      const double tau = __shfl(bd, depth - 1, 64);
-      const int tau_i = __shfl(bi, depth - 1, 64);
-      if (!(cv < tau || (cv == tau && ci < tau_i))) return;
-      const bool less = bd < cv || (bd == cv && bi < ci);
-      const int pos = __popcll(__ballot(less));
-      const double ud = __shfl_up(bd, 1, 64);
-      const int ui = __shfl_up(bi, 1, 64);
-      if (lane > pos) { bd = ud; bi = ui; }
-      if (lane == pos) { bd = cv; bi = ci; }
-    };
+    SortedList<int, EMPTY_ROW, false> wl;
+    wl.init();
     for (int blk0 = 0; blk0 < nblk; blk0 += cb) {
       if (tid == 0) cnt = 0;
       __syncthreads();
@@ -750,21 +693,18 @@ __global__ __launch_bounds__(256) void block_rescan_kernel(const RescanArgs PA, 
         wave_dist64_rows(q, gallery, jj, d, lane, sacc);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (c0 + u < n_list) offer(sacc[u], jj[u]);
+          if (c0 + u < n_list) wl.offer<false>(sacc[u], jj[u], 0, lane, depth);
       }
       __syncthreads();
     }
-    sd[wave][lane] = bd;
-    si[wave][lane] = bi;
+    sd[wave][lane] = wl.bd;
+    si[wave][lane] = wl.bi;
     __syncthreads();
     if (wave == 0) {
-      for (int w = 1; w < 4; ++w)
-        for (int e = 0; e < depth; ++e)
-          if (si[w][e] != 0x7fffffff) offer(sd[w][e], si[w][e]);
-      if (lane < depth) {
-        ids[(size_t)r * depth + lane] = bi == 0x7fffffff ? -1 : (int64_t)bi;
-        if (dists) dists[(size_t)r * depth + lane] = (float)bd;
-      }
+      SortedList<int, EMPTY_ROW, false> m;
+      m.init();
+      merge_lists<false>(m, LdsLists<int>{&sd[0][0], &si[0][0], nullptr}, 4, 0, 64, depth, lane);
+      write_result_row(m, r, depth, lane, 0, ids, dists, nullptr);
     }
     __syncthreads();
   }
@@ -822,9 +762,6 @@ struct SweepWs {
   size_t total;
 };
 constexpr int MAX_CSEG = 8;
-
-// candidate list depth of the EXACT mode: 21 spare ranks behind the requested ones, at least 32, at most 64 / n_gallery
-int exact_cdepth(int depth, int ng) { return std::min(std::min(64, ng), std::max(32, depth + 21)); }
 
 SweepWs plan(char *ws, int ng, int nq, int d, int precision, int rows_per_block, bool bidir = false) {
   SweepWs s;
