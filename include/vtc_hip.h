@@ -602,6 +602,28 @@ int vtc_l2_range_count(const void *gallery, int gallery_is_half, const float *qu
 int vtc_l2_range_fill(const void *gallery, int gallery_is_half, const float *queries, int n_gallery, int n_queries, int d,
                       const int64_t *lims, int64_t capacity, int64_t id_base, int64_t *ids, float *dists, double *dists64, void *ws,
                       size_t ws_bytes, void *stream);
+/* THE COUNT PASS FOR MANY QUERIES over a half gallery.  DEFINITION: the result is that of vtc_l2_range_count(gallery, 1, ...) on the same
+ * arguments, BIT FOR BIT -- lims, the hit words at the head of the workspace (bits past n_gallery 0), the bits ORed into nonfinite, a
+ * dead row influencing nothing, live == NULL meaning every row, a NaN / negative / +inf radius2 -- and behind the hit words the workspace
+ * holds, at vtc_l2_range_workspace_bytes' offsets, what vtc_l2_range_fill(gallery, 1, ...) needs: that call follows on the SAME workspace,
+ * unchanged.  The entry has no specification of its own.
+ * MECHANISM (range_many.hip): three launches whatever the data, no host synchronisation, no allocation, nothing read back.  The query
+ * prologue of vtc_l2_search_many_half; ONE pass that streams the gallery through v_mfma_f32_16x16x32_f16 for the approximate distance A
+ * of that entry, whose bound holds per pair, |A - D| <= eps = kappa (|q|^2 + |g|^2) + 1e-35: a pair with A + eps <= radius2 is a hit,
+ * one with A - eps > radius2 is not, and only a pair in between -- or one whose A is not finite, or whose query is too small for the
+ * split -- is decided by its fp64 distance D, formed by the scan's own device function from the bits the scan reads; then
+ * vtc_l2_range_count's prefix launch.  A hit word with no live row inside the gallery issues no gallery load.
+ * COST: one gallery pass per call for up to 64 queries (vtc_l2_range_count: one per 8); measured in profiles/range_many.md.
+ * THE COUNTER: behind vtc_l2_range_count's regions -- at byte vtc_l2_range_workspace_bytes(n_gallery, n_queries, d) +
+ * ceil(n_queries / 16) * 64 * d + 768 of the workspace -- one int64 holds the number of (query, row) pairs of this call that were
+ * decided by their fp64 distance.
+ * LIMITS and refusals (a status, vtc_last_error, nothing launched): vtc_l2_range_count's -- 1 <= n_queries <= 64 (more: slice them),
+ * d % 64 == 0 and 64 <= d <= 2048, n_gallery >= 1, non-null gallery / queries / radius2 / lims / ws -- and ws_bytes >=
+ * vtc_l2_range_many_workspace_bytes(...), which is 0 for a refused shape and at least vtc_l2_range_workspace_bytes(...).
+ * NOT PROVIDED: fp32 galleries (their rows are no MFMA operand), a grouped (distinct-video) range, more than 64 queries per call. */
+size_t vtc_l2_range_many_workspace_bytes(int n_gallery, int n_queries, int d);
+int vtc_l2_range_count_many_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const double *radius2, int n_gallery,
+                                 int n_queries, int d, int64_t *lims, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
 /* hits[j] +=#{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);

@@ -136,6 +136,9 @@ SIGNATURES = {
     "vtc_l2_range_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vtc_l2_range_count": (C.c_int, [vp, C.c_int, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),
     "vtc_l2_range_fill": (C.c_int, [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int64, ip, fp, fp, vp, C.c_size_t, vp]),
+    # the count pass for many queries over a half gallery (range_many.hip): an MFMA pass, the band decided in fp64 -- vtc_l2_range_count's bits
+    "vtc_l2_range_many_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vtc_l2_range_count_many_half": (C.c_int, [vp, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),
     "vtc_recall_hits": (C.c_int, [ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp]),
     "vtc_recall_hits_pair": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp, vp]),
     "vtc_l2_recall_bidir_supported": (C.c_int, [C.c_int, C.c_int]),

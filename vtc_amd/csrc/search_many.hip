@@ -6,7 +6,8 @@
 // brute-force scan behind an uncertified list) makes the answer exact again.  Four launches, whatever the data:
 //
 //   many_prep_kernel      a wave per query: |q|^2, the power-of-two scale s, the fp16 (hi, lo) split of s q laid out as the MFMA's B
-//                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.
+//                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.  (many_common.h, with
+//                         the image's layout and the A-fragment loader: range_many.hip's pass shares them.)
 //   many_pass_kernel      the candidate pass.  A workgroup is one wave per 16 queries; every wave walks the workgroup's tiles of 16 gallery
 //                         rows (round-robin over the grid), loads a row tile straight from global memory into A fragments -- a lane's 16
 //                         bytes are 8 consecutive halves of one row, no LDS, no conversion -- one item ahead of the one it multiplies,
@@ -40,21 +41,14 @@
 // So |A - D| <= eps(q) = many_kappa(d) (qn + max_j gn) + 1e-35 with many_kappa(d) = (6 d + 8) 2^-24 + 2^-20, the maximum over the LIVE
 // rows with a FINITE norm (a row with a NaN / inf is never a candidate, and a dead one is never looked at).
 #include "exact_list.h"
+#include "many_common.h"
 #include "search_scan.h"
 
 namespace {
 using namespace vtcsweep;
 
 constexpr int MANY_MAX_DEPTH = 32;     // at least 21 spare ranks in a lane-per-entry list
-constexpr int MANY_KC = 512;           // columns of a K chunk: 16 MFMA steps, 32 KB of B fragments a wave
-constexpr int MANY_KS = MANY_KC / 32;
 constexpr int MANY_MAX_BLOCKS = 1024;  // workgroups of the pass at most (four one-wave workgroups a CU): lists per query in the workspace
-constexpr int QF_DEAD = 1, QF_FALLBACK = 2;
-
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-
-inline float many_kappa(int d) { return (6.0f * d + 8.0f) / 16777216.0f + 1.0f / 1048576.0f; }
-inline int many_qgroups(int nq) { return cdiv(nq, 16); }
 // workgroups of the pass the workspace has lists for: a workgroup of g waves holds g x 32 KB of the LDS, so 4 / g fit a CU
 inline int many_max_blocks(int ng, int nq) {
   const int g = many_qgroups(nq), per_cu = g == 1 ? 4 : (g == 2 ? 2 : 1);      // 40 KB a wave with its lists: 160 KiB a CU
@@ -79,7 +73,7 @@ ManyWs many_ws(void *ws, int ng, int nq, int d, int depth) {
   const size_t blocks = many_max_blocks(ng, nq), entries = (size_t)nq * exact_cdepth(depth, ng);
   s.dists64 = (double *)b.take((size_t)nq * depth * sizeof(double));
   s.flags = (int *)b.take((1 + SEARCH_MAX_Q) * sizeof(int));
-  s.qimg = (uint4 *)b.take((size_t)many_qgroups(nq) * 16 * d * 2 * sizeof(_Float16));
+  s.qimg = (uint4 *)b.take(many_img_bytes(nq, d));
   s.qn = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
   s.inv_s = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
   s.qflag = (int *)b.take(SEARCH_MAX_Q * sizeof(int));
@@ -89,55 +83,6 @@ ManyWs many_ws(void *ws, int ng, int nq, int d, int depth) {
   s.list_i = (int *)b.take(entries * blocks * sizeof(int));
   s.total = b.off;
   return s;
-}
-
-// One wave per query slot (16 x qgroups of them; a slot past the last query is a dead row of zeros, as a query with a NaN / inf is).
-__global__ __launch_bounds__(64) void many_prep_kernel(const float *__restrict__ queries, int nq, int d, uint4 *__restrict__ qimg,
-                                                       float *__restrict__ qn, float *__restrict__ inv_s, int *__restrict__ qflag,
-                                                       int *__restrict__ flags, int *__restrict__ nonfinite) {
-  const int q = blockIdx.x, lane = threadIdx.x;
-  if (q == 0 && lane == 0) flags[0] = 0;
-  const float *row = queries + (size_t)min(q, nq - 1) * d;
-  float m = 0.f, n2 = 0.f;
-  bool bad = false;
-  for (int c = lane * 4; c < d; c += 256) {
-    const float4 v = *reinterpret_cast<const float4 *>(row + c);
-    bad = bad || !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    n2 = fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, fmaf(v.w, v.w, n2))));
-  }
-  const bool nonfin = __ballot(bad) != 0, dead = nonfin || q >= nq;
-  m = wave_max(dead ? 0.f : m);
-  n2 = wave_sum(n2);
-  int flag = dead ? QF_DEAD : 0, e = 13;                   // m == 0: s = 1
-  if (m > 0.f) e = ilogbf(m);
-  int se = 13 - e;                                         // s = 2^se puts m into [2^13, 2^14)
-  if (se > 126) {                                          // a query below 2^-113: s would leave fp32, the split has no bound
-    se = 126;
-    flag |= QF_FALLBACK;
-  }
-  const float s = __int_as_float((se + 127) << 23);
-  if (lane == 0) {
-    qn[q] = dead ? 0.f : n2;
-    inv_s[q] = __int_as_float((127 - se) << 23);
-    qflag[q] = flag;
-    if (nonfin && q < nq && nonfinite) atomicOr(nonfinite, 2);
-  }
-  // the B fragment of MFMA step ks: lane (kq, u) = 16 kq + u holds the 8 halves k = 32 ks + 8 kq .. + 7 of query u of the group
-  const int grp = q >> 4, u = q & 15;
-  for (int b = lane; b < d / 8; b += 64) {
-    f16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float x = dead ? 0.f : row[b * 8 + j] * s;
-      hi[j] = (_Float16)x;
-      lo[j] = (_Float16)(x - (float)hi[j]);
-    }
-    const int ks = b >> 2, kq = b & 3;
-    const size_t o = ((size_t)(grp * (d / 32) + ks) * 2) * 64 + kq * 16 + u;
-    qimg[o] = __builtin_bit_cast(uint4, hi);
-    qimg[o + 64] = __builtin_bit_cast(uint4, lo);
-  }
 }
 
 // The sorted candidate list of one query: entry e on lane e, ascending A, kept in the LDS ([list][lane], a float and an int: 512 bytes a
@@ -212,14 +157,8 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
     const unsigned inside = left >= 16 ? 0xffffu : (1u << left) - 1;
     return (unsigned)uniform_of((int)(word & inside));
   };
-  // the A fragments of an item: lane (kq, u) holds row u of the tile, halves 32 ks + 8 kq .. + 7 of the chunk.  A dead row (or one past
-  // the gallery) is pointed at a live row of the tile: its memory is not read, its results are dropped.  bits != 0.
-  auto load_frags = [&](long long t, int chunk, unsigned bits, f16x8 (&ga)[NKS]) {
-    const long long row = t * 16 + (((bits >> u) & 1) ? u : __ffs((int)bits) - 1);
-    const _Float16 *p = gallery + (size_t)row * d + chunk * (NKS * 32) + kq * 8;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) ga[ks] = *reinterpret_cast<const f16x8 *>(p + ks * 32);
-  };
+  // the A fragments of an item (many_common.h); bits != 0
+  auto load_frags = [&](long long t, int chunk, unsigned bits, f16x8 (&ga)[NKS]) { many_load_frags<NKS>(gallery, d, t, chunk, bits, u, kq, ga); };
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   float nrm = 0.f;
@@ -434,7 +373,7 @@ extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *que
   const int qg = many_qgroups(nq), cdepth = exact_cdepth(depth, ng);
   const int per_cu = qg == 1 ? 4 : (qg == 2 ? 2 : 1);
   const int blocks = std::min(many_max_blocks(ng, nq), per_cu * vtcgemm::num_cus());
-  const int ksteps = d / 32, nks = ksteps % 16 == 0 ? 16 : (ksteps % 8 == 0 ? 8 : (ksteps % 4 == 0 ? 4 : 2));      // d % 64 == 0: ksteps is even
+  const int ksteps = d / 32, nks = many_item_steps(d);
   const size_t lds = (size_t)qg * ((d <= MANY_KC ? ksteps : nks) * 2 * 64 * sizeof(uint4) + MANY_LIST_BYTES);      // at most all 160 KiB of a CU
   // the pass of this call: MASKED by `live`, NKS the largest of 16, 8, 4, 2 MFMA steps an item that divides the row
   auto pass = [&](auto masked, auto steps) -> int {
@@ -453,7 +392,7 @@ extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *que
     return pass(masked, std::integral_constant<int, 2>{});
   };
 
-  hipLaunchKernelGGL(many_prep_kernel, dim3(qg * 16), dim3(64), 0, stream, queries, nq, d, s.qimg, s.qn, s.inv_s, s.qflag, s.flags, nonfinite);
+  hipLaunchKernelGGL(many_prep_kernel, dim3(qg * 16), dim3(64), 0, stream, queries, nq, d, s.qimg, s.qn, s.inv_s, s.qflag, s.flags, 1, nonfinite);
   VTC_LAUNCH_CHECK2(name, "prep");
   if (live ? pass_of(std::true_type{}) : pass_of(std::false_type{})) return 1;
   VTC_LAUNCH_CHECK2(name, "pass");

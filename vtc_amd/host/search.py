@@ -38,6 +38,15 @@ search (vtc_l2_range_count / vtc_l2_range_fill: the same fp64 distances, compare
     counts = index.range_count(queries, min_score=0.9)                 # how many, without fetching them: no host sync
     near = index.range_subset(query, min_score=0.8)                    # the hits of one query as a RowSubset: filters chain
 
+The range search has a batch form too, for the workloads that ask many range questions at once -- near-duplicate and repost detection,
+which asks of every stored row which other rows score at least s, and thresholded retrieval for a batch of texts.  On a half index 64
+queries are ONE pass of the stored rows through the matrix cores, and only the pairs the pass's error bound cannot decide are taken in
+fp64 (vtc_l2_range_count_many_half); the result is ``range_search``'s, bit for bit:
+
+    lims, ids, scores = index.range_search_many(queries, min_score=0.9)  # and range_count_many: range_search / range_count for a batch
+    lims, ids, scores = index.similar_within(row_ids, min_score=0.9)     # the range form of ``similar``: stored rows, each without itself
+    pairs, scores = index.near_duplicates(min_score=0.9)                 # every pair a < b of live rows that score at least 0.9
+
 Between the two lies "the next page", and a ranking deeper than 64 -- a re-ranker, a hard-negative miner, recall at 100 or 1000.  The
 search order is a total order on (fp64 distance, row), so "the k nearest rows after row r" is well defined and needs no state
 (vtc_l2_search_after: a cursor in the scan):
@@ -146,6 +155,11 @@ class VideoIndex:
     an fp32 index (profiles/search.md: the scan takes 4.5 x vtc_l2_topk's time at 64 queries) -- through ``search``.  ``search_many``
     is the batch form: the same result, and on a half index with k <= 32 one pass of the stored rows through the matrix cores per 64
     queries with an exact fp64 finish (vtc_l2_search_many_half, profiles/search_many.md).  ``converted`` moves an index over.
+    ``range_search_many`` / ``range_count_many`` are the batch forms of the range search: the same result, and on a half index from
+    ROUTE_RANGE_MANY_MIN_QUERIES queries on one pass of the stored rows through the matrix cores per 64 queries, the pairs inside the
+    error band decided in fp64 (vtc_l2_range_count_many_half, profiles/range_many.md); ``similar_within`` (the range form of
+    ``similar``) and ``near_duplicates`` (every pair of live rows above a score) are built on them and run through the scan on an fp32
+    index.
     ``exclude`` / ``exclude_videos`` (one row or one video per query that it is never given), ``similar`` and ``similar_videos`` (the
     neighbours of a stored row without itself / without its own video) are the excluding scan (vtc_l2_search_excluding), by the same
     rules: any number of queries in slices of 64, only enqueued.  ``search_videos(after=)`` and ``search_videos_deep`` page the grouped
@@ -173,6 +187,20 @@ class VideoIndex:
     #: 9 is the first count from which the new entry wins by more than 5 % at both sizes, masked or not (9 is from the tool's second
     #: run, --queries 8,9,10,11,12, where 10 and 11 won as well): the scan starts its second gallery pass there.
     ROUTE_MANY_MIN_QUERIES = 9
+    #: queries per call from which range_search_many() / range_count_many() / similar_within() on a HALF index go through
+    #: ops.l2_range_count_many instead of the scan's count pass (a call of more than 64 queries counts as 64, so 65 means never).
+    #: Measured, profiles/range_many.md (d = 512, a radius about 10 rows of a query pass, medians of 30 alternating calls; us at
+    #: 10^5 / 10^6 half rows, new count vs the scan's count over the same rows; in brackets under a random 50 % mask; a radius that
+    #: 1 % of the rows pass moves no figure by more than 5 %):
+    #:    8 queries    58.8 vs 193.7 (3.30 x) [ 60.6 vs 131.6, 2.17 x]       240.2 vs 1 288.0 ( 5.36 x) [3.69 x]   new entry faster
+    #:    9            61.0 vs 306.6 (5.03 x) [ 64.4 vs 187.6, 2.92 x]       244.0 vs 2 386.7 ( 9.78 x) [6.63 x]   new entry faster
+    #:   12            62.6 vs 306.8 (4.90 x) [ 65.3 vs 189.8, 2.91 x]       247.4 vs 2 383.0 ( 9.63 x) [6.52 x]   new entry faster
+    #:   16            66.2 vs 311.9 (4.71 x) [ 68.4 vs 194.2, 2.84 x]       260.7 vs 2 406.9 ( 9.23 x) [6.41 x]   new entry faster
+    #:   32            79.7 vs 537.5 (6.74 x) [ 83.7 vs 320.8, 3.83 x]       366.6 vs 4 567.3 (12.5 x)  [7.74 x]   new entry faster
+    #:   64           105.2 vs 998.6 (9.49 x) [109.2 vs 573.7, 5.25 x]       570.1 vs 8 949.5 (15.7 x)  [9.22 x]   new entry faster
+    #: 8 is the first MEASURED count, and the new entry wins there by more than 5 % at both sizes, masked or not.  Fewer than 8 queries
+    #: were not measured: the scan runs them as one tile, in one gallery pass.
+    ROUTE_RANGE_MANY_MIN_QUERIES = 8
     MAX_K = 64                # one list entry per lane of a wavefront, as everywhere in the sweeps
     STORAGE = {"float32": torch.float32, "float16": torch.float16}      # the state dict's names of the storage dtypes
 
@@ -820,13 +848,14 @@ class VideoIndex:
         return self.search(self._text_queries(model, title_tokens, comments, "search_text"), k, subset=subset, after=after, exclude=exclude)
 
     # ---- range search ----------------------------------------------------------------------------
-    def _range_setup(self, queries, min_score, subset, what):
+    def _range_setup(self, queries, min_score, subset, what, many=False, stored=False):
         """([(the prepared queries [<= 64, width] of a slice, their radius2 as Python doubles)], the packed words of the rows that take
-        part or None, the workspace of a slice's call)."""
+        part or None, the workspace of a slice's call).  ``many``: the slices go through the many-query count pass, whose workspace is
+        larger.  ``stored``: the queries are stored rows [Q, width] widened to fp32 (``similar_within``), taken as they are."""
         self._check_subset(subset, what)
         if self._n == 0:
             raise ValueError(f"VideoIndex.{what}: the index is empty")
-        q = self._prepared(queries, "queries", check=False)
+        q = queries if stored else self._prepared(queries, "queries", check=False)
         if q.shape[0] == 0:
             raise ValueError(f"VideoIndex.{what}: no queries")
         if isinstance(min_score, torch.Tensor):
@@ -839,8 +868,13 @@ class VideoIndex:
                 raise ValueError(f"VideoIndex.{what}: min_score must be a float or one per query ({q.shape[0]}), got {len(scores)}")
         radius2 = [2.0 * (1.0 - s) for s in scores]             # score = 1 - D / 2, in Python doubles
         words = self._live_words() if subset is None else subset.words()
-        ws = self._workspace(ops.l2_range_workspace_bytes(self._n, min(q.shape[0], ops.SEARCH_MAX_QUERIES), self.width))
-        return self._sliced(q, radius2), words, ws
+        ws_bytes = ops.l2_range_many_workspace_bytes if many else ops.l2_range_workspace_bytes
+        ws = self._workspace(ws_bytes(self._n, min(q.shape[0], ops.SEARCH_MAX_QUERIES), self.width))
+        return q, radius2, words, ws
+
+    def _range_many_route(self, n_queries):
+        """Whether a range call of ``n_queries`` goes through vtc_l2_range_count_many_half."""
+        return self.storage == torch.float16 and min(n_queries, ops.SEARCH_MAX_QUERIES) >= self.ROUTE_RANGE_MANY_MIN_QUERIES
 
     def range_search(self, queries, min_score, subset=None, sort=True, max_results=1 << 22):
         """EVERY live row that scores at least ``min_score`` against a query, however many: (lims [Q + 1] int64, ids [total] int64,
@@ -852,11 +886,16 @@ class VideoIndex:
         of queries, 64 per call.  A non-finite query has no hits.
         One host sync per 64 queries: the number of hits is read back before the result is allocated, and more than ``max_results`` in
         total raise ValueError before that allocation (``range_count`` tells the size without fetching)."""
-        slices, words, ws = self._range_setup(queries, min_score, subset, "range_search")
+        return self._range_search(queries, min_score, subset, sort, max_results, "range_search", False)
+
+    def _range_search(self, queries, min_score, subset, sort, max_results, what, many, stored=False, exclude=None):
+        """``range_search`` and what is built on it: ``many`` chooses the count pass of every slice, ``stored`` takes the queries as they
+        are, ``exclude`` (int64 [Q] row ids) is a row per query that it is never given."""
+        q, radius2, words, ws = self._range_setup(queries, min_score, subset, what, many, stored)
+        search = ops.l2_range_search_many if many else ops.l2_range_search
         lims, ids, dists, total = [torch.zeros(1, dtype=torch.int64, device=self.device)], [], [], 0
-        for q, radius2 in slices:
-            l, i, d32, d64 = ops.l2_range_search(self.rows, q, radius2, live=words, max_results=int(max_results) - total, return_dists64=True,
-                                                 ws=ws)
+        for qs, r2, ex in self._sliced(q, radius2, exclude):
+            l, i, d32, d64 = search(self.rows, qs, r2, live=words, max_results=int(max_results) - total, return_dists64=True, ws=ws, exclude=ex)
             if sort and i.numel():
                 n_q = l.shape[0] - 1
                 seg = torch.repeat_interleave(torch.arange(n_q, device=self.device), l[1:] - l[:-1], output_size=i.numel())
@@ -872,12 +911,90 @@ class VideoIndex:
     def range_count(self, queries, min_score, subset=None):
         """int64 [Q] on the device: how many live rows (of the ``subset``) score at least ``min_score`` against every query -- the sizes
         of ``range_search``'s segments without fetching them.  Only enqueued: no host sync."""
-        slices, words, ws = self._range_setup(queries, min_score, subset, "range_count")
+        return self._range_count(queries, min_score, subset, "range_count", False)
+
+    def _range_count(self, queries, min_score, subset, what, many):
+        q, radius2, words, ws = self._range_setup(queries, min_score, subset, what, many)
+        count = ops.l2_range_count_many if many else ops.l2_range_count
         out = []
-        for q, radius2 in slices:
-            l = ops.l2_range_count(self.rows, q, radius2, live=words, ws=ws)
+        for qs, r2 in self._sliced(q, radius2):
+            l = count(self.rows, qs, r2, live=words, ws=ws)
             out.append(l[1:] - l[:-1])
         return out[0] if len(out) == 1 else torch.cat(out)
+
+    def range_search_many(self, queries, min_score, subset=None, sort=True, max_results=1 << 22):
+        """``range_search(queries, min_score, subset, sort, max_results)`` for a BATCH: the same (lims, ids, scores), bit for bit, on
+        every index.  On a half index with at least ROUTE_RANGE_MANY_MIN_QUERIES queries the count pass of every slice of 64 is
+        vtc_l2_range_count_many_half -- one pass of the stored half rows through the matrix cores, only the pairs its error bound
+        cannot decide taken in fp64, where ``range_search`` forms every distance in fp64, a gallery pass per 8 queries -- and the
+        fill is ``range_search``'s.  The masked route's rules hold: removed rows and ``subset`` honoured, a non-finite query has no
+        hits, one host sync per 64 queries.  In every other case (an fp32 index, fewer queries) the call IS ``range_search``.
+        Not here: a grouped (distinct-video) range, more than 64 queries a library call, an MFMA pass over fp32 rows."""
+        if not self._range_many_route(len(queries)):
+            return self.range_search(queries, min_score, subset=subset, sort=sort, max_results=max_results)
+        return self._range_search(queries, min_score, subset, sort, max_results, "range_search_many", True)
+
+    def range_count_many(self, queries, min_score, subset=None):
+        """``range_count(queries, min_score, subset)`` for a BATCH: the same int64 [Q], bit for bit, on every index; routed as
+        ``range_search_many`` is (vtc_l2_range_count_many_half on a half index from ROUTE_RANGE_MANY_MIN_QUERIES queries on, otherwise
+        the call IS ``range_count``).  Only enqueued: no host sync.  Not here: a grouped (distinct-video) range, more than 64 queries
+        a library call, an MFMA pass over fp32 rows."""
+        if not self._range_many_route(len(queries)):
+            return self.range_count(queries, min_score, subset=subset)
+        return self._range_count(queries, min_score, subset, "range_count_many", True)
+
+    def similar_within(self, ids, min_score, subset=None, sort=True, max_results=1 << 22):
+        """THE RANGE FORM OF ``similar``: (lims [Q + 1] int64, ids [total] int64, scores [total] fp32), every live row (of ``subset``)
+        that scores at least ``min_score`` against the STORED row ``ids[q]`` (an int64 [Q] tensor of row ids), that row itself left
+        out -- ``range_search_many`` with the stored rows as the queries (as ``similar`` takes them: never normalised again, a half
+        index's row widened exactly) and routed as it is, so on a half index the slices of 64 go through the matrix cores.  A bit-equal
+        duplicate of the row scores exactly 1 and IS returned: it is another row.  The query row need not be live nor a member of
+        ``subset`` (the hits are).  An id outside [0, ntotal) cannot be validated without a host read: its segment is empty and the
+        others are left alone.  ``min_score``, ``sort``, ``max_results`` and the one host sync per 64 queries: ``range_search``'s; the
+        own row is dropped with torch ops whose sizes come back in that same read, no further sync.  On an fp32 index the call runs
+        through the scan (vtc_l2_range_count).  Not here: a grouped (distinct-video) range, more than 64 queries a library call, an
+        MFMA pass over fp32 rows."""
+        ids, q = self._stored_queries(ids, "similar_within")
+        return self._range_search(q, min_score, subset, sort, max_results, "similar_within", self._range_many_route(q.shape[0]), stored=True,
+                                  exclude=ids)
+
+    NEAR_DUPLICATES_SLICE = 16 * ops.SEARCH_MAX_QUERIES      # stored rows a ``similar_within`` call of ``near_duplicates``
+
+    def near_duplicates(self, min_score, subset=None, max_results=1 << 22):
+        """(pairs int64 [P, 2], scores fp32 [P]) on the device: EVERY unordered pair a < b of live rows (of ``subset``) whose stored rows
+        score at least ``min_score`` against each other, ascending by (a, b) -- near-duplicate and repost detection over the whole
+        gallery.  A loop of ``similar_within(sort=False)`` over the live rows in slices of NEAR_DUPLICATES_SLICE that keeps the hits
+        above the own id; a pair's score is that of row b against the stored row a as the query.  On a half index every 64 rows are
+        one pass of the gallery through the matrix cores (profiles/range_many.md); on an fp32 index the call runs through the scan, a
+        gallery pass per 8 rows.  More than ``max_results`` pairs in total raise ValueError.  Host syncs: one to list the live rows,
+        one per 64 rows (``range_search``'s) and one per slice.  Not here: restricting a slice's gallery to the rows above it (every
+        pair is found from both ends and one is dropped), a grouped (distinct-video) range, more than 64 queries a library call, an
+        MFMA pass over fp32 rows."""
+        self._check_subset(subset, "near_duplicates")
+        if self._n == 0:
+            raise ValueError("VideoIndex.near_duplicates: the index is empty")
+        words = self._live_words() if subset is None else subset.words()
+        if words is None:
+            rows = torch.arange(self._n, dtype=torch.int64, device=self.device)
+        else:
+            shifts = torch.arange(32, dtype=torch.int32, device=self.device)
+            rows = torch.nonzero(((words[:, None] >> shifts[None]) & 1).reshape(-1)[:self._n]).reshape(-1)
+        pairs, scores, total = [], [], 0
+        for lo in range(0, rows.shape[0], self.NEAR_DUPLICATES_SLICE):
+            own = rows[lo:lo + self.NEAR_DUPLICATES_SLICE]
+            # an unordered pair is a hit from both of its ends: twice max_results hits in a slice are more than max_results pairs
+            lims, hit, score = self.similar_within(own, min_score, subset=subset, sort=False, max_results=2 * int(max_results))
+            a = torch.repeat_interleave(own, lims[1:] - lims[:-1], output_size=hit.numel())
+            above = hit > a
+            pairs.append(torch.stack([a[above], hit[above]], dim=1))
+            scores.append(score[above])
+            total += pairs[-1].shape[0]
+            if total > int(max_results):
+                raise ValueError(f"VideoIndex.near_duplicates: more than max_results={int(max_results)} pairs score at least {min_score} "
+                                 "(raise it or the score)")
+        if not pairs:
+            return torch.empty(0, 2, dtype=torch.int64, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        return torch.cat(pairs), torch.cat(scores)
 
     def range_search_text(self, model, title_tokens, min_score, comments=None, **kw):
         """``range_search`` of text queries given as token ids, encoded as ``search_text`` encodes them."""
@@ -892,7 +1009,7 @@ class VideoIndex:
             query = query[None]
         if query.dim() != 2 or query.shape[0] != 1:
             raise ValueError(f"VideoIndex.range_subset: one query ([{self.dim}] or [1, {self.dim}]), got {tuple(query.shape)}")
-        ((q, radius2),), words, ws = self._range_setup(query, min_score, subset, "range_subset")
+        q, radius2, words, ws = self._range_setup(query, min_score, subset, "range_subset")
         ops.l2_range_count(self.rows, q, radius2, live=words, ws=ws)
         hit = ops.range_hit_words(ws, self._n, 1)[0].clone()
         shifts = torch.arange(32, dtype=torch.int32, device=self.device)

@@ -589,8 +589,11 @@ def range_hit_words(ws: torch.Tensor, n_gallery: int, n_queries: int) -> torch.T
     return ws[:n_queries * nw * 4].view(torch.int32).view(n_queries, nw)
 
 
-def _range_args(gallery, queries, radius2, live, ws, what):
+def _range_args(gallery, queries, radius2, live, ws, what, many=False):
+    """``many``: the call is the many-query count pass -- a half gallery, and the larger workspace."""
     gallery, queries, _, ng, nq, d = _search_inputs(what, gallery, queries)
+    if many and gallery.dtype != torch.float16:
+        raise ValueError(f"{what}: the gallery must be torch.float16 (the stored rows are the matrix cores' operand), got {gallery.dtype}")
     if isinstance(radius2, torch.Tensor) and radius2.is_cuda:
         radius2 = _gpu(radius2, torch.float64, "radius2")
     elif isinstance(radius2, (int, float)):
@@ -601,18 +604,22 @@ def _range_args(gallery, queries, radius2, live, ws, what):
     if radius2.device != gallery.device or tuple(radius2.shape) != (nq,):
         raise ValueError(f"{what}: radius2 must be a float or float64 [{nq}] (one squared radius per query), got {tuple(radius2.shape)}")
     live = _live_arg(live, ng, gallery.device, what)
-    ws = _search_ws_arg(ws, L.lib().vtc_l2_range_workspace_bytes(ng, nq, d), gallery.device, what)      # the hit words stay in it
+    ws_bytes = L.lib().vtc_l2_range_many_workspace_bytes if many else L.lib().vtc_l2_range_workspace_bytes
+    ws = _search_ws_arg(ws, ws_bytes(ng, nq, d), gallery.device, what)      # the hit words stay in it
     return gallery, queries, radius2, live, ws
 
 
-def _range_count(gallery, queries, radius2, live, ws):
+def _range_count(gallery, queries, radius2, live, ws, many=False):
     ng, d = gallery.shape
     nq = queries.shape[0]
     lims = torch.empty(nq + 1, dtype=torch.int64, device=gallery.device)
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
-    L.check(L.lib().vtc_l2_range_count(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
-                                       live.data_ptr() if live is not None else None, radius2.data_ptr(), ng, nq, d, lims.data_ptr(),
-                                       bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_range_count")
+    tail = (_ptr(live), radius2.data_ptr(), ng, nq, d, lims.data_ptr(), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if many:
+        L.check(L.lib().vtc_l2_range_count_many_half(gallery.data_ptr(), queries.data_ptr(), *tail), "vtc_l2_range_count_many_half")
+    else:
+        L.check(L.lib().vtc_l2_range_count(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), *tail),
+                "vtc_l2_range_count")
     return lims, bits
 
 
@@ -631,22 +638,43 @@ def l2_range_count(gallery: torch.Tensor, queries: torch.Tensor, radius2, live: 
 
 @on_device
 def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live: Optional[torch.Tensor] = None, id_base: int = 0,
-                    max_results: int = 1 << 22, return_dists64: bool = False, return_words: bool = False, ws: Optional[torch.Tensor] = None):
+                    max_results: int = 1 << 22, return_dists64: bool = False, return_words: bool = False, ws: Optional[torch.Tensor] = None,
+                    exclude: Optional[torch.Tensor] = None):
     """Range search (vtc_l2_range_count + vtc_l2_range_fill): EVERY gallery row with a finite fp64 squared distance D <= radius2[q] to
     query q, for at most 64 queries.  Returns (lims int64 [Q + 1], ids int64 [total] = id_base + row, dists fp32 [total] = (float) D
     [, dists64 float64 [total]] [, words int32 [Q, ceil(n / 32)]]), all on the device: query q's hits are [lims[q], lims[q + 1]), in
     ascending row order.  ``words`` are the hit words, a copy; words[q] is a valid ``live`` of ``l2_search``.
     ONE host sync: lims[-1] is read back between the two passes, because the size of the output depends on the data.  A total above
     ``max_results`` raises ValueError BEFORE anything is allocated for it (``l2_range_count`` tells the size without fetching).
-    ``radius2`` / ``live`` / a ``torch.float16`` gallery: as ``l2_range_count``."""
-    gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, "l2_range_search")
+    ``radius2`` / ``live`` / a ``torch.float16`` gallery: as ``l2_range_count``.
+    ``exclude``: int64 [Q] on the gallery's device; query q is never given the row with the GLOBAL id ``exclude[q]`` (-1, or any id
+    outside [id_base, id_base + n), excludes nothing).  Whether that row is a hit is read from the hit words and comes back in the SAME
+    host read as lims[-1]; the entry is dropped after the fill with torch ops and lims counts what is returned.  ``words`` stay the count
+    pass's, the excluded row's bit included.  None: the call above, unchanged."""
+    return _range_search(gallery, queries, radius2, live, id_base, max_results, return_dists64, return_words, ws, exclude, "l2_range_search",
+                         False)
+
+
+def _range_search(gallery, queries, radius2, live, id_base, max_results, return_dists64, return_words, ws, exclude, what, many):
+    """The count pass (``many``: vtc_l2_range_count_many_half), the one host read of lims[-1], then vtc_l2_range_fill on the same workspace."""
+    gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, what, many)
     ng, d = gallery.shape
     nq = queries.shape[0]
-    lims, _ = _range_count(gallery, queries, radius2, live, ws)
-    total = int(lims[-1])                                     # the one device-to-host read
-    if total > int(max_results):
-        raise ValueError(f"l2_range_search: {total} rows lie within the radius, max_results={int(max_results)} (raise it, tighten the radius, "
-                         "or count with l2_range_count)")
+    if exclude is not None:
+        exclude = _exclude_arg(exclude, nq, gallery.device, what)
+    lims, _ = _range_count(gallery, queries, radius2, live, ws, many)
+    n_self = 0
+    if exclude is None:
+        total = int(lims[-1])                                 # the one device-to-host read
+    else:                                                     # ... which also says how many queries hit their excluded row: its bit
+        row = exclude - int(id_base)
+        at = row.clamp(0, ng - 1)
+        word = range_hit_words(ws, ng, nq)[torch.arange(nq, device=gallery.device), at >> 5]
+        self_hit = (row >= 0) & (row < ng) & (((word >> (at & 31).to(torch.int32)) & 1) != 0)
+        total, n_self = torch.stack([lims[-1], self_hit.sum()]).tolist()
+    if total - n_self > int(max_results):
+        raise ValueError(f"{what}: {total - n_self} rows lie within the radius, max_results={int(max_results)} (raise it, tighten the radius, "
+                         f"or count with {'l2_range_count_many' if many else 'l2_range_count'})")
     dev = gallery.device
     ids = torch.empty(total, dtype=torch.int64, device=dev)
     dists = torch.empty(total, dtype=torch.float32, device=dev)
@@ -654,12 +682,66 @@ def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live:
     L.check(L.lib().vtc_l2_range_fill(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), ng, nq, d, lims.data_ptr(),
                                       total, int(id_base), ids.data_ptr(), dists.data_ptr(), dists64.data_ptr() if return_dists64 else None,
                                       ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_range_fill")
+    if exclude is not None and total:
+        # The excluded entries leave: every kept entry moves to its rank among the kept ones, the dropped ones to a spare slot behind
+        # the result.  The sizes are host numbers already, so nothing here reads the device.
+        seg = torch.repeat_interleave(torch.arange(nq, device=dev), lims[1:] - lims[:-1], output_size=total)
+        keep = ids != exclude[seg]
+        dest = torch.where(keep, torch.cumsum(keep, 0) - 1, total - n_self)
+
+        def kept(x):
+            out = x.new_empty(total - n_self + 1)
+            out[dest] = x
+            return out[:total - n_self]
+        ids, dists, dists64 = kept(ids), kept(dists), kept(dists64) if return_dists64 else None
+        lims = lims - torch.nn.functional.pad(torch.cumsum(self_hit, 0), (1, 0))
     out = (lims, ids, dists)
     if return_dists64:
         out += (dists64,)
     if return_words:
         out += (range_hit_words(ws, ng, nq).clone(),)
     return out
+
+
+@on_device
+def l2_range_count_many(gallery_half: torch.Tensor, queries: torch.Tensor, radius2, live: Optional[torch.Tensor] = None,
+                        ws: Optional[torch.Tensor] = None, return_bits: bool = False):
+    """``l2_range_count`` of a ``torch.float16`` gallery for MANY queries (vtc_l2_range_count_many_half): at most 64 queries, the same
+    ``lims`` (and non-finite word) with the same bits, the same hit words ``range_hit_words(ws, n, Q)`` in a caller's ``ws`` (at least
+    ``l2_range_many_workspace_bytes``) -- by ONE pass of the gallery through the matrix cores, only the pairs the error bound cannot decide
+    taken in fp64, instead of an fp64 scan per 8 queries.  ``range_many_stats(ws, n, Q)`` tells how many pairs that were.  An fp32 gallery
+    raises ValueError: the pass multiplies the stored half rows as they are.  Only enqueued."""
+    gallery, queries, radius2, live, ws = _range_args(gallery_half, queries, radius2, live, ws, "l2_range_count_many", many=True)
+    lims, bits = _range_count(gallery, queries, radius2, live, ws, many=True)
+    return (lims, bits) if return_bits else lims
+
+
+@on_device
+def l2_range_search_many(gallery_half: torch.Tensor, queries: torch.Tensor, radius2, live: Optional[torch.Tensor] = None, id_base: int = 0,
+                         max_results: int = 1 << 22, return_dists64: bool = False, return_words: bool = False,
+                         ws: Optional[torch.Tensor] = None, exclude: Optional[torch.Tensor] = None):
+    """``l2_range_search`` of a ``torch.float16`` gallery for MANY queries: ``l2_range_count_many``'s pass, the one host read of lims[-1],
+    then vtc_l2_range_fill on the same workspace.  The arguments and the returns are ``l2_range_search``'s, bit for bit; ``ws`` is at least
+    ``l2_range_many_workspace_bytes``.  An fp32 gallery raises ValueError."""
+    return _range_search(gallery_half, queries, radius2, live, id_base, max_results, return_dists64, return_words, ws, exclude,
+                         "l2_range_search_many", True)
+
+
+def l2_range_many_workspace_bytes(n_gallery: int, n_queries: int, d: int) -> int:
+    """0 for a shape vtc_l2_range_count_many_half refuses; never less than ``l2_range_workspace_bytes``."""
+    return int(L.lib().vtc_l2_range_many_workspace_bytes(int(n_gallery), int(n_queries), int(d)))
+
+
+def range_many_stats(ws: torch.Tensor, n_gallery: int, n_queries: int, d: int = None) -> dict:
+    """What the last ``l2_range_count_many`` / ``l2_range_search_many`` on workspace ``ws`` left behind the scan's regions
+    (include/vtc_hip.h): ``exact_pairs``, the (query, row) pairs of that call that the error bound could not decide and the fp64
+    distance did.  The counter is the last region of the workspace the call asked for, so ``d`` is needed only to find it in a LARGER
+    ``ws`` (None: ``ws`` is exactly ``l2_range_many_workspace_bytes`` long).  A device-to-host read."""
+    if d is None:
+        at = ws.numel() - 256
+    else:
+        at = l2_range_workspace_bytes(n_gallery, n_queries, d) + (n_queries + 15) // 16 * 64 * d + 768
+    return {"exact_pairs": int(ws[at:at + 8].view(torch.int64).item())}
 
 
 @on_device
