@@ -624,6 +624,46 @@ int vtc_l2_range_fill(const void *gallery, int gallery_is_half, const float *que
 size_t vtc_l2_range_many_workspace_bytes(int n_gallery, int n_queries, int d);
 int vtc_l2_range_count_many_half(const uint16_t *gallery, const float *queries, const uint32_t *live, const double *radius2, int n_gallery,
                                  int n_queries, int d, int64_t *lims, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+/* ---- 8-BIT GALLERY STORAGE (q8): one signed byte per component and one fp32 scale per row, searched exactly AS STORED.
+ * A Q8 ROW of width d (a multiple of 64 in [64, 2048]) is d + 16 = vtc_q8_row_bytes(d) bytes: d signed codes c_k (int8; -128 is legal),
+ * then the row's fp32 scale s at byte d, then 12 bytes that are written as zero and never read.  A q8 gallery is [n][d + 16] bytes with
+ * a 16-byte aligned base: one pointer.  THE STORED VALUE of component k is the IEEE single-precision product fl32(s * c_k), subnormal
+ * results kept.  (The quantiser below only produces scales with 16 significant bits, low 8 mantissa bits zero: with |c| <= 128 the
+ * product is then exact; a caller's scale with more bits gets the rounded product.)  A row whose scale is NaN or +-inf is a non-finite
+ * row: it sets bit 1 of nonfinite and is never a candidate, as a half row with an inf is.  A scale of 0 is a row of zeros.
+ * THE SEARCH over a q8 gallery is, BIT FOR BIT, the fp32 search over the fp32 gallery of those stored values -- ids, dists, the fp64
+ * distances at the head of the workspace, groups, hit words and lims, in every mode: the kernels are the fp32 ones with another row
+ * loader (4 bytes a lane a piece, one load of the scale a row, four conversions, four multiplies) and the same summation order.
+ * Nothing about the search is defined a second time: each entry below is the named entry without gallery_is_half, with that entry's
+ * workspace size (vtc_l2_search_workspace_bytes / _grouped_ / _sets_ / vtc_l2_range_workspace_bytes), limits, refusals and messages.
+ * vtc_l2_search_merge / vtc_l2_search_merge_grouped take windows of q8 galleries as they are.
+ *   vtc_l2_search_q8            all six scans: vtc_l2_search_masked (only live, nullable), vtc_l2_search_grouped (groups), vtc_l2_search_after
+ *                               (after_d / after_i), vtc_l2_search_excluding (exclude; with groups or with a nullable cursor) and
+ *                               vtc_l2_search_grouped_after (groups + ban + n_groups + the cursor; exclude nullable).  Everything from live to
+ *                               after_i is nullable; n_groups is looked at only with ban; the combinations are those entries'.
+ *   vtc_l2_search_sets_q8, vtc_l2_group_mark_before_q8, vtc_l2_pair_dists64_q8, vtc_l2_range_count_q8, vtc_l2_range_fill_q8
+ * THE QUANTISER, vtc_quantize_rows_q8: x [n][d] fp32 -> rows_out [n][d + 16], one launch, a wave per row, all in fp32 arithmetic with
+ * correctly rounded divisions:  m = max_k |x_k|;  t = fl32(m / 127);  s = t rounded UP to 16 significant bits, bits(s) = (bits(t) +
+ * 0xFF) & ~0xFF;  s = 1 when m = 0;  c_k = clamp(rint(fl32(x_k / s)), -127, 127), rint to nearest even.  So |x_k - s c_k| <=
+ * 0.5 (1 + 2^-15) s.  A row with a NaN / inf gets s = NaN and all-zero codes and sets bit 1 of nonfinite (nullable).
+ * NOT PROVIDED: the many-query MFMA passes over q8 galleries; vtc_l2_topk; per-block or asymmetric scales; quantised queries. */
+size_t vtc_q8_row_bytes(int d);      /* d + 16; 0 for a d the search refuses */
+int vtc_quantize_rows_q8(const float *x, int n, int d, void *rows_out, int *nonfinite, void *stream);
+int vtc_l2_search_q8(const void *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_groups, const uint32_t *ban,
+                     const int64_t *exclude, const double *after_d, const int64_t *after_i, int n_gallery, int n_queries, int d, int depth,
+                     int64_t id_base, int64_t *ids, int32_t *out_groups, float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+int vtc_l2_search_sets_q8(const void *gallery, const float *queries, const uint32_t *live, const int32_t *groups, const int64_t *exclude,
+                          int n_gallery, int n_sets, int set_size, int d, int depth, int64_t id_base, int64_t *ids, int32_t *out_groups,
+                          float *dists, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+int vtc_l2_group_mark_before_q8(const void *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_groups,
+                                const double *after_d, const int64_t *after_i, int n_gallery, int n_queries, int d, int64_t id_base,
+                                uint32_t *ban, void *stream);
+int vtc_l2_pair_dists64_q8(const void *gallery, const float *queries, const int64_t *rows, int n_gallery, int n_queries, int d, int64_t id_base,
+                           double *out, void *stream);
+int vtc_l2_range_count_q8(const void *gallery, const float *queries, const uint32_t *live, const double *radius2, int n_gallery, int n_queries,
+                          int d, int64_t *lims, int *nonfinite, void *ws, size_t ws_bytes, void *stream);
+int vtc_l2_range_fill_q8(const void *gallery, const float *queries, int n_gallery, int n_queries, int d, const int64_t *lims, int64_t capacity,
+                         int64_t id_base, int64_t *ids, float *dists, double *dists64, void *ws, size_t ws_bytes, void *stream);
 /* hits[j] +=#{ i : (target_offset + i) in ids[i, :k_vals[j]] }   (hits: int64 device) */
 int vtc_recall_hits(const int64_t *ids, int n_queries, int depth, int64_t target_offset, const int *k_vals_host,
                     int nk, long long *hits, void *stream);

@@ -55,6 +55,21 @@ Per (n_gallery, n_queries, variant) one JSON line:
                            groups) that the half index returns too: what rounding the stored rows to 11 bits costs
 profiles/search_half.md holds a run's table.
 
+With --storage int8 the tool measures the scan over a gallery STORED AS 8-BIT CODES and one scale a row (ops.quantize_rows_q8; ops.l2_search
+with a torch.int8 gallery = vtc_l2_search_q8) against the fp32 scan and the half scan of the SAME unit rows, all three in one run:
+
+    python tools/search_bench.py --storage int8 [--queries 1,8,64] ...
+
+Per (n_gallery, n_queries) one JSON line:
+  fp32_us / half_us / int8_us   the three scans, in alternation as above; int8_over_fp32 / int8_over_half: ratios of the medians
+  *_mb                          the bytes each gallery holds (int8: (d + 16) a row)
+  same_bits_as_stored_fp32      ids and fp32 dists of the int8 scan equal the fp32 scan's over the dequantised rows (asserted)
+  top10_overlap                 the share of the 10 nearest ids of the fp32 index of the unit rows that the int8 index returns too (half_: the
+                                half index's share), averaged over the queries
+  max_score_diff                the largest |score over the int8 rows - score over the fp32 rows| among the returned (query, row) pairs,
+                                score = 1 - D / 2 with both D in fp64 (half_: the half index's)
+profiles/search_q8.md holds a run's table.
+
 With --hits (or --min-score) the tool measures the RANGE search (ops.l2_range_count / vtc_l2_range_fill) against the scan:
 
     python tools/search_bench.py --hits 100,10000,all [--storage float16] [--queries 1,8,64] ...
@@ -361,6 +376,56 @@ def half_main(args):
                 assert same_host, "the half scan and the host's full fp64 order over the widened rows returned different ids"
                 del ws_h, ws_f
         del unrounded, half, wide
+        torch.cuda.empty_cache()
+    return lines
+
+
+def q8_main(args):
+    """--storage int8: the scan over q8 rows against the fp32 scan and the half scan of the same unit rows."""
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    lines = []
+    for ng in [int(x) for x in args.galleries.split(",")]:
+        fp32 = ops.normalize_rows(torch.randn(ng, args.d, device="cuda", generator=gen))
+        galleries = {"fp32": fp32, "half": fp32.to(torch.float16), "int8": ops.quantize_rows_q8(fp32)}
+        for nq in [int(x) for x in args.queries.split(",")]:
+            pick = torch.randint(0, ng, (nq,), device="cuda", generator=gen)
+            queries = ops.normalize_rows(fp32[pick] + 0.5 * ops.normalize_rows(torch.randn(nq, args.d, device="cuda", generator=gen)))
+            need = ops.l2_search_workspace_bytes(ng, nq, args.d, args.depth)
+            ws = {name: ops.workspace(need, fp32.device) for name in galleries}
+            entries = {name: (lambda g=g, w=ws[name]: ops.l2_search(g, queries, args.depth, ws=w)[:2]) for name, g in galleries.items()}
+            for _ in range(args.warmup):
+                for fn in entries.values():
+                    fn()
+            torch.cuda.synchronize()
+            times, outs = {name: [] for name in entries}, {}
+            for _ in range(args.calls):
+                for name, fn in entries.items():
+                    us, outs[name] = timed(fn)
+                    times[name].append(us)
+            stored = ops.l2_search(ops.dequantize_rows_q8(galleries["int8"]), queries, args.depth)[:2]
+            same_bits = bool(torch.equal(outs["int8"][0], stored[0]) and torch.equal(outs["int8"][1], stored[1]))
+            top = min(10, args.depth)
+            line = {"n_gallery": ng, "n_queries": nq, "d": args.d, "depth": args.depth, "calls": args.calls, "passes": passes(nq)}
+            for name, g in galleries.items():
+                line[name + "_us"] = stat(times[name])
+                line[name + "_mb"] = round(g.numel() * g.element_size() / 2 ** 20, 1)
+            for name in ("half", "int8"):
+                line[f"{name}_over_fp32"] = round(line[name + "_us"]["median"] / line["fp32_us"]["median"], 3)
+                ids = outs[name][0]
+                overlap = float(np.mean([np.isin(a[:top], b[:top]).mean() for a, b in zip(outs["fp32"][0].cpu().numpy(), ids.cpu().numpy())]))
+                rep = queries[:, None].expand(nq, args.depth, args.d).reshape(-1, args.d).contiguous()
+                own = ops.l2_pair_dists64(galleries[name], rep, ids.reshape(-1))
+                ref = ops.l2_pair_dists64(fp32, rep, ids.reshape(-1))
+                prefix = "" if name == "int8" else "half_"
+                line[prefix + "top10_overlap"] = round(overlap, 4)
+                line[prefix + "max_score_diff"] = float(((own - ref).abs() / 2).max())
+            line["int8_over_half"] = round(line["int8_us"]["median"] / line["half_us"]["median"], 3)
+            line["same_bits_as_stored_fp32"] = same_bits
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            assert same_bits, "the int8 scan and the fp32 scan over the dequantised rows returned different bits"
+            del ws, entries
+        del fp32, galleries
         torch.cuda.empty_cache()
     return lines
 
@@ -748,8 +813,9 @@ def main(argv=None):
     ap.add_argument("--topk-gathered", action="store_true", help="with --live: also time gather + l2_topk(EXACT) over the live rows")
     ap.add_argument("--rows-per-video", type=str, default=None, help="rows per video, e.g. 1,5,20: measure the grouped scan (see above)")
     ap.add_argument("--video-layout", type=str, default="contiguous", choices=("contiguous", "scattered"))
-    ap.add_argument("--storage", type=str, default="float32", choices=("float32", "float16"),
-                    help="float16: measure the scan over a half gallery against the fp32 scan (see above); works with --live / --rows-per-video")
+    ap.add_argument("--storage", type=str, default="float32", choices=("float32", "float16", "int8"),
+                    help="float16: measure the scan over a half gallery against the fp32 scan (see above); works with --live / --rows-per-video.  "
+                         "int8: the scan over q8 rows against the fp32 and the half scan of the same rows (see above)")
     ap.add_argument("--hits", type=str, default=None, help="hits per query, e.g. 100,10000,all: measure the range search (see above)")
     ap.add_argument("--min-score", type=str, default=None, help="score thresholds, e.g. 0.9,0.5: the range search at radius 2 (1 - s)")
     ap.add_argument("--after-pages", type=int, default=None, help="P: measure the cursor scan, the cursor on the (64 P)-th neighbour (see above)")
@@ -763,6 +829,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
     assert args.calls >= 30, "at least 30 timed calls per entry"
+    if args.storage == "int8":
+        assert not (args.live or args.rows_per_video or args.hits or args.min_score or args.exclude or args.after_pages is not None or
+                    args.grouped_after is not None), "the int8 mode measures the plain scan of the three storages"
+        write_out(args.out, q8_main(args))
+        return
     if args.grouped_after is not None:
         assert args.grouped_after >= 1 and not (args.live or args.hits or args.min_score or args.after_pages is not None or args.exclude), \
             "the page mode takes --rows-per-video and --baseline-lib only"

@@ -139,6 +139,17 @@ SIGNATURES = {
     # the count pass for many queries over a half gallery (range_many.hip): an MFMA pass, the band decided in fp64 -- vtc_l2_range_count's bits
     "vtc_l2_range_many_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "vtc_l2_range_count_many_half": (C.c_int, [vp, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),
+    # 8-bit gallery storage (search_q8.hip, search_sets_q8.hip, range_q8.hip): rows of d codes + an fp32 scale, searched as stored
+    "vtc_q8_row_bytes": (C.c_size_t, [C.c_int]),
+    "vtc_quantize_rows_q8": (C.c_int, [fp, C.c_int, C.c_int, vp, ip, vp]),
+    "vtc_l2_search_q8": (C.c_int, [vp, fp, ip, ip, C.c_int, ip, ip, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp,
+                                   C.c_size_t, vp]),
+    "vtc_l2_search_sets_q8": (C.c_int, [vp, fp, ip, ip, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, ip, ip, fp, ip, vp, C.c_size_t,
+                                        vp]),
+    "vtc_l2_group_mark_before_q8": (C.c_int, [vp, fp, ip, ip, C.c_int, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int64, ip, vp]),
+    "vtc_l2_pair_dists64_q8": (C.c_int, [vp, fp, ip, C.c_int, C.c_int, C.c_int, C.c_int64, fp, vp]),
+    "vtc_l2_range_count_q8": (C.c_int, [vp, fp, ip, fp, C.c_int, C.c_int, C.c_int, ip, ip, vp, C.c_size_t, vp]),
+    "vtc_l2_range_fill_q8": (C.c_int, [vp, fp, C.c_int, C.c_int, C.c_int, ip, C.c_int64, C.c_int64, ip, fp, fp, vp, C.c_size_t, vp]),
     "vtc_recall_hits": (C.c_int, [ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp]),
     "vtc_recall_hits_pair": (C.c_int, [ip, ip, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, vp, vp, vp]),
     "vtc_l2_recall_bidir_supported": (C.c_int, [C.c_int, C.c_int]),

@@ -16,10 +16,11 @@
 //                      disjoint gallery windows (Src = PartLists, vtc_l2_search_merge*): the lists are sorted, so a lane follows one
 //                      list and leaves at its first entry that does not beat the current depth-th.
 //
-// The scan, the merge, their lists and the host driver are in search_scan.h, which search_sets.hip shares; this file holds the mark pass,
-// the pair distances, the mask packer and the entries -- and, through the entries, every non-SET instantiation.
+// The scan, the merge, their lists, the mark pass, the pair distances and the host driver are in search_scan.h, which search_sets.hip and
+// the q8 files (search_q8.hip, search_sets_q8.hip) share; this file holds the mask packer and the entries -- and, through the entries,
+// every non-SET instantiation over float and _Float16 galleries.
 //
-// G is the gallery's element type.  _Float16 (rows stored as IEEE binary16) differs in the row loader alone (sweep_common.h, row_piece):
+// G is the gallery's element type.  q8_t (8-bit codes and a scale a row) is search_q8.hip's.  _Float16 (rows stored as IEEE binary16) differs in the row loader alone (sweep_common.h, row_piece):
 // a lane loads 8 bytes a piece where the fp32 scan loads 16, widens them exactly and forms the distance with the same statements in the
 // same order -- the fp64 bits of the fp32 scan over the widened rows.  The workspace, the lists and the merges do not know how the
 // gallery is stored.  (NQ, NR) is the tile shape of the call's query count (search_walk.h, tile_plan).  The mode flags, and what each
@@ -77,83 +78,6 @@
 namespace {
 using namespace vtcsweep;
 
-// The mark pass (vtc_l2_group_mark_before): the scan's walk with the distances of wave_dist64_queries, so the bits the page scan
-// compares, and no lists.  A live row with a finite distance that lies AT OR BEFORE query u's cursor, the exact negation of the scan's
-// test, sets bit groups[row] of ban[q0 + u]: an atomicOr from one lane.  A NaN cursor therefore marks every such row (and admits
-// nothing in the scan), -inf none.  A group outside [0, n_grp) marks nothing: it is checked before the address is formed.  The pass
-// only ORs.
-template <typename G, int NQ, int NR, bool MASKED>
-__global__ __launch_bounds__(256) void mark_kernel(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
-                                                   const int *__restrict__ groups, const double *__restrict__ after_d,
-                                                   const int64_t *__restrict__ after_i, int64_t id_base, int n_grp, int ng, int nq, int d,
-                                                   unsigned *__restrict__ ban) {
-  extern __shared__ float4 smem4[];
-  const float *qt = reinterpret_cast<const float *>(smem4);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.y * NQ;
-  const unsigned dead = load_query_tile<NQ>(queries, q0, nq, d, smem4, nullptr);      // bit u: query q0 + u marks nothing
-  double cd[NQ];
-  int cr[NQ];
-  load_cursors<NQ, false>(after_d, after_i, id_base, ng, q0, nq, cd, cr);
-  const size_t ban_words = ((size_t)(unsigned)n_grp + 31) >> 5;
-  const long long n_steps = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
-  long long s = (long long)blockIdx.x * 4 + wave;
-  unsigned next_word = 0;
-  if constexpr (MASKED) {
-    if (s < n_steps) next_word = live_word<NR>(live, s);
-  }
-  for (; s < n_steps; s += GW) {
-    unsigned bits = 0;
-    if constexpr (MASKED) {
-      bits = live_bits<NR>(ng, s, next_word);
-      if (s + GW < n_steps) next_word = live_word<NR>(live, s + GW);
-      if (!bits) continue;                                 // nothing live in this step: no gallery load
-    }
-    int jj[NR];
-    step_rows<NR, MASKED>(s, bits, ng, jj);
-    int gv[NR];                                            // loaded before the step's gallery rows, as the scan's
-#pragma unroll
-    for (int r = 0; r < NR; ++r) gv[r] = groups[jj[r]];
-    double dist[NQ * NR];
-    wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-      if (row_taken<NR, MASKED>(s, bits, r, ng)) {
-#pragma unroll
-        for (int u = 0; u < NQ; ++u) {
-          const double cv = dist[u * NR + r];
-          if (!(cv < INFINITY) || ((dead >> u) & 1)) continue;
-          if (cv > cd[u] || (cv == cd[u] && jj[r] > cr[u])) continue;      // after the cursor: the page scan's business
-          const int cg = uniform_of(gv[r]);
-          if ((unsigned)cg >= (unsigned)n_grp) continue;                  // no bit: checked before the address is formed
-          if (lane == 0) atomicOr(ban + (size_t)(q0 + u) * ban_words + ((unsigned)cg >> 5), 1u << (cg & 31));      // q0 + u < nq: not dead
-        }
-      }
-    }
-  }
-}
-
-// out[q] = D(queries[q], gallery[rows[q] - id_base]), the fp64 distance with the bits the scans form (the same wave_dist64_core), one
-// wave per query; +inf for a row id outside [id_base, id_base + ng) -- -1 included -- whose memory is not touched.  The row is read
-// WHETHER OR NOT IT IS LIVE: there is no mask here, a removed row keeps its memory (VideoIndex), and a cursor may stand on one.  The
-// query is read as it is: one with a NaN / inf gives a non-finite out[q], which as a cursor admits nothing.
-template <typename G>
-__global__ __launch_bounds__(256) void pair_dists64_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
-                                                           const int64_t *__restrict__ rows, int ng, int nq, int d, int64_t id_base,
-                                                           double *__restrict__ out) {
-  const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq) return;                                     // wave-uniform
-  const long long row = uniform_of((long long)rows[q]);
-  double v = INFINITY;
-  if (row >= id_base && row - id_base < ng) {
-    const int jj[1] = {(int)(row - id_base)};
-    double dist[1];
-    wave_dist64_queries<1, 1>(queries + (size_t)q * d, gallery, jj, d, lane, dist);
-    v = dist[0];
-  }
-  if (lane == 0) out[q] = v;
-}
-
 // words[w] bit b = (flags[32 w + b] != 0) & and_mask[w] bit b: a thread per row, a ballot per wave -- 64 rows, two words, written by
 // two lanes.  A row past n_rows votes 0, so the tail bits are 0.
 __global__ __launch_bounds__(256) void row_mask_pack_kernel(const uint8_t *__restrict__ flags, int n_rows, const unsigned *__restrict__ and_mask,
@@ -167,26 +91,6 @@ __global__ __launch_bounds__(256) void row_mask_pack_kernel(const uint8_t *__res
     if (and_mask) v &= and_mask[w];
     words[w] = v;
   }
-}
-
-// The mark pass runs the scan's grid without its occupancy question: no lists depend on the number of workgroups, and a workgroup that is
-// not resident at once only starts later.
-template <typename G>
-void launch_mark_of(const ScanArgs &a, unsigned *ban, hipStream_t stream) {
-  const TilePlan p = tile_plan(a.nq);
-  with_tile(p, [&](auto tq, auto tr) {
-    constexpr int NQ = decltype(tq)::value, NR = decltype(tr)::value;
-    const long long n_steps = ((long long)a.ng + NR - 1) / NR;
-    const int blocks = (int)std::min<long long>(std::min(search_max_lists(a.ng), 4 * vtcgemm::num_cus()), (n_steps + 3) / 4);
-    const size_t lds = (size_t)NQ * a.d * sizeof(float);
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(blocks, p.tiles), dim3(256), lds, stream, static_cast<const G *>(a.gallery), a.queries, a.live, a.groups,
-                         a.after_d, a.after_i, a.id_base, a.n_grp, a.ng, a.nq, a.d, ban);
-    };
-    if (a.live) launch(mark_kernel<G, NQ, NR, true>);
-    else launch(mark_kernel<G, NQ, NR, false>);
-    return 0;
-  });
 }
 
 int merge_parts(const char *name, const int64_t *ids_parts, const double *dists_parts, const int32_t *groups_parts, int n_parts, int nq, int depth,
@@ -273,30 +177,14 @@ extern "C" int vtc_l2_search_grouped_after(const void *gallery, int gallery_is_h
 extern "C" int vtc_l2_group_mark_before(const void *gallery, int gallery_is_half, const float *queries, const uint32_t *live, const int32_t *groups,
                                         int n_groups, const double *after_d, const int64_t *after_i, int ng, int nq, int d, int64_t id_base,
                                         uint32_t *ban, void *stream) {
-  const char *name = "l2_group_mark_before (the grouped search's cursor)";
-  VTC_CHECK(gallery && queries && groups && after_d && after_i && ban, "%s: null argument", name);
-  if (check_shape(name, ng, nq, SEARCH_MAX_Q, "", &n_groups, nullptr, d, id_base)) return 1;
-  const ScanArgs a{gallery, queries, live, groups, after_d, after_i, id_base, nullptr, nullptr, n_groups, ng, nq, d, 0, nullptr, nullptr, nullptr, nullptr};
-  if (gallery_is_half) launch_mark_of<_Float16>(a, ban, (hipStream_t)stream);
-  else launch_mark_of<float>(a, ban, (hipStream_t)stream);
-  VTC_LAUNCH_CHECK("l2_group_mark_before");
-  return 0;
+  return gallery_is_half ? mark_before<_Float16>(gallery, queries, live, groups, n_groups, after_d, after_i, ng, nq, d, id_base, ban, stream)
+                         : mark_before<float>(gallery, queries, live, groups, n_groups, after_d, after_i, ng, nq, d, id_base, ban, stream);
 }
 
 extern "C" int vtc_l2_pair_dists64(const void *gallery, int gallery_is_half, const float *queries, const int64_t *rows, int ng, int nq, int d,
-                                   int64_t id_base, double *out, void *stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const char *name = "l2_pair_dists64 (the search's cursor distances)";
-  VTC_CHECK(gallery && queries && rows && out, "%s: null argument", name);
-  if (check_shape(name, ng, nq, 0, "", nullptr, nullptr, d, id_base)) return 1;
-  if (gallery_is_half)
-    hipLaunchKernelGGL(pair_dists64_kernel<_Float16>, dim3(cdiv(nq, 4)), dim3(256), 0, stream, reinterpret_cast<const _Float16 *>(gallery), queries,
-                       rows, ng, nq, d, id_base, out);
-  else
-    hipLaunchKernelGGL(pair_dists64_kernel<float>, dim3(cdiv(nq, 4)), dim3(256), 0, stream, reinterpret_cast<const float *>(gallery), queries, rows,
-                       ng, nq, d, id_base, out);
-  VTC_LAUNCH_CHECK("l2_pair_dists64");
-  return 0;
+                                   int64_t id_base, double *out, void *stream) {
+  return gallery_is_half ? pair_dists64<_Float16>(gallery, queries, rows, ng, nq, d, id_base, out, stream)
+                         : pair_dists64<float>(gallery, queries, rows, ng, nq, d, id_base, out, stream);
 }
 
 extern "C" int vtc_l2_search_merge(const int64_t *ids_parts, const double *dists_parts, int n_parts, int nq, int depth, int64_t *ids,

@@ -1,5 +1,6 @@
-// search_scan.h -- the scan, the merge and the host driver of the query-time search, shared by the two files that instantiate them:
-// search.hip (a tile is NQ queries, a list each) and search_sets.hip (SET: a tile is NQ members of ONE set query, one list).  What the
+// search_scan.h -- the scan, the merge, the mark pass, the pair distances and the host driver of the query-time search, shared by the
+// files that instantiate them: search.hip (a tile is NQ queries, a list each), search_sets.hip (SET: a tile is NQ members of ONE set
+// query, one list), and search_q8.hip / search_sets_q8.hip (the same two tables over q8 rows).  What the
 // kernels do and why the merges are exact is told at the head of search.hip.  One scan kernel, one launch site (launch_scan), one
 // driver (run_search); the kernels keep internal linkage, so each file holds only the instantiations its entries launch --
 // tests/test_build_search_no_spills.py pins search.hip's by name and number, and the SET ones live in search_sets.hip.
@@ -285,6 +286,83 @@ __global__ __launch_bounds__(256) void merge_kernel(Src src, int nlists, int dep
   }
 }
 
+// The mark pass (vtc_l2_group_mark_before): the scan's walk with the distances of wave_dist64_queries, so the bits the page scan
+// compares, and no lists.  A live row with a finite distance that lies AT OR BEFORE query u's cursor, the exact negation of the scan's
+// test, sets bit groups[row] of ban[q0 + u]: an atomicOr from one lane.  A NaN cursor therefore marks every such row (and admits
+// nothing in the scan), -inf none.  A group outside [0, n_grp) marks nothing: it is checked before the address is formed.  The pass
+// only ORs.
+template <typename G, int NQ, int NR, bool MASKED>
+__global__ __launch_bounds__(256) void mark_kernel(const G *__restrict__ gallery, const float *__restrict__ queries, const unsigned *__restrict__ live,
+                                                   const int *__restrict__ groups, const double *__restrict__ after_d,
+                                                   const int64_t *__restrict__ after_i, int64_t id_base, int n_grp, int ng, int nq, int d,
+                                                   unsigned *__restrict__ ban) {
+  extern __shared__ float4 smem4[];
+  const float *qt = reinterpret_cast<const float *>(smem4);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q0 = blockIdx.y * NQ;
+  const unsigned dead = load_query_tile<NQ>(queries, q0, nq, d, smem4, nullptr);      // bit u: query q0 + u marks nothing
+  double cd[NQ];
+  int cr[NQ];
+  load_cursors<NQ, false>(after_d, after_i, id_base, ng, q0, nq, cd, cr);
+  const size_t ban_words = ((size_t)(unsigned)n_grp + 31) >> 5;
+  const long long n_steps = ((long long)ng + NR - 1) / NR, GW = (long long)gridDim.x * 4;
+  long long s = (long long)blockIdx.x * 4 + wave;
+  unsigned next_word = 0;
+  if constexpr (MASKED) {
+    if (s < n_steps) next_word = live_word<NR>(live, s);
+  }
+  for (; s < n_steps; s += GW) {
+    unsigned bits = 0;
+    if constexpr (MASKED) {
+      bits = live_bits<NR>(ng, s, next_word);
+      if (s + GW < n_steps) next_word = live_word<NR>(live, s + GW);
+      if (!bits) continue;                                 // nothing live in this step: no gallery load
+    }
+    int jj[NR];
+    step_rows<NR, MASKED>(s, bits, ng, jj);
+    int gv[NR];                                            // loaded before the step's gallery rows, as the scan's
+#pragma unroll
+    for (int r = 0; r < NR; ++r) gv[r] = groups[jj[r]];
+    double dist[NQ * NR];
+    wave_dist64_queries<NQ, NR>(qt, gallery, jj, d, lane, dist);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      if (row_taken<NR, MASKED>(s, bits, r, ng)) {
+#pragma unroll
+        for (int u = 0; u < NQ; ++u) {
+          const double cv = dist[u * NR + r];
+          if (!(cv < INFINITY) || ((dead >> u) & 1)) continue;
+          if (cv > cd[u] || (cv == cd[u] && jj[r] > cr[u])) continue;      // after the cursor: the page scan's business
+          const int cg = uniform_of(gv[r]);
+          if ((unsigned)cg >= (unsigned)n_grp) continue;                  // no bit: checked before the address is formed
+          if (lane == 0) atomicOr(ban + (size_t)(q0 + u) * ban_words + ((unsigned)cg >> 5), 1u << (cg & 31));      // q0 + u < nq: not dead
+        }
+      }
+    }
+  }
+}
+
+// out[q] = D(queries[q], gallery[rows[q] - id_base]), the fp64 distance with the bits the scans form (the same wave_dist64_core), one
+// wave per query; +inf for a row id outside [id_base, id_base + ng) -- -1 included -- whose memory is not touched.  The row is read
+// WHETHER OR NOT IT IS LIVE: there is no mask here, a removed row keeps its memory (VideoIndex), and a cursor may stand on one.  The
+// query is read as it is: one with a NaN / inf gives a non-finite out[q], which as a cursor admits nothing.
+template <typename G>
+__global__ __launch_bounds__(256) void pair_dists64_kernel(const G *__restrict__ gallery, const float *__restrict__ queries,
+                                                           const int64_t *__restrict__ rows, int ng, int nq, int d, int64_t id_base,
+                                                           double *__restrict__ out) {
+  const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;                                     // wave-uniform
+  const long long row = uniform_of((long long)rows[q]);
+  double v = INFINITY;
+  if (row >= id_base && row - id_base < ng) {
+    const int jj[1] = {(int)(row - id_base)};
+    double dist[1];
+    wave_dist64_queries<1, 1>(queries + (size_t)q * d, gallery, jj, d, lane, dist);
+    v = dist[0];
+  }
+  if (lane == 0) out[q] = v;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 bool search_args_ok(int ng, int nq, int d, int depth) {
   return ng >= 1 && nq >= 1 && nq <= SEARCH_MAX_Q && depth >= 1 && depth <= SEARCH_MAX_DEPTH && depth <= ng && d >= 64 && d <= SEARCH_MAX_D &&
@@ -363,6 +441,26 @@ int launch_scan_of(const ScanArgs &a, hipStream_t stream) {
   }
   return mode(no, no, no);
 }
+// The mark pass runs the scan's grid without its occupancy question: no lists depend on the number of workgroups, and a workgroup that is
+// not resident at once only starts later.
+template <typename G>
+void launch_mark_of(const ScanArgs &a, unsigned *ban, hipStream_t stream) {
+  const TilePlan p = tile_plan(a.nq);
+  with_tile(p, [&](auto tq, auto tr) {
+    constexpr int NQ = decltype(tq)::value, NR = decltype(tr)::value;
+    const long long n_steps = ((long long)a.ng + NR - 1) / NR;
+    const int blocks = (int)std::min<long long>(std::min(search_max_lists(a.ng), 4 * vtcgemm::num_cus()), (n_steps + 3) / 4);
+    const size_t lds = (size_t)NQ * a.d * sizeof(float);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(blocks, p.tiles), dim3(256), lds, stream, static_cast<const G *>(a.gallery), a.queries, a.live, a.groups,
+                         a.after_d, a.after_i, a.id_base, a.n_grp, a.ng, a.nq, a.d, ban);
+    };
+    if (a.live) launch(mark_kernel<G, NQ, NR, true>);
+    else launch(mark_kernel<G, NQ, NR, false>);
+    return 0;
+  });
+}
+
 // The checks every entry over a gallery window makes, in this order; `name` is what the entry calls itself in its messages.
 // max_q = 0: any number of queries.  n_groups / depth null: the entry has none.  sets: {n_sets, set_size} of an entry whose queries are
 // the members of sets, max_q together.
@@ -381,6 +479,29 @@ int check_shape(const char *name, int ng, int nq, int max_q, const char *nq_hint
   VTC_CHECK(d >= 64 && d <= SEARCH_MAX_D && d % 64 == 0, "%s: d=%d must be a multiple of 64 in [64, %d]", name, d, SEARCH_MAX_D);
   VTC_CHECK(id_base >= 0 && id_base <= INT64_MAX - ng, "%s: id_base=%lld must be non-negative (and id_base + n_gallery an int64)", name,
             (long long)id_base);
+  return 0;
+}
+
+// vtc_l2_group_mark_before and vtc_l2_pair_dists64 over a gallery of G: the entries (search.hip, search_q8.hip) only choose G.
+template <typename G>
+int mark_before(const void *gallery, const float *queries, const uint32_t *live, const int32_t *groups, int n_groups, const double *after_d,
+                const int64_t *after_i, int ng, int nq, int d, int64_t id_base, uint32_t *ban, void *stream) {
+  const char *name = "l2_group_mark_before (the grouped search's cursor)";
+  VTC_CHECK(gallery && queries && groups && after_d && after_i && ban, "%s: null argument", name);
+  if (check_shape(name, ng, nq, SEARCH_MAX_Q, "", &n_groups, nullptr, d, id_base)) return 1;
+  const ScanArgs a{gallery, queries, live, groups, after_d, after_i, id_base, nullptr, nullptr, n_groups, ng, nq, d, 0, nullptr, nullptr, nullptr, nullptr};
+  launch_mark_of<G>(a, ban, (hipStream_t)stream);
+  VTC_LAUNCH_CHECK("l2_group_mark_before");
+  return 0;
+}
+template <typename G>
+int pair_dists64(const void *gallery, const float *queries, const int64_t *rows, int ng, int nq, int d, int64_t id_base, double *out, void *stream) {
+  const char *name = "l2_pair_dists64 (the search's cursor distances)";
+  VTC_CHECK(gallery && queries && rows && out, "%s: null argument", name);
+  if (check_shape(name, ng, nq, 0, "", nullptr, nullptr, d, id_base)) return 1;
+  hipLaunchKernelGGL(pair_dists64_kernel<G>, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const G *>(gallery), queries, rows,
+                     ng, nq, d, id_base, out);
+  VTC_LAUNCH_CHECK("l2_pair_dists64");
   return 0;
 }
 
@@ -450,6 +571,12 @@ int run_search(const char *name, const SearchCall &c) {
   }
   VTC_LAUNCH_CHECK2(name, "merge");
   return 0;
+}
+// the entry of a file whose galleries are all of G (search_q8.hip, search_sets_q8.hip: SearchCall::half is not looked at)
+template <typename G, bool SET = false>
+int search_entry_of(const char *name, const SearchCall &c) {
+  if (check_search_call(name, c)) return 1;
+  return run_search<G, SET>(name, c);
 }
 template <bool SET = false>
 int search_entry(const char *name, const SearchCall &c) {

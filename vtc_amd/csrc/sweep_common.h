@@ -3,6 +3,8 @@
 #pragma once
 #include "common.h"
 
+#include <type_traits>
+
 namespace vtcsweep {
 
 // ---- the fp64 squared distance of VTC_SWEEP_EXACT, the recall-only finish and the full-rank sweep --------------------------------------
@@ -20,6 +22,31 @@ __device__ __forceinline__ float4 row_piece(const _Float16 *p) {
   typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
   const half4_t h = *reinterpret_cast<const half4_t *>(p);
   return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+}
+// A row stored as 8-bit codes with one fp32 scale (include/vtc_hip.h, "a q8 row"): d signed codes, the scale at byte d, 12 bytes that
+// are never read -- d + 16 bytes a row, so FORMING A ROW'S ADDRESS is part of what the element type decides (q8_row).  The value of a
+// column is fl32(scale * code), subnormals kept: 4 bytes loaded, four int -> fp32 conversions (exact), four v_mul_f32 -- the float4 is
+// bit for bit what the fp32 load returns from the gallery of those products and everything after it is shared.  The scale is not
+// part of a piece: the caller loads it once per row, every lane the one address, before the row's first piece (wave_dist64_queries).
+struct q8_t {
+  signed char code;
+};
+constexpr int Q8_TAIL = 16;                                // bytes of a row behind its codes: the scale and 12 of padding
+struct Q8Piece {
+  const q8_t *p;
+  float scale;
+};
+struct Q8Row {
+  const q8_t *p;
+  float scale;
+  __device__ __forceinline__ Q8Piece operator+(int c) const { return {p + c, scale}; }
+};
+__device__ __forceinline__ const q8_t *q8_row(const q8_t *gallery, long long row, int d) { return gallery + (size_t)row * (size_t)(d + Q8_TAIL); }
+__device__ __forceinline__ float q8_scale(const q8_t *row, int d) { return *reinterpret_cast<const float *>(row + d); }
+__device__ __forceinline__ float4 row_piece(const Q8Piece g) {
+  typedef signed char char4_t __attribute__((ext_vector_type(4)));
+  const char4_t c = *reinterpret_cast<const char4_t *>(g.p);
+  return make_float4(g.scale * (float)c.x, g.scale * (float)c.y, g.scale * (float)c.z, g.scale * (float)c.w);
 }
 // fp64 sum_k (q_k - g_k)^2 of NB (query row, gallery row) pairs by the whole wave: qrow(u) / grow(u) are pair u's rows.  Per pair a lane adds
 // the steps of its chunks in ascending k, then the xor butterfly leaves every lane with the same bits.  EVERY kernel that forms a distance --
@@ -71,11 +98,23 @@ __device__ __forceinline__ void wave_dist64_pairs(const float *__restrict__ qs, 
 }
 // the NB consecutive query rows qs[0 .. NB) (row stride d; global memory or LDS) against the NR gallery rows jj[] (valid indices, as above):
 // out[u * NR + r] = query u, gallery row jj[r].  The query-time search (search.hip): its tile of queries stays put while the gallery streams by.
-// G is the gallery's element type, float or _Float16 (row_piece); the queries are fp32 either way.
+// G is the gallery's element type, float or _Float16 (row_piece); the queries are fp32 either way.  G = q8_t: the rows' scales are requested
+// first, one load a row that every lane makes of the one address, and ride with the rows into the same loop -- the summation order,
+// and so the fp64 bits, of the fp32 gallery of the stored values.
 template <int NB, int NR = 1, typename G = float>
 __device__ __forceinline__ void wave_dist64_queries(const float *qs, const G *__restrict__ gallery, const int (&jj)[NR], int d, int lane,
                                                     double (&out)[NB * NR]) {
-  wave_dist64_core<NB * NR>([&](int p) { return qs + (size_t)(p / NR) * d; }, [&](int p) { return gallery + (size_t)jj[p % NR] * d; }, d, lane, out);
+  if constexpr (std::is_same_v<G, q8_t>) {
+    Q8Row rows[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      rows[r].p = q8_row(gallery, jj[r], d);
+      rows[r].scale = q8_scale(rows[r].p, d);
+    }
+    wave_dist64_core<NB * NR>([&](int p) { return qs + (size_t)(p / NR) * d; }, [&](int p) { return rows[p % NR]; }, d, lane, out);
+  } else {
+    wave_dist64_core<NB * NR>([&](int p) { return qs + (size_t)(p / NR) * d; }, [&](int p) { return gallery + (size_t)jj[p % NR] * d; }, d, lane, out);
+  }
 }
 
 // ---- host pieces, defined in sweep_front.hip ----------------------------------------------------------------------------------------

@@ -31,6 +31,15 @@ A stored row is then the unit row rounded to nearest-even to the 11 significant 
 over the rows AS STORED: the fp64 distances of the fp32 queries and the widened half rows, bit for bit what an fp32 index holding those
 widened rows returns.
 
+Or as 8-bit codes with one fp32 scale a row, the scalar quantiser of every vector-search library (vtc_quantize_rows_q8 / vtc_l2_search_q8):
+
+    index = VideoIndex(512, storage=torch.int8)       # or: index = fp32_index.converted(torch.int8)
+
+A stored row is then ``width`` signed bytes and its scale, width + 16 bytes: (width + 16) / (4 width) of fp32, 0.258 at 512 columns.  The
+loss happens once, at ``add``; every search stays exact over the rows AS STORED, bit for bit what an fp32 index holding the dequantised
+rows returns.  It saves memory, not time (profiles/search_q8.md: one query over 10^6 rows takes 385 us, the fp32 scan 390, the half scan
+271; from 8 queries on the three are equal within 1 %).
+
 Every search above returns the nearest k, k <= 64.  The other question -- WHICH rows score at least s, however many -- is the range
 search (vtc_l2_range_count / vtc_l2_range_fill: the same fp64 distances, compared with the threshold in fp64):
 
@@ -160,6 +169,17 @@ class VideoIndex:
     error band decided in fp64 (vtc_l2_range_count_many_half, profiles/range_many.md); ``similar_within`` (the range form of
     ``similar``) and ``near_duplicates`` (every pair of live rows above a score) are built on them and run through the scan on an fp32
     index.
+    ``storage=torch.int8`` keeps every row as ``width`` signed 8-bit codes and one fp32 scale (``index.rows`` is int8 [ntotal, width + 16]:
+    the codes, the scale at byte ``width``, 12 zero bytes): ``add`` normalises in fp32 and quantises with one kernel launch
+    (ops.quantize_rows_q8: scale = max |x| / 127 rounded up to 16 significant bits, code = the quotient rounded to nearest even, so
+    |x - scale * code| <= 0.5 (1 + 2^-15) scale), and every search is exact over the stored values scale * code -- bit for bit the search
+    of an fp32 index holding ``ops.dequantize_rows_q8(index.rows)``.  An int8 index searches by the half index's rules (always the scan,
+    vtc_l2_search_q8 and its siblings, slices of 64 queries, only enqueued); ``search_many`` / ``range_search_many`` /
+    ``range_count_many`` ARE the scan on it, the matrix-core passes read half rows only.  The memory is (width + 16) / (4 width) of an
+    fp32 index's.  The time is not less (profiles/search_q8.md, d = 512, depth 11): one query over 10^6 rows takes 385 us against the
+    fp32 scan's 390 and the half scan's 271 (1.42 x half), over 10^5 rows 91 against 87 and 82; at 8 and 64 queries all three storages
+    take the same time within 1 %.  On that file's synthetic rows the int8 index returned 97.2 - 100 % of the fp32 index's top 10 and
+    moved no score by more than 1.6e-3.
     ``exclude`` / ``exclude_videos`` (one row or one video per query that it is never given), ``similar`` and ``similar_videos`` (the
     neighbours of a stored row without itself / without its own video) are the excluding scan (vtc_l2_search_excluding), by the same
     rules: any number of queries in slices of 64, only enqueued.  ``search_videos(after=)`` and ``search_videos_deep`` page the grouped
@@ -202,7 +222,7 @@ class VideoIndex:
     #: were not measured: the scan runs them as one tile, in one gallery pass.
     ROUTE_RANGE_MANY_MIN_QUERIES = 8
     MAX_K = 64                # one list entry per lane of a wavefront, as everywhere in the sweeps
-    STORAGE = {"float32": torch.float32, "float16": torch.float16}      # the state dict's names of the storage dtypes
+    STORAGE = {"float32": torch.float32, "float16": torch.float16, "int8": torch.int8}      # the state dict's names of the storage dtypes
 
     def __init__(self, dim, device="cuda", normalized=False, storage=torch.float32):
         device = torch.device(device)
@@ -217,9 +237,10 @@ class VideoIndex:
         self.device = device
         self.normalized = bool(normalized)
         if storage not in self.STORAGE.values():
-            raise ValueError(f"VideoIndex: storage={storage} must be torch.float32 or torch.float16")
+            raise ValueError(f"VideoIndex: storage={storage} must be torch.float32, torch.float16 or torch.int8")
         self.storage = storage
-        self._rows = torch.empty(0, self.width, dtype=storage, device=device)       # capacity rows; the first _n are the index
+        self.row_width = self.width + (ops.Q8_TAIL if storage == torch.int8 else 0)      # columns of a stored row: a q8 row ends in its scale
+        self._rows = torch.empty(0, self.row_width, dtype=storage, device=device)   # capacity rows; the first _n are the index
         self._n = 0
         self._ws = None
         self._live = None                   # bool [ntotal] on the device once a row was removed; None: every row is live
@@ -260,15 +281,23 @@ class VideoIndex:
         with ``check``, NaN / inf rows are rejected as the eval entry points reject them (ops.nonfinite_bits: a 4-byte device-to-host
         read, so a host sync).  ``stored``: the rows as the index keeps them -- for half storage rounded to nearest-even AFTER the fp32
         normalisation and BEFORE the check, which then sees what the rounding made of them (a component above 65504 of a
-        ``normalized`` index's row has become inf)."""
+        ``normalized`` index's row has become inf).  For int8 storage the padded fp32 rows are quantised (ops.quantize_rows_q8: the
+        padding is codes of 0) and the check sees the dequantised rows; the q8 rows [n, width + 16] come back."""
         x = torch.as_tensor(x)
         if x.dim() != 2 or x.shape[1] != self.dim:
             raise ValueError(f"VideoIndex: {what} must be [n, {self.dim}], got {tuple(x.shape)}")
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         if x.shape[0] == 0:
-            return x.new_zeros(0, self.width)
+            return x.new_zeros(0, self.row_width, dtype=self.storage) if stored else x.new_zeros(0, self.width)
         if not self.normalized:
             x = ops.normalize_rows(x)
+        if stored and self.storage == torch.int8:
+            rows = ops.quantize_rows_q8(torch.nn.functional.pad(x, (0, self.width - self.dim)) if self.width != self.dim else x)
+            x = ops.dequantize_rows_q8(rows)                   # a NaN scale (a non-finite row) makes the whole row NaN
+            if check and ops.nonfinite_bits(x, x):
+                raise ValueError("VideoIndex: non-finite values in the " + what + ("" if self.normalized else " (after normalisation: a NaN, "
+                                 "an inf or an all-zero row)") + " -- such a row has no distance to anything")
+            return rows
         if stored and self.storage != torch.float32:
             x = x.to(self.storage).float()                     # rounded; widened again (exactly) for the check and the padding
         if check and ops.nonfinite_bits(x, x):
@@ -281,7 +310,9 @@ class VideoIndex:
     def add(self, embeddings, video_ids=None):
         """Appends [n, dim] fp32 rows; their ids are their positions in insertion order (removed ids are not reused).  Returns the id of
         the first one, which is ``ntotal`` before the call.  A half index normalises in fp32 as an fp32 one does and then rounds to
-        nearest-even (``.to(torch.float16)``); the non-finite check runs on the rounded rows.
+        nearest-even (``.to(torch.float16)``); the non-finite check runs on the rounded rows.  An int8 index normalises in fp32 too, pads
+        to ``width`` and quantises every row to 8-bit codes and one scale with the kernel (ops.quantize_rows_q8, one launch); the check
+        runs on the dequantised rows.
         ``video_ids`` (an integer [n] tensor or sequence, values in [0, 2^31)) names the video of every row; one video's rows may come in
         different calls.  An index is GROUPED iff its first non-empty add passed them, and every later add must do the same as the first:
         mixing the two forms raises ValueError and changes nothing."""
@@ -292,7 +323,7 @@ class VideoIndex:
             raise ValueError("VideoIndex.add: this index " + ("has a video id for every row: pass video_ids" if self.grouped else
                              "was started without video_ids: its rows have none, so later rows cannot either"))
         if first + n > self._rows.shape[0]:                 # amortised doubling
-            grown = torch.empty(max(first + n, 2 * self._rows.shape[0], 1024), self.width, dtype=self.storage, device=self.device)
+            grown = torch.empty(max(first + n, 2 * self._rows.shape[0], 1024), self.row_width, dtype=self.storage, device=self.device)
             grown[:first] = self._rows[:first]
             self._rows = grown
         self._rows[first:first + n] = x
@@ -364,15 +395,23 @@ class VideoIndex:
 
     @property
     def rows(self):
-        """The stored rows [ntotal, width] (a view) in the storage dtype, removed ones included."""
+        """The stored rows [ntotal, width] (a view) in the storage dtype, removed ones included; of an int8 index the q8 rows
+        [ntotal, width + 16]: ``width`` codes, the row's fp32 scale, 12 zero bytes (``ops.dequantize_rows_q8`` gives their values)."""
         return self._rows[:self._n]
+
+    def _widened(self, rows):
+        """Stored rows (any selection of ``self.rows``) as the fp32 values they hold [m, width]: exact for every storage."""
+        return ops.dequantize_rows_q8(rows) if self.storage == torch.int8 else rows.float()
 
     def state_dict(self):
         """The rows in the storage dtype; a half index writes "storage": "float16" beside them.  An fp32 index's state has the keys it
-        always had -- a state without "storage" IS fp32 (``load_state_dict`` also takes an explicit "float32")."""
+        always had -- a state without "storage" IS fp32 (``load_state_dict`` also takes an explicit "float32").  An int8 index writes
+        "storage": "int8", its codes [n, dim] as "rows" and the rows' fp32 "scales" [n]."""
         state = {"rows": self.rows[:, :self.dim].clone(), "count": self._n, "dim": self.dim, "normalized": self.normalized}
         if self.storage != torch.float32:
             state["storage"] = {v: k for k, v in self.STORAGE.items()}[self.storage]
+        if self.storage == torch.int8:
+            state["scales"] = ops.q8_scales(self.rows)
         if self._live is not None:
             state["live"] = self._live.clone()
         if self.grouped:
@@ -381,7 +420,8 @@ class VideoIndex:
 
     def load_state_dict(self, state):
         """A state whose storage differs from the index's raises ValueError (``converted`` changes the storage); rows are taken bit
-        for bit, never rounded or normalised again."""
+        for bit, never rounded or normalised again.  An int8 state's "scales" must be finite fp32 [count] with their low 8 mantissa bits
+        clear -- the quantiser's 16 significant bits, with which every stored value is an exact product."""
         storage = state.get("storage", "float32")
         if self.STORAGE.get(storage) != self.storage:
             raise ValueError(f"VideoIndex.load_state_dict: the state's storage is {storage}, the index's {self.storage} "
@@ -392,10 +432,21 @@ class VideoIndex:
         if int(state.get("dim", self.dim)) != self.dim or rows.dim() != 2 or rows.shape[1] != self.dim or int(state["count"]) != rows.shape[0]:
             raise ValueError(f"VideoIndex.load_state_dict: rows {tuple(rows.shape)}, count {state.get('count')} do not fit dim {self.dim}")
         rows = rows.to(device=self.device, dtype=self.storage)
-        wide = rows.float().contiguous()
-        if rows.shape[0] and ops.nonfinite_bits(wide, wide):
-            raise ValueError("VideoIndex.load_state_dict: non-finite values in the stored rows")
-        self._rows = torch.nn.functional.pad(rows, (0, self.width - self.dim)).contiguous()     # stored rows are final: not normalised again
+        if storage == "int8":
+            scales = state.get("scales")
+            scales = None if scales is None else torch.as_tensor(scales)
+            if scales is None or scales.dtype != torch.float32 or tuple(scales.shape) != (rows.shape[0],):
+                raise ValueError(f"VideoIndex.load_state_dict: an int8 state holds float32 scales [{rows.shape[0]}], one per row")
+            scales = scales.to(self.device).contiguous()
+            if rows.shape[0] and (not bool(torch.isfinite(scales).all()) or bool((scales.view(torch.int32) & 0xFF).any())):
+                raise ValueError("VideoIndex.load_state_dict: an int8 state's scales must be finite with their low 8 mantissa bits clear "
+                                 "(16 significant bits: every stored value is then an exact product)")
+            self._rows = ops.q8_rows(torch.nn.functional.pad(rows, (0, self.width - self.dim)), scales)
+        else:
+            wide = rows.float().contiguous()
+            if rows.shape[0] and ops.nonfinite_bits(wide, wide):
+                raise ValueError("VideoIndex.load_state_dict: non-finite values in the stored rows")
+            self._rows = torch.nn.functional.pad(rows, (0, self.width - self.dim)).contiguous()     # stored rows are final: not normalised again
         live = state.get("live")
         if live is not None:
             live = torch.as_tensor(live)
@@ -416,12 +467,19 @@ class VideoIndex:
         self._generation += 1
 
     def converted(self, storage):
-        """A new index of ``storage`` (torch.float32 or torch.float16) with the same ids, ``ntotal``, live mask and video ids: fp32 ->
-        half rounds every stored row to nearest-even, half -> fp32 widens exactly, the same storage gives a copy.  This index is not
-        changed; RowSubsets belong to the index they were built on."""
+        """A new index of ``storage`` (torch.float32, torch.float16 or torch.int8) with the same ids, ``ntotal``, live mask and video
+        ids: fp32 -> half rounds every stored row to nearest-even, half -> fp32 widens exactly, the same storage gives a copy.  To
+        int8: the stored rows, widened to fp32, are quantised (ops.quantize_rows_q8) -- never normalised again.  From int8: the rows
+        are dequantised, which is exact, and for half then rounded as an fp32 -> half conversion rounds.  This index is not changed;
+        RowSubsets belong to the index they were built on."""
         other = VideoIndex(self.dim, device=self.device, normalized=self.normalized, storage=storage)
-        rows = self.rows.to(other.storage)
-        if other.storage != self.storage and self._n:
+        if other.storage == self.storage:
+            rows = self.rows
+        elif other.storage == torch.int8:
+            rows = ops.quantize_rows_q8(self.rows.float()) if self._n else self.rows.new_zeros(0, other.row_width, dtype=torch.int8)
+        else:
+            rows = self._widened(self.rows).to(other.storage)
+        if other.storage != self.storage and self._n and other.storage != torch.int8:
             wide = rows.float().contiguous()                   # fp32 -> half can only overflow for a ``normalized`` index's rows
             if ops.nonfinite_bits(wide, wide):
                 raise ValueError(f"VideoIndex.converted: a stored row has a component that {storage} cannot hold")
@@ -453,7 +511,8 @@ class VideoIndex:
         (vtc_l2_search_half), 64 queries per call, only enqueued, a non-finite query a row of -1 / -inf -- whatever the number of
         queries: vtc_l2_topk reads fp32 rows.  Batches of many queries are therefore slower than on an fp32 index
         (profiles/search.md: 4.5 x at 64 queries).  The scores are 1 - D/2 over the stored rows, each the unit row rounded to
-        binary16's 11 significant bits per component.
+        binary16's 11 significant bits per component.  An int8 index (``storage=torch.int8``) takes the same route by the same rules
+        (vtc_l2_search_q8); its scores are 1 - D/2 over the stored values scale * code.
         ``after`` (an int64 [Q] tensor of row ids, typically ``ids[:, -1]`` of the previous page): the k nearest rows that come AFTER
         that row in the query's search order -- by (fp64 distance, row), the order every search returns -- so the pages chained by their
         last ids are, concatenated, the exact ranking to any depth, without repeats or gaps.  Stateless: the cursor's distance is formed
@@ -679,13 +738,14 @@ class VideoIndex:
         if self._n == 0:
             raise ValueError(f"VideoIndex.{what}: the index is empty")
         inside = (ids >= 0) & (ids < self._n)
-        q = self.rows[ids.clamp(0, self._n - 1)].float()                 # half -> fp32 is exact, the zero padding included
+        q = self._widened(self.rows[ids.clamp(0, self._n - 1)])          # half -> fp32 and scale * code are exact, the zero padding included
         return ids, torch.where(inside[:, None], q, q.new_full((), float("nan"))).contiguous()
 
     def similar(self, ids, k, subset=None, after=None):
         """MORE LIKE THIS: (ids [Q, k] int64, scores [Q, k] fp32), the k nearest rows of the STORED row ``ids[q]`` (an int64 [Q]
         tensor of row ids), that row itself left out -- ``search`` with the stored row as the query and ``exclude=ids``.  The query is
-        the row as the index keeps it, never normalised again: a half index's row widened exactly, zero padding included.  So a
+        the row as the index keeps it, never normalised again: a half index's row widened exactly, an int8 index's dequantised exactly, zero
+        padding included.  So a
         bit-equal duplicate of the row scores exactly 1 and IS returned: it is another row.  The query row need not be live nor a
         member of ``subset`` (the neighbours are).  ``after``: ``search``'s cursor, the next page.  An id outside [0, ntotal) (-1
         included) cannot be validated without a host read: that query comes back as -1 / -inf and the others are left alone.  Any
@@ -820,7 +880,7 @@ class VideoIndex:
         rows = order[(lo[:, None] + torch.arange(m, device=self.device)[None]).clamp(max=n - 1)]      # [V, m]; past the count: replaced below
         member = torch.arange(m, device=self.device)[None] < count[:, None]
         rows = torch.where(member, rows, rows[:, :1])                                    # padded by member 0, as ``sizes`` pads
-        q = self.rows[rows.reshape(-1)].float().view(v.shape[0], m, self.width)           # half -> fp32 is exact
+        q = self._widened(self.rows[rows.reshape(-1)]).view(v.shape[0], m, self.width)    # half -> fp32 and scale * code are exact
         q = torch.where((count > 0)[:, None, None], q, q.new_full((), float("nan"))).contiguous()      # no live row: no member
         return self._search_sets(q, k, subset, v, "similar_to_video", True, return_members)
 

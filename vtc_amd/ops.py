@@ -363,12 +363,67 @@ def l2_topk_bidir(a: torch.Tensor, b: torch.Tensor, depth: int, precision: int =
 SEARCH_MAX_QUERIES = 64       # vtc_l2_search's limit; more queries go through l2_topk
 
 
+Q8_TAIL = 16                  # bytes of a q8 row behind its codes: the fp32 scale and 12 bytes of zero padding (include/vtc_hip.h)
+
+
 def _search_gallery(gallery: torch.Tensor) -> torch.Tensor:
-    """The gallery of a query-time search: fp32, or IEEE half (vtc_l2_search_half); every other dtype raises TypeError."""
+    """The gallery of a query-time search: fp32, IEEE half (vtc_l2_search_half) or q8 rows (``torch.int8`` [n, d + 16]: d codes, the fp32
+    scale, 12 bytes of padding -- ``quantize_rows_q8``; the *_q8 entries); every other dtype raises TypeError."""
     gallery = _gpu(gallery, None, "gallery")
-    if gallery.dtype not in (torch.float32, torch.float16):
-        raise TypeError(f"vtc_amd: gallery must be torch.float32 or torch.float16, got {gallery.dtype}")
+    if gallery.dtype not in (torch.float32, torch.float16, torch.int8):
+        raise TypeError(f"vtc_amd: gallery must be torch.float32, torch.float16 or torch.int8 (q8 rows), got {gallery.dtype}")
+    if gallery.dtype == torch.int8 and (gallery.dim() != 2 or gallery.shape[1] <= Q8_TAIL or gallery.data_ptr() % 16):
+        raise ValueError(f"vtc_amd: a torch.int8 gallery is q8 rows [n, d + {Q8_TAIL}] with a 16-byte aligned base, got {tuple(gallery.shape)}")
     return gallery
+
+
+def _gallery_shape(gallery: torch.Tensor):
+    """(rows, columns) of a search gallery: a q8 row is its d codes and ``Q8_TAIL`` more bytes."""
+    ng, d = gallery.shape
+    return ng, d - Q8_TAIL if gallery.dtype == torch.int8 else d
+
+
+@on_device
+def quantize_rows_q8(x: torch.Tensor, nonfinite: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 rows [n, d] (d a multiple of 64 in [64, 2048]) -> q8 rows, ``torch.int8`` [n, d + 16] (vtc_quantize_rows_q8, one launch): d signed
+    codes, the row's fp32 scale at byte d, 12 zero bytes.  In fp32 arithmetic, per row: m = max |x_k|; s = fl32(m / 127) rounded UP to 16
+    significant bits (1 for a row of zeros); code_k = clamp(rint(fl32(x_k / s)), -127, 127), ties to even -- so s * code is exact in fp32
+    and |x_k - s code_k| <= 0.5 (1 + 2^-15) s.  A row with a NaN / inf gets a NaN scale and codes of 0 and ORs 1 into ``nonfinite`` (a
+    device int32 [1], optional).  Every search takes the result as its gallery and searches it AS STORED: ``dequantize_rows_q8`` gives the
+    fp32 rows whose search it is, bit for bit.  n = 0 gives an empty [0, d + 16].  Only enqueued."""
+    x = _gpu(x, torch.float32, "x")
+    if x.dim() != 2 or x.shape[1] < 64 or x.shape[1] % 64:
+        raise ValueError(f"quantize_rows_q8: x must be [n, d] with d a multiple of 64, got {tuple(x.shape)}")
+    n, d = x.shape
+    rows = torch.empty(n, d + Q8_TAIL, dtype=torch.int8, device=x.device)
+    if nonfinite is not None:
+        nonfinite = _gpu(nonfinite, torch.int32, "nonfinite")
+    if n:
+        L.check(L.lib().vtc_quantize_rows_q8(x.data_ptr(), n, d, rows.data_ptr(), _ptr(nonfinite), _stream()), "vtc_quantize_rows_q8")
+    return rows
+
+
+def q8_scales(rows: torch.Tensor) -> torch.Tensor:
+    """The fp32 scales [n] of q8 rows [n, d + 16] (a copy)."""
+    d = rows.shape[1] - Q8_TAIL
+    return rows[:, d:d + 4].contiguous().view(torch.float32).reshape(-1)
+
+
+def dequantize_rows_q8(rows: torch.Tensor) -> torch.Tensor:
+    """q8 rows [n, d + 16] -> the fp32 rows [n, d] they store: fl32(scale * code), one IEEE multiply per component (exact for the
+    quantiser's 16-bit scales).  A torch expression."""
+    if rows.dtype != torch.int8 or rows.dim() != 2 or rows.shape[1] <= Q8_TAIL:
+        raise ValueError(f"dequantize_rows_q8: q8 rows are torch.int8 [n, d + {Q8_TAIL}], got {rows.dtype} {tuple(rows.shape)}")
+    return rows[:, :rows.shape[1] - Q8_TAIL].float() * q8_scales(rows)[:, None]
+
+
+def q8_rows(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """int8 codes [n, d] and fp32 scales [n] -> q8 rows [n, d + 16] with a zero tail, bit for bit (no rounding, no check)."""
+    n, d = codes.shape
+    rows = torch.zeros(n, d + Q8_TAIL, dtype=torch.int8, device=codes.device)
+    rows[:, :d] = codes
+    rows[:, d:d + 4] = scales.to(device=codes.device, dtype=torch.float32).contiguous().view(torch.int8).view(n, 4)
+    return rows
 
 
 def _search_inputs(what, gallery, queries, groups=None, rows=None):
@@ -376,7 +431,7 @@ def _search_inputs(what, gallery, queries, groups=None, rows=None):
     call has one, its ``groups`` (int32, one per gallery row) or ``rows`` (int64, one per query) on the gallery's device.  Returns
     (gallery, queries, that vector or None, n_gallery, n_queries, d); ``what`` names the caller in every message."""
     gallery, queries = _search_gallery(gallery), _gpu(queries, torch.float32, "queries")
-    ng, d = gallery.shape
+    ng, d = _gallery_shape(gallery)
     nq = queries.shape[0]
     vec = groups if rows is None else rows
     if vec is not None:
@@ -455,7 +510,9 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     row is neither read nor counted in nonfinite_bits.  ``depth`` is still bounded by the physical row count.
     A ``torch.float16`` gallery (vtc_l2_search_half) is searched as stored: the distances are the fp64 ones of the fp32 queries and the
     half rows widened to fp32, which is exact -- every output, the fp64 distances in ``ws`` included, has the bits of this call over
-    ``gallery.float()``.  The queries stay fp32; any other gallery dtype raises TypeError.
+    ``gallery.float()``.  A ``torch.int8`` gallery [n, d + 16] is q8 rows (``quantize_rows_q8``; vtc_l2_search_q8), searched as stored
+    likewise: the bits of this call over ``dequantize_rows_q8(gallery)``, in every mode below.  The queries stay fp32; any other gallery
+    dtype raises TypeError.
     ``after`` (vtc_l2_search_after): a cursor per query, ``(after_d64 [Q] float64, after_ids [Q] int64)`` on the gallery's device; only
     the rows whose key (fp64 distance, id_base + row) lies strictly after it are returned -- the next page of a search whose previous
     page ended in that key.  ``after_d64`` must carry the bits the scan forms: ``search_dists64(ws, Q, depth)[:, -1]`` of the previous
@@ -479,7 +536,10 @@ def l2_search(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_base:
     tail = (_ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     # The narrowest entry that takes the call.  A ladder on purpose: a table of (condition, entry, arguments) forms every entry's
     # arguments at every call, 2 us of host time on a 50 us call.
-    if exclude is not None:
+    if gallery.dtype == torch.int8:
+        L.check(lib.vtc_l2_search_q8(gallery.data_ptr(), queries.data_ptr(), _ptr(live), None, 0, None, _ptr(exclude), _ptr(after_d), _ptr(after_i),
+                                     *shape, None, *tail), "vtc_l2_search_q8")
+    elif exclude is not None:
         L.check(lib.vtc_l2_search_excluding(gallery.data_ptr(), half, queries.data_ptr(), _ptr(live), None, exclude.data_ptr(), _ptr(after_d),
                                             _ptr(after_i), *shape, None, *tail), "vtc_l2_search_excluding")
     elif after is not None:
@@ -559,9 +619,13 @@ def l2_pair_dists64(gallery: torch.Tensor, queries: torch.Tensor, rows: torch.Te
     """float64 [Q] on the device (vtc_l2_pair_dists64): the fp64 squared distance of query q and the gallery row ``rows[q] - id_base``,
     one pair per query, with the bits ``l2_search`` leaves in its workspace for that pair -- what ``l2_search(after=...)`` takes as the
     cursor's distance when only the cursor's id is at hand.  ``rows``: int64 [Q]; -1, or any id outside [id_base, id_base + n), gives
-    +inf and reads nothing.  The row is read whether or not any mask calls it live.  fp32 or ``torch.float16`` gallery; any Q >= 1."""
+    +inf and reads nothing.  The row is read whether or not any mask calls it live.  fp32, ``torch.float16`` or q8 gallery; any Q >= 1."""
     gallery, queries, rows, ng, nq, d = _search_inputs("l2_pair_dists64", gallery, queries, rows=rows)
     out = torch.empty(nq, dtype=torch.float64, device=gallery.device)
+    if gallery.dtype == torch.int8:
+        L.check(L.lib().vtc_l2_pair_dists64_q8(gallery.data_ptr(), queries.data_ptr(), rows.data_ptr(), ng, nq, d, int(id_base), out.data_ptr(),
+                                               _stream()), "vtc_l2_pair_dists64_q8")
+        return out
     L.check(L.lib().vtc_l2_pair_dists64(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), rows.data_ptr(), ng, nq, d,
                                         int(id_base), out.data_ptr(), _stream()), "vtc_l2_pair_dists64")
     return out
@@ -610,13 +674,15 @@ def _range_args(gallery, queries, radius2, live, ws, what, many=False):
 
 
 def _range_count(gallery, queries, radius2, live, ws, many=False):
-    ng, d = gallery.shape
+    ng, d = _gallery_shape(gallery)
     nq = queries.shape[0]
     lims = torch.empty(nq + 1, dtype=torch.int64, device=gallery.device)
     bits = torch.zeros(1, dtype=torch.int32, device=gallery.device)
     tail = (_ptr(live), radius2.data_ptr(), ng, nq, d, lims.data_ptr(), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     if many:
         L.check(L.lib().vtc_l2_range_count_many_half(gallery.data_ptr(), queries.data_ptr(), *tail), "vtc_l2_range_count_many_half")
+    elif gallery.dtype == torch.int8:
+        L.check(L.lib().vtc_l2_range_count_q8(gallery.data_ptr(), queries.data_ptr(), *tail), "vtc_l2_range_count_q8")
     else:
         L.check(L.lib().vtc_l2_range_count(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), *tail),
                 "vtc_l2_range_count")
@@ -629,7 +695,7 @@ def l2_range_count(gallery: torch.Tensor, queries: torch.Tensor, radius2, live: 
     """Range search, the count pass alone (vtc_l2_range_count): ``lims`` int64 [Q + 1] on the device, lims[0] = 0 and lims[q + 1] - lims[q]
     the number of gallery rows with a finite fp64 squared distance D <= radius2[q] to query q (at most 64 queries).  Only enqueued: no
     host sync.  ``radius2``: a float, or float64 [Q].  ``live``: packed row mask as ``l2_search`` takes it.  A ``torch.float16`` gallery
-    is searched as stored.  With a caller's ``ws`` (``l2_range_workspace_bytes``) the hit words are ``range_hit_words(ws, n, Q)``.
+    and a q8 one (``torch.int8`` [n, d + 16]) are searched as stored.  With a caller's ``ws`` (``l2_range_workspace_bytes``) the hit words are ``range_hit_words(ws, n, Q)``.
     ``return_bits``: also the non-finite word (device int32 [1]: 1 = a live gallery row holds a NaN / inf, 2 = a query does)."""
     gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, "l2_range_count")
     lims, bits = _range_count(gallery, queries, radius2, live, ws)
@@ -658,7 +724,7 @@ def l2_range_search(gallery: torch.Tensor, queries: torch.Tensor, radius2, live:
 def _range_search(gallery, queries, radius2, live, id_base, max_results, return_dists64, return_words, ws, exclude, what, many):
     """The count pass (``many``: vtc_l2_range_count_many_half), the one host read of lims[-1], then vtc_l2_range_fill on the same workspace."""
     gallery, queries, radius2, live, ws = _range_args(gallery, queries, radius2, live, ws, what, many)
-    ng, d = gallery.shape
+    ng, d = _gallery_shape(gallery)
     nq = queries.shape[0]
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, what)
@@ -679,9 +745,12 @@ def _range_search(gallery, queries, radius2, live, id_base, max_results, return_
     ids = torch.empty(total, dtype=torch.int64, device=dev)
     dists = torch.empty(total, dtype=torch.float32, device=dev)
     dists64 = torch.empty(total, dtype=torch.float64, device=dev) if return_dists64 else None
-    L.check(L.lib().vtc_l2_range_fill(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), ng, nq, d, lims.data_ptr(),
-                                      total, int(id_base), ids.data_ptr(), dists.data_ptr(), dists64.data_ptr() if return_dists64 else None,
-                                      ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_range_fill")
+    fill = (queries.data_ptr(), ng, nq, d, lims.data_ptr(), total, int(id_base), ids.data_ptr(), dists.data_ptr(),
+            dists64.data_ptr() if return_dists64 else None, ws.data_ptr(), ws.numel(), _stream())
+    if gallery.dtype == torch.int8:
+        L.check(L.lib().vtc_l2_range_fill_q8(gallery.data_ptr(), *fill), "vtc_l2_range_fill_q8")
+    else:
+        L.check(L.lib().vtc_l2_range_fill(gallery.data_ptr(), int(gallery.dtype == torch.float16), *fill), "vtc_l2_range_fill")
     if exclude is not None and total:
         # The excluded entries leave: every kept entry moves to its rank among the kept ones, the dropped ones to a spare slot behind
         # the result.  The sizes are host numbers already, so nothing here reads the device.
@@ -753,7 +822,7 @@ def l2_search_part(gallery: torch.Tensor, queries: torch.Tensor, depth: int, id_
     fp32 or ``torch.float16``; the fp64 lists do not depend on how the rows are stored, so l2_search_merge takes both.
     ``after``: the cursor of l2_search in GLOBAL ids, the same pair for every window -- the merged lists are then the page after it.
     ``exclude``: the excluded rows of l2_search in GLOBAL ids, the same tensor for every window -- the merged lists then exclude them."""
-    ng, d = gallery.shape
+    ng, d = _gallery_shape(gallery)
     nq = queries.shape[0]
     ws = workspace(l2_search_workspace_bytes(ng, nq, d, depth), gallery.device)
     ids, _, bits = l2_search(gallery, queries, depth, id_base, return_dists=False, ws=ws, live=live, after=after, exclude=exclude)
@@ -810,7 +879,7 @@ def l2_group_mark_before(gallery: torch.Tensor, queries: torch.Tensor, groups: t
     ``l2_search_grouped(after=...)`` must not return again.  ``groups``: int32 [n] with DENSE ids in [0, n_groups); a row whose group is
     outside the range marks nothing.  ``ban``: int32 [Q, ceil(n_groups / 32)] on the gallery's device, bit g & 31 of word g >> 5; None
     allocates and zeroes one, a given one is ORed into in place (the windows of one gallery mark into the same buffer, with their
-    ``id_base``).  Returns ``ban``.  One gallery pass per tile of queries, only enqueued; fp32 or ``torch.float16`` gallery.  Wrong
+    ``id_base``).  Returns ``ban``.  One gallery pass per tile of queries, only enqueued; fp32, ``torch.float16`` or q8 gallery.  Wrong
     dtypes, shapes or devices raise ValueError."""
     gallery, queries, groups, ng, nq, d = _search_inputs("l2_group_mark_before", gallery, queries, groups)
     n_groups = _n_groups_arg(n_groups, "l2_group_mark_before")
@@ -820,6 +889,11 @@ def l2_group_mark_before(gallery: torch.Tensor, queries: torch.Tensor, groups: t
         ban = torch.zeros(nq, (n_groups + 31) // 32, dtype=torch.int32, device=gallery.device)
     else:
         ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_group_mark_before")
+    if gallery.dtype == torch.int8:
+        L.check(L.lib().vtc_l2_group_mark_before_q8(gallery.data_ptr(), queries.data_ptr(), _ptr(live), groups.data_ptr(), n_groups,
+                                                    after_d.data_ptr(), after_i.data_ptr(), ng, nq, d, int(id_base), ban.data_ptr(), _stream()),
+                "vtc_l2_group_mark_before_q8")
+        return ban
     L.check(L.lib().vtc_l2_group_mark_before(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(),
                                              _ptr(live), groups.data_ptr(), n_groups, after_d.data_ptr(),
                                              after_i.data_ptr(), ng, nq, d, int(id_base), ban.data_ptr(), _stream()),
@@ -837,7 +911,8 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
     Returns (ids [Q, depth] int64 = id_base + that row, -1 where fewer groups have a finite distance; groups [Q, depth] int32, -1 there
     too -- read ``ids`` to tell an empty entry, -1 is a legal group id; dists fp32 or None; nonfinite_bits as l2_search).  ``live`` and
     ``ws`` as in l2_search, the workspace being ``l2_search_grouped_workspace_bytes``; its head holds the fp64 distances.  A
-    ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``.
+    ``torch.float16`` gallery is searched as stored (vtc_l2_search_half), with the bits of this call over ``gallery.float()``; a q8 one
+    (``torch.int8`` [n, d + 16], vtc_l2_search_q8) with the bits of this call over ``dequantize_rows_q8(gallery)``.
     ``exclude`` (vtc_l2_search_excluding): int64 [Q] on the gallery's device; query q is never given a row of the GROUP ``exclude[q]`` --
     the grouped search of the gallery without that group's rows.  A value outside int32 is no group and excludes nothing (-1 is a legal
     group).  A wrong dtype, shape or device raises ValueError.  None: the call above, unchanged.
@@ -861,6 +936,7 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
             _stream())
     if exclude is not None:
         exclude = _exclude_arg(exclude, nq, gallery.device, "l2_search_grouped")
+    after_d = after_i = None
     if after is not None:                                      # the narrowest entry that takes the call: a ladder, as in l2_search
         after_d, after_i = _after_arg(after, nq, gallery.device, "l2_search_grouped")
         n_groups = _n_groups_arg(n_groups, "l2_search_grouped")
@@ -868,6 +944,11 @@ def l2_search_grouped(gallery: torch.Tensor, queries: torch.Tensor, groups: torc
             ban = l2_group_mark_before(gallery, queries, groups, n_groups, (after_d, after_i), live=live, id_base=id_base)
         else:
             ban = _ban_arg(ban, nq, n_groups, gallery.device, "l2_search_grouped")
+    if gallery.dtype == torch.int8:
+        paged = after is not None
+        L.check(lib.vtc_l2_search_q8(gallery.data_ptr(), *head, n_groups if paged else 0, ban.data_ptr() if paged else None, _ptr(exclude),
+                                     _ptr(after_d), _ptr(after_i), *tail), "vtc_l2_search_q8")
+    elif after is not None:
         L.check(lib.vtc_l2_search_grouped_after(gallery.data_ptr(), half, *head, n_groups, ban.data_ptr(), _ptr(exclude), after_d.data_ptr(),
                                                 after_i.data_ptr(), *tail), "vtc_l2_search_grouped_after")
     elif exclude is not None:
@@ -896,7 +977,7 @@ def l2_search_sets(gallery: torch.Tensor, query_sets: torch.Tensor, depth: int, 
     a global row id ungrouped and a group grouped, deleted from the order before the cut; -1, or a key that is not there, excludes nothing.
     A member with a NaN / inf takes no part (bit 2 of nonfinite_bits); a set with no finite member is a row of -1 / (-1) / +inf.  A set of
     one member is l2_search / l2_search_grouped of that vector, bit for bit; repeating a member changes nothing, which is how ragged sets
-    are padded.  ``live``, ``id_base``, a ``torch.float16`` gallery and ``ws`` as in l2_search: with a caller's ``ws`` of at least
+    are padded.  ``live``, ``id_base``, a ``torch.float16`` or q8 gallery and ``ws`` as in l2_search: with a caller's ``ws`` of at least
     ``l2_search_sets_workspace_bytes`` the fp64 distances are ``search_dists64(ws, S, depth)``.  S * M <= 64, otherwise ValueError.
     One gallery pass per started tile of 8 members per set.  There is no ``after``: a set of several tiles has no cursor a tile could test
     (include/vtc_hip.h)."""
@@ -915,9 +996,12 @@ def l2_search_sets(gallery: torch.Tensor, query_sets: torch.Tensor, depth: int, 
     ws = _search_ws_arg(ws, lib.vtc_l2_search_sets_workspace_bytes(ng, n_sets, set_size, d, depth, int(groups is not None)), gallery.device,
                         "l2_search_sets")
     ids, out_groups, dists, bits = _search_outputs(n_sets, depth, gallery.device, return_dists, grouped=groups is not None)
-    L.check(lib.vtc_l2_search_sets(gallery.data_ptr(), int(gallery.dtype == torch.float16), queries.data_ptr(), _ptr(live), _ptr(groups),
-                                   _ptr(exclude), ng, n_sets, set_size, d, depth, int(id_base), ids.data_ptr(), _ptr(out_groups), _ptr(dists),
-                                   bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vtc_l2_search_sets")
+    tail = (queries.data_ptr(), _ptr(live), _ptr(groups), _ptr(exclude), ng, n_sets, set_size, d, depth, int(id_base), ids.data_ptr(),
+            _ptr(out_groups), _ptr(dists), bits.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if gallery.dtype == torch.int8:
+        L.check(lib.vtc_l2_search_sets_q8(gallery.data_ptr(), *tail), "vtc_l2_search_sets_q8")
+    else:
+        L.check(lib.vtc_l2_search_sets(gallery.data_ptr(), int(gallery.dtype == torch.float16), *tail), "vtc_l2_search_sets")
     return ids, out_groups, dists, bits
 
 
@@ -938,7 +1022,7 @@ def l2_search_grouped_part(gallery: torch.Tensor, queries: torch.Tensor, groups:
     know what lies before the cursor in the others)."""
     if after is not None and ban is None:
         raise ValueError("l2_search_grouped_part: a cursor needs the ban bitmap marked over every window (l2_group_mark_before)")
-    ng, d = gallery.shape
+    ng, d = _gallery_shape(gallery)
     nq = queries.shape[0]
     ws = workspace(l2_search_grouped_workspace_bytes(ng, nq, d, depth), gallery.device)
     ids, out_groups, _, bits = l2_search_grouped(gallery, queries, groups, depth, id_base, return_dists=False, ws=ws, live=live, exclude=exclude,
