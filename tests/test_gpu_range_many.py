@@ -181,13 +181,17 @@ def _dead_run(ng, lo, hi):
     return live
 
 
-@pytest.mark.parametrize("kind", ["random_0.5", "dead_front", "dead_middle", "dead_end", "none"])
+@pytest.mark.parametrize("kind", ["random_0.5", "dead_front", "dead_middle", "dead_end", "none", "dead_front_d2048", "dead_middle_d2048",
+                                  "first_tiles"])
 def test_masks(kind):
-    """A run of wholly dead words at the front, in the middle and at the end, a random half, every row dead.  NaN stands in the dead
-    rows: it is not read, not a hit and not flagged."""
-    ng, d, nq = 1333, 64, 33
+    """A run of wholly dead words at the front, in the middle and at the end, a random half, every row dead; the runs at the front and in
+    the middle also at d = 2048, where the image is reloaded per item behind a barrier; `first_tiles`: the low half of every word
+    dead, a live word whose first tile is skipped.  NaN stands in the dead rows: it is not read, not a hit and not flagged."""
+    ng, d, nq = 1333, 2048 if kind.endswith("_d2048") else 64, 33
+    kind = kind.replace("_d2048", "")
     g, q = _separated(ng, d, nq)
-    live = {"dead_front": _dead_run(ng, 0, 200), "dead_middle": _dead_run(ng, 500, 900), "dead_end": _dead_run(ng, 1000, ng)}.get(kind)
+    live = {"dead_front": _dead_run(ng, 0, 200), "dead_middle": _dead_run(ng, 500, 900), "dead_end": _dead_run(ng, 1000, ng),
+            "first_tiles": np.arange(ng) % 32 >= 16}.get(kind)
     if live is None:
         live = MR.make_mask(kind, ng, seed=4)
     g[~live] = np.float16(np.nan)

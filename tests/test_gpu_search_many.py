@@ -282,6 +282,42 @@ def test_masks(kind):
         assert bool((many[0][:, n_live:] == -1).all()) and bool(torch.isinf(many[1][:, n_live:]).all())
 
 
+def _walk_mask(kind, ng):
+    live = np.ones(ng, bool)
+    if kind == "first_tiles":
+        live[np.arange(ng) % 32 < 16] = False                                # the low half of every mask word: its first tile
+    else:
+        lo, hi = {"dead_front": (0, ng // 2), "dead_middle": (ng // 4, 3 * ng // 4), "dead_end": (ng // 2, ng)}[kind]
+        live[lo:hi] = False
+    return live
+
+
+@pytest.mark.parametrize("ng,d,nq,kind", [(16384, 64, 33, "dead_front"), (16384, 64, 33, "dead_middle"), (16384, 64, 33, "dead_end"),
+                                          (16384, 64, 33, "first_tiles"), (8192, 2048, 64, "dead_front")])
+def test_the_walk_skips_runs_of_dead_tiles(ng, d, nq, kind):
+    """The pass's walk over more than one tile per workgroup.  33 queries are three waves a workgroup and one workgroup a CU: on 256 CUs
+    the 1024 tiles of 16 384 rows are 4 per workgroup, so a dead half of the gallery is a run of two dead tiles at the front, in the
+    middle or at the end of every workgroup's walk, and `first_tiles` a dead tile between any two live ones.  d = 2048 is the image
+    that is reloaded per item behind a barrier, with the front half dead.  NaN stands in the dead rows: it is not read, not returned
+    and not flagged.  The data is separated -- the gap between the depth-th and the cdepth-th live distance exceeds 2 eps for every
+    query, recomputed here from the reference's fp32 distances, whose rounding (2^-22 of a distance below 4) is allowed for -- so every
+    list is certified by the pass itself: the fallback counter is 0."""
+    depth, cdepth = 11, 32
+    g, q = _separated(ng, d, nq)
+    live = _walk_mask(kind, ng)
+    g[~live] = np.float16(np.nan)
+    ids, d32, ref_gap = HR.reference_search_masked(g, q, live, cdepth, 3)
+    assert ref_gap > 1e-12, ref_gap
+    gap = (d32[:, cdepth - 1].astype(np.float64) - d32[:, depth - 1].astype(np.float64)).min() - 2.0 ** -21
+    gmax = (HR.widen(g[live]).astype(np.float64) ** 2).sum(1).max()
+    eps = (KAPPA(d) * ((q.astype(np.float64) ** 2).sum(1) + gmax) + 1e-35).max()
+    print(f"{kind} d={d}: smallest gap {gap:.4g}, 2 eps {2 * eps:.4g}")
+    assert gap > 2 * eps, (gap, eps)
+    many, fallbacks = _check(g, q, depth, live=live, id_base=3, ref=(ids[:, :depth], d32[:, :depth].astype(np.float64)))
+    assert fallbacks == 0
+    assert int(many[2].item()) == 0
+
+
 # ---- windows ---------------------------------------------------------------------------------------------------------------------------
 def test_three_windows_merge_to_the_whole():
     ops = _ops()

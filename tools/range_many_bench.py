@@ -14,6 +14,8 @@ The protocol of tools/search_many_bench.py (profiles/search_many.md): per (n_gal
   hits_per_query        mean over the queries of the call
   exact_pairs           of the new entry's last call (ops.range_many_stats): the pairs the error bound could not decide
   same_bits             lims, the hit words and the non-finite word of the two are equal (asserted)
+  outputs_sha1          SHA-1 over the new entry's lims, non-finite word and hit words of its last call: equal between two builds of the
+                        library (VTC_HIP_LIB) that compute the same
 --hits: a value >= 1 is a number of rows, below 1 a fraction of the live rows; the radius of a query is the midpoint between its
 distances at that rank and the next (fp32 distances, good enough to choose a radius).  Unit rows from a seeded generator on the device
 rounded to half, queries = gallery rows plus noise.  A live fraction below 1 draws every row's bit independently.
@@ -23,6 +25,7 @@ Every step -- one (n_gallery, live fraction), or the near-duplicates run -- is a
 never opens the GPU and stops at the first step that fails.  One process at a time on an otherwise idle card.  profiles/range_many.md
 holds a run's table; VideoIndex.ROUTE_RANGE_MANY_MIN_QUERIES cites it."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -96,6 +99,9 @@ def step(args, ng, frac):
             same = (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and
                     torch.equal(ops.range_hit_words(ws_many, ng, nq), ops.range_hit_words(ws_scan, ng, nq)))
             assert same, (ng, nq, frac, hits)
+            sha = hashlib.sha1()
+            for t in (*a, ops.range_hit_words(ws_many, ng, nq)):
+                sha.update(t.cpu().numpy().tobytes())
             m_many, m_scan, m_topk = statistics.median(t_many), statistics.median(t_scan), statistics.median(t_topk)
             spread = lambda t, m: dict(median=round(m, 1), min=round(min(t), 1), max=round(max(t), 1))
             emit(dict(n_gallery=ng, n_queries=nq, d=d, live=frac, hits=hits, hits_per_query=round(float(a[0][-1]) / nq, 1),
@@ -104,7 +110,7 @@ def step(args, ng, frac):
                       faster="many" if m_many < 0.95 * m_scan else ("scan" if m_scan < 0.95 * m_many else "neither"),
                       gallery_tb_per_s=round(ng * d * 2 / m_many / 1e6, 3),
                       exact_pairs=ops.range_many_stats(ws_many, ng, nq, d)["exact_pairs"],
-                      workspace_bytes=dict(many=ws_many.numel(), scan=ws_scan.numel()), same_bits=same), args.out)
+                      workspace_bytes=dict(many=ws_many.numel(), scan=ws_scan.numel()), same_bits=same, outputs_sha1=sha.hexdigest()), args.out)
 
 
 def near_duplicates(args, n):

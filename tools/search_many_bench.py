@@ -12,10 +12,13 @@ The protocol of tools/search_bench.py (profiles/search.md): per (n_gallery, n_qu
   fallback_queries      of the new entry's last call (ops.search_many_stats): 0 means every list was certified
   workspace_bytes       of the new entry and of the scan
   same_bits             ids, fp32 dists and the fp64 heads of the two are equal (asserted)
+  outputs_sha1          SHA-1 over the new entry's ids, fp32 dists, non-finite word and fp64 head of its last call: equal between two
+                        builds of the library (VTC_HIP_LIB) that compute the same
 Unit rows from a seeded generator on the device rounded to half, queries = gallery rows plus noise.  A live fraction below 1 draws every
 row's bit independently.  One process on an otherwise idle card.  profiles/search_many.md holds a run's table;
 VideoIndex.ROUTE_MANY_MIN_QUERIES cites it."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -75,6 +78,9 @@ def main():
                 same = (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]) and
                         torch.equal(ops.search_dists64(ws_many, nq, args.depth), ops.search_dists64(ws_scan, nq, args.depth)))
                 assert same, (ng, nq, frac)
+                sha = hashlib.sha1()
+                for t in (*a, ops.search_dists64(ws_many, nq, args.depth)):
+                    sha.update(t.cpu().numpy().tobytes())
                 m_many, m_scan = statistics.median(t_many), statistics.median(t_scan)
                 line = dict(n_gallery=ng, n_queries=nq, d=args.d, depth=args.depth, live=frac,
                             many_us=dict(median=round(m_many, 1), min=round(min(t_many), 1), max=round(max(t_many), 1)),
@@ -83,7 +89,7 @@ def main():
                             faster="many" if m_many < 0.95 * m_scan else ("scan" if m_scan < 0.95 * m_many else "neither"),
                             gallery_tb_per_s=round(ng * args.d * 2 / m_many / 1e6, 3),
                             fallback_queries=ops.search_many_stats(ws_many, nq, args.depth)["fallback_queries"],
-                            workspace_bytes=dict(many=ws_many.numel(), scan=ws_scan.numel()), same_bits=same)
+                            workspace_bytes=dict(many=ws_many.numel(), scan=ws_scan.numel()), same_bits=same, outputs_sha1=sha.hexdigest())
                 print(json.dumps(line), flush=True)
                 if out:
                     out.write(json.dumps(line) + "\n")

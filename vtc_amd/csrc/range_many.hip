@@ -2,22 +2,19 @@
 // stored as IEEE binary16.  The result is vtc_l2_range_count(gallery, /*half*/ 1, ...)'s, bit for bit -- lims, the hit words at the head of
 // the workspace, the bits ORed into nonfinite (include/vtc_hip.h) -- and vtc_l2_range_fill follows it on the same workspace unchanged; only
 // the way there differs.  range.hip's scan forms every (query, row) distance in fp64, a gallery pass per started tile of 8 queries.  Here
-// the gallery is streamed ONCE through v_mfma_f32_16x16x32_f16 for the APPROXIMATE distance A of search_many.hip, whose bound holds per pair,
-//     |A - D| <= eps = many_kappa(d) (|q|^2 + |g|^2) + 1e-35        (derived in search_many.hip; A finite, the query not QF_FALLBACK)
+// the gallery is streamed ONCE through the matrix cores for the APPROXIMATE distance A of search_many.hip, whose bound holds per pair,
+//     |A - D| <= eps = many_eps(many_kappa(d), |q|^2, |g|^2)        (derived in many_common.h; A finite, the query not QF_FALLBACK)
 // so a pair is decided on the spot: a hit when A + eps <= r, a miss when A - eps > r, and only a pair inside the BAND is decided by its fp64
 // distance D -- formed by the function the scan and the fill use, from the bits they read.  A range search keeps no candidate list and needs
 // no certificate over unseen rows.  Three launches, whatever the data:
 //
 //   many_prep_kernel        (many_common.h, search_many.hip's) a wave per query: |q|^2, the scale, the fp16 (hi, lo) B fragments, the dead
 //                           and below-range flags, bit 2 of nonfinite; zeroes the counter of the pairs decided in fp64.
-//   range_many_pass_kernel  a workgroup is one wave per 16 queries.  The unit of the walk is ONE hit word: 32 rows, two MFMA tiles of 16;
-//                           workgroup b of G takes the words b, b + G, ... and every wave walks the same words, owning the words of its
-//                           own 16 queries -- one writer a word, a plain store, zero words included (the workspace is not cleared), so
-//                           the result does not depend on the grid.  A fragments straight from global memory (16 bytes a lane), one item
-//                           ahead of the multiply; the B image resident in the LDS up to 512 columns; |g|^2 from the loaded fragments.
-//                           The mask word of a unit is read one unit ahead; a word with no live row inside the gallery loads nothing of
-//                           the gallery, and neither does a tile of a live word that has none.  Popcounts go into the scan's count slots,
-//                           one per (query, workgroup).
+//   range_many_pass_kernel  a workgroup is one wave per 16 queries.  The unit of the walk (many_walk, many_common.h, with an item's
+//                           fragments, its multiply step and A) is ONE hit word: 32 rows, two MFMA tiles of 16; every wave walks the
+//                           workgroup's words, owning the words of its own 16 queries -- one writer a word, a plain store, zero words
+//                           included (the workspace is not cleared; a word the walk skips is written where it is skipped), so the
+//                           result does not depend on the grid.  Popcounts go into the scan's count slots, one per (query, workgroup).
 //   range_prefix_kernel     (range_common.h, range.hip's) lims and the chunk bases, from the words and the counts.
 //
 // Not here: a grouped (distinct-video) range, more than 64 queries a call, an MFMA pass over fp32 rows (their rows are no MFMA operand).
@@ -29,9 +26,7 @@ using namespace vtcsweep;
 
 struct RangeManyWs {
   RangeWs head;             // range_ws's regions at range_ws's offsets: what vtc_l2_range_fill reads
-  uint4 *qimg;              // the B-fragment image (many_common.h)
-  float *qn, *inv_s;        // [64]
-  int *qflag;               // [64]
+  ManyPrologue pro;         // what many_prep_kernel writes
   unsigned long long *exact_pairs;      // the documented counter: the pairs of the call decided by their fp64 distance
   size_t total;
 };
@@ -40,19 +35,10 @@ RangeManyWs range_many_ws(void *ws, int ng, int nq, int d) {
   s.head = range_ws(ws, ng, nq);
   Bump b(ws);
   b.off = s.head.total;
-  s.qimg = (uint4 *)b.take(many_img_bytes(nq, d));
-  s.qn = (float *)b.take(MANY_MAX_Q * sizeof(float));
-  s.inv_s = (float *)b.take(MANY_MAX_Q * sizeof(float));
-  s.qflag = (int *)b.take(MANY_MAX_Q * sizeof(int));
+  s.pro = many_prologue_ws(b, nq, d);
   s.exact_pairs = (unsigned long long *)b.take(sizeof(unsigned long long));
   s.total = b.off;
   return s;
-}
-// workgroups a CU holds: a workgroup of g waves keeps g x 32 KB of B fragments in the LDS (no lists here, but four one-wave workgroups
-// already give every SIMD a wave)
-inline int range_many_per_cu(int nq) {
-  const int g = many_qgroups(nq);
-  return g == 1 ? 4 : (g == 2 ? 2 : 1);
 }
 
 // Row j is a hit of query q iff it is live, D is finite and D <= radius2[q] in fp64 (range.hip).  A dead query -- one with a NaN / inf, a
@@ -68,39 +54,19 @@ __global__ __launch_bounds__(256) void range_many_pass_kernel(const _Float16 *__
   extern __shared__ uint4 smem_range_many[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;        // wave: the group of 16 queries
   const int u = lane & 15, kq = lane >> 4;
-  // an item of the walk is NKS MFMA steps of a tile, as in many_pass_kernel: d = 32 NKS nchunks, the B image resident up to 512 columns
-  const int nchunks = d / (32 * NKS);
-  const bool resident = d <= MANY_KC;
-  const int img_vecs = (resident ? d / 32 : NKS) * 2 * 64;  // of a wave
-  uint4 *img = smem_range_many + (size_t)wave * img_vecs;
-  const uint4 *gimg = qimg + (size_t)wave * (d / 32) * 2 * 64;
-  if (resident)
-    for (int x = lane; x < d / 32 * 2 * 64; x += 64) img[x] = gimg[x];
-  __syncthreads();
+  const int nchunks = d / (32 * NKS);                      // an item is NKS MFMA steps of a tile
+  const ManyImage<NKS> image(smem_range_many, qimg, d, wave, lane);
 
   const int q = wave * 16 + u;                             // the lane's query: column u of the MFMA's result
   const float qn = qn_all[q], m2inv_s = -2.f * inv_s_all[q];
   const int flag = qflag[q];
   const bool qdead = (flag & QF_DEAD) != 0, qexact = (flag & QF_FALLBACK) != 0;      // dead covers q >= nq
   const double r2 = qdead ? -1.0 : radius2[q];
-  const double kd = (double)kappa, qn_d = (double)qn;
   int count = 0;                                           // hits of the lane's query in this workgroup's words
   unsigned hw = 0;                                         // the word being built, of the lane's query (every kq lane the same)
   long long n_exact = 0;                                   // band pairs of the wave: uniform
   bool gallery_bad = false;
 
-  const long long G = gridDim.x;
-  auto word_at = [&](long long w) -> unsigned {           // the mask word of unit w, as loaded
-    if constexpr (!MASKED) return 0xffffffffu;
-    if (w >= nwords) return 0;
-    return live[w];
-  };
-  auto avail_at = [&](long long w, unsigned word) -> unsigned {      // ... its rows inside the gallery, wave-uniform; 0 past the end
-    if (w >= nwords) return 0;
-    const long long left = (long long)ng - w * 32;
-    const unsigned inside = left >= 32 ? 0xffffffffu : (1u << left) - 1;
-    return (unsigned)uniform_of((int)(word & inside));
-  };
   auto put_word = [&](long long w, unsigned v) {          // w < nwords; the one writer of the word
     if (kq == 0 && q < nq) words[(size_t)q * nwords + w] = v;
   };
@@ -109,28 +75,11 @@ __global__ __launch_bounds__(256) void range_many_pass_kernel(const _Float16 *__
   float nrm = 0.f;
   // tile h (0, 1) of word w, chunk `chunk`; avail: the word's live rows inside the gallery, those of the tile != 0
   auto compute = [&](long long w, int h, unsigned avail, int chunk, const f16x8 (&ga)[NKS]) {
-    if (!resident) {                                       // every wave of the workgroup walks the same items
-      __syncthreads();
-      for (int x = lane; x < NKS * 2 * 64; x += 64) img[x] = gimg[(size_t)chunk * NKS * 2 * 64 + x];
-      __syncthreads();
-    }
-    const uint4 *bi = img + (resident ? chunk * NKS * 2 * 64 : 0) + lane;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {                     // many_pass_kernel's step: the hi and lo products, |g|^2 from the fragment
-      const f16x8 bh = __builtin_bit_cast(f16x8, bi[(ks * 2) * 64]), bl = __builtin_bit_cast(f16x8, bi[(ks * 2 + 1) * 64]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bl, acc, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const half2_t h = {ga[ks][2 * j], ga[ks][2 * j + 1]};
-        nrm = __builtin_amdgcn_fdot2(h, h, nrm, false);
-      }
-    }
+    many_multiply<NKS>(ga, image.item(chunk, lane), acc, nrm);
     if (chunk != nchunks - 1) return;
     // ---- the tile's epilogue: acc[i] = query u x row 4 kq + i of the tile
     const unsigned bits = (avail >> (16 * h)) & 0xffffu;
-    nrm += __shfl_xor(nrm, 16, 64);
-    nrm += __shfl_xor(nrm, 32, 64);                        // every lane: |g|^2 of row u
+    nrm = many_row_norm(nrm);                              // every lane: |g|^2 of row u
     if (((bits >> u) & 1) && !(fabsf(nrm) < INFINITY)) gallery_bad = true;      // a live row with a NaN / inf: never a hit, bit 1
     const int row0 = (int)(w * 32) + 16 * h;
     unsigned mine = 0;                                     // bit i: row 4 kq + i of the tile is a hit of query u
@@ -138,9 +87,9 @@ __global__ __launch_bounds__(256) void range_many_pass_kernel(const _Float16 *__
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * kq + i;
       const float gn = __shfl(nrm, r, 64);
-      const float A = fmaf(m2inv_s, acc[i], qn + gn);
+      const float A = many_dist(acc[i], qn, gn, m2inv_s);
       const bool pair = ((bits >> r) & 1) && fabsf(gn) < INFINITY && !qdead;
-      const double eps = kd * (qn_d + (double)gn) * (1.0 + 1e-6) + 1e-35;
+      const double eps = many_eps(kappa, qn, gn);
       const bool bounded = fabsf(A) < INFINITY && !qexact;
       const bool sure_hit = bounded && (double)A + eps <= r2, sure_miss = bounded && (double)A - eps > r2;
       if (pair && sure_hit) mine |= 1u << i;
@@ -168,51 +117,8 @@ __global__ __launch_bounds__(256) void range_many_pass_kernel(const _Float16 *__
     nrm = 0.f;
   };
 
-  // The walk.  A word with no live row is written as 0 where it is skipped, before anything of it is loaded, so every item that is loaded
-  // is multiplied: the loads of an item are unconditional and counted, and waiting for one item's fragments leaves the next item's in
-  // flight.  Two fragment sets; after the last item the loads are issued once more for the item itself and dropped.
-  f16x8 fa[NKS], fb[NKS];
-  long long wc = blockIdx.x;
-  unsigned ac = avail_at(wc, word_at(wc));
-  while (wc < nwords && !ac) {
-    put_word(wc, 0);
-    wc += G;
-    ac = avail_at(wc, word_at(wc));
-  }
-  if (wc < nwords) {                                       // uniform for the workgroup
-    unsigned w1 = word_at(wc + G);
-    int hc = (ac & 0xffffu) ? 0 : 1, chunk = 0;
-    many_load_frags<NKS>(gallery, d, 2 * wc + hc, 0, (ac >> (16 * hc)) & 0xffffu, u, kq, fa);
-    auto step = [&](const f16x8 (&cur)[NKS], f16x8 (&nxt)[NKS]) -> bool {
-      long long wn = wc;
-      unsigned an = ac;
-      int hn = hc, cn = chunk + 1;
-      if (cn == nchunks) {
-        cn = 0;
-        if (hc == 0 && (ac >> 16)) {
-          hn = 1;                                          // the word's second tile
-        } else {
-          wn = wc + G;
-          an = avail_at(wn, w1);
-          while (wn < nwords && !an) {
-            put_word(wn, 0);
-            wn += G;
-            an = avail_at(wn, word_at(wn));
-          }
-          w1 = word_at(wn + G);
-          hn = (an & 0xffffu) ? 0 : 1;
-        }
-      }
-      const bool last = wn >= nwords;
-      if (last) many_load_frags<NKS>(gallery, d, 2 * wc + hc, chunk, (ac >> (16 * hc)) & 0xffffu, u, kq, nxt);
-      else many_load_frags<NKS>(gallery, d, 2 * wn + hn, cn, (an >> (16 * hn)) & 0xffffu, u, kq, nxt);
-      compute(wc, hc, ac, chunk, cur);
-      wc = wn, ac = an, hc = hn, chunk = cn;
-      return !last;
-    };
-    while (step(fa, fb) && step(fb, fa)) {
-    }
-  }
+  // the unit is a hit word (nwords of them: ceil(ng / 32)); a word with no live row is written as 0 where the walk skips it
+  many_walk<MASKED, NKS, 2>(gallery, live, ng, d, u, kq, compute, [&](long long w) { put_word(w, 0); });
 
   if (kq == 0 && q < nq) cnt[(size_t)q * gridDim.x + blockIdx.x] = count;      // the workgroup's slot of the query: a plain store
   if (wave == 0 && nonfinite && __ballot(gallery_bad) && lane == 0) atomicOr(nonfinite, 1);
@@ -238,31 +144,21 @@ extern "C" int vtc_l2_range_count_many_half(const uint16_t *gallery, const float
 
   const _Float16 *g = reinterpret_cast<const _Float16 *>(gallery);
   const int qg = many_qgroups(nq), nwords = range_words(ng);
-  const int blocks = std::max(1, std::min(range_max_blocks(ng), range_many_per_cu(nq) * vtcgemm::num_cus()));      // at most the count slots
-  const int ksteps = d / 32, nks = many_item_steps(d);
-  const size_t lds = (size_t)qg * (d <= MANY_KC ? ksteps : nks) * 2 * 64 * sizeof(uint4);      // at most 128 KiB
-  // the pass of this call: MASKED by `live`, NKS the largest of 16, 8, 4, 2 MFMA steps an item that divides the row
+  const int blocks = std::max(1, std::min(range_max_blocks(ng), many_per_cu(nq) * vtcgemm::num_cus()));      // at most the count slots
   auto pass = [&](auto masked, auto steps) -> int {
     constexpr bool MASKED = decltype(masked)::value;
     constexpr int NKS = decltype(steps)::value;
     static PerDeviceOnce attr;
-    if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&range_many_pass_kernel<MASKED, NKS>), 4 * MANY_KS * 2 * 64 * (int)sizeof(uint4), name))
-      return 1;
-    hipLaunchKernelGGL((range_many_pass_kernel<MASKED, NKS>), dim3(blocks), dim3(64 * qg), lds, stream, g, queries, live, radius2, s.qimg, s.qn,
-                       s.inv_s, s.qflag, ng, nq, d, nwords, many_kappa(d), s.head.words, s.head.cnt, s.exact_pairs, nonfinite);
+    if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&range_many_pass_kernel<MASKED, NKS>), 4 * MANY_IMG_MAX_BYTES, name)) return 1;
+    hipLaunchKernelGGL((range_many_pass_kernel<MASKED, NKS>), dim3(blocks), dim3(64 * qg), many_img_lds_bytes(nq, d), stream, g, queries, live,
+                       radius2, s.pro.qimg, s.pro.qn, s.pro.inv_s, s.pro.qflag, ng, nq, d, nwords, many_kappa(d), s.head.words, s.head.cnt,
+                       s.exact_pairs, nonfinite);
     return 0;
   };
-  auto pass_of = [&](auto masked) -> int {
-    if (nks == 16) return pass(masked, std::integral_constant<int, 16>{});
-    if (nks == 8) return pass(masked, std::integral_constant<int, 8>{});
-    if (nks == 4) return pass(masked, std::integral_constant<int, 4>{});
-    return pass(masked, std::integral_constant<int, 2>{});
-  };
 
-  hipLaunchKernelGGL(many_prep_kernel, dim3(qg * 16), dim3(64), 0, stream, queries, nq, d, s.qimg, s.qn, s.inv_s, s.qflag, (int *)s.exact_pairs, 2,
-                     nonfinite);
+  many_launch_prep(queries, nq, d, s.pro, (int *)s.exact_pairs, 2, nonfinite, stream);
   VTC_LAUNCH_CHECK2(name, "prep");
-  if (live ? pass_of(std::true_type{}) : pass_of(std::false_type{})) return 1;
+  if (many_with_pass(live != nullptr, d, pass)) return 1;
   VTC_LAUNCH_CHECK2(name, "pass");
   hipLaunchKernelGGL(range_prefix_kernel, dim3(nq), dim3(256), 0, stream, s.head.words, s.head.cnt, blocks, nwords, range_chunks(ng),
                      (long long *)lims, s.head.chunk_base);

@@ -1,13 +1,12 @@
 // search_many.hip -- vtc_l2_search_many_half: the top-`depth` of MANY queries (up to 64 a pass) over a gallery stored as IEEE binary16.
 // The result is vtc_l2_search_half's without groups, bit for bit (include/vtc_hip.h); only the way there differs.  The scan of search.hip
 // forms every (query, row) distance in fp64, which at 64 queries is all it does: 8 gallery passes of fp64 arithmetic.  A half row already
-// IS an fp16 MFMA operand, so here the gallery is streamed ONCE through v_mfma_f32_16x16x32_f16 for an APPROXIMATE distance A, a few more
+// IS an fp16 MFMA operand, so here the gallery is streamed ONCE through the matrix cores for an APPROXIMATE distance A, a few more
 // candidates than were asked for are kept, and the exact finish the sweeps use too (exact_list.h: the fp64 re-rank of the candidates, the
 // brute-force scan behind an uncertified list) makes the answer exact again.  Four launches, whatever the data:
 //
 //   many_prep_kernel      a wave per query: |q|^2, the power-of-two scale s, the fp16 (hi, lo) split of s q laid out as the MFMA's B
-//                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.  (many_common.h, with
-//                         the image's layout and the A-fragment loader: range_many.hip's pass shares them.)
+//                         fragments, the dead / fallback flags of the query; zeroes the call's fallback counter.  (many_common.h)
 //   many_pass_kernel      the candidate pass.  A workgroup is one wave per 16 queries; every wave walks the workgroup's tiles of 16 gallery
 //                         rows (round-robin over the grid), loads a row tile straight from global memory into A fragments -- a lane's 16
 //                         bytes are 8 consecutive halves of one row, no LDS, no conversion -- one item ahead of the one it multiplies,
@@ -25,21 +24,9 @@
 //   many_fallback_kernel  the flagged queries only (normally none): a workgroup per query scans the live rows in fp64 (fallback_scan, with
 //                         the scan's list insertion), and overwrites the query's row of the result.
 //
-// THE BOUND.  A(q, j) = fl(fl(qn + gn) - 2 acc / s) with qn, gn the fp32 squared norms and acc the MFMA's fp32 sum over k of
-// g_k hi_k + g_k lo_k, where x = s q, hi = fl16(x), lo = fl16(x - hi) and s = 2^(13 - e) puts the largest |x_k| into [2^13, 2^14)
-// (scaling by a power of two is exact).  With u = 2^-24, S = |q|^2 + |g|^2, |q||g| <= S / 2:
-//   split      x_k - hi_k is exact in fp32 and |x_k - hi_k - lo_k| <= 2^-22 |x_k| while hi_k and lo_k are normal halves.  A subnormal one is
-//              a component below 2^-27 of the largest; even if the matrix core FLUSHED a subnormal operand (it does not: the tests'
-//              subnormal rows), that is an absolute 2^-13 per component, sum_k |g_k| 2^-13 <= 2^-13 sqrt(d) |g| <= 2^-20.5 |x||g| as
-//              |x| >= 2^13 and d <= 2048.  Together < 2^-20 |q||g| on the dot product, 2^-20 S on the distance.
-//   MFMA       2 d exact fp16 x fp16 products summed in fp32, in an order and with an internal rounding the hardware does not
-//              promise: two units a term, 4 d u |q||g| on the dot product, 4 d u S on the distance.
-//   norms      gn: d / 2 dot2 steps of two roundings and the two lane adds, qn: d fused steps and the butterfly: <= 2 d u S together.
-//   epilogue   fl(qn + gn) and the final fused multiply-add, each one rounding of a value <= 2 S: <= 8 u S with slack.
-//   range      acc / s, qn and the scaled components may UNDERFLOW for queries far below fp32's normal range: an absolute 1e-35, far
-//              above d 2^-149.  Overflow is not bounded but detected: a live row with a finite norm whose A is not finite flags the query.
-// So |A - D| <= eps(q) = many_kappa(d) (qn + max_j gn) + 1e-35 with many_kappa(d) = (6 d + 8) 2^-24 + 2^-20, the maximum over the LIVE
-// rows with a FINITE norm (a row with a NaN / inf is never a candidate, and a dead one is never looked at).
+// THE BOUND |A - D| <= eps is derived in many_common.h, with everything else this pass shares with range_many.hip's: the prologue, an item's
+// fragments and its multiply step, A itself, the walk over the gallery and the host's choice of the instantiation.  What is here is what
+// only the search has: the candidate lists, the finish and its certificate, the fallback.
 #include "exact_list.h"
 #include "many_common.h"
 #include "search_scan.h"
@@ -49,18 +36,15 @@ using namespace vtcsweep;
 
 constexpr int MANY_MAX_DEPTH = 32;     // at least 21 spare ranks in a lane-per-entry list
 constexpr int MANY_MAX_BLOCKS = 1024;  // workgroups of the pass at most (four one-wave workgroups a CU): lists per query in the workspace
-// workgroups of the pass the workspace has lists for: a workgroup of g waves holds g x 32 KB of the LDS, so 4 / g fit a CU
+// workgroups of the pass the workspace has lists for
 inline int many_max_blocks(int ng, int nq) {
-  const int g = many_qgroups(nq), per_cu = g == 1 ? 4 : (g == 2 ? 2 : 1);      // 40 KB a wave with its lists: 160 KiB a CU
-  return (int)std::min<long long>(MANY_MAX_BLOCKS / 4 * per_cu, ((long long)ng + 15) / 16);
+  return (int)std::min<long long>(MANY_MAX_BLOCKS / 4 * many_per_cu(nq), ((long long)ng + 15) / 16);
 }
 
 struct ManyWs {
   double *dists64;      // [nq][depth]: the documented head
   int *flags;           // flags[0]: the queries the fallback finished (the documented counter); flags[1 ..]: which
-  uint4 *qimg;          // [qgroups][d / 32][hi, lo][64 lanes]: B fragments
-  float *qn, *inv_s;    // [64]
-  int *qflag;           // [64]
+  ManyPrologue pro;     // what many_prep_kernel writes
   float *gmax;          // [blocks]
   int *over;            // [blocks][64]
   float *list_a;        // [nq][cdepth][blocks]
@@ -72,13 +56,10 @@ ManyWs many_ws(void *ws, int ng, int nq, int d, int depth) {
   ManyWs s;
   const size_t blocks = many_max_blocks(ng, nq), entries = (size_t)nq * exact_cdepth(depth, ng);
   s.dists64 = (double *)b.take((size_t)nq * depth * sizeof(double));
-  s.flags = (int *)b.take((1 + SEARCH_MAX_Q) * sizeof(int));
-  s.qimg = (uint4 *)b.take(many_img_bytes(nq, d));
-  s.qn = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
-  s.inv_s = (float *)b.take(SEARCH_MAX_Q * sizeof(float));
-  s.qflag = (int *)b.take(SEARCH_MAX_Q * sizeof(int));
+  s.flags = (int *)b.take((1 + MANY_MAX_Q) * sizeof(int));
+  s.pro = many_prologue_ws(b, nq, d);
   s.gmax = (float *)b.take(blocks * sizeof(float));
-  s.over = (int *)b.take(blocks * SEARCH_MAX_Q * sizeof(int));
+  s.over = (int *)b.take(blocks * MANY_MAX_Q * sizeof(int));
   s.list_a = (float *)b.take(entries * blocks * sizeof(float));
   s.list_i = (int *)b.take(entries * blocks * sizeof(int));
   s.total = b.off;
@@ -118,19 +99,10 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
   extern __shared__ uint4 smem_many[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;        // wave: the group of 16 queries
   const int u = lane & 15, kq = lane >> 4;
-  // an item of the walk is NKS MFMA steps of a tile (a template parameter: the loads of an item are then unconditional and the
-  // compiler counts them, so waiting for one item's fragments leaves the next item's in flight); d = 32 NKS nchunks.  Up to 512
-  // columns the wave's whole B image is RESIDENT in the LDS; a longer row reloads the item's part of it per item.
-  const int nchunks = d / (32 * NKS);
-  const bool resident = d <= MANY_KC;
-  const int img_vecs = (resident ? d / 32 : NKS) * 2 * 64;  // of a wave; the waves' lists follow the images
-  uint4 *img = smem_many + (size_t)wave * img_vecs;
-  float *la = reinterpret_cast<float *>(smem_many + (size_t)(blockDim.x >> 6) * img_vecs) + wave * (16 * 64 * 2) + lane;
-  int *li = reinterpret_cast<int *>(la + 16 * 64);       // la[64 v] / li[64 v]: this lane's entry of list v
-  const uint4 *gimg = qimg + (size_t)wave * (d / 32) * 2 * 64;
-  if (resident)
-    for (int x = lane; x < d / 32 * 2 * 64; x += 64) img[x] = gimg[x];
-  __syncthreads();
+  const int nchunks = d / (32 * NKS);                      // an item is NKS MFMA steps of a tile
+  const ManyImage<NKS> image(smem_many, qimg, d, wave, lane);
+  float *la = reinterpret_cast<float *>(smem_many + (size_t)(blockDim.x >> 6) * many_img_vecs(d, NKS)) + wave * (16 * 64 * 2) + lane;
+  int *li = reinterpret_cast<int *>(la + 16 * 64);       // the waves' lists follow the images; la[64 v] / li[64 v]: this lane's entry of list v
 
   const int q = wave * 16 + u;                             // the lane's query: column u of the MFMA's result
   const float qn = qn_all[q], m2inv_s = -2.f * inv_s_all[q];
@@ -141,49 +113,14 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
   bool over = false, gallery_bad = false;
   float gmax = 0.f;
 
-  // The walk: workgroup b takes the tiles b, b + G, ... and SKIPS a tile none of whose rows is live before anything of it is loaded, so
-  // every item that is loaded is multiplied: the loads of an item are unconditional, the compiler counts them, and waiting for one
-  // item's fragments leaves the next item's in flight.  The mask word of a tile (its address is uniform: a scalar load, which the
-  // vector loads' counter does not see) is read one tile ahead; only a run of dead tiles is searched word by word.
-  const long long n_tiles = ((long long)ng + 15) / 16, G = gridDim.x;
-  auto word_at = [&](long long t) -> unsigned {           // the 16 mask bits of tile t, as loaded
-    if constexpr (!MASKED) return 0xffffu;
-    if (t >= n_tiles) return 0;
-    return live[t >> 1] >> ((t & 1) * 16);
-  };
-  auto bits_at = [&](long long t, unsigned word) -> unsigned {      // ... of its rows inside the gallery, wave-uniform; 0 past the end
-    if (t >= n_tiles) return 0;
-    const long long left = (long long)ng - t * 16;
-    const unsigned inside = left >= 16 ? 0xffffu : (1u << left) - 1;
-    return (unsigned)uniform_of((int)(word & inside));
-  };
-  // the A fragments of an item (many_common.h); bits != 0
-  auto load_frags = [&](long long t, int chunk, unsigned bits, f16x8 (&ga)[NKS]) { many_load_frags<NKS>(gallery, d, t, chunk, bits, u, kq, ga); };
-
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   float nrm = 0.f;
-  auto compute = [&](long long t, int chunk, unsigned bits, const f16x8 (&ga)[NKS]) {
-    if (!resident) {                                       // every wave of the workgroup walks the same items
-      __syncthreads();
-      for (int x = lane; x < NKS * 2 * 64; x += 64) img[x] = gimg[(size_t)chunk * NKS * 2 * 64 + x];
-      __syncthreads();
-    }
-    const uint4 *bi = img + (resident ? chunk * NKS * 2 * 64 : 0) + lane;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const f16x8 bh = __builtin_bit_cast(f16x8, bi[(ks * 2) * 64]), bl = __builtin_bit_cast(f16x8, bi[(ks * 2 + 1) * 64]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ga[ks], bl, acc, 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const half2_t h = {ga[ks][2 * j], ga[ks][2 * j + 1]};
-        nrm = __builtin_amdgcn_fdot2(h, h, nrm, false);
-      }
-    }
+  // chunk `chunk` of tile t (the walk's unit: its one tile); bits: the tile's live rows inside the gallery
+  auto compute = [&](long long t, int, unsigned bits, int chunk, const f16x8 (&ga)[NKS]) {
+    many_multiply<NKS>(ga, image.item(chunk, lane), acc, nrm);
     if (chunk != nchunks - 1) return;
     // ---- the tile's epilogue: acc[i] = query u x row 4 kq + i of the tile
-    nrm += __shfl_xor(nrm, 16, 64);
-    nrm += __shfl_xor(nrm, 32, 64);                        // every lane: |g|^2 of row u
+    nrm = many_row_norm(nrm);                              // every lane: |g|^2 of row u
     const bool row_live = (bits >> u) & 1, row_fin = fabsf(nrm) < INFINITY;
     if (row_live && !row_fin) gallery_bad = true;
     if (row_live && row_fin) gmax = fmaxf(gmax, nrm);
@@ -192,7 +129,7 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * kq + i;
       const float gn = __shfl(nrm, r, 64);
-      const float A = fmaf(m2inv_s, acc[i], qn + gn);
+      const float A = many_dist(acc[i], qn, gn, m2inv_s);
       const bool cand = ((bits >> r) & 1) && fabsf(gn) < INFINITY && !qdead;
       const bool fin = fabsf(A) < INFINITY;
       if (cand && !fin) over = true;                       // D is finite, A is not: the query goes to the fallback
@@ -210,43 +147,7 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
     nrm = 0.f;
   };
 
-  // two fragment sets: the loads of the next item are in flight while this one is multiplied.  After the last item the loads are
-  // issued once more for the item itself (a live tile) and dropped, which keeps their number fixed.
-  f16x8 fa[NKS], fb[NKS];
-  long long tc = blockIdx.x;
-  unsigned bc = bits_at(tc, word_at(tc));
-  while (tc < n_tiles && !bc) {
-    tc += G;
-    bc = bits_at(tc, word_at(tc));
-  }
-  if (tc < n_tiles) {                                      // uniform for the workgroup
-    unsigned w1 = word_at(tc + G);
-    int chunk = 0;
-    load_frags(tc, 0, bc, fa);
-    auto step = [&](const f16x8 (&cur)[NKS], f16x8 (&nxt)[NKS]) -> bool {
-      long long tn = tc;
-      unsigned bn = bc;
-      int cn = chunk + 1;
-      if (cn == nchunks) {
-        cn = 0;
-        tn = tc + G;
-        bn = bits_at(tn, w1);
-        while (tn < n_tiles && !bn) {
-          tn += G;
-          bn = bits_at(tn, word_at(tn));
-        }
-        w1 = word_at(tn + G);
-      }
-      const bool last = tn >= n_tiles;
-      if (last) load_frags(tc, chunk, bc, nxt);
-      else load_frags(tn, cn, bn, nxt);
-      compute(tc, chunk, bc, cur);
-      tc = tn, bc = bn, chunk = cn;
-      return !last;
-    };
-    while (step(fa, fb) && step(fb, fa)) {
-    }
-  }
+  many_walk<MASKED, NKS, 1>(gallery, live, ng, d, u, kq, compute, [](long long) {});      // a dead tile leaves nothing behind
 
   if (wave == 0) {
     const float g = wave_max(gmax);
@@ -254,7 +155,7 @@ __global__ __launch_bounds__(256) void many_pass_kernel(const _Float16 *__restri
     if (nonfinite && __ballot(gallery_bad) && lane == 0) atomicOr(nonfinite, 1);
   }
   const unsigned long long ov = __ballot(over);
-  if (kq == 0 && q < nq) over_out[(size_t)blockIdx.x * SEARCH_MAX_Q + q] = ((ov >> u) & 0x0001000100010001ull) != 0;
+  if (kq == 0 && q < nq) over_out[(size_t)blockIdx.x * MANY_MAX_Q + q] = ((ov >> u) & 0x0001000100010001ull) != 0;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
     const int qq = wave * 16 + v;
@@ -303,7 +204,7 @@ __global__ __launch_bounds__(256) void many_finish_kernel(const _Float16 *__rest
   bool over = false;
   for (int l = lane; l < nlists; l += 64) {
     gmax = fmaxf(gmax, gmax_parts[l]);
-    over = over || over_parts[(size_t)l * SEARCH_MAX_Q + q] != 0;
+    over = over || over_parts[(size_t)l * MANY_MAX_Q + q] != 0;
   }
   gmax = wave_max(gmax);
   over = __ballot(over) != 0;
@@ -326,7 +227,7 @@ __global__ __launch_bounds__(256) void many_finish_kernel(const _Float16 *__rest
   if (flag & QF_DEAD) return;
   const unsigned long long last = __ballot(my >= 0 && rank == depth - 1);
   const double d_depth = last ? __shfl(md, __ffsll((long long)last) - 1, 64) : (double)INFINITY;
-  const double eps = (double)kappa * ((double)qn[q] + (double)gmax) * (1.0 + 1e-6) + 1e-35;
+  const double eps = many_eps(kappa, qn[q], gmax);
   const bool whole = !(a_out < INFINITY) || n_cand >= ng;  // fewer than C candidates exist, or every row is one: nothing is outside
   const bool sure = !over && !(flag & QF_FALLBACK) && (whole || a_out - eps > d_depth);
   if (!sure && lane == 0) flags[1 + atomicAdd(flags, 1)] = q;
@@ -350,6 +251,7 @@ __global__ __launch_bounds__(1024) void many_fallback_kernel(const _Float16 *__r
   }
 }
 
+static_assert(MANY_MAX_Q == SEARCH_MAX_Q, "search_args_ok bounds the queries of a call");
 bool many_args_ok(int ng, int nq, int d, int depth) { return search_args_ok(ng, nq, d, depth) && depth <= MANY_MAX_DEPTH; }
 }  // namespace
 
@@ -363,7 +265,7 @@ extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *que
   const char *name = "l2_search_many_half";
   hipStream_t stream = (hipStream_t)stream_;
   VTC_CHECK(gallery && queries && ids, "%s: null argument", name);
-  if (check_shape(name, ng, nq, SEARCH_MAX_Q, " (more queries: slice them)", nullptr, &depth, d, id_base)) return 1;
+  if (check_shape(name, ng, nq, MANY_MAX_Q, " (more queries: slice them)", nullptr, &depth, d, id_base)) return 1;
   VTC_CHECK(depth <= MANY_MAX_DEPTH, "%s: depth=%d must be at most %d (deeper: vtc_l2_search_half)", name, depth, MANY_MAX_DEPTH);
   const size_t need = many_ws(nullptr, ng, nq, d, depth).total;
   VTC_CHECK(ws && ws_bytes >= need, "%s: workspace too small (%zu < %zu)", name, ws_bytes, need);
@@ -371,33 +273,24 @@ extern "C" int vtc_l2_search_many_half(const uint16_t *gallery, const float *que
   const ManyWs s = many_ws(ws, ng, nq, d, depth);
   const _Float16 *g = reinterpret_cast<const _Float16 *>(gallery);
   const int qg = many_qgroups(nq), cdepth = exact_cdepth(depth, ng);
-  const int per_cu = qg == 1 ? 4 : (qg == 2 ? 2 : 1);
-  const int blocks = std::min(many_max_blocks(ng, nq), per_cu * vtcgemm::num_cus());
-  const int ksteps = d / 32, nks = many_item_steps(d);
-  const size_t lds = (size_t)qg * ((d <= MANY_KC ? ksteps : nks) * 2 * 64 * sizeof(uint4) + MANY_LIST_BYTES);      // at most all 160 KiB of a CU
-  // the pass of this call: MASKED by `live`, NKS the largest of 16, 8, 4, 2 MFMA steps an item that divides the row
+  const int blocks = std::min(many_max_blocks(ng, nq), many_per_cu(nq) * vtcgemm::num_cus());
+  const size_t lds = many_img_lds_bytes(nq, d) + (size_t)qg * MANY_LIST_BYTES;      // at most all 160 KiB of a CU
   auto pass = [&](auto masked, auto steps) -> int {
     constexpr bool MASKED = decltype(masked)::value;
     constexpr int NKS = decltype(steps)::value;
     static PerDeviceOnce attr;
-    if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&many_pass_kernel<MASKED, NKS>), 4 * (MANY_KS * 2 * 64 * (int)sizeof(uint4) + MANY_LIST_BYTES), name)) return 1;
-    hipLaunchKernelGGL((many_pass_kernel<MASKED, NKS>), dim3(blocks), dim3(64 * qg), lds, stream, g, live, s.qimg, s.qn, s.inv_s, s.qflag, ng, nq, d,
-                       cdepth, s.list_a, s.list_i, s.gmax, s.over, nonfinite);
+    if (ensure_dynamic_lds(attr, reinterpret_cast<const void *>(&many_pass_kernel<MASKED, NKS>), 4 * (MANY_IMG_MAX_BYTES + MANY_LIST_BYTES), name)) return 1;
+    hipLaunchKernelGGL((many_pass_kernel<MASKED, NKS>), dim3(blocks), dim3(64 * qg), lds, stream, g, live, s.pro.qimg, s.pro.qn, s.pro.inv_s,
+                       s.pro.qflag, ng, nq, d, cdepth, s.list_a, s.list_i, s.gmax, s.over, nonfinite);
     return 0;
   };
-  auto pass_of = [&](auto masked) -> int {
-    if (nks == 16) return pass(masked, std::integral_constant<int, 16>{});
-    if (nks == 8) return pass(masked, std::integral_constant<int, 8>{});
-    if (nks == 4) return pass(masked, std::integral_constant<int, 4>{});
-    return pass(masked, std::integral_constant<int, 2>{});
-  };
 
-  hipLaunchKernelGGL(many_prep_kernel, dim3(qg * 16), dim3(64), 0, stream, queries, nq, d, s.qimg, s.qn, s.inv_s, s.qflag, s.flags, 1, nonfinite);
+  many_launch_prep(queries, nq, d, s.pro, s.flags, 1, nonfinite, stream);
   VTC_LAUNCH_CHECK2(name, "prep");
-  if (live ? pass_of(std::true_type{}) : pass_of(std::false_type{})) return 1;
+  if (many_with_pass(live != nullptr, d, pass)) return 1;
   VTC_LAUNCH_CHECK2(name, "pass");
-  hipLaunchKernelGGL(many_finish_kernel, dim3(nq), dim3(256), 0, stream, g, queries, ManyLists{s.list_a, s.list_i, blocks, cdepth, 0}, s.qn, s.qflag,
-                     s.gmax, s.over, ng, d, depth, many_kappa(d), id_base, ids, dists, s.dists64, s.flags);
+  hipLaunchKernelGGL(many_finish_kernel, dim3(nq), dim3(256), 0, stream, g, queries, ManyLists{s.list_a, s.list_i, blocks, cdepth, 0}, s.pro.qn,
+                     s.pro.qflag, s.gmax, s.over, ng, d, depth, many_kappa(d), id_base, ids, dists, s.dists64, s.flags);
   VTC_LAUNCH_CHECK2(name, "finish");
   hipLaunchKernelGGL(many_fallback_kernel, dim3(nq), dim3(1024), 0, stream, g, queries, live, ng, d, depth, id_base, s.flags, ids, dists, s.dists64);
   VTC_LAUNCH_CHECK2(name, "fallback");
